@@ -7,7 +7,7 @@ split); there is no collective in the data path.  Prints ONE JSON line (rank 0).
 the N ranks itself; under `python -m torch.distributed.run` it uses the launcher's ranks.
 
 N > 1 (first exercised on hardware by the driver's scaling run): the time of a rank is its own K steps (synchronize on both sides,
-a barrier before and after), `value` = all ranks' columns / the MAX over ranks.  Rank 0 prints the timing line -- every field of the
+a barrier before and after), `value` = all ranks' columns / the MAX over ranks.  With `--full`, rank 0 prints the timing line -- every field of the
 contract -- as soon as that MAX is known, and the full line (the same plus the self-tests' verdicts reduced over the ranks) LAST, so
 that a run that ends in the verdict legs still leaves its measurement on stdout; `python bench.py --gpus N` (own launcher) relays
 only the last line.  `--budget-s` (420) bounds the whole launch and, by a fraction of at most 120 s, every rendezvous / collective.
@@ -17,7 +17,10 @@ The state is the first and only allocation of the process and comes from the lib
 not search.  `roofline.unplaced_first_allocation`
 is the same measurement in a fresh process with the placement switched off.
 
-The line also carries `cpu_baseline` (the reference on rank 0's host cores) and, at N=1, from child processes run
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs of the last step if
+`--dump-outputs DIR` is given (dump_outputs), print the line.  Everything below comes with `--full` only.
+
+With `--full` the line also carries `cpu_baseline` (the reference on rank 0's host cores) and, at N=1, from child processes run
 after the measurement: `companion_kernels` (the same bench for TL and AD -- BASELINE.json's metric names all three; AD with its
 design floor, ad_design_floor), `nproma_sweep` (NL at NPROMA 32 / 64 / 128 / 256, BASELINE configs[1]), `roofline.traffic` measured in this run (two `rocprofv3 --pmc` child passes), `target_config` (NL at
 1 048 576 columns, north_star's target), `host_array_driver` (the PCIe-inclusive rate of the reference-signature path, never `value`)
@@ -422,6 +425,31 @@ def timed_steps(torch, dev, stream, step, steps, warmup, barrier=None):
     return elapsed, np.array([a.elapsed_time(b) for a, b in ev])  # per-launch device time on the launch stream
 
 
+DUMP_COLUMNS = 1024          # columns sampled by --dump-outputs (all of them when the rank has fewer)
+DUMP_LIMIT_BYTES = 64 << 20  # the whole dump stays below this
+
+
+def dump_outputs(torch, outdir, ds, keep, kernel, seed=0):
+    """--dump-outputs: what the last timed step left for its caller, one DIR/<name>.npy per array, in the library's precision
+    (float64, float32 for --precision single).  NL: the arrays the sweep writes (DeviceState.WRITTEN) and PLUDE; TL / AD also the
+    perturbation set, `pert_in_<x>` (AD: the input adjoints it accumulates) and `pert_out_<x>`.  Each array is (columns, ...) over ONE
+    sorted sample of this rank's columns drawn with a fixed seed, so two runs with the same arguments dump the same columns."""
+    arrays = {n: getattr(ds, n) for n in ds.WRITTEN + ("PLUDE",)}
+    if kernel != "nl":
+        inc, dout = keep[1], keep[2]
+        arrays.update({f"pert_in_{n}": t for n, t in inc.t.items()})
+        arrays.update({f"pert_out_{n}": t for n, t in dout.t.items()})
+    per_col = sum(t[0, ..., 0].numel() * t.element_size() for t in arrays.values())
+    ncol = min(ds.ngptot, DUMP_COLUMNS, DUMP_LIMIT_BYTES // per_col)
+    cols = np.sort(np.random.default_rng(seed).choice(ds.ngptot, size=ncol, replace=False))
+    blk = torch.as_tensor(cols // ds.nproma, device=ds.device)
+    lane = torch.as_tensor(cols % ds.nproma, device=ds.device)
+    torch.cuda.synchronize(ds.device)
+    os.makedirs(outdir, exist_ok=True)
+    for n, t in arrays.items():
+        np.save(os.path.join(outdir, f"{n}.npy"), t[blk, ..., lane].cpu().numpy())  # (columns, [planes,] levels)
+
+
 def child_bench(extra_args, env=None, timeout=900):
     """Run this script as a fresh child process (own device memory, own placement) and return its JSON line."""
     import subprocess
@@ -442,13 +470,19 @@ def main():
     ap.add_argument("--ngptot", type=int, default=160000, help="columns per GPU")
     ap.add_argument("--nproma", type=int, default=128)
     ap.add_argument("--kernel", choices=["nl", "tl", "ad"], default="nl")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the CPU baseline, the companion kernels and configurations from child processes, "
+                         "the HBM traffic measured in this run, the self-tests; at N > 1 the TL / AD companions and the verdict reductions")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (the arrays the timed path hands "
+                         "its caller, on a fixed seeded sample of the columns; rank 0's columns at N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-companions", action="store_true",
-                    help="skip everything appended to the headline line from child processes: TL and AD timings, the 1 M-column "
+                    help="--full without everything appended to the headline line from child processes: TL and AD timings, the 1 M-column "
                          "NL target configuration, the unplaced first allocation")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="do not measure the HBM traffic in this run (two rocprofv3 --pmc child passes, ~25 s): `roofline.traffic` then comes "
-                         "from the newest committed pass under profiles/")
+                    help="--full without measuring the HBM traffic in this run (two rocprofv3 --pmc child passes, ~25 s): `roofline.traffic` then "
+                         "comes from the newest committed pass under profiles/")
     ap.add_argument("--precision", choices=["double", "single"], default=os.environ.get("CLOUDSC2_PRECISION", "double"),
                     help="single = the fp32 library (the reference's -DSINGLE build); the headline metric is double")
     ap.add_argument("--ad-assign", action="store_true",
@@ -636,13 +670,15 @@ def main():
                    "placement": placement},
         "roofline": roofline,
     }
-    if world > 1 and rank == 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, ds, keep, args.kernel)
+    if world > 1 and rank == 0 and args.full:
         # The timing is complete here: it goes out NOW, as a line of its own with every field of the contract, before the verdict
         # legs below touch RCCL again -- whatever happens there (a collective that never answers is ended by the watchdog with the
         # process), the measurement is on record.  The full line, with `verdicts`, follows as the LAST line.
         print(json.dumps({**out, "stage": "timing (the full line with the self-tests' verdicts follows; this one stands if it does not)",
                           "seconds_since_start": round(time.monotonic() - t_start, 1)}), flush=True)
-    companions = rank == 0 and world == 1 and args.kernel == "nl" and not args.no_companions
+    companions = rank == 0 and world == 1 and args.kernel == "nl" and args.full and not args.no_companions
     if companions:
         # Everything below comes from fresh child processes started after this process has given its device memory back; none of
         # it is inside the timed region or part of `value`; `--no-companions` skips it.
@@ -751,11 +787,11 @@ def main():
         except Exception as e:  # noqa: BLE001
             bc["error"] = repr(e)
         out["baseline_configs_2_3"] = bc
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.kernel == "nl":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.kernel == "nl":
         cb = cpu_baseline(tab, prm, 32, args.ngptot)
         if cb:
             out["cpu_baseline"] = cb
-    if world > 1 and args.kernel == "nl" and not args.no_companions:
+    if world > 1 and args.kernel == "nl" and args.full and not args.no_companions:
         # BASELINE.json configs[4] names NL + TL + AD on the node: every rank times the other two kernels IN-PROCESS on its own
         # columns (the NL state is given back first; 160 000 columns with their perturbation sets are 17 GB of the GPU's 288), with
         # the protocol of the headline -- barrier, K steps, barrier, MAX over ranks -- and `value` = all ranks' columns over that
@@ -787,7 +823,7 @@ def main():
         out["companion_kernels"] = comp
         ds = step = keep = None
     native_hung = False
-    if world > 1:
+    if world > 1 and args.full:
         # The only inter-GPU exchange of the path: max-reduce the two self-tests' verdict norms (outside the timing).  Each rank
         # runs the Taylor test and the adjoint test on its own 1024-column sub-range; ZNORMG(10) and ZNORMG are all-reduced
         # (MAX) over RCCL -- cloudsc_driver_tl_mod.F90:125, cloudsc_driver_ad_mod.F90:107 carried across ranks.
@@ -837,7 +873,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["verdicts"] = {"error": repr(e)}
     if rank == 0:
-        if world > 1 and not args.no_cpu_baseline and args.kernel == "nl" and not native_hung:
+        if world > 1 and args.full and not args.no_cpu_baseline and args.kernel == "nl" and not native_hung:
             # rank 0's host cores, after the last collective (no rank waits for it), only while the budget has room: the launcher's
             # deadline must not take the final line with it
             left = budgets(args.budget_s)[0] - (time.monotonic() - t_start)
@@ -850,7 +886,7 @@ def main():
                     out["cpu_baseline"] = {"error": repr(e)}
             else:
                 out["cpu_baseline"] = {"skipped": f"{left:.0f} s of --budget-s left"}
-        if world > 1:
+        if world > 1 and args.full:
             out["stage"] = "final"
             out["seconds_since_start"] = round(time.monotonic() - t_start, 1)
         print(json.dumps(out), flush=True)

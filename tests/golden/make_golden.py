@@ -9,6 +9,8 @@ The fixtures hold data only: a checksum of the (deterministic, regenerated) inpu
   evap_rand24.npz      the same three kernels with LEVAPLS2=.true. (the block that is dead in the shipped configs)
   drivers.json         what the reference's own TL and AD test drivers print (Taylor ratios, verdicts, max AD error)
   table_numpy.npz      the fields of the synthetic table as numpy evaluates the recipe (rounds 1-4), where they differ from the library's
+  py_restatement24.npz SATUR + CLOUDSC2 as the reference's own numpy restatement computes them (src/cloudsc2_nl_gt4py/cloudsc2_py.py),
+                       written by `python tests/golden/make_golden.py --py-restatement <reference checkout>`
 """
 from __future__ import annotations
 
@@ -176,5 +178,51 @@ def main():
     print(json.dumps(drivers, indent=1))
 
 
+def restatement_inputs(oracle_lib, ncol=24):
+    """The first `ncol` columns of the synthetic atmosphere as one block, the parameters set in `oracle_lib`; QSAT left zero.
+    Returns (state, inputs, params, digest of the inputs)."""
+    tab = c2.synthetic_table()
+    tab = {k: (np.ascontiguousarray(v[:, :ncol]) if isinstance(v, np.ndarray) else v) for k, v in tab.items()}
+    prm = make_params(tab)
+    set_lib_params(oracle_lib, prm)
+    st = c2.state_from_table(tab, ncol, ncol, real=np.float64)
+    inp = refcall.block_inputs(st, 0)
+    return st, inp, prm, input_digest(inp)
+
+
+def py_restatement(checkout):
+    """py_restatement24.npz: the reference's numpy restatement of SATUR + CLOUDSC2 (numpy + math only, LEVAPLS2 hard-wired off),
+    imported from the checkout, on the 24 columns of restatement_inputs; CLOUDSC2 gets the C oracle's QSAT, as the test does."""
+    import importlib.util
+    import types
+
+    spec = importlib.util.spec_from_file_location("_ref_cloudsc2_py", os.path.join(checkout, "src", "cloudsc2_nl_gt4py", "cloudsc2_py.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    oracle = refcall.OracleLib()
+    st, inp, prm, digest = restatement_inputs(oracle)
+    nlev, ncol = st.nlev, st.nproma
+    ns = types.SimpleNamespace
+    cst = ns(rg=prm.rg, rd=prm.rd, rcpd=prm.rcpd, retv=prm.retv, rlvtt=prm.rlvtt, rlstt=prm.rlstt, rlmlt=prm.rlmlt, rtt=prm.rtt)
+    ethf = ns(r2es=prm.r2es, r3les=prm.r3les, r3ies=prm.r3ies, r4les=prm.r4les, r4ies=prm.r4ies, r5les=prm.r5les,
+              r5ies=prm.r5ies, r5alvcp=prm.r5alvcp, r5alscp=prm.r5alscp, ralvdcp=prm.ralvdcp, ralsdcp=prm.ralsdcp,
+              rtwat=prm.rtwat, rtice=prm.rtice, rtwat_rtice_r=prm.rtwat_rtice_r, rvtmp2=prm.rvtmp2)
+    ecldp = ns(rclcrit=prm.rclcrit, rkconv=prm.rkconv, rlmin=prm.rlmin, rpecons=prm.rpecons)
+    ecld = ns(ceta=prm.ceta_array())
+    ephli = ns(lphylin=True, rlptrc=prm.rlptrc)
+    qs_py = np.zeros((nlev, ncol))
+    mod.satur(1, ncol, ncol, 1, nlev, True, inp["pap"], inp["t"], qs_py, 2, ethf, cst)
+    inp["qsat"] = oracle.satur(inp["pap"], inp["t"])
+    out = refcall.new_outputs(nlev, ncol)
+    a = refcall.kernel_arg_order({k: v.copy() for k, v in inp.items()}, out)
+    mod.cloudsc2_py(1, ncol, ncol, 1, nlev, False, st.ptsphy, *a, ecldp, ecld, cst, ethf, ephli)
+    path = os.path.join(HERE, "py_restatement24.npz")
+    np.savez_compressed(path, digest=np.array(digest), qsat=qs_py, **{"out_" + n: v for n, v in out.items()})
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) == 3 and sys.argv[1] == "--py-restatement":
+        py_restatement(sys.argv[2])
+    else:
+        main()

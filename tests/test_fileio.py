@@ -2,8 +2,10 @@
 code, no GPU.  Reference behaviour: cloudsc2_array_state_mod.F90:153-287, expand_mod.F90:30-46, validate_mod.F90:263-296."""
 from __future__ import annotations
 
+import gzip
 import math
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -11,7 +13,8 @@ import pytest
 from tests.util import ROOT, B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import fileio
 
-REF_H5 = "/root/reference/config-files/reference.h5"
+# config-files/reference.h5 of the reference checkout, as distributed there (gzip-compressed)
+REF_H5_GZ = os.path.join(ROOT, "tests", "golden", "reference.h5.gz")
 
 
 def test_input_file_round_trip(tmp_path):
@@ -44,13 +47,15 @@ def test_input_file_round_trip(tmp_path):
         assert np.array_equal(getattr(a, n), getattr(b, n)), n
 
 
-@pytest.mark.skipif(not os.path.exists(REF_H5), reason="reference checkout not present")
-def test_reads_the_reference_h5_of_the_checkout():
+def test_reads_the_reference_h5_of_the_checkout(tmp_path):
+    ref_h5 = str(tmp_path / "reference.h5")
+    with gzip.open(REF_H5_GZ, "rb") as src, open(ref_h5, "wb") as dst:
+        shutil.copyfileobj(src, dst)
     gold = np.load(os.path.join(ROOT, "tests", "golden", "reference_h5.npz"))
-    ref = fileio.read_reference_file(REF_H5)
+    ref = fileio.read_reference_file(ref_h5)
     for n in fileio.REFERENCE_FIELDS:
         assert np.array_equal(ref[n], gold[n]), n
-    with fileio.H5File(REF_H5) as f:
+    with fileio.H5File(ref_h5) as f:
         assert f.scalar("KLON", np.int32) == 100 and f.scalar("KLEV", np.int32) == 137
 
 

@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests.util import ROOT
@@ -37,8 +38,32 @@ def test_one_gpu_line_carries_both_byte_conventions():
     assert 0.2 < rf["frac"] < 1.0 and d["ms_per_step"] >= rf["kernel_ms_avg"] * 0.999
 
 
+def test_plain_line_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line carries the headline alone; --dump-outputs writes the last step's arrays on a fixed column sample,
+    the same from run to run."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = _bench(["--steps", 7, "--warmup", 2, "--ngptot", 20000, "--kernel", "tl", "--dump-outputs", d])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 7 and line["ms_per_step"] > 0 and abs(line["value"] - 20000 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+        for key in ("companion_kernels", "cpu_baseline", "nproma_sweep", "target_config", "self_tests", "baseline_configs_2_3"):
+            assert key not in line, key
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert {"B_LOC.npy", "PA.npy", "PFPLSL.npy", "pert_out_tent.npy", "pert_in_t.npy"} <= set(a) and set(a) == set(b)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["PA.npy"].shape == (1024, 137) and a["PFPLSL.npy"].shape == (1024, 138) and a["B_LOC.npy"].shape == (1024, 8, 137)
+    for n in a:
+        assert a[n].dtype == np.float64 and np.array_equal(a[n], b[n]), n
+    assert np.any(a["pert_out_tent.npy"] != 0.0) and np.all(np.isfinite(a["PA.npy"]))
+
+
 def test_two_ranks_on_one_gpu_rehearse_the_multi_gpu_path(tmp_path):
-    r = _bench(["--gpus", 2, "--steps", 10, "--warmup", 2, "--ngptot", 16384, "--budget-s", 300],
+    r = _bench(["--gpus", 2, "--steps", 10, "--warmup", 2, "--ngptot", 16384, "--budget-s", 300, "--full"],
                env={"CLOUDSC2_DIST_BACKEND": "gloo", "CLOUDSC2_BENCH_LOGDIR": str(tmp_path)})
     assert r.returncode == 0, r.stderr[-3000:] + open(tmp_path / "bench_rank0.err").read()[-3000:]
     relayed = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -77,7 +102,7 @@ def test_two_ranks_on_one_gpu_rehearse_the_multi_gpu_path(tmp_path):
 def test_the_default_line_carries_the_nproma_sweep_and_the_adjoints_floor():
     """BASELINE.json configs[1] names an NPROMA sweep 32-256: the driver-run line carries NL at all four blockings (children with their
     own placed state), and the AD companion carries the design floor next to the algorithmic fraction."""
-    r = _bench(["--steps", 50, "--warmup", 3, "--no-cpu-baseline"], timeout=900)
+    r = _bench(["--steps", 50, "--warmup", 3, "--no-cpu-baseline", "--full"], timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     sw = d["nproma_sweep"]

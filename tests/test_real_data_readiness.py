@@ -5,79 +5,32 @@
 edited: the loaders of this build (csrc/cloudsc2_io.cpp `kScalars`, fileio.py, fortran/cloudsc2_hip_state_mod.F90) ask the file
 for exactly the dataset names -- and shapes -- the reference's own loader asks for, restricted to what the hot path reads.
 
-The expectation is EXTRACTED from the reference's sources as text (study, not execution; nothing is copied into the repo):
+The expectation is EXTRACTED from the reference's sources as text (study, not execution; only dataset names and shapes are kept,
+in tests/golden/reference_loaders.json, written by tests/golden/extract_reference_loaders.py):
   * every `LOAD_SCALAR('<dataset>', <variable>)` of yomcst.F90 / yoethf.F90 / yoecldp.F90 / yoephli.F90,
   * of those, the ones whose variable is READ by the hot path: the executable statements of satur / cuadjtqs / cloudsc2 /
     cuadjtqstl / cloudsc2tl / cuadjtqsad / cloudsc2ad plus the statement functions of fcttre*.func.h they reach (transitively),
   * every `LOAD_AND_EXPAND('<dataset>', ...)` of CLOUDSC2_ARRAY_STATE_LOAD (cloudsc2_array_state_mod.F90:164-199) and the four
     dataset suffixes of LOAD_AND_EXPAND_STATE (expand_mod.F90:151-154), with the level count each is read with.
-CPU-only; skipped where /root/reference does not exist (the GPU box)."""
+CPU-only."""
 from __future__ import annotations
 
+import json
 import os
 import re
 
-import pytest
-
 from tests.util import ROOT
 
-REF = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is not on this box")
-
-KERNELS = (("cloudsc2_nl", ("satur", "cuadjtqs", "cloudsc2")), ("cloudsc2_tl", ("cuadjtqstl", "cloudsc2tl", "cloudsc2")),
-           ("cloudsc2_ad", ("cuadjtqsad", "cloudsc2ad")))
-
-
-def _code(text: str) -> str:
-    """Executable text: comments, preprocessor lines and USE statements dropped, continuation lines joined, upper case."""
-    lines = []
-    for ln in text.splitlines():
-        if ln.lstrip().startswith(("!", "#")):
-            continue
-        lines.append(ln.split("!")[0])
-    joined = re.sub(r"&\s*\n\s*&?", " ", "\n".join(lines)).upper()
-    return "\n".join(ln for ln in joined.splitlines() if not re.match(r"\s*USE\b", ln))
-
-
-def _loaded_scalars() -> dict:
-    """dataset name -> Fortran variable, for the four *_LOAD_PARAMETERS routines."""
-    out = {}
-    for mod in ("yomcst", "yoethf", "yoecldp", "yoephli"):
-        for ln in open(f"{REF}/common/module/{mod}.F90"):
-            m = re.search(r"LOAD_SCALAR\('(\w+)',\s*([\w%]+)\)", ln)
-            if m:
-                out[m.group(1)] = m.group(2).upper()
-    return out
-
-
-def _hot_path_text() -> str:
-    body = "\n".join(_code(open(f"{REF}/{d}/{f}.F90").read()) for d, fs in KERNELS for f in fs)
-    funcs = {}  # statement functions of the include files: name -> right-hand side
-    for h in ("fcttre", "fcttretl", "fcttread", "fccld"):
-        for ln in _code(open(f"{REF}/common/include/{h}.func.h").read()).splitlines():
-            m = re.match(r"\s*(\w+)\s*\(([^)]*)\)\s*=\s*(.*)$", ln)
-            if m and not re.match(r"\s*REAL", ln):
-                funcs[m.group(1)] = m.group(3)
-    used, todo = set(), [f for f in funcs if re.search(rf"\b{f}\s*\(", body)]
-    while todo:
-        f = todo.pop()
-        if f in used:
-            continue
-        used.add(f)
-        todo += [g for g in funcs if g not in used and re.search(rf"\b{g}\s*\(", funcs[f])]
-    assert {"FOEALFA", "FOEEWM"} <= used  # the saturation formulas (fcttre.func.h:74,...)
-    return body + "\n" + "\n".join(funcs[f] for f in used)
+LOADERS = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_loaders.json")))
 
 
 def test_the_scalar_datasets_asked_for_are_exactly_what_the_hot_path_reads():
-    loaded = _loaded_scalars()
+    loaded = LOADERS["loaded_scalars"]
     assert len(loaded) > 150 and loaded["RG"] == "RG" and loaded["YRECLDP_RCLCRIT"] == "YRECLDP%RCLCRIT"
-    text = _hot_path_text()
-    need = {n for n, v in loaded.items() if re.search(r"(?<![\w%])" + re.escape(v) + r"\b", text)}
+    need = set(LOADERS["hot_path_scalars"])
     # YREPHLI%LPHYLIN is loaded and then overwritten by every main before the first kernel call (dwarf_cloudsc.F90:106-107 of
     # cloudsc2_nl / _tl / _ad: "overload LPHYLIN"): a flag of cloudsc2_params (lphylin, default 1), not a dataset this build reads
-    for d in ("cloudsc2_nl", "cloudsc2_tl", "cloudsc2_ad"):
-        assert re.search(r"^\s*YREPHLI%LPHYLIN\s*=\s*\.true\.", open(f"{REF}/{d}/dwarf_cloudsc.F90").read(), flags=re.M | re.I)
+    assert LOADERS["lphylin_overloaded_by_every_main"]
     need.discard("YREPHLI_LPHYLIN")
     io = open(os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", "cloudsc2_io.cpp")).read()
     asked = re.findall(r'\{"(\w+)",\s*&cloudsc2_params::(\w+)\}', io)
@@ -92,21 +45,8 @@ def test_the_scalar_datasets_asked_for_are_exactly_what_the_hot_path_reads():
         assert f'"{ds}"' in io, ds
 
 
-def _reference_fields() -> dict:
-    """dataset name -> ('KLEV' | 'KLEV+1', ndim) as CLOUDSC2_ARRAY_STATE_LOAD reads them."""
-    src = open(f"{REF}/common/module/cloudsc2_array_state_mod.F90").read()
-    out = {}
-    for m in re.finditer(r"CALL LOAD_AND_EXPAND\('(\w+)',\s*SELF%\w+,\s*KLON,\s*SELF%(KLEV(?:\+1)?),\s*(NCLV,)?", src):
-        out[m.group(1)] = (m.group(2), 5 if m.group(3) else 1)
-    m = re.search(r"CALL LOAD_AND_EXPAND_STATE\('(\w+)'", src)
-    ex = open(f"{REF}/common/module/expand_mod.F90").read()
-    for sfx, nd in re.findall(r"load_array\(name//'(_\w+)',\s*start,\s*end,\s*size,\s*nlon,\s*nlev,\s*(ndim,)?", ex):
-        out[m.group(1) + sfx] = ("KLEV", 5 if nd else 1)
-    return out
-
-
 def test_the_field_datasets_asked_for_are_the_reference_loaders():
-    want = _reference_fields()
+    want = {n: tuple(v) for n, v in LOADERS["field_datasets"].items()}
     assert set(want) == {"PT", "PQ", "PAP", "PAPH", "PLU", "PLUDE", "PMFU", "PMFD", "PA", "PCLV", "PSUPSAT", "TENDENCY_CML_T",
                          "TENDENCY_CML_A", "TENDENCY_CML_Q", "TENDENCY_CML_CLD"}, sorted(want)
     assert want["PAPH"] == ("KLEV+1", 1) and want["PCLV"] == ("KLEV", 5) and want["TENDENCY_CML_CLD"] == ("KLEV", 5)
@@ -133,8 +73,7 @@ def test_the_field_datasets_asked_for_are_the_reference_loaders():
 def test_the_reference_file_datasets_compared_are_the_validators():
     """VALIDATE (cloudsc2_array_state_mod.F90:246-256) compares these ten datasets of reference.h5; WRITE_REFERENCE (:275-284)
     writes them.  The checkout's reference.h5 holds them with the shapes this build reads (tests/test_fileio.py reads the file)."""
-    src = open(f"{REF}/common/module/cloudsc2_array_state_mod.F90").read()
-    written = set(re.findall(r"CALL WRITE_ARRAY\('(\w+)'", src))
+    written = set(LOADERS["reference_file_datasets"])
     from dwarf_p_cloudsc2_tl_ad_amd import fileio
 
     assert written == set(fileio.REFERENCE_FIELDS), sorted(written ^ set(fileio.REFERENCE_FIELDS))

@@ -30,7 +30,8 @@ def _build(single: bool) -> str:
     src = os.path.join(HOSTCHECK_DIR, "hostcheck.hip")
     deps = [src] + [os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
     if (not os.path.exists(lib)) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call([HIPCC, "--cuda-host-only", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address",
+        # host code only: --cuda-host-only builds no device code, and -fno-gpu-sanitize keeps the sanitizer off the device side
+        subprocess.check_call([HIPCC, "--cuda-host-only", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address", "-fno-gpu-sanitize",
                                "-shared-libasan", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"] +
                               (["-DCLOUDSC2_SINGLE"] if single else []) + ["-o", lib, src])
     return lib
@@ -43,7 +44,9 @@ def test_column_sweeps_under_address_sanitizer(single):
         pytest.skip("no AddressSanitizer runtime in this toolchain")
     if single and not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libcloudsc2_ref_sp.so")):
         pytest.skip("oracle/_ref/libcloudsc2_ref_sp.so not built")
-    env = dict(os.environ, CLOUDSC2_HOSTCHECK_LIB=_build(single), LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0",
+    # the sanitizer runtime must come first; whatever the environment already preloads stays behind it
+    preload = ":".join(p for p in (rt, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, CLOUDSC2_HOSTCHECK_LIB=_build(single), LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0",
                CLOUDSC2_PRECISION="single" if single else "double")
     cmd = ([sys.executable, os.path.join(ROOT, "tests", "single_checks.py"), "host"] if single else
            [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hostcheck.py"), "-x", "-q", "-p", "no:cacheprovider"])

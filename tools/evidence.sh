@@ -14,7 +14,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smok
 rocm-smi --showproductname --showclocks --showpower --showperflevel --showmemvendor > $out/rocm_smi_idle.txt 2>&1
 (for i in 1 2 3 4 5 6 7 8; do sleep 2; rocm-smi --showclocks --showpower --showtemp 2>/dev/null | grep -E "sclk|mclk|fclk|Power|Temperature" | tr '\n' ';'; echo; done > $out/rocm_smi_during_bench.txt) &
 smi_pid=$!
-timeout -k 10 600 python bench.py > $out/bench_default.json 2> $out/bench_default.err && cut -c1-600 $out/bench_default.json || exit 1
+timeout -k 10 600 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err && cut -c1-600 $out/bench_default.json || exit 1
 wait $smi_pid
 # rocprofv3 --stats of the same bench command (no child processes under the profiler); the library's placement probes show up as
 # place_probe_kernel, the hot kernel's average must agree with the HIP-event figure of the JSON line

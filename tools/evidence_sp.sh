@@ -4,7 +4,7 @@
 tag=${1:-evsp}; out=gpurun_out/$tag; mkdir -p $out
 export CLOUDSC2_PRECISION=single
 timeout -k 10 300 python tests/single_checks.py gpu > $out/single_checks_gpu.log 2>&1 && tail -1 $out/single_checks_gpu.log || { tail -5 $out/single_checks_gpu.log; exit 1; }
-timeout -k 10 600 python bench.py > $out/bench_default.json 2> $out/bench_default.err && cat $out/bench_default.json || exit 1
+timeout -k 10 600 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err && cat $out/bench_default.json || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --no-cpu-baseline --no-companions > $out/bench_prof.json 2> $out/bench_prof.err || exit 1
 python tools/trace_timed_region.py $out/prof/*/*_kernel_trace.csv nl_kernel 1000 > $out/bench_prof_timed_region.json
 for n in 160000 1048576; do
