@@ -378,6 +378,10 @@ enum : unsigned {
                      // (cloudsc_driver_ad_mod.F90:240-264) instead of re-reading the 32 planes afterwards
   C2F_OFF32 = 32u,   // every buffer of the launch < 4 GiB: 32-bit byte offsets (LaneOff32)
   C2F_NOLIN = 64u,   // NL only: .NOT.(LPHYLIN .OR. LDRAIN1D), the FOEALFA / FOEEWM form of stage A (cloudsc2.F90:365-369)
+  C2F_VJP = 64u,     // AD reverse sweep, assign form only (never with ADNORM): the vector-Jacobian product of the NL sweep
+                     // (cloudsc2_vjp_launch): the output adjoints are only read (not zeroed) and the PSUPSAT adjoint is the true
+                     // derivative zqp1 instead of the reference's PTSPHY*zqp1 (cloudsc2ad.F90:1733 vs cloudsc2tl.F90:345).
+                     // It shares its bit with NOLIN: the fused ad_kernel, which hands its flags on to nl_column, never takes it.
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1008,7 +1012,9 @@ template <unsigned F>
 C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| of the column with C2F_ADNORM (+inf for NaN), else 0
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0;
   constexpr bool OFF32 = (F & C2F_OFF32) != 0, ASSIGN = (F & C2F_ASSIGN) != 0, ADNORM = (F & C2F_ADNORM) != 0;
+  constexpr bool VJP = (F & C2F_VJP) != 0;
   static_assert(!ADNORM || ASSIGN, "the fused norms are those of the adjoint test: assign form");
+  static_assert(!VJP || (ASSIGN && !ADNORM), "the vector-Jacobian product assigns its input adjoints and forms no norms");
   typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
   LaneOff o, oa64; bool active;
   if (!lane_setup(&a->nl.g, &a->nl.s, gcol, o, active)) return 0.0;
@@ -1085,7 +1091,9 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     stg(px.gq, oa.cml + d, xo.gq + ax.gq);
     stg(px.gl, oa.cml + d, xo.gl + ax.gl);
     stg(px.gi, oa.cml + d, xo.gi + ax.gi);
-    stg(px.supsat, oa.full + d, ax.supsat);
+    // VJP: d(zqp1)/d(PSUPSAT) = 1 (cloudsc2tl.F90:345), so the PSUPSAT adjoint is zqp1's own (ax.q); ax.supsat = PTSPHY*zqp1 is the
+    // reference's CLOUDSC2AD, which the other forms reproduce
+    stg(px.supsat, oa.full + d, VJP ? ax.q : ax.supsat);
     if (!last) stg(px.lu, oa.full + d1, xo.lu_k1 + ax.lu_k1);
     surf_acc += ax.paph_surf;
     if (last) {
@@ -1103,22 +1111,23 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     }
     paph_pending = ax.paph_k;
 
-    // output adjoints are consumed (cloudsc2ad.F90:917-919,955-966,1173,1572)
-    stg(pa.tent, oa.loc + d, RC(0.0));
-    stg(pa.tenq, oa.loc + d, RC(0.0));
-    stg(pa.tenl, oa.loc + d, RC(0.0));
-    stg(pa.teni, oa.loc + d, RC(0.0));
-    stg(pa.clc, oa.full + d, RC(0.0));
-    stg(pa.covptot, oa.full + d, RC(0.0));
-    stg(pa.fplsl, oa.half + d1, RC(0.0));
-    stg(pa.fplsn, oa.half + d1, RC(0.0));
-    stg(pa.fhpsl, oa.half + d1, RC(0.0));
-    stg(pa.fhpsn, oa.half + d1, RC(0.0));
+    // output adjoints are consumed (cloudsc2ad.F90:917-919,955-966,1173,1572); VJP: they are the caller's, read only
+    if constexpr (!VJP) {
+      stg(pa.tent, oa.loc + d, RC(0.0));
+      stg(pa.tenq, oa.loc + d, RC(0.0));
+      stg(pa.tenl, oa.loc + d, RC(0.0));
+      stg(pa.teni, oa.loc + d, RC(0.0));
+      stg(pa.clc, oa.full + d, RC(0.0));
+      stg(pa.covptot, oa.full + d, RC(0.0));
+      stg(pa.fplsl, oa.half + d1, RC(0.0));
+      stg(pa.fplsn, oa.half + d1, RC(0.0));
+      stg(pa.fhpsl, oa.half + d1, RC(0.0));
+      stg(pa.fhpsn, oa.half + d1, RC(0.0));
+    }
 
     paph_k1 = L.paph_k;
   }
   InPtrsRWP ain = &a->ain;
-  OutPtrsP aout = &a->aout;
   if (ASSIGN) {
     ain->paph[oa64.half] = paph_pending;
     ain->paph[oa64.half + (long long)nlev * nproma] = surf_acc;
@@ -1128,10 +1137,13 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     ain->paph[oa64.half + (long long)nlev * nproma] += surf_acc;
   }
   // the adjoint of the (constant zero) top fluxes is discarded (cloudsc2ad.F90:1678-1679,917-919)
-  aout->fplsl[oa64.half] = RC(0.0);
-  aout->fplsn[oa64.half] = RC(0.0);
-  aout->fhpsl[oa64.half] = RC(0.0);
-  aout->fhpsn[oa64.half] = RC(0.0);
+  if constexpr (!VJP) {
+    OutPtrsP aout = &a->aout;
+    aout->fplsl[oa64.half] = RC(0.0);
+    aout->fplsn[oa64.half] = RC(0.0);
+    aout->fhpsl[oa64.half] = RC(0.0);
+    aout->fhpsn[oa64.half] = RC(0.0);
+  }
   if (ADNORM) {
     // the two half levels the loop does not store: PAPHP1(1) (paph_k1 now holds the trajectory's value there) and PAPHP1(KLEV+1)
     n2 += ((double)paph_k1 * 0.01) * paph_pending + ((double)paph_bottom * 0.01) * surf_acc;

@@ -734,6 +734,7 @@ std::vector<int> paced_kernel_occupancies() {
     add((const void*)ad_variant(f));
     add((const void*)ad_reverse_variant(f));
   }
+  for (unsigned f = 64; f < 128; ++f) add((const void*)ad_reverse_variant(f));  // the vector-Jacobian forms (C2F_VJP)
   return out;
 }
 
@@ -1170,7 +1171,8 @@ int cloudsc2_tl_launch_self(const cloudsc2_params* prm, double ptsphy, int nprom
 static int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
                           const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
                           const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out, cloudsc2_real* scratch,
-                          void* stream, bool assign, int which = 0, double* norms = nullptr, double* gmax = nullptr) {
+                          void* stream, bool assign, int which = 0, double* norms = nullptr, double* gmax = nullptr,
+                          bool vjp = false) {
   Geom g;
   int rc = check_geom(prm, nproma, nlev, ngptot, g);
   if (rc) return rc;
@@ -1204,6 +1206,10 @@ static int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
   if (precise_of(prm)) f |= C2F_PRECISE;
   if (args.nl.c.evap) f |= C2F_EVAP;
   if (assign) f |= C2F_ASSIGN;
+  if (vjp) {  // the vector-Jacobian product: reverse sweep alone, assign form, adj_out read only, true PSUPSAT adjoint
+    if (which != 2 || !assign || norms) return fail(CLOUDSC2_EINVAL, "vector-Jacobian product: reverse sweep alone, assign form, no norms");
+    f |= C2F_VJP;
+  }
   if (norms) {  // the adjoint test's norm2 / norm3 formed in the reverse sweep
     if (which != 2 || !assign || args.nl.c.evap || !gmax) return fail(CLOUDSC2_EINVAL, "fused adjoint norms: reverse sweep alone, assign form, no evaporation branch");
     f |= C2F_ADNORM;
@@ -1252,6 +1258,14 @@ int cloudsc2_ad_launch_reverse(const cloudsc2_params* prm, double ptsphy, int np
                                int assign, void* stream) {
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
                         stream, assign != 0, 2);
+}
+
+int cloudsc2_vjp_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                        const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                        const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                        const cloudsc2_real* scratch, void* stream) {
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
+                        stream, true, 2, nullptr, nullptr, true);
 }
 
 int cloudsc2_ad_launch_reverse_norms(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,

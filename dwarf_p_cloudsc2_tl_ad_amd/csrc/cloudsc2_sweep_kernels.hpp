@@ -1,6 +1,6 @@
 // cloudsc2_sweep_kernels.hpp -- the __global__ wrappers of the column sweeps (NL, TL, AD, the Taylor test's lambda sweep), their
 // compile-time variant tables and what they share.  The library is built from five translation units so that an edit to one sweep
-// does not rebuild every variant table (384 slots, ~65 s as one unit): cloudsc2_kernels.hip (host code, launchers, the data-format
+// does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kernels.hip (host code, launchers, the data-format
 // and norm kernels) and one unit per kernel family -- cloudsc2_kern_{nl,tl,ad,taylor}.hip --, each of which instantiates its table and
 // exports it through one accessor (nl_variant(F) ...).  -DC2_SINGLE_TU compiles everything as ONE unit again (cloudsc2_kernels.hip
 // then includes the family files): the experiment builds of `make variant`, `make asm`, `make resources` and the -DC2_WAVE_TIMES
@@ -129,6 +129,7 @@ __global__ void C2_BOUNDS(C2_AD_WAVES) ad_reverse_kernel(AdArgs args) {
 }
 template <unsigned F>
 __global__ void C2_BOUNDS(C2_AD_WAVES) ad_kernel(AdArgs args) {
+  static_assert(!(F & C2F_VJP), "C2F_VJP is C2F_NOLIN to nl_column: the fused kernel has no vector-Jacobian form");
   C2_KERNEL_BODY(C2_WAVE_LOG_BEGIN);
   C2_KERNEL_BODY((nl_column<(F & ~C2F_ASSIGN) | C2F_CKPT>(global_column(), &kernarg<AdArgs>()->nl)));
   C2_KERNEL_BODY((ad_reverse_column<F>(global_column(), kernarg<AdArgs>())));

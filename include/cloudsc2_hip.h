@@ -275,6 +275,24 @@ int cloudsc2_ad_launch_reverse(const cloudsc2_params* prm, double ptsphy, int np
                                const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                                const cloudsc2_real* scratch, int assign, void* stream);
 
+/* The vector-Jacobian product of the NL sweep, for reverse-mode differentiation (the package's autograd op): the reverse sweep of
+ * cloudsc2_ad_launch_reverse in the assign form, adj_in = J^T adj_out, with two differences:
+ *   - adj_out is READ ONLY: the output adjoints are not zeroed (cloudsc2_ad_launch* consume them), so a caller's gradients stay
+ *     as they are and need no copy;
+ *   - the PSUPSAT adjoint is the true derivative zqp1, not PTSPHY*zqp1.  The reference's TL forms
+ *     ZQP1 = PQM1 + PTSPHY*PGTENQ + PSUPSAT (cloudsc2tl.F90:345: coefficient 1), its AD assigns PSUPSAT = PTSPHY*ZQP1
+ *     (cloudsc2ad.F90:1733); its adjoint test never sees this, its PSUPSAT increment being 0 (cloudsc_driver_ad_mod.F90:139).
+ *     Every other input adjoint equals cloudsc2_ad_launch_assign's bit for bit, and fl(PTSPHY * adj_in->supsat) equals its PSUPSAT.
+ * traj_out->fplsl / fplsn (PFPLSL5, PFPLSN5) are read, the other traj_out fields may be NULL.  `scratch` holds the cover checkpoints
+ * cloudsc2_ad_launch_forward wrote; it is read with LEVAPLS2 .OR. LDRAIN1D only (otherwise it may be NULL).  Padded tail columns of the
+ * last block are not written.  Strides, pacing and first-use behaviour are those of the other launchers: it takes one block stride
+ * per layout group, and apart from the CETA table every launcher uploads on a grid's first use (see cloudsc2_nl_launch) it neither
+ * allocates nor synchronises. */
+int cloudsc2_vjp_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                        const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                        const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                        const cloudsc2_real* scratch, void* stream);
+
 /* The AD leg of the adjoint test with its norms formed in the sweep (cloudsc_driver_ad_mod.F90:198-267): the reverse sweep alone
  * in the assign form (zeroed input adjoints + CLOUDSC2AD), and for every active column norm2 = <x0, x_adj> with x0 = 0.01 * the
  * trajectory inputs (ZSUPSAT0 = 0, :139,240-256) and norm3 = |norm1 - norm2| / EPSILON(1._8) [/ norm2] (:258-264), taken while

@@ -1,0 +1,291 @@
+"""The differentiable op (dwarf_p_cloudsc2_tl_ad_amd.autograd) on the MI355X: its forward is the NL sweep, its backward the
+vector-Jacobian product (cloudsc2_vjp_launch), its jvp the TL sweep -- bit for bit against the C-ABI launchers, through
+torch.autograd, torch.autograd.forward_ad and torch.func, composed with other torch ops and captured in a graph."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests.util import B, c2
+from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+
+
+def make_inputs(tab, nproma, ngptot, prm):
+    st = c2.state_from_table(tab, nproma, ngptot)
+    src = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "t": st.PT, "l": st.PCLV[:, 0], "i": st.PCLV[:, 1], "lude": st.PLUDE,
+           "lu": st.PLU, "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, 0], "gtenq": st.B_CML[:, 2], "gtenl": st.B_CML[:, 3],
+           "gteni": st.B_CML[:, 4], "supsat": st.PSUPSAT}
+    x = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in src.items()}
+    x["qsat"] = ag.satur(x["pap"], x["t"], prm, ngptot)
+    return {n: x[n] for n in B.IN_NAMES}, float(st.ptsphy), ag.Layout(st.nblocks, st.nlev, nproma, ngptot)
+
+
+def stream():
+    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
+
+
+def new(names, lay, fill=0.0):
+    return {n: torch.full(lay.shape(n), fill, dtype=B.torch_real(), device=DEV) for n in names}
+
+
+def nl_launch(x, prm, ptsphy, lay):
+    out = new(B.OUT_NAMES, lay)
+    B.check(B.lib.cloudsc2_nl_launch(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
+                                     C.byref(ag._block("out", out, lay)), B.Field(), 0.0, stream()))
+    return out
+
+
+def ad_assign_launch(x, u, prm, ptsphy, lay):
+    traj, xa = new(B.OUT_NAMES, lay), new(B.IN_NAMES, lay)
+    y = {n: u[n].clone() for n in B.OUT_NAMES}
+    scratch = torch.zeros((lay.nblocks, lay.nlev, lay.nproma), dtype=B.torch_real(), device=DEV)
+    B.check(B.lib.cloudsc2_ad_launch_assign(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
+                                            C.byref(ag._block("out", traj, lay)), C.byref(ag._block("in", xa, lay)),
+                                            C.byref(ag._block("out", y, lay)), C.c_void_p(scratch.data_ptr()), stream()))
+    return xa
+
+
+def tl_launch(x, dx, prm, ptsphy, lay):
+    dy = new(B.OUT_NAMES, lay)
+    B.check(B.lib.cloudsc2_tl_launch(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
+                                     C.byref(B.Outputs()), C.byref(ag._block("in", dx, lay)), C.byref(ag._block("out", dy, lay)),
+                                     stream()))
+    return dy
+
+
+def seeded(names, lay, seed, scale=1.0):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    out = {}
+    for n in names:
+        t = torch.randn(lay.shape(n), generator=g, dtype=B.torch_real(), device=DEV) * scale
+        if lay.tail < lay.nproma:
+            t[-1, :, lay.tail:] = 0
+        out[n] = t
+    return out
+
+
+def same_bits(a, b):
+    return torch.equal(a.view(torch.int64 if a.dtype == torch.float64 else torch.int32),
+                       b.view(torch.int64 if b.dtype == torch.float64 else torch.int32))
+
+
+def tail_zero(t, lay):
+    return lay.tail == lay.nproma or bool(torch.all(t[-1, :, lay.tail:] == 0))
+
+
+def params(tab, math_mode=0, **flags):
+    prm = c2.default_params(c2.ceta_from_table(tab), **flags)
+    prm.math_mode = math_mode
+    return prm
+
+
+@pytest.mark.parametrize("nproma,ngptot", [(32, 100), (128, 16384), (4096, 4096)])
+def test_forward_is_the_nl_sweep(nproma, ngptot):
+    tab = c2.synthetic_table()
+    prm = params(tab)
+    x, ptsphy, lay = make_inputs(tab, nproma, ngptot, prm)
+    out = ag.cloudsc2(x, prm, ptsphy, ngptot)
+    want = nl_launch(x, prm, ptsphy, lay)
+    torch.cuda.synchronize()
+    assert isinstance(out, ag.Cloudsc2Outputs) and out._fields == B.OUT_NAMES
+    for n in B.OUT_NAMES:
+        assert same_bits(getattr(out, n), want[n]), n
+        assert tail_zero(getattr(out, n), lay), n
+
+
+@pytest.mark.parametrize("math_mode", [1, 2])
+@pytest.mark.parametrize("flags", [dict(), dict(levapls2=True), dict(ldrain1d=True), dict(lregcl=True)])
+def test_backward_is_the_assign_form_with_the_true_supsat_adjoint(math_mode, flags):
+    tab = c2.random_table(137, 100, seed=5)  # nonzero PSUPSAT
+    prm = params(tab, math_mode, **flags)
+    x, ptsphy, lay = make_inputs(tab, 32, 100, prm)
+    xs = {n: t.clone().requires_grad_() for n, t in x.items()}
+    out = ag.cloudsc2(xs, prm, ptsphy, lay.ngptot)
+    u = seeded(B.OUT_NAMES, lay, seed=1)
+    u0 = {n: t.clone() for n, t in u.items()}
+    grads = torch.autograd.grad([getattr(out, n) for n in B.OUT_NAMES], [xs[n] for n in B.IN_NAMES], [u[n] for n in B.OUT_NAMES])
+    g = dict(zip(B.IN_NAMES, grads))
+    want = ad_assign_launch(x, u, prm, ptsphy, lay)
+    torch.cuda.synchronize()
+    for n in B.OUT_NAMES:
+        assert same_bits(u[n], u0[n]), ("grad_outputs changed", n)
+    for n in B.IN_NAMES:
+        assert tail_zero(g[n], lay), n
+        a, v = want[n][..., :], g[n]
+        if n == "supsat":
+            assert same_bits(ptsphy * v, a), "fl(PTSPHY * supsat gradient) != CLOUDSC2AD's PSUPSAT adjoint"
+            assert torch.any(v != 0)
+        else:
+            assert same_bits(v, a), n
+
+
+def test_vjp_launch_writes_every_active_element():
+    tab = c2.random_table(137, 100, seed=6)
+    prm = params(tab, levapls2=True)
+    x, ptsphy, lay = make_inputs(tab, 32, 100, prm)
+    traj = new(B.OUT_NAMES, lay)
+    scratch = torch.zeros((lay.nblocks, lay.nlev, lay.nproma), dtype=B.torch_real(), device=DEV)
+    B.check(B.lib.cloudsc2_ad_launch_forward(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
+                                             C.byref(ag._block("out", traj, lay)), C.c_void_p(scratch.data_ptr()), stream()))
+    xa = new(B.IN_NAMES, lay, fill=float("nan"))
+    y = seeded(B.OUT_NAMES, lay, seed=2)
+    y0 = {n: t.clone() for n, t in y.items()}
+    B.check(B.lib.cloudsc2_vjp_launch(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
+                                      C.byref(ag._block("out", {"fplsl": traj["fplsl"], "fplsn": traj["fplsn"]}, lay)),
+                                      C.byref(ag._block("in", xa, lay)), C.byref(ag._block("out", y, lay)),
+                                      C.c_void_p(scratch.data_ptr()), stream()))
+    torch.cuda.synchronize()
+    for n in B.IN_NAMES:
+        assert bool(torch.all(torch.isfinite(xa[n][:-1]))) and bool(torch.all(torch.isfinite(xa[n][-1, :, :lay.tail]))), n
+        assert bool(torch.all(torch.isnan(xa[n][-1, :, lay.tail:]))), ("tail written", n)
+    for n in B.OUT_NAMES:
+        assert same_bits(y[n], y0[n]), n
+
+
+def test_jvp_is_the_tl_sweep():
+    tab = c2.random_table(137, 100, seed=7)
+    prm = params(tab, lregcl=True)
+    x, ptsphy, lay = make_inputs(tab, 64, 1000, prm)
+    dx = {n: 0.01 * t for n, t in x.items()}
+    dx["supsat"] = 1e-3 * x["q"]
+    keys = list(B.IN_NAMES)
+
+    def f(*xs):
+        return tuple(ag.cloudsc2(dict(zip(keys, xs)), prm, ptsphy, lay.ngptot))
+
+    prim, tan = torch.func.jvp(f, tuple(x[n] for n in keys), tuple(dx[n] for n in keys))
+    import torch.autograd.forward_ad as fwAD
+
+    with fwAD.dual_level():
+        out = ag.cloudsc2({n: fwAD.make_dual(x[n], dx[n]) for n in keys}, prm, ptsphy, lay.ngptot)
+        tan2 = [fwAD.unpack_dual(getattr(out, n)).tangent for n in B.OUT_NAMES]
+    want = tl_launch(x, dx, prm, ptsphy, lay)
+    nl = nl_launch(x, prm, ptsphy, lay)
+    torch.cuda.synchronize()
+    for k, n in enumerate(B.OUT_NAMES):
+        assert same_bits(tan[k], want[n]), ("torch.func.jvp", n)
+        assert same_bits(tan2[k], want[n]), ("forward_ad", n)
+        assert same_bits(prim[k], nl[n]), ("primal", n)
+        assert tail_zero(tan[k], lay), n
+    # tangents given for some inputs only: the others are zero
+    _, tan3 = torch.func.jvp(lambda t, q: f(*[t if n == "t" else q if n == "q" else x[n] for n in keys]), (x["t"], x["q"]),
+                             (dx["t"], dx["q"]))
+    dx0 = {n: (dx[n] if n in ("t", "q") else torch.zeros_like(x[n])) for n in keys}
+    want3 = tl_launch(x, dx0, prm, ptsphy, lay)
+    torch.cuda.synchronize()
+    for k, n in enumerate(B.OUT_NAMES):
+        assert same_bits(tan3[k], want3[n]), ("partial tangents", n)
+
+
+@pytest.mark.parametrize("table,supsat_tangent", [("synthetic", False), ("synthetic", True), ("random", False)])
+def test_adjoint_identity_through_the_torch_apis(table, supsat_tangent):
+    tab = c2.synthetic_table() if table == "synthetic" else c2.random_table(137, 100, seed=8)
+    prm = params(tab, lregcl=True)
+    x, ptsphy, lay = make_inputs(tab, 128, 4000, prm)
+    keys = list(B.IN_NAMES)
+    v = {n: 0.01 * t for n, t in x.items()}  # the reference's direction (cloudsc_driver_ad_mod.F90:124-139) ...
+    if supsat_tangent:
+        v["supsat"] = 1e-3 * x["q"]  # ... and a PSUPSAT direction, which the synthetic state's zero PSUPSAT does not give
+    if table == "random":
+        assert torch.any(v["supsat"] != 0)
+
+    def f(*xs):
+        return tuple(ag.cloudsc2(dict(zip(keys, xs)), prm, ptsphy, lay.ngptot))
+
+    _, u = torch.func.jvp(f, tuple(x[n] for n in keys), tuple(v[n] for n in keys))
+    _, pullback = torch.func.vjp(f, *(x[n] for n in keys))
+    xa = pullback(u)
+    lhs = sum(float(torch.sum(t.double() * t.double())) for t in u)
+    rhs = sum(float(torch.sum(v[n].double() * a.double())) for n, a in zip(keys, xa))
+    assert abs(lhs - rhs) / abs(lhs) <= 1e-12, (lhs, rhs)
+
+
+def test_composition_with_packed_views_and_upstream_ops():
+    tab = c2.random_table(137, 100, seed=9)
+    prm = params(tab)
+    x, ptsphy, lay = make_inputs(tab, 32, 1000, prm)
+    nb, nlev, nproma = lay.nblocks, lay.nlev, lay.nproma
+    # the four PGTEN* planes of one packed leaf (their block stride is usable as it is) and q / lude as planes of another (a
+    # full-level block stride the op copies away); t comes out of an upstream op
+    cml = torch.stack([x["gtent"], x["gtenq"], x["gtenl"], x["gteni"]], dim=1).requires_grad_()
+    fl = torch.stack([x["q"], x["lude"]], dim=1).requires_grad_()
+    t0 = (x["t"] - 1.0).requires_grad_()
+    xs = dict(x)
+    xs.update(gtent=cml[:, 0], gtenq=cml[:, 1], gtenl=cml[:, 2], gteni=cml[:, 3], q=fl[:, 0], lude=fl[:, 1], t=t0 + 1.0)
+    w = seeded(B.OUT_NAMES, lay, seed=3)
+    out = ag.cloudsc2(xs, prm, ptsphy, lay.ngptot)
+    loss = sum(torch.sum(w[n] * getattr(out, n)) for n in B.OUT_NAMES)
+    g_cml, g_fl, g_t0 = torch.autograd.grad(loss, [cml, fl, t0])
+    # hand-applied chain rule on plain contiguous inputs
+    xd = {n: t.clone().requires_grad_() for n, t in x.items()}
+    xd["t"] = (t0.detach() + 1.0).requires_grad_()
+    outd = ag.cloudsc2(xd, prm, ptsphy, lay.ngptot)
+    gd = dict(zip(B.IN_NAMES, torch.autograd.grad([getattr(outd, n) for n in B.OUT_NAMES], [xd[n] for n in B.IN_NAMES],
+                                                   [w[n] for n in B.OUT_NAMES])))
+    torch.cuda.synchronize()
+    assert g_cml.shape == (nb, 4, nlev, nproma) and g_fl.shape == (nb, 2, nlev, nproma)
+    for k, n in enumerate(("gtent", "gtenq", "gtenl", "gteni")):
+        assert same_bits(g_cml[:, k], gd[n]), n
+    assert same_bits(g_fl[:, 0], gd["q"]) and same_bits(g_fl[:, 1], gd["lude"])
+    assert same_bits(g_t0, gd["t"])
+
+
+def test_partial_gradients():
+    tab = c2.random_table(137, 100, seed=10)
+    prm = params(tab, levapls2=True)
+    x, ptsphy, lay = make_inputs(tab, 32, 100, prm)
+    u = seeded(B.OUT_NAMES, lay, seed=4)
+    full = {n: t.clone().requires_grad_() for n, t in x.items()}
+    out = ag.cloudsc2(full, prm, ptsphy, lay.ngptot)
+    gfull = dict(zip(B.IN_NAMES, torch.autograd.grad(list(out), [full[n] for n in B.IN_NAMES], [u[n] for n in B.OUT_NAMES])))
+    part = dict(x)
+    part["t"] = x["t"].clone().requires_grad_()
+    part["supsat"] = x["supsat"].clone().requires_grad_()
+    out = ag.cloudsc2(part, prm, ptsphy, lay.ngptot)
+    # only some outputs feed the loss: the others' adjoints are zero
+    loss = torch.sum(u["tent"] * out.tent) + torch.sum(u["fplsl"] * out.fplsl)
+    loss.backward()
+    want = ad_assign_launch(x, {n: (u[n] if n in ("tent", "fplsl") else torch.zeros_like(u[n])) for n in B.OUT_NAMES}, prm, ptsphy, lay)
+    torch.cuda.synchronize()
+    assert same_bits(part["t"].grad, want["t"]) and same_bits(ptsphy * part["supsat"].grad, want["supsat"])
+    assert all(x[n].grad is None for n in B.IN_NAMES)
+    g_t = torch.autograd.grad(list(ag.cloudsc2(part, prm, ptsphy, lay.ngptot)), [part["t"]], [u[n] for n in B.OUT_NAMES])[0]
+    assert same_bits(g_t, gfull["t"])
+
+
+def test_graph_capture_replays_the_eager_bits():
+    tab = c2.random_table(137, 100, seed=12)
+    prm = params(tab, levapls2=True)
+    x, ptsphy, lay = make_inputs(tab, 64, 1000, prm)
+    xs = {n: t.clone().requires_grad_() for n, t in x.items()}
+    u = seeded(B.OUT_NAMES, lay, seed=5)
+
+    def step():
+        out = ag.cloudsc2(xs, prm, ptsphy, lay.ngptot)
+        grads = torch.autograd.grad(list(out), [xs[n] for n in B.IN_NAMES], [u[n] for n in B.OUT_NAMES])
+        return [t.detach() for t in out], list(grads)
+
+    eager_out, eager_g = step()  # the eager call: device probe and CETA table before the capture
+    eager_out = [t.clone() for t in eager_out]
+    eager_g = [t.clone() for t in eager_g]
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream(DEV))
+    with torch.cuda.stream(side):
+        step()
+    torch.cuda.current_stream(DEV).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        cap_out, cap_g = step()
+    for t in cap_out + cap_g:
+        t.fill_(float("nan"))
+    graph.replay()
+    torch.cuda.synchronize()
+    for a, b in zip(eager_out + eager_g, cap_out + cap_g):
+        assert same_bits(a, b)
