@@ -47,7 +47,7 @@ Cloudsc2Outputs = namedtuple("Cloudsc2Outputs", B.OUT_NAMES)
 
 HALF_IN = ("paph",)
 HALF_OUT = ("fplsl", "fplsn", "fhpsl", "fhpsn")
-# layout groups of the C ABI (resolve_in / resolve_out in csrc/cloudsc2_kernels.hip): one block stride each; the output groups
+# layout groups of the C ABI (resolve_in / resolve_out in csrc/cloudsc2_launch.hip): one block stride each; the output groups
 # "full" and "half" must have the input groups' strides, "loc" is free
 IN_GROUPS = {"full": ("pap", "q", "qsat", "t", "lude", "lu", "mfu", "mfd", "supsat"), "half": ("paph",),
              "cml": ("gtent", "gtenq", "gtenl", "gteni"), "clv": ("l", "i")}

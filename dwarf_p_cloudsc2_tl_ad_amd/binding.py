@@ -296,7 +296,7 @@ STATE_ALLOC_TORCH = os.environ.get("CLOUDSC2_STATE_ALLOC", "library").strip().lo
 
 class DeviceArena:
     """ONE placed allocation (cloudsc2_device_malloc) from which a set of arrays is carved, 256-byte aligned -- the Python
-    counterpart of the library's own Arena (csrc/cloudsc2_driver.inc).  One allocation per state means one placement scan
+    counterpart of the library's own Arena (csrc/cloudsc2_driver.hip).  One allocation per state means one placement scan
     per state, and no array wastes the tail of a chunk."""
 
     ALIGN = 256

@@ -1,4 +1,4 @@
-// cloudsc2_alloc.inc -- device memory for the state (included by cloudsc2_kernels.hip).
+// cloudsc2_alloc.hip -- device memory for the state: the placement allocator behind cloudsc2_device_malloc*.
 //
 // Why the library has its own allocator.  On MI355X, WRITE streams run 10-20 % slower into some parts of the HBM than into
 // others (profiles/r02_hbm_placement.md; tools/hbm_probe.cpp, hbm_state.cpp, hbm_alloc2.cpp, hbm_vmm*.cpp):
@@ -14,7 +14,7 @@
 //     time changes when another kernel rewrites the buffer (see device_malloc_impl) -- only hipMalloc memory can be placed.
 // Hence the remedy is placement at the scale of the buffer, done here once per allocation instead of in every caller: for a large
 // request the allocator makes several candidate hipMalloc allocations of the full size, times a sweep over each -- the caller's own
-// (the NL kernel on a state laid out in the candidate: cloudsc2_device_malloc_state, cloudsc2_driver.inc state_probe) or two
+// (the NL kernel on a state laid out in the candidate: cloudsc2_device_malloc_state, cloudsc2_driver.hip state_probe) or two
 // generic streams (the sweeps' write stream: 1 KiB rows of 5 of 8 planes, one workgroup per 1096 KiB block; and the NL sweep's
 // whole read/write pattern) -- keeps the best and frees the others.
 // Environment (measurements only): CLOUDSC2_PLACE=0 no search, CLOUDSC2_PLACE_SPAN_GB (96), CLOUDSC2_PLACE_CANDIDATES,
@@ -25,6 +25,12 @@
 // (one plain hipMalloc) when several ranks share the device -- LOCAL_WORLD_SIZE above the number of visible devices, the shm
 // rehearsal of libcloudsc2_comm.so, or CLOUDSC2_PLACE_SHARED=1 -- because hipMemGetInfo and hipMalloc are not coordinated between
 // processes.  A search that cannot get a single candidate frees everything and retries one plain hipMalloc before reporting OOM.
+
+#include <array>
+#include "cloudsc2_host.hpp"
+
+using namespace cloudsc2;
+
 namespace {
 
 struct DevAlloc {
@@ -39,17 +45,6 @@ size_t env_gib(const char* name, size_t dflt) {
 std::mutex g_alloc_mutex;
 std::vector<std::pair<void*, DevAlloc>> g_allocs;
 
-// do other processes allocate on this device at the same time?  (more local ranks than visible devices, or said so)
-bool device_is_shared() {
-  const char* sh = getenv("CLOUDSC2_PLACE_SHARED");
-  if (sh) return atoi(sh) != 0;
-  const char* comm = getenv("CLOUDSC2_COMM");
-  if (comm && !strcmp(comm, "shm")) return true;  // rehearsal transport: more ranks than GPUs by construction
-  const char* lws = getenv("LOCAL_WORLD_SIZE");
-  int ndev = 0;
-  if (lws && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return atoi(lws) > ndev;
-  return false;
-}
 // bytes the placement search may hold at once, given what is free now
 size_t search_budget(size_t bytes, size_t free_b) {
   double share = bytes > (env_gib("CLOUDSC2_PLACE_WHOLE_MAX_GB", 12) << 30) ? 0.85 : 0.6;
@@ -100,7 +95,6 @@ __global__ void __launch_bounds__(128) place_probe_mixed_kernel(double* base, lo
   }
 }
 
-extern "C" int cloudsc2_device_probe(void* ptr, size_t bytes, int kind, int rounds, double* ms);
 // The probes of the placement search: kind 0 the sweeps' write stream, kind 1 the NL sweep's whole pattern.  Candidates that no
 // caller's sweep judges are ranked by BOTH (the mixed stream's time plus a fifth of the write stream's, each relative to the best
 // candidate's): on one box the NL kernel's time on 20 consecutive allocations of one process correlated 0.999 with the mixed probe (two clean classes, 1.10 vs 1.29 ms, noise < 1 %)
@@ -110,11 +104,10 @@ extern "C" int cloudsc2_device_probe(void* ptr, size_t bytes, int kind, int roun
 // CLOUDSC2_PLACE_PROBE=write|mixed ranks by one of them (measurements only).  2 GiB chunks of the composed form are ranked by the
 // write stream alone (the mixed pattern inside one chunk says less about the composition: 4.96-5.04 vs 4.98-5.38 ms at 1 M columns).
 // kProbeCustom: the caller's own sweep (a std::function that launches ONE pass over a buffer on the null stream).  The state-level
-// allocations use it with the real NL kernel on a state laid out in the candidate (cloudsc2_driver.inc: state_probe): at 1 M
+// allocations use it with the real NL kernel on a state laid out in the candidate (cloudsc2_driver.hip: state_probe): at 1 M
 // columns neither generic stream predicts the kernel (correlation 0.5-0.8 over five 42 GB allocations; a composition that probed
 // at 6.98 ms ran the kernel at 5.43 ms, one at 7.40 ms ran it at 4.87 ms: profiles/r02_placement/r_1m_probe_vs_kernel.txt).
 enum ProbeKind { kProbeWrite = 0, kProbeMixed = 1, kProbeCustom = 2 };
-using ProbeFn = std::function<void(void* base, size_t bytes)>;
 const ProbeFn* g_custom_probe = nullptr;  // set for the duration of one device_malloc_impl call (under g_place_mutex)
 std::mutex g_place_mutex;
 void launch_probe(void* p, size_t bytes, int kind) {
@@ -314,20 +307,39 @@ int device_malloc_chunks(void** out, size_t bytes, PlaceStats& st) {
   return 0;
 }
 
+std::atomic<long long> g_searches{0}, g_plain_allocs{0};  // cloudsc2_device_malloc_counts (tests: who searched, who did not)
+
+}  // namespace
+
+namespace cloudsc2 {
+
+// do other processes allocate on this device at the same time?  (more local ranks than visible devices, or said so; read once)
+bool device_is_shared() {
+  static const bool shared = [] {
+    const char* sh = getenv("CLOUDSC2_PLACE_SHARED");
+    if (sh) return atoi(sh) != 0;
+    const char* comm = getenv("CLOUDSC2_COMM");
+    if (comm && !strcmp(comm, "shm")) return true;  // rehearsal transport: more ranks than GPUs by construction
+    const char* lws = getenv("LOCAL_WORLD_SIZE");
+    int ndev = 0;
+    if (lws && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return atoi(lws) > ndev;
+    return false;
+  }();
+  return shared;
+}
+
 // `policy`: kPlaceSearch = the search described above (resident states and what callers ask for through cloudsc2_device_malloc*);
 // kPlaceOnRequest = one plain hipMalloc unless CLOUDSC2_PLACE=1 is set explicitly (the workspace of the host-array drivers, whose
 // calls are PCIe-bound: 55-71 ms per call against a 0.1 ms difference of the kernel, and a host model's HBM is not ours to take
 // transiently); kPlacePlain = never searched (staging buffers touched once per transfer).
-enum PlacePolicy { kPlaceSearch = 0, kPlaceOnRequest = 1, kPlacePlain = 2 };
-std::atomic<long long> g_searches{0}, g_plain_allocs{0};  // cloudsc2_device_malloc_counts (tests: who searched, who did not)
-int device_malloc_impl(void** out, size_t bytes, const ProbeFn* custom = nullptr, PlacePolicy policy = kPlaceSearch) {
+int device_malloc_impl(void** out, size_t bytes, const ProbeFn* custom, PlacePolicy policy) {
   if (!out) return fail(CLOUDSC2_EINVAL, "cloudsc2_device_malloc: NULL result pointer");
   *out = nullptr;
   if (bytes == 0) return 0;
   std::lock_guard<std::mutex> place_lock(g_place_mutex);  // one placement search at a time (they time the device)
   static const bool allow_custom = !(getenv("CLOUDSC2_PLACE_PROBE") && strcmp(getenv("CLOUDSC2_PLACE_PROBE"), "kernel") != 0);
   struct Scope { Scope(const ProbeFn* f) { g_custom_probe = f; } ~Scope() { g_custom_probe = nullptr; } } scope(allow_custom ? custom : nullptr);
-  if (!device_ok()) return fail(CLOUDSC2_ENODEVICE, "no HIP device available (this library has no CPU path)");
+  if (int rc = require_device()) return rc;
   // an allocation is a synchronous moment: the device's dispatch rules are checked here (once per device and process), BEFORE the
   // placement search times the NL sweep -- which then runs with the nap the launches will run with
   (void)device_prepare();
@@ -488,15 +500,14 @@ int device_free_impl(void* p) {
   return 0;
 }
 
-}  // namespace
+}  // namespace cloudsc2
 
 extern "C" {
 int cloudsc2_device_malloc(void** ptr, size_t bytes) { return device_malloc_impl(ptr, bytes); }
 int cloudsc2_device_free(void* ptr) { return device_free_impl(ptr); }
-int cloudsc2_device_malloc_state(void** ptr, size_t bytes, int nproma, int nlev, int ngptot);  // cloudsc2_driver.inc (needs the NL launcher)
 int cloudsc2_device_probe(void* ptr, size_t bytes, int kind, int rounds, double* ms) {
   if (!ptr || !ms || rounds < 1 || rounds > 64 || (kind != 0 && kind != 1)) return fail(CLOUDSC2_EINVAL, "cloudsc2_device_probe: bad argument");
-  if (!device_ok()) return fail(CLOUDSC2_ENODEVICE, "no HIP device available (this library has no CPU path)");
+  if (int rc = require_device()) return rc;
   const long long nblocks = kind == 0 ? (long long)(bytes / (size_t)kProbeBlockBytes) : (long long)(bytes / (size_t)((kMixIn + kMixOut) * kMixBlockElems * 8));
   if (nblocks < 1 || nblocks > 0x7fffffffLL) return fail(CLOUDSC2_EINVAL, "cloudsc2_device_probe: buffer too small or too large");
   hipEvent_t ea = nullptr, eb = nullptr;

@@ -1,9 +1,14 @@
-// cloudsc2_driver.inc -- driver-level entry points (host pointers in the GLOBAL_STATE layout).
-// Included at the end of cloudsc2_kernels.hip.  These replace the bodies of the reference's three driver
-// procedures: the OpenMP block loop becomes one launch over all blocks, thread-private scratch arrays
-// (cloudsc_driver_tl_mod.F90:77-95, cloudsc_driver_ad_mod.F90:66-79) become device arrays over all blocks.
+// cloudsc2_driver.hip -- driver-level entry points (host pointers in the GLOBAL_STATE layout) and the resident state.
+// These replace the bodies of the reference's three driver procedures: the OpenMP block loop becomes one launch over all blocks,
+// thread-private scratch arrays (cloudsc_driver_tl_mod.F90:77-95, cloudsc_driver_ad_mod.F90:66-79) become device arrays over all blocks.
+
+#include <thread>
+#include "cloudsc2_host.hpp"
+
+using namespace cloudsc2;
 
 namespace {
+
 
 __global__ void __launch_bounds__(256)
 scale_planes_kernel(real_t* dst, long long dst_stride, const real_t* src, long long src_stride, long long plane, long long nblocks,
@@ -12,6 +17,25 @@ scale_planes_kernel(real_t* dst, long long dst_stride, const real_t* src, long l
   if (i >= plane * nblocks) return;
   long long ibl = i / plane, r = i - ibl * plane;
   dst[ibl * dst_stride + r] = src[ibl * src_stride + r] * factor;
+}
+
+// One (NPROMA, nrows, NBLOCKS) array from one blocking to another (resident states the library blocks differently from the caller:
+// cloudsc2_state_upload / _download).  Columns g < ncopy are copied; ncopy <= g < nzero are written as zero (whole blocks of the
+// two arrays the driver zeroes, cloudsc_driver_mod.F90:87-88); everything else keeps its value.
+__global__ void __launch_bounds__(256)
+reblock_kernel(const real_t* __restrict__ src, int np_src, long long stride_src, real_t* __restrict__ dst, int np_dst,
+               long long stride_dst, long long nrows, long long ncopy, long long nzero) {
+  const long long total = nrows * nzero;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+    const long long row = e / nzero, g = e - row * nzero;
+    const long long bd = g / np_dst, jd = g - bd * np_dst;
+    real_t v = 0;
+    if (g < ncopy) {
+      const long long bs = g / np_src, js = g - bs * np_src;
+      v = src[bs * stride_src + row * np_src + js];
+    }
+    dst[bd * stride_dst + row * np_dst + jd] = v;
+  }
 }
 
 constexpr size_t kAlignReals = 256 / sizeof(real_t);
@@ -30,7 +54,7 @@ struct Arena {
     HIP_TRY(hipGetDevice(&dev));
     if (base && (cap < nreals || dev != device)) { (void)device_free_impl(base); base = nullptr; cap = 0; }
     if (!base) {
-      // placed: the fastest of several candidate allocations / compositions (cloudsc2_alloc.inc)
+      // placed: the fastest of several candidate allocations / compositions (cloudsc2_alloc.hip)
       int rc = device_malloc_impl((void**)&base, nreals * sizeof(real_t), probe, policy);
       if (rc) { base = nullptr; return rc; }
       cap = nreals;
@@ -434,7 +458,7 @@ int cloudsc2_nl_run(const cloudsc2_params* prm, int nproma, int nlev, int ngptot
   if (rc) return rc;
   std::lock_guard<std::mutex> lock(g_arena_mutex);
   const ProbeFn probe = state_probe(nproma, nlev, ngptot);
-  // (the call is PCIe-bound: its workspace is one plain hipMalloc unless CLOUDSC2_PLACE=1 asks for the search; cloudsc2_alloc.inc)
+  // (the call is PCIe-bound: its workspace is one plain hipMalloc unless CLOUDSC2_PLACE=1 asks for the search; cloudsc2_alloc.hip)
   if ((rc = g_arena.reserve(state_reals(g.ncols_pad, nlev), &probe, kPlaceOnRequest))) return rc;
   DevState d;
   state_take(g_arena, d, g.ncols_pad, nproma, nlev);
@@ -707,7 +731,7 @@ int cloudsc2_state_create(int nproma, int nlev, int ngptot, cloudsc2_state** out
   if (!out) return fail(CLOUDSC2_EINVAL, "NULL result pointer");
   *out = nullptr;
   if (nproma < 1 || nlev < 2 || ngptot < 1 || nlev > CLOUDSC2_MAX_NLEV) return fail(CLOUDSC2_EINVAL, "bad dimensions");
-  if (!device_ok()) return fail(CLOUDSC2_ENODEVICE, "no HIP device available (this library has no CPU path)");
+  if (int rc = require_device()) return rc;
   cloudsc2_state* s = new cloudsc2_state;
   s->nproma_user = nproma;
   s->ncols_pad_user = (((long long)ngptot + nproma - 1) / nproma) * nproma;
@@ -718,7 +742,7 @@ int cloudsc2_state_create(int nproma, int nlev, int ngptot, cloudsc2_state** out
   int rc = hipGetDevice(&s->device) == hipSuccess ? 0 : fail(CLOUDSC2_EINVAL, "hipGetDevice failed");
   const size_t n = state_reals(s->g.ncols_pad, nlev);
   const ProbeFn probe = state_probe(nproma, nlev, ngptot);
-  if (!rc) rc = s->arena.reserve(n, &probe);  // ONE placed allocation for the whole state (cloudsc2_alloc.inc), judged by the NL sweep
+  if (!rc) rc = s->arena.reserve(n, &probe);  // ONE placed allocation for the whole state (cloudsc2_alloc.hip), judged by the NL sweep
   if (!rc && hipMemset(s->arena.base, 0, n * sizeof(real_t)) != hipSuccess) rc = fail(CLOUDSC2_EINVAL, "hipMemset failed");
   if (rc) { s->arena.release(); delete s; return rc; }
   state_take(s->arena, s->d, s->g.ncols_pad, nproma, nlev);  // FIELD_INIT: everything zero (cloudsc2_array_state_mod.F90:186-190)

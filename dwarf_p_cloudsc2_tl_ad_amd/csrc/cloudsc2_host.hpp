@@ -1,0 +1,92 @@
+// cloudsc2_host.hpp -- what the host units of libcloudsc2_hip share (internal: not part of the C ABI, not installed).
+//
+//   cloudsc2_launch.hip   the C ABI launchers (sweeps, SATUR, expand / validate, Taylor sums and sweep, adjoint norms), the error
+//                         state, the math mode, the level-table cache, the argument checks, and the small kernels they launch
+//   cloudsc2_policy.hip   launch policy: the device probes, device_prepare and its verdicts, the occupancy lookup, the pacing rule,
+//                         and the fair / nap / pacing decision of every launch (schedule)
+//   cloudsc2_alloc.hip    the placement allocator behind cloudsc2_device_malloc*
+//   cloudsc2_driver.hip   the host-array drivers and the resident state
+//   cloudsc2_helpers.hip  host-only helpers of the C ABI (default parameters, offsets, validation text, the synthetic table, verdicts)
+//
+// The sweeps' kernels are in cloudsc2_kern_{nl,tl,ad,taylor}.hip (cloudsc2_sweep_kernels.hpp).  A __global__ kernel stays in the unit
+// that launches it: without relocatable device code a kernel cannot be launched by name from another unit's code object.  Everything
+// here has external linkage inside namespace cloudsc2; the link's version script (cloudsc2_hip.map) keeps it out of the dynamic symbol
+// table, where only the C ABI appears.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <functional>
+#include <initializer_list>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/cloudsc2_hip.h"
+#include "cloudsc2_sweep_kernels.hpp"
+
+namespace cloudsc2 {
+
+// ---- error state (cloudsc2_launch.hip) ---------------------------------------------------------------------------------------------
+extern thread_local std::string g_err;  // cloudsc2_last_error()
+int fail(int code, const char* msg);
+
+#define HIP_TRY(expr)                                                                     \
+  do {                                                                                    \
+    hipError_t e_ = (expr);                                                               \
+    if (e_ != hipSuccess) {                                                               \
+      g_err = std::string(#expr) + ": " + hipGetErrorString(e_);                          \
+      return (int)e_;                                                                     \
+    }                                                                                     \
+  } while (0)
+
+bool device_ok();
+int no_device();  // CLOUDSC2_ENODEVICE, with its message
+inline int require_device() { return device_ok() ? 0 : no_device(); }
+
+// ---- argument checks and launch helpers (cloudsc2_launch.hip) -----------------------------------------------------------------------
+bool precise_of(const cloudsc2_params* prm);  // the arithmetic of one call: its own request, else the process default
+int check_geom(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, Geom& g);
+int resolve_in(const cloudsc2_inputs& in, bool need_qsat, Strides& s, InPtrs& p);
+int resolve_out(const cloudsc2_outputs& out, bool all_required, Strides& s, OutPtrs& p);
+int get_tables(const cloudsc2_params& p, const LevelTab** dev, int* kb0, int* kb1);
+int validate_launch_impl(const cloudsc2_real* table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
+                         long long ngptot, cloudsc2_field field, double* workspace, double* stats, void* stream, long long ncols_minmax);
+
+inline unsigned grid_for(long long ncols, int block) { return (unsigned)((ncols + block - 1) / block); }
+
+template <class Args>
+int launch_variant(KernelFn<Args> fn, const Args& args, long long ncols, hipStream_t st) {
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  Args a = args;
+  void* argv[] = {&a};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(ncols, kBlock)), dim3(kBlock), argv, 0, st));
+  return 0;
+}
+
+// ---- launch policy (cloudsc2_policy.hip) --------------------------------------------------------------------------------------------
+// The scheduling fields of one launch's Geom (fair, pace_slots, pace_first, pace_recip_q16), set from nothing but the launch's size, the
+// kernels' occupancy and the cached device verdicts (it never touches the device):
+//   fair  the kernel whose waves keep abreast when the launch is one round of them (nullptr: fair = 0),
+//   nap   the lighter SIMDs of the fullest CUs may nap on top of that (the NL sweep's own launches),
+//   pace  the kernel whose launch of a few partial rounds of workgroups is paced (nullptr: not paced).
+void schedule(Geom& g, const void* fair, bool nap, const void* pace);
+int device_prepare();  // the synchronous moment: probes the current device once per process, caches the verdicts
+
+// ---- placement allocator (cloudsc2_alloc.hip) ---------------------------------------------------------------------------------------
+bool device_is_shared();  // do other processes use this device at the same time?  (read once per process)
+// the caller's own sweep, which the placement search times on every candidate (a pass over the buffer on the null stream)
+using ProbeFn = std::function<void(void* base, size_t bytes)>;
+// kPlaceSearch: the search (resident states, cloudsc2_device_malloc*); kPlaceOnRequest: one plain hipMalloc unless CLOUDSC2_PLACE=1
+// (the host-array drivers' workspace); kPlacePlain: never searched (staging buffers)
+enum PlacePolicy { kPlaceSearch = 0, kPlaceOnRequest = 1, kPlacePlain = 2 };
+int device_malloc_impl(void** out, size_t bytes, const ProbeFn* custom = nullptr, PlacePolicy policy = kPlaceSearch);
+int device_free_impl(void* p);
+
+}  // namespace cloudsc2

@@ -1,0 +1,902 @@
+// cloudsc2_launch.hip -- the launchers of the CLOUDSC2 NL/TL/AD engine's C ABI (include/cloudsc2_hip.h), what they check and share,
+// and the small kernels only they launch.
+//
+// Mapping: one lane = one grid column, lanes run over the global column index g = ibl*NPROMA + jl of the
+// reference's (NPROMA, NLEV, NBLOCKS) layout, so a wave64 reads 64 consecutive doubles (512 B) of every
+// input plane per level: fully coalesced for any NPROMA (for NPROMA in {64,128,256} and blockDim = NPROMA one
+// thread block is exactly one NPROMA block).  The 137-level sweep is sequential per lane with three carried
+// scalars; inputs of level JK+1 are requested before level JK is computed (register double buffer).
+// There is no MFMA (pointwise physics) and no inter-lane traffic in the kernels proper; wave/LDS reductions
+// appear only in the two test-norm kernels.
+
+#include "cloudsc2_host.hpp"
+#ifdef C2_SINGLE_TU  // one translation unit (experiment / diagnostic builds): the family units are part of this one
+#include "cloudsc2_kern_nl.hip"
+#include "cloudsc2_kern_tl.hip"
+#include "cloudsc2_kern_ad.hip"
+#include "cloudsc2_kern_taylor.hip"
+#endif
+
+using namespace cloudsc2;
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------
+// kernels: the sweeps' __global__ wrappers and their variant tables are cloudsc2_sweep_kernels.hpp + the family units
+// cloudsc2_kern_{nl,tl,ad,taylor}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
+// ---------------------------------------------------------------------------------------------------------
+template <bool P>
+__global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
+  C2_KERNEL_BODY(satur_column<P>(global_column(), kernarg<SaturArgs>()));
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Data-format kernels either side of the path: the input file holds KLON (=100) columns,
+// the model state is their periodic tiling into NPROMA blocks (expand_mod.F90:270-335), and the validator compares
+// the outputs with a KLON-column reference (validate_mod.F90:165-261).  Both work from the small table on the
+// device, so a 1M-column state never exists on the host and the reference is never expanded at all.
+// ---------------------------------------------------------------------------------------------------------
+// field(jl, jk, jm, ibl) = table((start + (ibl*NPROMA + jl) mod period) mod KLON, jk, jm) for active columns, 0 for the
+// padded tail of the last block: the rank's table slice START..END (get_offsets, expand_mod.F90:30-46) tiled with period
+// SIZE (load_and_expand + expand_r2, :101-116,283-296).  The outer mod KLON never acts for those pairs (start + period <= KLON);
+// it lets period = KLON with any start >= 0 express "the periodic tiling continues at global column `start`".
+__global__ void __launch_bounds__(256)
+expand_kernel(const real_t* __restrict__ table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
+              long long ngptot, long long nblocks, real_t* __restrict__ field, long long block_stride) {
+  const long long per_block = (long long)nproma * nlevx * ndim;
+  const long long total = per_block * nblocks;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+    const long long ibl = e / per_block;
+    const long long r = e - ibl * per_block;
+    const int jl = (int)(r % nproma);
+    const long long lev = r / nproma;  // jk + nlevx*jm
+    const long long g = ibl * nproma + jl;
+    real_t v = 0;
+    if (g < ngptot) v = table[(start + g % period) % klon + (long long)klon * lev];
+    field[ibl * block_stride + r] = v;
+  }
+}
+
+// Per-workgroup partial statistics of VALIDATE_R2/R3 (validate_mod.F90:165-261): min and max of FIELD over whole
+// blocks (padding included, like MINVAL(FIELD(:,:,B))), max |FIELD-REF|, sum |FIELD-REF|, sum |REF| over the active
+// columns.  part[5*blockIdx.x + {0..4}]; a second launch folds the partials in a fixed order (deterministic sums).
+__global__ void __launch_bounds__(256)
+validate_partial_kernel(const real_t* __restrict__ table, int klon, int period, long long start, int nlevx, int ndim,
+                        int nproma, long long ngptot, long long nblocks, const real_t* __restrict__ field,
+                        long long block_stride, double* __restrict__ part, long long ncols_minmax) {
+  const long long per_block = (long long)nproma * nlevx * ndim;
+  const long long total = per_block * nblocks;
+  double vmin = INFINITY, vmax = -INFINITY, emax = 0.0, esum = 0.0, rsum = 0.0;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+    const long long ibl = e / per_block;
+    const long long r = e - ibl * per_block;
+    const int jl = (int)(r % nproma);
+    const long long lev = r / nproma;
+    const long long g = ibl * nproma + jl;
+    const double f = field[ibl * block_stride + r];
+    if (g < ncols_minmax) {  // MINVAL / MAXVAL run over whole blocks of the CALLER's blocking (resident states may be blocked otherwise)
+      vmin = fmin(vmin, f);
+      vmax = fmax(vmax, f);
+    }
+    if (g < ngptot) {
+      const double ref = table[(start + g % period) % klon + (long long)klon * lev];
+      const double d = fabs(f - ref);
+      emax = fmax(emax, d);
+      esum += d;
+      rsum += fabs(ref);
+    }
+  }
+  __shared__ double red[5][4];
+  for (int off = 32; off > 0; off >>= 1) {
+    vmin = fmin(vmin, __shfl_down(vmin, off, 64));
+    vmax = fmax(vmax, __shfl_down(vmax, off, 64));
+    emax = fmax(emax, __shfl_down(emax, off, 64));
+    esum += __shfl_down(esum, off, 64);
+    rsum += __shfl_down(rsum, off, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[0][w] = vmin; red[1][w] = vmax; red[2][w] = emax; red[3][w] = esum; red[4][w] = rsum; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 4; ++i) {
+      red[0][0] = fmin(red[0][0], red[0][i]); red[1][0] = fmax(red[1][0], red[1][i]); red[2][0] = fmax(red[2][0], red[2][i]);
+      red[3][0] += red[3][i]; red[4][0] += red[4][i];
+    }
+    for (int k = 0; k < 5; ++k) part[5 * (long long)blockIdx.x + k] = red[k][0];
+  }
+}
+
+// fold_zero: the caller's blocking has padded columns the field's own blocking does not hold (caller NPROMA 100 pads 256 columns to
+// 300, the device's 2 x 128 blocks have none): they are zero in the caller's arrays and MINVAL / MAXVAL(FIELD(:,:,B)) include them
+__global__ void validate_final_kernel(const double* __restrict__ part, int nparts, double* __restrict__ stats, int fold_zero) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double vmin = fold_zero ? 0.0 : INFINITY, vmax = fold_zero ? 0.0 : -INFINITY, emax = 0.0, esum = 0.0, rsum = 0.0;
+  for (int i = 0; i < nparts; ++i) {
+    vmin = fmin(vmin, part[5 * i + 0]); vmax = fmax(vmax, part[5 * i + 1]); emax = fmax(emax, part[5 * i + 2]);
+    esum += part[5 * i + 3]; rsum += part[5 * i + 4];
+  }
+  stats[0] = vmin; stats[1] = vmax; stats[2] = emax; stats[3] = esum; stats[4] = rsum;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Test-norm kernels
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool lane_setup_v(const Geom& g, const Strides& s, long long gcol, LaneOff& o, bool& active) {
+  if (gcol >= g.ncols_pad) return false;
+  long long ibl = gcol / g.nproma;
+  long long jl = gcol - ibl * g.nproma;
+  o.full = ibl * s.full + jl; o.half = ibl * s.half + jl; o.cml = ibl * s.cml + jl; o.clv = ibl * s.clv + jl;
+  o.loc = ibl * s.loc + jl;
+  active = gcol < g.ngptot;
+  return true;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// ERROR_NORM sums (cloudsc_driver_tl_mod.F90:21-31): one thread block per NPROMA block, lanes stride the
+// block's active columns, per-lane level sums, wave shuffles, then one LDS stage.
+// sums[(ibl*10 + f)*2 + {0,1}] = { sum(F - F5), sum(TL*lambda) }.
+// (TenPtrs: cloudsc2_column.hpp)
+
+// The 256 threads of a workgroup are laid over the block as (column, level slice): all of them work whatever NPROMA is -- with one
+// thread per column only, the README's NPROMA 32 left 7 of 8 lanes idle.  (For ONE lambda and perturbed outputs that are in memory;
+// the Taylor driver itself runs all ten lambdas in one sweep that stores nothing, taylor_kernel + taylor_reduce_kernel.)
+__global__ void __launch_bounds__(256) taylor_sums_kernel(int nproma, int nlev, int ngptot, TenPtrs f, TenPtrs f5, TenPtrs tl,
+                                                          double lambda, double* sums) {
+  (void)nlev;
+  const int ibl = blockIdx.x;
+  const int icend = min(nproma, ngptot - ibl * nproma);
+  const int ncolt = min(nproma, (int)blockDim.x);    // threads along the columns
+  const int nslice = (int)blockDim.x / ncolt;        // level slices (>= 1)
+  const int jl0 = threadIdx.x % ncolt, slice = threadIdx.x / ncolt;
+  __shared__ double red[2][4];
+  for (int fi = 0; fi < 10; ++fi) {
+    double s0 = 0.0, s1 = 0.0;
+    const int nl = f.nlevx[fi];
+    if (slice < nslice) {
+      for (int jl = jl0; jl < icend; jl += ncolt) {
+        const real_t* a = f.p[fi] + (long long)ibl * f.stride[fi] + jl;
+        const real_t* b = f5.p[fi] + (long long)ibl * f5.stride[fi] + jl;
+        const real_t* t = tl.p[fi] + (long long)ibl * tl.stride[fi] + jl;
+        for (int jk = slice; jk < nl; jk += nslice) {
+          long long d = (long long)jk * nproma;
+          s0 += a[d] - b[d];
+          s1 += t[d] * lambda;
+        }
+      }
+    }
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[0][w] = s0; red[1][w] = s1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double r0 = 0.0, r1 = 0.0;
+      for (int i = 0; i < (int)(blockDim.x >> 6); ++i) { r0 += red[0][i]; r1 += red[1][i]; }
+      sums[((long long)ibl * 10 + fi) * 2 + 0] = r0;
+      sums[((long long)ibl * 10 + fi) * 2 + 1] = r1;
+    }
+    __syncthreads();
+  }
+}
+
+// Second stage of the Taylor sweep: the per-column level sums of taylor_kernel summed over the active columns of each block of
+// the STATISTIC (ERROR_NORM sums over one block of the caller's NPROMA), in column order (deterministic), into the layout of
+// taylor_sums_kernel: sums[((il*nblocks + ibl)*10 + f)*2 + {0,1}] = { sum(F - F5(lambda_il)), sum(TL)*lambda_il }.
+struct TenLambdas { double v[kTaylorLambdas]; };
+__global__ void __launch_bounds__(128) taylor_reduce_kernel(int nproma, int ngptot, long long ncols_pad, long long nblocks, TenLambdas lam,
+                                                            const double* colsum, double* sums) {
+  const long long ibl = blockIdx.x;
+  const int t = threadIdx.x;
+  if (t >= 10 * kTaylorLambdas) return;
+  const int il = t / 10, f = t - 10 * il;
+  const long long c0 = ibl * nproma;
+  const int icend = (int)min((long long)nproma, (long long)ngptot - c0);
+  const double* s1 = colsum + (long long)t * ncols_pad + c0;
+  const double* s2 = colsum + (long long)(10 * kTaylorLambdas + f) * ncols_pad + c0;
+  double r0 = 0.0, r1 = 0.0;
+  for (int j = 0; j < icend; ++j) { r0 += s1[j]; r1 += s2[j]; }
+  double* o = sums + (((long long)il * nblocks + ibl) * 10 + f) * 2;
+  o[0] = r0;
+  o[1] = r1 * lam.v[il];
+}
+
+// The same for LARGE blocks of the statistic (one thread per value would walk thousands of columns one after the other): one
+// workgroup per (block, value), its threads stride the block's columns, fixed-order reduction (wave shuffles, one LDS stage) --
+// deterministic as well.  blockIdx.y < 100: sum(F - F5) of (lambda, field) = blockIdx.y; 100..109: sum(TL) of field blockIdx.y - 100,
+// written once per lambda with its factor.
+__global__ void __launch_bounds__(256) taylor_reduce_wide_kernel(int nproma, int ngptot, long long ncols_pad, long long nblocks, TenLambdas lam,
+                                                                 const double* colsum, double* sums) {
+  const long long ibl = blockIdx.x;
+  const int t = blockIdx.y;
+  const long long c0 = ibl * nproma;
+  const int icend = (int)min((long long)nproma, (long long)ngptot - c0);
+  const double* src = colsum + (long long)t * ncols_pad + c0;
+  double r = 0.0;
+  for (int j = threadIdx.x; j < icend; j += blockDim.x) r += src[j];
+  r = wave_sum(r);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  r = (red[0] + red[1]) + (red[2] + red[3]);
+  if (t < 10 * kTaylorLambdas) {
+    const int il = t / 10, f = t - 10 * il;
+    sums[(((long long)il * nblocks + ibl) * 10 + f) * 2 + 0] = r;
+  } else {
+    const int f = t - 10 * kTaylorLambdas;
+    for (int il = 0; il < kTaylorLambdas; ++il) sums[(((long long)il * nblocks + ibl) * 10 + f) * 2 + 1] = r * lam.v[il];
+  }
+}
+
+// Adjoint-test norms (cloudsc_driver_ad_mod.F90:184-195,240-264): lane = column, level sums in registers
+// (cloudsc2_column.hpp), wave max by shuffles, one atomic max per wave.
+__global__ void __launch_bounds__(kBlock) adjoint_norm1_kernel(Geom g, Strides sa, OutPtrs y, double* norms) {
+  long long gcol = global_column();
+  LaneOff oa; bool active;
+  if (!lane_setup_v(g, sa, gcol, oa, active) || !active) return;
+  norms[gcol] = adjoint_norm1_column(g.nlev, g.nproma, oa, y);
+}
+
+__global__ void __launch_bounds__(kBlock)
+adjoint_norm2_kernel(Geom g, Strides s, Strides sa, InPtrs in, const real_t* qsat, long long qsat_stride, InPtrs xa,
+                     double* norms, long long ncols_pad, double* gmax) {
+  long long gcol = global_column();
+  LaneOff o, oa; bool active;
+  double n3 = 0.0;
+  if (lane_setup_v(g, s, gcol, o, active) && active) {
+    lane_setup_v(g, sa, gcol, oa, active);
+    const long long oq = (gcol / g.nproma) * qsat_stride + (gcol % g.nproma);
+    double n2 = adjoint_norm2_column(g.nlev, g.nproma, o, oa, oq, in, qsat, xa);
+    double n1 = norms[gcol];
+    n3 = adjoint_norm3(n1, n2);
+    norms[ncols_pad + gcol] = n2;
+    norms[2 * ncols_pad + gcol] = n3;
+    n3 = fabs(n3);
+    if (!(n3 == n3)) n3 = __longlong_as_double(0x7ff0000000000000LL);  // NaN counts as failure (+inf)
+  }
+  double m = wave_max(n3);
+  if ((threadIdx.x & 63) == 0) atomic_max_pos(gmax, m);
+}
+}  // namespace
+
+namespace cloudsc2 {
+
+// ---------------------------------------------------------------------------------------------------------
+// error handling
+// ---------------------------------------------------------------------------------------------------------
+thread_local std::string g_err;
+
+int fail(int code, const char* msg) {
+  g_err = msg;
+  return code;
+}
+
+bool device_ok() {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess) { (void)hipGetLastError(); return false; }
+  return n > 0;
+}
+
+int no_device() { return fail(CLOUDSC2_ENODEVICE, "no HIP device available (this library has no CPU path)"); }
+
+// 0 = fast math (shared reciprocals, branch-free exp), 1 = precise (IEEE division, libm exp/tanh, reference order)
+namespace {
+int initial_math_mode() {
+  const char* e = getenv("CLOUDSC2_MATH");
+  return (e && (!strcmp(e, "precise") || !strcmp(e, "1"))) ? 1 : 0;
+}
+std::atomic<int> g_precise{initial_math_mode()};
+}  // namespace
+
+// arithmetic of one call: the call's own request, else the process default (read, never written, by the launchers)
+bool precise_of(const cloudsc2_params* prm) {
+  if (prm->math_mode == 2) return true;
+  if (prm->math_mode == 1) return false;
+  return g_precise.load() != 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// launch-invariant constants and per-level tables
+// ---------------------------------------------------------------------------------------------------------
+// Device copies of the level tables are immutable once created and keyed by content, so launches on
+// different streams never race on them.
+namespace {
+struct TabEntry {
+  int device;
+  int nlev;
+  std::vector<double> ceta;
+  LevelTab* dev;
+  int kb0, kb1;  // tropopause band: levels jk (0-based) in [kb0,kb1) can have 0.1 < ceta < 0.4 and jk < nlev-1
+};
+std::mutex g_tab_mutex;
+std::vector<TabEntry> g_tabs;
+}  // namespace
+
+int get_tables(const cloudsc2_params& p, const LevelTab** dev, int* kb0, int* kb1) {
+  int device = 0;
+  HIP_TRY(hipGetDevice(&device));
+  std::lock_guard<std::mutex> lock(g_tab_mutex);
+  for (auto& e : g_tabs) {
+    if (e.device == device && e.nlev == p.nlev && memcmp(e.ceta.data(), p.ceta, sizeof(double) * p.nlev) == 0) {
+      *dev = e.dev; *kb0 = e.kb0; *kb1 = e.kb1;
+      return 0;
+    }
+  }
+  // CETA is a property of the vertical grid: a process sees one or two of them.  A caller that varies it per call would
+  // grow the cache without bound, so it is capped; an evicted table must not be freed while a launch may still read it,
+  // hence the device-wide synchronisation (rare by construction).
+  constexpr size_t kMaxTables = 16;
+  if (g_tabs.size() >= kMaxTables) {
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(g_tabs.front().dev);
+    g_tabs.erase(g_tabs.begin());
+  }
+  TabEntry e;
+  e.device = device;
+  e.nlev = p.nlev;
+  e.ceta.assign(p.ceta, p.ceta + p.nlev);
+  LevelTab host;
+  memset(&host, 0, sizeof(host));
+  e.kb0 = p.nlev; e.kb1 = 0;
+  for (int jk = 0; jk < p.nlev; ++jk) {
+    host.lev[jk].ceta = p.ceta[jk];
+    // cloudsc2.F90:266  ZSCALM(JK)=ZSCAL*MAX((CETA(JK)-0.2),ZEPS1)**0.2, ZSCAL=0.9 (:172)
+    host.lev[jk].zscalm = 0.9 * pow(fmax(p.ceta[jk] - 0.2, 1.e-12), 0.2);
+    if (jk < p.nlev - 1 && p.ceta[jk] > 0.1 && p.ceta[jk] < 0.4) {  // cloudsc2.F90:318-321
+      if (jk < e.kb0) e.kb0 = jk;
+      if (jk + 1 > e.kb1) e.kb1 = jk + 1;
+    }
+  }
+  if (e.kb1 <= e.kb0) { e.kb0 = 0; e.kb1 = 0; }
+  // (a launcher may be the first to ask for this table, possibly while ANOTHER stream of the process is being captured into a graph:
+  //  the thread's capture mode is relaxed for the allocation, and the upload goes through a private non-blocking stream instead of
+  //  the legacy stream, which would synchronise with -- and invalidate -- such a capture.  A launch on a stream that is itself
+  //  capturing needs its table to exist already: any earlier launch, cloudsc2_state_* call or driver call with the same CETA made it.)
+  {
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    const bool exchanged = hipThreadExchangeStreamCaptureMode(&mode) == hipSuccess;
+    hipStream_t up = nullptr;
+    hipError_t err = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipMalloc((void**)&e.dev, sizeof(LevelTab));
+    if (err == hipSuccess) err = hipMemcpyAsync(e.dev, &host, sizeof(LevelTab), hipMemcpyHostToDevice, up);
+    if (err == hipSuccess) err = hipStreamSynchronize(up);
+    if (up) (void)hipStreamDestroy(up);
+    if (exchanged) (void)hipThreadExchangeStreamCaptureMode(&mode);
+    if (err != hipSuccess) {
+      if (e.dev) (void)hipFree(e.dev);
+      (void)hipGetLastError();
+      g_err = std::string("level tables: ") + hipGetErrorString(err);
+      return (int)err;
+    }
+  }
+  g_tabs.push_back(e);
+  *dev = e.dev; *kb0 = e.kb0; *kb1 = e.kb1;
+  return 0;
+}
+namespace {
+struct GroupStride {
+  long long v;
+  bool set;
+  bool ok;
+  GroupStride() : v(0), set(false), ok(true) {}
+  void add(const cloudsc2_field& f) {
+    if (!f.ptr) return;
+    if (!set) { v = f.block_stride; set = true; }
+    else if (v != f.block_stride) ok = false;
+  }
+};
+}  // namespace
+
+int resolve_in(const cloudsc2_inputs& in, bool need_qsat, Strides& s, InPtrs& p) {
+  const cloudsc2_field* req[] = {&in.paph, &in.pap, &in.q, &in.t, &in.l, &in.i, &in.lude, &in.lu,
+                                 &in.mfu,  &in.mfd, &in.gtent, &in.gtenq, &in.gtenl, &in.gteni, &in.supsat};
+  for (auto f : req)
+    if (!f->ptr) return fail(CLOUDSC2_EINVAL, "a required input field has a NULL pointer");
+  if (need_qsat && !in.qsat.ptr) return fail(CLOUDSC2_EINVAL, "qsat field required");
+  GroupStride full, half, cml, clv;
+  full.add(in.pap); full.add(in.q); full.add(in.qsat); full.add(in.t); full.add(in.lude); full.add(in.lu);
+  full.add(in.mfu); full.add(in.mfd); full.add(in.supsat);
+  half.add(in.paph);
+  cml.add(in.gtent); cml.add(in.gtenq); cml.add(in.gtenl); cml.add(in.gteni);
+  clv.add(in.l); clv.add(in.i);
+  if (!full.ok || !half.ok || !cml.ok || !clv.ok)
+    return fail(CLOUDSC2_EINVAL, "fields of one layout group (full-level / PGTEN* / PL,PI) must share one block stride");
+  s.full = full.v; s.half = half.v; s.cml = cml.v; s.clv = clv.v;
+  p.paph = in.paph.ptr; p.pap = in.pap.ptr; p.q = in.q.ptr; p.qsat = in.qsat.ptr; p.t = in.t.ptr; p.l = in.l.ptr;
+  p.i = in.i.ptr; p.lude = in.lude.ptr; p.lu = in.lu.ptr; p.mfu = in.mfu.ptr; p.mfd = in.mfd.ptr;
+  p.gt = in.gtent.ptr; p.gq = in.gtenq.ptr; p.gl = in.gtenl.ptr; p.gi = in.gteni.ptr; p.supsat = in.supsat.ptr;
+  return 0;
+}
+
+int resolve_out(const cloudsc2_outputs& out, bool all_required, Strides& s, OutPtrs& p) {
+  const cloudsc2_field* all[] = {&out.tent, &out.tenq, &out.tenl, &out.teni, &out.clc,
+                                 &out.fplsl, &out.fplsn, &out.fhpsl, &out.fhpsn, &out.covptot};
+  if (all_required)
+    for (auto f : all)
+      if (!f->ptr) return fail(CLOUDSC2_EINVAL, "a required output field has a NULL pointer");
+  GroupStride full, half, loc;
+  full.add(out.clc); full.add(out.covptot);
+  half.add(out.fplsl); half.add(out.fplsn); half.add(out.fhpsl); half.add(out.fhpsn);
+  loc.add(out.tent); loc.add(out.tenq); loc.add(out.tenl); loc.add(out.teni);
+  if (!full.ok || !half.ok || !loc.ok)
+    return fail(CLOUDSC2_EINVAL, "output fields of one layout group must share one block stride");
+  if (full.set) { if (s.full && s.full != full.v) return fail(CLOUDSC2_EINVAL, "PCLC/PCOVPTOT stride differs from the input full-level stride"); s.full = full.v; }
+  if (half.set) { if (s.half && s.half != half.v) return fail(CLOUDSC2_EINVAL, "flux stride differs from the PAPH stride"); s.half = half.v; }
+  s.loc = loc.v;
+  p.tent = out.tent.ptr; p.tenq = out.tenq.ptr; p.tenl = out.tenl.ptr; p.teni = out.teni.ptr; p.clc = out.clc.ptr;
+  p.fplsl = out.fplsl.ptr; p.fplsn = out.fplsn.ptr; p.fhpsl = out.fhpsl.ptr; p.fhpsn = out.fhpsn.ptr;
+  p.covptot = out.covptot.ptr;
+  return 0;
+}
+
+int check_geom(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, Geom& g) {
+  if (!prm) return fail(CLOUDSC2_EINVAL, "params is NULL");
+  if (nproma < 1 || nlev < 2 || ngptot < 1) return fail(CLOUDSC2_EINVAL, "nproma >= 1, nlev >= 2, ngptot >= 1 required");
+  if (nlev > CLOUDSC2_MAX_NLEV) return fail(CLOUDSC2_EINVAL, "nlev exceeds CLOUDSC2_MAX_NLEV");
+  if (prm->nlev != nlev) return fail(CLOUDSC2_EINVAL, "params.nlev does not match nlev");
+  if (prm->math_mode < 0 || prm->math_mode > 2) return fail(CLOUDSC2_EINVAL, "params.math_mode must be 0 (default), 1 (fast) or 2 (precise)");
+  if (!device_ok()) return no_device();
+  long long nblocks = ((long long)ngptot + nproma - 1) / nproma;
+  g.nproma = nproma; g.nlev = nlev; g.ngptot = ngptot; g.ncols_pad = nblocks * nproma;
+  g.kb0 = 0; g.kb1 = 0; g.fair = 0;
+  return 0;
+}
+namespace {
+
+// The start every sweep launcher shares: check (the geometry; `missing`: the message for a NULL argument block) -> resolve (the
+// trajectory's inputs and outputs; a launcher resolves its own further blocks after these) -> tables -> constants -> common flags.
+struct Sweep {
+  Geom g;
+  Strides s = {0, 0, 0, 0, 0};
+  InPtrs in;
+  OutPtrs out;
+  const LevelTab* tab = nullptr;
+  Consts c;
+  unsigned f = 0;
+
+  int begin(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, const char* missing) {
+    const int rc = check_geom(prm, nproma, nlev, ngptot, g);
+    return rc ? rc : missing ? fail(CLOUDSC2_EINVAL, missing) : 0;
+  }
+  int trajectory(const cloudsc2_inputs& ti, const cloudsc2_outputs& to, bool out_required) {
+    const int rc = resolve_in(ti, false, s, in);
+    return rc ? rc : resolve_out(to, out_required, s, out);
+  }
+  // C2F_QSAT, C2F_PRECISE, C2F_EVAP, and C2F_OFF32 (32-bit byte offsets) when every buffer the sweep touches -- the trajectory's and
+  // those of the `more` strides -- is smaller than 4 GiB
+  int finish(const cloudsc2_params& prm, double ptsphy, bool qsat, std::initializer_list<long long> more) {
+    if (int rc = get_tables(prm, &tab, &g.kb0, &g.kb1)) return rc;
+    c = make_consts(prm, ptsphy);
+    if (qsat) f |= C2F_QSAT;
+    if (precise_of(&prm)) f |= C2F_PRECISE;
+    if (c.evap) f |= C2F_EVAP;
+    static const bool allow32 = !(getenv("CLOUDSC2_OFF32") && atoi(getenv("CLOUDSC2_OFF32")) == 0);  // 0: measurements only
+    long long stride = std::max({s.full, s.half, s.cml, s.clv, s.loc});
+    for (long long x : more) stride = std::max(stride, x);
+    const long long span = stride * (g.ncols_pad / g.nproma) + (long long)g.nproma * (g.nlev + 2);
+    if (allow32 && span * (long long)sizeof(real_t) < (1LL << 32)) f |= C2F_OFF32;
+    return 0;
+  }
+  // the NL sweep's argument block (no zero plane, no perturbation, no checkpoint)
+  NlArgs nl() const {
+    NlArgs a;
+    a.c = c; a.g = g; a.s = s; a.in = in; a.out = out; a.tab = tab;
+    a.zero_plane = nullptr; a.zero_stride = 0; a.lam = 0.0; a.ckpt = nullptr;
+    return a;
+  }
+};
+
+// pert_in == NULL: the increments are 0.01*x of the trajectory inputs (supsat_inc * PSUPSAT for PSUPSAT), C2F_SELFINC
+int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                   const cloudsc2_outputs* traj_out, const cloudsc2_inputs* pert_in, double supsat_inc, const cloudsc2_outputs* pert_out,
+                   double* yy, void* stream) {
+  Sweep w;
+  int rc = w.begin(prm, nproma, nlev, ngptot, (!traj_in || !traj_out || !pert_out) ? "NULL argument block" : nullptr);
+  if (rc) return rc;
+#if C2_TL_DMA
+  if (nproma != 128) return fail(CLOUDSC2_EINVAL, "this experiment build (C2_TL_DMA) runs the TL sweep for NPROMA 128 only");
+#endif
+  const cloudsc2_field* tf[10] = {&traj_out->tent, &traj_out->tenq, &traj_out->tenl, &traj_out->teni, &traj_out->clc,
+                                  &traj_out->fplsl, &traj_out->fplsn, &traj_out->fhpsl, &traj_out->fhpsn, &traj_out->covptot};
+  int nset = 0;
+  for (auto f : tf) nset += f->ptr ? 1 : 0;
+  if (nset != 0 && nset != 10) return fail(CLOUDSC2_EINVAL, "traj_out: give all ten trajectory outputs or none");
+  if ((rc = w.trajectory(*traj_in, *traj_out, false))) return rc;
+  TlArgs args;
+  args.sp = Strides{0, 0, 0, 0, 0};
+  if (pert_in) {
+    if ((rc = resolve_in(*pert_in, true, args.sp, args.din))) return rc;
+  } else {
+    memset(&args.din, 0, sizeof(args.din));  // (sp: taken from the outputs by resolve_out)
+  }
+  if ((rc = resolve_out(*pert_out, true, args.sp, args.dout))) return rc;
+  const Strides& sp = args.sp;
+  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sp.full, sp.half, sp.cml, sp.clv, sp.loc}))) return rc;
+  if (!pert_in) w.f |= C2F_SELFINC;
+  if (nset == 10) w.f |= C2F_TRAJ;
+  args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.out = w.out; args.tab = w.tab;
+  args.supsat_inc = (real_t)supsat_inc;
+  args.yy = yy;
+  // the fp32 TL variants that run three waves per SIMD (tl_kernel's launch bounds) share their SIMDs like the NL kernel does:
+  // -3.7 % at 160 000 columns with the waves kept abreast; the fp64 TL and both adjoints run one wave per SIMD and lose 1-5 %
+  // (profiles/r03_wave_times.txt); they are paced instead
+  const void* tl = (const void*)tl_variant(w.f);
+  const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);
+  schedule(args.g, abreast ? tl : nullptr, false, abreast ? nullptr : tl);
+  return launch_variant(tl_variant(w.f), args, w.g.ncols_pad, (hipStream_t)stream);
+}
+
+// What an AD launch runs.  which 0: both sweeps (the fused kernel, or the two kernels in stream order); 1: the trajectory pass
+// alone; 2: the reverse sweep alone.  assign: the input adjoints are assigned, not accumulated.  vjp: the vector-Jacobian product.
+// norms / gmax: the adjoint test's norms formed in the reverse sweep.
+struct AdMode {
+  int which;
+  bool assign, vjp;
+  double* norms;
+  double* gmax;
+};
+
+int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                   const cloudsc2_outputs* traj_out, const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out, cloudsc2_real* scratch,
+                   void* stream, AdMode m) {
+  Sweep w;
+  int rc = w.begin(prm, nproma, nlev, ngptot,
+                   (!traj_in || !traj_out || (m.which != 1 && (!adj_in || !adj_out))) ? "NULL argument block" : nullptr);
+  if (rc) return rc;
+  // the reverse sweep alone reads PFPLSL5 / PFPLSN5 and nothing else of the trajectory outputs
+  if ((rc = w.trajectory(*traj_in, *traj_out, m.which != 2))) return rc;
+  if (m.which == 2 && (!w.out.fplsl || !w.out.fplsn)) return fail(CLOUDSC2_EINVAL, "reverse sweep: traj_out->fplsl and ->fplsn (PFPLSL5, PFPLSN5) are required");
+  AdArgs args;
+  memset(&args, 0, sizeof(args));
+  if (m.which != 1) {
+    InPtrs aip_c;
+    if ((rc = resolve_in(*adj_in, true, args.sa, aip_c))) return rc;
+    if ((rc = resolve_out(*adj_out, true, args.sa, args.aout))) return rc;
+    InPtrsRW& aip = args.ain;
+    aip.paph = adj_in->paph.ptr; aip.pap = adj_in->pap.ptr; aip.q = adj_in->q.ptr; aip.qsat = adj_in->qsat.ptr;
+    aip.t = adj_in->t.ptr; aip.l = adj_in->l.ptr; aip.i = adj_in->i.ptr; aip.lude = adj_in->lude.ptr;
+    aip.lu = adj_in->lu.ptr; aip.mfu = adj_in->mfu.ptr; aip.mfd = adj_in->mfd.ptr; aip.gt = adj_in->gtent.ptr;
+    aip.gq = adj_in->gtenq.ptr; aip.gl = adj_in->gtenl.ptr; aip.gi = adj_in->gteni.ptr; aip.supsat = adj_in->supsat.ptr;
+  }
+  const Strides& sa = args.sa;
+  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sa.full, sa.half, sa.cml, sa.clv, sa.loc, (long long)nproma * nlev /* scratch */})))
+    return rc;
+  if (w.c.evap && !scratch) return fail(CLOUDSC2_EINVAL, "LEVAPLS2/LDRAIN1D: the cover-checkpoint plane `scratch` is required");
+  args.nl = w.nl();
+  args.nl.ckpt = scratch;
+  unsigned f = w.f;
+  if (m.assign) f |= C2F_ASSIGN;
+  if (m.vjp) {  // the vector-Jacobian product: reverse sweep alone, assign form, adj_out read only, true PSUPSAT adjoint
+    if (m.which != 2 || !m.assign || m.norms) return fail(CLOUDSC2_EINVAL, "vector-Jacobian product: reverse sweep alone, assign form, no norms");
+    f |= C2F_VJP;
+  }
+  if (m.norms) {  // the adjoint test's norm2 / norm3 formed in the reverse sweep
+    if (m.which != 2 || !m.assign || w.c.evap || !m.gmax) return fail(CLOUDSC2_EINVAL, "fused adjoint norms: reverse sweep alone, assign form, no evaporation branch");
+    f |= C2F_ADNORM;
+    args.norms = m.norms; args.gmax = m.gmax;
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  const long long n = w.g.ncols_pad;
+  // the trajectory pass as a kernel of its own: the NL sweep, with the cover checkpoint when the evaporation branch is on; it runs the
+  // NL kernel's three waves per SIMD, kept abreast like cloudsc2_nl_launch does (inside the fused kernel, one wave per SIMD, the
+  // priority code is compiled out)
+  const unsigned f_fwd = (f & ~C2F_ASSIGN) | (w.c.evap ? C2F_CKPT : 0u);
+  const void* fwd = (const void*)nl_variant(f_fwd);
+  const void* rev = (const void*)ad_reverse_variant(f);
+  if (m.which == 1) {
+    schedule(args.nl.g, fwd, false, nullptr);
+    return launch_variant(nl_variant(f_fwd), args.nl, n, st);
+  }
+  if (m.which == 2) {
+    schedule(args.nl.g, nullptr, false, rev);
+    return launch_variant(ad_reverse_variant(f), args, n, st);
+  }
+  if (C2_AD_FUSED == 1 || (C2_AD_FUSED == 2 && n > kAdSplitBelow)) {
+    schedule(args.nl.g, nullptr, false, (const void*)ad_variant(f));
+    return launch_variant(ad_variant(f), args, n, st);
+  }
+  // trajectory pass, then the reverse pass, in stream order: one Geom carries the NL kernel's `fair` and the reverse kernel's pacing
+  // (the NL kernel does not look at the pacing fields unless fair & 4)
+  schedule(args.nl.g, fwd, false, rev);
+  if ((rc = launch_variant(nl_variant(f_fwd), args.nl, n, st))) return rc;
+  return launch_variant(ad_reverse_variant(f), args, n, st);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// state expansion / validation launchers
+// ---------------------------------------------------------------------------------------------------------
+int check_expand_args(const cloudsc2_real* table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
+                      long long ngptot, cloudsc2_field field, long long* nblocks) {
+  if (!device_ok()) return no_device();
+  if (!table || !field.ptr) return fail(CLOUDSC2_EINVAL, "NULL argument");
+  if (klon < 1 || period < 1 || period > klon || start < 0 || nlevx < 1 || ndim < 1 || nproma < 1 || ngptot < 1)
+    return fail(CLOUDSC2_EINVAL, "expand/validate: need 1 <= period <= KLON, start >= 0, positive dimensions");
+  *nblocks = (ngptot + nproma - 1) / nproma;
+  if (field.block_stride < (long long)nproma * nlevx * ndim)
+    return fail(CLOUDSC2_EINVAL, "expand/validate: block stride smaller than NPROMA*NLEV*NDIM");
+  return 0;
+}
+
+int ten_ptrs(const cloudsc2_outputs* o, int nlev, TenPtrs& t) {
+  // order of the ERROR_NORM calls, cloudsc_driver_tl_mod.F90:233-242
+  const cloudsc2_field* f[10] = {&o->tent, &o->tenq, &o->tenl, &o->teni, &o->clc,
+                                 &o->fplsl, &o->fplsn, &o->fhpsl, &o->fhpsn, &o->covptot};
+  const int half[10] = {0, 0, 0, 0, 0, 1, 1, 1, 1, 0};
+  for (int i = 0; i < 10; ++i) {
+    if (!f[i]->ptr) return fail(CLOUDSC2_EINVAL, "taylor sums: NULL field");
+    t.p[i] = f[i]->ptr; t.stride[i] = f[i]->block_stride; t.nlevx[i] = nlev + half[i];
+  }
+  return 0;
+}
+
+}  // namespace
+
+// ncols_minmax < 0: the field's own whole blocks
+int validate_launch_impl(const cloudsc2_real* table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
+                         long long ngptot, cloudsc2_field field, double* workspace, double* stats, void* stream,
+                         long long ncols_minmax) {
+  long long nblocks;
+  int rc = check_expand_args(table, klon, period, start, nlevx, ndim, nproma, ngptot, field, &nblocks);
+  if (rc) return rc;
+  if (!workspace || !stats) return fail(CLOUDSC2_EINVAL, "NULL argument");
+  const long long total = nblocks * nproma * nlevx * ndim;
+  const int nparts = (int)std::min<long long>((total + 255) / 256, 2048);
+  hipLaunchKernelGGL(validate_partial_kernel, dim3(nparts), dim3(256), 0, (hipStream_t)stream, table, klon, period, start,
+                     nlevx, ndim, nproma, ngptot, nblocks, (const real_t*)field.ptr, field.block_stride, workspace,
+                     ncols_minmax < 0 ? nblocks * nproma : ncols_minmax);
+  hipLaunchKernelGGL(validate_final_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, nparts, stats,
+                     (int)(ncols_minmax > nblocks * nproma));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+}  // namespace cloudsc2
+
+// =========================================================================================================
+// C ABI
+// =========================================================================================================
+extern "C" {
+
+const char* cloudsc2_last_error(void) { return g_err.c_str(); }
+
+int cloudsc2_device_available(void) { return device_ok() ? 1 : 0; }
+int cloudsc2_current_device(void) {
+  int dev = 0;
+  if (!device_ok() || hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  return dev;
+}
+int cloudsc2_real_bytes(void) { return (int)sizeof(cloudsc2_real); }
+
+#ifdef C2_WAVE_TIMES
+// diagnostic build only: host_buf == NULL: (re)allocate the log for `nwaves` waves and arm it; else: copy it back (4 x u64 per wave)
+int cloudsc2_debug_wave_log(unsigned long long* host_buf, long long nwaves) {
+  static unsigned long long* dev = nullptr;
+  static long long cap = 0;
+  if (!host_buf) {
+    if (dev) (void)hipFree(dev);
+    HIP_TRY(hipMalloc((void**)&dev, (size_t)nwaves * 32));
+    HIP_TRY(hipMemset(dev, 0, (size_t)nwaves * 32));
+    cap = nwaves;
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_wave_log), &dev, sizeof(dev)));
+    return 0;
+  }
+  if (!dev || nwaves > cap) return fail(CLOUDSC2_EINVAL, "wave log not armed");
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(host_buf, dev, (size_t)nwaves * 32, hipMemcpyDeviceToHost));
+  return 0;
+}
+#endif
+
+void cloudsc2_set_math_mode(int precise) { g_precise.store(precise ? 1 : 0); }
+int cloudsc2_get_math_mode(void) { return g_precise.load(); }
+
+int cloudsc2_satur_launch(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, cloudsc2_field pap,
+                          cloudsc2_field t, cloudsc2_field qsat, void* stream) {
+  Geom g;
+  int rc = check_geom(prm, nproma, nlev, ngptot, g);
+  if (rc) return rc;
+  if (!pap.ptr || !t.ptr || !qsat.ptr) return fail(CLOUDSC2_EINVAL, "NULL field");
+  if (pap.block_stride != t.block_stride || pap.block_stride != qsat.block_stride)
+    return fail(CLOUDSC2_EINVAL, "pap, t, qsat must share one block stride");
+  SaturArgs args;
+  args.c = make_consts(*prm, 1.0);
+  args.g = g;
+  args.s = Strides{pap.block_stride, 0, 0, 0, 0};
+  args.pap = pap.ptr; args.t = t.ptr; args.qsat = qsat.ptr;
+  hipLaunchKernelGGL(precise_of(prm) ? satur_kernel<true> : satur_kernel<false>, dim3(grid_for(g.ncols_pad, kBlock)), dim3(kBlock), 0,
+                     (hipStream_t)stream, args);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int cloudsc2_nl_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                       const cloudsc2_inputs* in, const cloudsc2_outputs* out, cloudsc2_field zero_plane,
+                       double pert_lambda, void* stream) {
+  Sweep w;
+  int rc;
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, (!in || !out) ? "NULL argument block" : nullptr)) || (rc = w.trajectory(*in, *out, true)) ||
+      (rc = w.finish(*prm, ptsphy, in->qsat.ptr, {(long long)zero_plane.block_stride})))
+    return rc;
+  if (pert_lambda != 0.0) w.f |= C2F_PERT;
+  if (!prm->lphylin && !prm->ldrain1d) w.f |= C2F_NOLIN;  // cloudsc2.F90:349 (CLOUDSC2TL / CLOUDSC2AD have the LPHYLIN form only)
+  if ((w.f & C2F_NOLIN) && (w.f & C2F_PERT))
+    return fail(CLOUDSC2_EINVAL, "pert_lambda != 0 with LPHYLIN = 0: the perturbed runs of the Taylor test exist in the LPHYLIN form only");
+  NlArgs args = w.nl();
+  args.zero_plane = zero_plane.ptr; args.zero_stride = zero_plane.block_stride; args.lam = pert_lambda;
+  schedule(args.g, (const void*)nl_variant(w.f), true, nullptr);
+  return launch_variant(nl_variant(w.f), args, w.g.ncols_pad, (hipStream_t)stream);
+}
+
+int cloudsc2_tl_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                       const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                       const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out, void* stream) {
+  if (!pert_in) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, pert_in, 0.0, pert_out, nullptr, stream);
+}
+
+int cloudsc2_tl_launch_self(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                            const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, double supsat_increment,
+                            const cloudsc2_outputs* pert_out, double* yy, void* stream) {
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, nullptr, supsat_increment, pert_out, yy, stream);
+}
+
+int cloudsc2_ad_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                       const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                       const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out, cloudsc2_real* scratch,
+                       void* stream) {
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, scratch, stream, AdMode{0, false, false});
+}
+
+int cloudsc2_ad_launch_assign(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                              const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out, cloudsc2_real* scratch,
+                              void* stream) {
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, scratch, stream, AdMode{0, true, false});
+}
+
+int cloudsc2_ad_launch_forward(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, cloudsc2_real* scratch,
+                               void* stream) {
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, nullptr, nullptr, scratch, stream, AdMode{1, false, false});
+}
+
+int cloudsc2_ad_launch_reverse(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                               const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out, const cloudsc2_real* scratch,
+                               int assign, void* stream) {
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
+                        stream, AdMode{2, assign != 0, false});
+}
+
+int cloudsc2_vjp_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                        const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                        const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                        const cloudsc2_real* scratch, void* stream) {
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
+                        stream, AdMode{2, true, true});
+}
+
+int cloudsc2_ad_launch_reverse_norms(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                                     const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                                     const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                                     double* norms, double* blockmax, void* stream) {
+  if (!norms || !blockmax) return fail(CLOUDSC2_EINVAL, "NULL argument");
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, nullptr, stream,
+                        AdMode{2, true, false, norms, blockmax});
+}
+
+int cloudsc2_expand_launch(const cloudsc2_real* table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
+                           long long ngptot, cloudsc2_field field, void* stream) {
+  long long nblocks;
+  int rc = check_expand_args(table, klon, period, start, nlevx, ndim, nproma, ngptot, field, &nblocks);
+  if (rc) return rc;
+  const long long total = nblocks * nproma * nlevx * ndim;
+  const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 256 * 32);
+  hipLaunchKernelGGL(expand_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, table, klon, period, start, nlevx, ndim,
+                     nproma, ngptot, nblocks, field.ptr, field.block_stride);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int cloudsc2_validate_workspace_doubles(void) { return 5 * 2048; }
+
+int cloudsc2_validate_launch(const cloudsc2_real* table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
+                             long long ngptot, cloudsc2_field field, double* workspace, double* stats, void* stream) {
+  return validate_launch_impl(table, klon, period, start, nlevx, ndim, nproma, ngptot, field, workspace, stats, stream, -1);
+}
+
+int cloudsc2_taylor_sums_launch(int nproma, int nlev, int ngptot, const cloudsc2_outputs* f,
+                                const cloudsc2_outputs* f_pert, const cloudsc2_outputs* tl, double lambda,
+                                double* sums, void* stream) {
+  if (!f || !f_pert || !tl || !sums) return fail(CLOUDSC2_EINVAL, "NULL argument");
+  if (!device_ok()) return no_device();
+  TenPtrs a, b, c;
+  int rc;
+  if ((rc = ten_ptrs(f, nlev, a))) return rc;
+  if ((rc = ten_ptrs(f_pert, nlev, b))) return rc;
+  if ((rc = ten_ptrs(tl, nlev, c))) return rc;
+  int nblocks = (ngptot + nproma - 1) / nproma;
+  hipLaunchKernelGGL(taylor_sums_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, nproma, nlev, ngptot, a, b, c, lambda, sums);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int cloudsc2_taylor_sweep_work_doubles(int nproma, int ngptot, long long* n) {
+  if (!n || nproma < 1 || ngptot < 1) return fail(CLOUDSC2_EINVAL, "taylor sweep: bad argument");
+  *n = (long long)(10 * kTaylorLambdas + 10) * (((long long)ngptot + nproma - 1) / nproma) * nproma;
+  return 0;
+}
+
+int cloudsc2_taylor_sweep_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int nproma_stat,
+                                 const cloudsc2_inputs* in, const cloudsc2_outputs* out, const cloudsc2_outputs* tl,
+                                 double* work, double* sums, void* stream) {
+  Sweep w;
+  int rc = w.begin(prm, nproma, nlev, ngptot, (!in || !out || !tl || !work || !sums) ? "NULL argument" : nullptr);
+  if (rc) return rc;
+  if (nproma_stat < 1) return fail(CLOUDSC2_EINVAL, "taylor sweep: the block of the statistic must be >= 1");
+  if (!prm->lphylin && !prm->ldrain1d) return fail(CLOUDSC2_EINVAL, "taylor sweep: CLOUDSC_DRIVER_TL runs with LPHYLIN (cloudsc2tl.F90 has that form only)");
+  TaylorArgs args;
+  if ((rc = w.trajectory(*in, *out, true))) return rc;
+  if ((rc = ten_ptrs(tl, nlev, args.tl))) return rc;
+  if ((rc = w.finish(*prm, ptsphy, in->qsat.ptr, {}))) return rc;
+  args.nl = w.nl();
+  TenLambdas lam;
+  for (int il = 0; il < kTaylorLambdas; ++il) {
+    lam.v[il] = pow(10.0, -(double)(il + 1));  // ZLAMBDA=10._JPRB**(-REAL(ILAM,JPRB)), cloudsc_driver_tl_mod.F90:199
+    args.lam[il] = (real_t)lam.v[il];
+  }
+  args.colsum = work;
+  const Geom& g = w.g;
+  const long long nwaves = (g.ncols_pad + kTaylorCols - 1) / kTaylorCols;
+  const long long per8 = 8LL * kBlock;  // the kernel's XCD mapping wants a multiple of 8 blocks
+  if ((rc = launch_variant(taylor_variant(w.f), args, (nwaves * 64 + per8 - 1) / per8 * per8, (hipStream_t)stream))) return rc;
+  const long long nblocks_stat = ((long long)ngptot + nproma_stat - 1) / nproma_stat;
+  if (nproma_stat <= 512) {
+    hipLaunchKernelGGL(taylor_reduce_kernel, dim3((unsigned)nblocks_stat), dim3(128), 0, (hipStream_t)stream, nproma_stat, ngptot,
+                       g.ncols_pad, nblocks_stat, lam, (const double*)work, sums);
+  } else {
+    hipLaunchKernelGGL(taylor_reduce_wide_kernel, dim3((unsigned)nblocks_stat, 10 * kTaylorLambdas + 10), dim3(256), 0, (hipStream_t)stream,
+                       nproma_stat, ngptot, g.ncols_pad, nblocks_stat, lam, (const double*)work, sums);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int cloudsc2_adjoint_norms_launch(int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                                  const cloudsc2_field* qsat, const cloudsc2_outputs* y,
+                                  const cloudsc2_inputs* x_adj, double* norms, double* blockmax, void* stream) {
+  // y == NULL: second half only (norm2/norm3 from norm1 already in norms); x_adj == NULL: first half only.
+  if (!norms) return fail(CLOUDSC2_EINVAL, "NULL argument");
+  if (!device_ok()) return no_device();
+  Geom g;
+  long long nblocks = ((long long)ngptot + nproma - 1) / nproma;
+  g.nproma = nproma; g.nlev = nlev; g.ngptot = ngptot; g.ncols_pad = nblocks * nproma; g.kb0 = g.kb1 = 0; g.fair = 0;
+  dim3 grid(grid_for(g.ncols_pad, kBlock)), block(kBlock);
+  int rc;
+  if (y) {
+    Strides sa = {0, 0, 0, 0, 0};
+    OutPtrs yp;
+    if ((rc = resolve_out(*y, true, sa, yp))) return rc;
+    hipLaunchKernelGGL(adjoint_norm1_kernel, grid, block, 0, (hipStream_t)stream, g, sa, yp, norms);
+    HIP_TRY(hipGetLastError());
+  }
+  if (x_adj) {
+    if (!traj_in || !qsat || !qsat->ptr || !blockmax) return fail(CLOUDSC2_EINVAL, "NULL argument");
+    Strides s = {0, 0, 0, 0, 0}, sa = {0, 0, 0, 0, 0};
+    InPtrs ip, xp;
+    if ((rc = resolve_in(*traj_in, false, s, ip))) return rc;
+    if ((rc = resolve_in(*x_adj, true, sa, xp))) return rc;
+    hipLaunchKernelGGL(adjoint_norm2_kernel, grid, block, 0, (hipStream_t)stream, g, s, sa, ip, (const real_t*)qsat->ptr,
+                       qsat->block_stride, xp, norms, g.ncols_pad, blockmax);
+    HIP_TRY(hipGetLastError());
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // cloudsc2_level.hpp -- one model level of one grid column of CLOUDSC2: trajectory, tangent-linear
-// and adjoint, as inline device functions.  All three HIP kernels (cloudsc2_kernels.hip) are built from
+// and adjoint, as inline device functions.  All three HIP kernels (cloudsc2_sweep_kernels.hpp) are built from
 // these, so the TL and the AD see bit-identical trajectory values and branch decisions
 // (the reference's linearisation freezes every branch on the trajectory).
 //

@@ -126,7 +126,7 @@ class FlatFields:
 
         # NPROMA < 64: a wave spans two or more blocks (twice the streams): interleaved (TL 2.86 -> 1.66 ms, AD 4.07 -> 3.23 ms at
         # NPROMA 32).  NPROMA >= 64: separate arrays are as fast (TL) or 4 % faster (AD).  The library's own test drivers follow
-        # the same rule (csrc/cloudsc2_driver.inc: pair_take).
+        # the same rule (csrc/cloudsc2_driver.hip: pair_take).
         layout = os.environ.get("CLOUDSC2_SCRATCH_LAYOUT") or ("blocked" if nproma < 64 else "flat")
         if arena is None:  # `arena`: carve the set out of an existing allocation (DeviceState.from_table(..., reserve=...))
             arena = B.DeviceArena(cls.pair_bytes(nb, nlev, nproma), device)
@@ -156,13 +156,13 @@ class DeviceState:
     # what the sweeps write (cloudsc2.F90:135-149); inside the arena the read-only arrays come first, like in the library's own state
     WRITTEN = ("PA", "PCOVPTOT", "PFPLSL", "PFPLSN", "PFHPSL", "PFHPSN", "B_LOC")
 
-    # the order of the arrays inside the arena = the library's own (csrc/cloudsc2_driver.inc: state_take), which is what
+    # the order of the arrays inside the arena = the library's own (csrc/cloudsc2_driver.hip: state_take), which is what
     # cloudsc2_device_malloc_state lays out in every candidate when it times the NL sweep on it
     ORDER = ("PT", "PQ", "PAP", "PLU", "PLUDE", "PMFU", "PMFD", "PSUPSAT", "PAPH", "B_CML", "PCLV",
              "PA", "PCOVPTOT", "QSAT", "PFPLSL", "PFPLSN", "PFHPSL", "PFHPSN", "B_LOC")
 
     def _make_arenas(self, read_shapes, written_shapes, reserve: int = 0):
-        """The whole state in ONE placed allocation (cloudsc2_device_malloc_state), like the library's own (csrc/cloudsc2_driver.inc:
+        """The whole state in ONE placed allocation (cloudsc2_device_malloc_state), like the library's own (csrc/cloudsc2_driver.hip:
         state_take): measured on one box, fresh processes, NL at 160 000 columns: 0.812 ms on 8 of 8, against 0.88-0.93 ms with
         the written arrays placed and the read-only ones in a separate (plain or placed) allocation, and 0.90-0.96 ms without
         placement (profiles/r02_placement/z_one_arena_vs_split.txt).  The allocator judges its candidates by the NL sweep on a state

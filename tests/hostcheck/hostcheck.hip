@@ -50,7 +50,7 @@ template <unsigned F> struct HcTaylor {
   }
 };
 
-// same derivation as get_tables() in cloudsc2_kernels.hip
+// same derivation as get_tables() in cloudsc2_launch.hip
 
 static void hc_tables(const cloudsc2_params& p, LevelTab& tab, Geom& g) {
   memset(&tab, 0, sizeof(tab));

@@ -118,9 +118,9 @@ def test_bench_cpu_baseline_leg_runs():
     assert cb["value"] > 0 and cb["numomp4_value"] > 0 and cb["cores"] >= 1
 
 
-def test_device_state_layout_lists_every_array_once_in_the_librarys_order():
+def test_device_state_layout_matches_state_take_in_cloudsc2_driver_hip():
     """DeviceState.ORDER is the order in which the arrays are carved out of the state's allocation; it has to be the library's own
-    (csrc/cloudsc2_driver.inc: state_take), because cloudsc2_device_malloc_state judges its candidates by running the NL sweep on a
+    (csrc/cloudsc2_driver.hip: state_take), because cloudsc2_device_malloc_state judges its candidates by running the NL sweep on a
     state laid out that way: read-only arrays first, then everything the sweeps write."""
     import re
 
@@ -130,7 +130,7 @@ def test_device_state_layout_lists_every_array_once_in_the_librarys_order():
     assert len(DeviceState.ORDER) == len(set(DeviceState.ORDER)) == len(names) and set(DeviceState.ORDER) == names
     written = [n for n in DeviceState.ORDER if n in DeviceState.WRITTEN or n == "QSAT"]
     assert DeviceState.ORDER[-len(written):] == tuple(written)  # what the sweeps write lies at the end of the allocation
-    src = open(os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", "cloudsc2_driver.inc")).read()
+    src = open(os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", "cloudsc2_driver.hip")).read()
     body = src[src.index("void state_take("):]
     body = body[:body.index("\n}\n")]
     lib_order = [m.upper() for m in re.findall(r"d\.(\w+) = a(?:in|out)\.take", body)]

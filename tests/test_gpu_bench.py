@@ -78,7 +78,7 @@ def test_two_ranks_on_one_gpu_rehearse_the_multi_gpu_path(tmp_path):
     assert abs(d["value"] - 2 * 16384 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]  # whole job: both ranks' columns / max time
     per = d["roofline"]["placement_per_rank"]
     assert [p["rank"] for p in per] == [0, 1] and all(p["kernel_ms_avg"] > 0 for p in per)
-    assert per[0]["candidates"] == 1  # two ranks share the device: nothing is searched (cloudsc2_alloc.inc)
+    assert per[0]["candidates"] == 1  # two ranks share the device: nothing is searched (cloudsc2_alloc.hip)
     assert len(d["roofline"]["kernel_ms_avg_per_rank"]) == 2
     v = d["verdicts"]
     assert v["backend"] == "gloo" and v["tl_passed"] and v["ad_ok"] and len(v["tl_znormg"]) == 10, v

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """When do the waves of one NL launch start and finish, and where do they run?  Needs a diagnostic build of the library:
-    hipcc <CXXFLAGS of csrc/Makefile> -DC2_WAVE_TIMES -DC2_SINGLE_TU -shared -o /tmp/wt.so csrc/cloudsc2_kernels.hip
-    CLOUDSC2_LIB=/tmp/wt.so python tools/wave_times.py [NGPTOT [NPROMA [nl|tl|ad|ad_reverse]]]
+    make -C dwarf_p_cloudsc2_tl_ad_amd/csrc variant NAME=wt DEFS=-DC2_WAVE_TIMES
+    CLOUDSC2_LIB=variants/wt.so python tools/wave_times.py [NGPTOT [NPROMA [nl|tl|ad|ad_reverse]]]
 Prints the distribution of the waves' start and end times (microseconds after the first wave's start; 100 MHz clock, 10 ns
 resolution) for a launch in steady state, per XCD and per number of waves sharing a SIMD."""
 import ctypes as C
@@ -65,7 +65,7 @@ for rep in range(5):
     for v in per_simd.values():
         for k, (a_, b_) in enumerate(v):
             nth.setdefault(k, []).append((a_, b_, b_ - a_))
-    # the pacing rule's prediction (cloudsc2_kernels.hip: set_pace; one wave per SIMD: 2 waves per workgroup, CUs x 2 slots): workgroups
+    # the pacing rule's prediction (cloudsc2_policy.hip: pace; one wave per SIMD: 2 waves per workgroup, CUs x 2 slots): workgroups
     # at position p < rem of a round are expected on the slots that run one workgroup more -- checked against where they really ran
     pace = None
     if kind != "nl":
