@@ -7,7 +7,7 @@ namespace cloudsc2 {
 namespace {
 C2_VARIANT_TABLE(g_ad_reverse_kernels, ad_reverse_kernel, AdArgs, 128,
                  (!(F & C2F_ADNORM) || ((F & C2F_ASSIGN) && !(F & C2F_EVAP))) && (!(F & C2F_VJP) || ((F & C2F_ASSIGN) && !(F & C2F_ADNORM))))
-C2_VARIANT_TABLE(g_ad_kernels, ad_kernel, AdArgs, 64, C2_AD_FUSED != 0 && !(F & C2F_ADNORM))
+C2_VARIANT_TABLE(g_ad_kernels, ad_kernel, AdArgs, 64, !(F & C2F_ADNORM))
 }  // namespace
 KernelFn<AdArgs> ad_reverse_variant(unsigned f) { return f < g_ad_reverse_kernels.size() ? g_ad_reverse_kernels[f] : nullptr; }
 KernelFn<AdArgs> ad_variant(unsigned f) { return f < g_ad_kernels.size() ? g_ad_kernels[f] : nullptr; }

@@ -499,9 +499,6 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   Sweep w;
   int rc = w.begin(prm, nproma, nlev, ngptot, (!traj_in || !traj_out || !pert_out) ? "NULL argument block" : nullptr);
   if (rc) return rc;
-#if C2_TL_DMA
-  if (nproma != 128) return fail(CLOUDSC2_EINVAL, "this experiment build (C2_TL_DMA) runs the TL sweep for NPROMA 128 only");
-#endif
   const cloudsc2_field* tf[10] = {&traj_out->tent, &traj_out->tenq, &traj_out->tenl, &traj_out->teni, &traj_out->clc,
                                   &traj_out->fplsl, &traj_out->fplsn, &traj_out->fhpsl, &traj_out->fhpsn, &traj_out->covptot};
   int nset = 0;
@@ -597,7 +594,7 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
     schedule(args.nl.g, nullptr, false, rev);
     return launch_variant(ad_reverse_variant(f), args, n, st);
   }
-  if (C2_AD_FUSED == 1 || (C2_AD_FUSED == 2 && n > kAdSplitBelow)) {
+  if (!kAdSplitSmall || n > kAdSplitBelow) {
     schedule(args.nl.g, nullptr, false, (const void*)ad_variant(f));
     return launch_variant(ad_variant(f), args, n, st);
   }

@@ -23,15 +23,6 @@
 #include <cmath>
 #include "../../include/cloudsc2_hip.h"
 
-// -DC2_EVAP_FAST=0: the evaporation block (LEVAPLS2 / LDRAIN1D variants) keeps IEEE divisions and pow() in fast mode too (A/B builds)
-#ifndef C2_EVAP_FAST
-#define C2_EVAP_FAST 1
-#endif
-// -DC2_EVAP_FAST_TLAD=0: only the tangent / adjoint blocks of level_tl / level_ad keep their divisions, pow() and sqrt() (A/B builds)
-#ifndef C2_EVAP_FAST_TLAD
-#define C2_EVAP_FAST_TLAD C2_EVAP_FAST
-#endif
-
 namespace cloudsc2 {
 
 // JPRB (src/common/module/parkind1.F90:40-44): fp64, or fp32 when the library is built with -DCLOUDSC2_SINGLE (the
@@ -750,7 +741,6 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
   t.zpreclr = RC(0.0); t.omc = RC(1.0); t.zsqp = RC(1.0);
   if (t.llo2) {
     t.omc = RC(1.0) - t.clc;
-#if C2_EVAP_FAST
     if (!P) {
       // fast arithmetic (round 5): the block's seven IEEE divisions on three refined v_rcp_f64 (1/covptot1 and 1/omc^2 from one,
       // 1/covpclr, 1/prtot and 1/p_surf from one, 1/(1 + beta dt corqs) alone), the division by ZDTGDP = dt g / dp as a product
@@ -780,26 +770,24 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
       t.zevaps = dq * t.sfln2;
       rfln = rfln - t.zevapr;
       sfln = sfln - t.zevaps;
-    } else
-#endif
-    {
-    t.zpreclr1 = t.zprtot * t.covpclr / t.covptot1;
-    t.zqe = x.qs - (x.qs - t.zqlim) * t.covpclr / (t.omc * t.omc);
-    t.zsqp = sqrt(x.pap / x.paph_surf);
-    t.zbeta = c->rg * c->rpecons * pow(t.zsqp / RC(5.09e-3) * t.zpreclr1 / t.covpclr, RC(0.5777));
-    t.zb = ptsphy4 * t.zbeta * (x.qs - t.zqe) / (RC(1.0) + t.zbeta * ptsphy4 * t.zcorqs);
-    t.zdtgdp = ptsphy4 * c->rg / (x.paph_k1 - x.paph_k);
-    t.zdpr1 = t.covpclr * t.zb / t.zdtgdp;
-    t.dpr_clip = t.zdpr1 > t.zpreclr1;
-    t.zdpr = t.dpr_clip ? t.zpreclr1 : t.zdpr1;
-    t.zpreclr = t.zpreclr1 - t.zdpr;
-    t.reset = t.zpreclr <= RC(0.0);
-    if (t.reset) covptot = t.clc;
-    pcovptot = covptot;
-    t.zevapr = t.zdpr * t.rfln2 / t.zprtot;
-    rfln = rfln - t.zevapr;
-    t.zevaps = t.zdpr * t.sfln2 / t.zprtot;
-    sfln = sfln - t.zevaps;
+    } else {
+      t.zpreclr1 = t.zprtot * t.covpclr / t.covptot1;
+      t.zqe = x.qs - (x.qs - t.zqlim) * t.covpclr / (t.omc * t.omc);
+      t.zsqp = sqrt(x.pap / x.paph_surf);
+      t.zbeta = c->rg * c->rpecons * pow(t.zsqp / RC(5.09e-3) * t.zpreclr1 / t.covpclr, RC(0.5777));
+      t.zb = ptsphy4 * t.zbeta * (x.qs - t.zqe) / (RC(1.0) + t.zbeta * ptsphy4 * t.zcorqs);
+      t.zdtgdp = ptsphy4 * c->rg / (x.paph_k1 - x.paph_k);
+      t.zdpr1 = t.covpclr * t.zb / t.zdtgdp;
+      t.dpr_clip = t.zdpr1 > t.zpreclr1;
+      t.zdpr = t.dpr_clip ? t.zpreclr1 : t.zdpr1;
+      t.zpreclr = t.zpreclr1 - t.zdpr;
+      t.reset = t.zpreclr <= RC(0.0);
+      if (t.reset) covptot = t.clc;
+      pcovptot = covptot;
+      t.zevapr = t.zdpr * t.rfln2 / t.zprtot;
+      rfln = rfln - t.zevapr;
+      t.zevaps = t.zdpr * t.sfln2 / t.zprtot;
+      sfln = sfln - t.zevaps;
     }
   }
 
@@ -1059,7 +1047,6 @@ C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
   real_t zevapr = RC(0.0), zevaps = RC(0.0), pcovptot = RC(0.0);
   if (t.llo2) {
     real_t zprtot = zrfln + zsfln;
-#if C2_EVAP_FAST_TLAD
     // The block's seventeen divisions, its pow() and its sqrt() on six reciprocals (two refined v_rcp_f64), and the tangent of
     // ZBETA = RG RPECONS (B / 5.09e-3)^0.5777, B = sqrt(p / p_surf) ZPRECLR / ZCOVPCLR, as 0.5777 ZBETA5 dB / B with
     //   dB / B = dZPRECLR / ZPRECLR5 + dp / (2 p) - dp_surf / (2 p_surf) - dZCOVPCLR / ZCOVPCLR5
@@ -1085,29 +1072,6 @@ C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
     const real_t q2 = t.zdpr * zprtot * (r_prtot * r_prtot);
     zevapr = (t.zdpr * zrfln + t.rfln2 * zdpr) * r_prtot - t.rfln2 * q2;
     zevaps = (t.zdpr * zsfln + t.sfln2 * zdpr) * r_prtot - t.sfln2 * q2;
-#else
-    real_t zpreclr = (t.zprtot * zcovpclr + t.covpclr * zprtot) / t.covptot1 -
-                     t.zprtot * t.covpclr * zcovptot / (t.covptot1 * t.covptot1);
-    real_t omc2 = t.omc * t.omc;
-    real_t zqe = dx.qs - ((x.qs - t.zqlim) * zcovpclr + t.covpclr * dx.qs - t.covpclr * zqlim) / omc2 -
-                 RC(2.0) * (x.qs - t.zqlim) * t.covpclr * pclc / (omc2 * t.omc);
-    real_t zbeta = RC(0.5777) * (rg * c->rpecons / RC(5.09e-3)) *
-                   pow(RC(5.09e-3) * t.covpclr / (t.zpreclr1 * t.zsqp), RC(0.4223)) *
-                   ((t.zsqp * zpreclr + RC(0.5) * t.zpreclr1 * dx.pap / sqrt(x.pap * x.paph_surf) -
-                     RC(0.5) * t.zpreclr1 * t.zsqp * dx.paph_surf / x.paph_surf) / t.covpclr -
-                    t.zpreclr1 * t.zsqp * zcovpclr / (t.covpclr * t.covpclr));
-    real_t den = RC(1.0) + t.zbeta * ptsphy * t.zcorqs;
-    real_t zb = ptsphy * ((x.qs - t.zqe) * zbeta + t.zbeta * dx.qs - t.zbeta * zqe) / den -
-                (ptsphy * ptsphy) * t.zbeta * (x.qs - t.zqe) * (t.zbeta * zcorqs + t.zcorqs * zbeta) / (den * den);
-    real_t zdtgdp = -ptsphy * rg * (dx.paph_k1 - dx.paph_k) * rdp2;
-    real_t zdpr = (t.covpclr * zb + t.zb * zcovpclr) / t.zdtgdp - t.covpclr * t.zb * zdtgdp / (t.zdtgdp * t.zdtgdp);
-    if (t.dpr_clip) zdpr = zpreclr;
-    zpreclr = zpreclr - zdpr;
-    if (t.reset) zcovptot = pclc;
-    pcovptot = zcovptot;
-    zevapr = (t.zdpr * zrfln + t.rfln2 * zdpr) / t.zprtot - t.zdpr * t.rfln2 * zprtot / (t.zprtot * t.zprtot);
-    zevaps = (t.zdpr * zsfln + t.sfln2 * zdpr) / t.zprtot - t.zdpr * t.sfln2 * zprtot / (t.zprtot * t.zprtot);
-#endif
     zrfln = zrfln - zevapr;
     zsfln = zsfln - zevaps;
   }
@@ -1331,7 +1295,6 @@ C2_HD void level_ad(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
   real_t a_prtot = RC(0.0);
   if (t.llo2) {
     real_t zdpr = RC(0.0), zpreclr = RC(0.0), zb = RC(0.0), zbeta = RC(0.0), zqe = RC(0.0), a_dtgdp = RC(0.0);
-#if C2_EVAP_FAST_TLAD
     // the transpose of level_tl's fast block, term by term: six reciprocals from two refined v_rcp_f64, 1 / ZDTGDP5 = dp / (dt g),
     // and the adjoint of ZBETA through dB / B (w = 0.5777 ZBETA5 zbeta*), the power and the root cancelled
     real_t r_cov1, r_omc, r_clr, r_prtot, r_psurf, r_den;
@@ -1386,55 +1349,6 @@ C2_HD void level_ad(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
     a_covpclr += t.zprtot * zpreclr * r_cov1;
     a_prtot += t.covpclr * zpreclr * r_cov1;
     a_covptot -= t.zprtot * t.covpclr * zpreclr * (r_cov1 * r_cov1);
-#else
-    // ice proportion
-    a_evaps -= a_sfln;
-    a_sfln += t.zdpr * a_evaps / t.zprtot;
-    zdpr += t.sfln2 * a_evaps / t.zprtot;
-    a_prtot -= t.zdpr * t.sfln2 * a_evaps / (t.zprtot * t.zprtot);
-    // warm proportion
-    a_evapr -= a_rfln;
-    a_rfln += t.zdpr * a_evapr / t.zprtot;
-    zdpr += t.rfln2 * a_evapr / t.zprtot;
-    a_prtot -= t.zdpr * t.rfln2 * a_evapr / (t.zprtot * t.zprtot);
-    // clear-sky flux
-    a_covptot += ya.covptot;
-    if (t.reset) { a_clc += a_covptot; a_covptot = RC(0.0); }
-    zdpr -= zpreclr;
-    if (t.dpr_clip) { zpreclr += zdpr; zdpr = RC(0.0); }
-    zb += t.covpclr * zdpr / t.zdtgdp;
-    a_covpclr += t.zb * zdpr / t.zdtgdp;
-    a_dtgdp -= t.covpclr * t.zb * zdpr / (t.zdtgdp * t.zdtgdp);
-    {
-      real_t g = ptsphy * rg * a_dtgdp * (t.rdp * t.rdp);
-      a_paph_k1 -= g;
-      a_paph_k += g;
-    }
-    // implicit solution
-    real_t den = RC(1.0) + t.zbeta * ptsphy * t.zcorqs;
-    zbeta += ptsphy * (x.qs - t.zqe) * zb / den;
-    a_qs += ptsphy * t.zbeta * zb / den;
-    zqe -= ptsphy * t.zbeta * zb / den;
-    a_corqs -= (ptsphy * ptsphy) * t.zbeta * (x.qs - t.zqe) * t.zbeta * zb / (den * den);
-    zbeta -= (ptsphy * ptsphy) * t.zbeta * (x.qs - t.zqe) * t.zcorqs * zb / (den * den);
-    // zbeta
-    real_t zxx = RC(0.5777) * (rg * c->rpecons / RC(5.09e-3)) * pow(RC(5.09e-3) * t.covpclr / (t.zpreclr1 * t.zsqp), RC(0.4223));
-    zpreclr += zxx * t.zsqp * zbeta / t.covpclr;
-    a_pap += (zxx * RC(0.5) * t.zpreclr1 * zbeta / sqrt(x.pap * x.paph_surf)) / t.covpclr;
-    a_paph_surf -= (zxx * RC(0.5) * t.zpreclr1 * t.zsqp * zbeta / x.paph_surf) / t.covpclr;
-    a_covpclr -= zxx * t.zpreclr1 * t.zsqp * zbeta / (t.covpclr * t.covpclr);
-    // zqe
-    real_t omc2 = t.omc * t.omc;
-    a_qs += zqe;
-    a_covpclr -= (x.qs - t.zqlim) * zqe / omc2;
-    a_qs -= t.covpclr * zqe / omc2;
-    a_qlim += t.covpclr * zqe / omc2;
-    a_clc -= RC(2.0) * (x.qs - t.zqlim) * t.covpclr * zqe / (omc2 * t.omc);
-    // zpreclr
-    a_covpclr += t.zprtot * zpreclr / t.covptot1;
-    a_prtot += t.covpclr * zpreclr / t.covptot1;
-    a_covptot -= t.zprtot * t.covpclr * zpreclr / (t.covptot1 * t.covptot1);
-#endif
     a_evapr = RC(0.0);
     a_evaps = RC(0.0);
   }

@@ -19,21 +19,7 @@ namespace cloudsc2 {
 // kernels: thin wrappers around the per-column functions of cloudsc2_column.hpp.  Every kernel has ONE by-value
 // argument block; the device code reads it in place from the kernel-argument segment (scalar cache).
 // ---------------------------------------------------------------------------------------------------------
-#ifndef C2_BLOCK
-#define C2_BLOCK 128
-#endif
-constexpr int kBlock = C2_BLOCK;
-// minimum waves per SIMD requested from the register allocator (0 = let the compiler decide)
-#ifndef C2_NL_WAVES
-#define C2_NL_WAVES 0
-#endif
-#ifndef C2_TL_WAVES
-#define C2_TL_WAVES 0
-#endif
-#ifndef C2_AD_WAVES
-#define C2_AD_WAVES 0
-#endif
-#define C2_BOUNDS(w) __launch_bounds__(kBlock, (w) > 0 ? (w) : 1)
+constexpr int kBlock = 128;
 
 __device__ __forceinline__ long long global_column() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
 
@@ -47,8 +33,6 @@ __device__ __forceinline__ const C2_CONST_AS T* kernarg() {
 #define C2_KERNEL_BODY(call)
 #endif
 
-// The NL variants without the evaporation branch fit 168 VGPRs (3 waves per SIMD) even with the two-level-deep
-// prefetch; asking for it keeps the allocator from spending a few registers too many.  The others take what they need.
 // -DC2_WAVE_TIMES (diagnostic build, tools/wave_times.py): every wave of the NL kernel logs when it started and ended (the 100 MHz
 // constant clock) and where it ran (HW_ID, XCC_ID) -- how evenly a launch's waves start, progress and finish.
 #ifdef C2_WAVE_TIMES
@@ -67,8 +51,11 @@ __device__ unsigned long long* g_wave_log = nullptr;  // [wave][4]: start, end, 
 #define C2_WAVE_LOG_BEGIN
 #define C2_WAVE_LOG_END
 #endif
+
+// The NL variants without the evaporation branch fit 168 VGPRs (3 waves per SIMD) even with the two-level-deep
+// prefetch; asking for it keeps the allocator from spending a few registers too many.  The others take what they need.
 template <unsigned F>
-__global__ void __launch_bounds__(kBlock, (C2_NL_WAVES > 0) ? C2_NL_WAVES : ((F & C2F_EVAP) ? 1 : 3)) nl_kernel(NlArgs args) {
+__global__ void __launch_bounds__(kBlock, (F & C2F_EVAP) ? 1 : 3) nl_kernel(NlArgs args) {
   C2_KERNEL_BODY(C2_WAVE_LOG_BEGIN);
   C2_KERNEL_BODY((nl_column<F>(global_column(), kernarg<NlArgs>())));
   C2_KERNEL_BODY(C2_WAVE_LOG_END);
@@ -78,32 +65,20 @@ __global__ void __launch_bounds__(kBlock, (C2_NL_WAVES > 0) ? C2_NL_WAVES : ((F 
 // per SIMD) they spill at most 7 dwords, and all 2500 waves of a 160 000-column launch are resident at once instead of
 // 2048 + 452 (0.94 -> 0.88 ms).  Every other TL variant, and the fp64 ones, spill heavily below what they ask for.
 template <unsigned F>
-__global__ void __launch_bounds__(kBlock, (C2_TL_WAVES > 0) ? C2_TL_WAVES
-                                          : (sizeof(real_t) == 4 && (F & C2F_OFF32) && !(F & C2F_EVAP)) ? 3 : 1)
+__global__ void __launch_bounds__(kBlock, (sizeof(real_t) == 4 && (F & C2F_OFF32) && !(F & C2F_EVAP)) ? 3 : 1)
 tl_kernel(TlArgs args) {
   C2_KERNEL_BODY(C2_WAVE_LOG_BEGIN);
-#if C2_TL_DMA  // experiment build (profiles/EXPERIMENTS.md section 6): the look-ahead through LDS-DMA; NPROMA 128, fp64 only
-  static_assert(sizeof(real_t) == 8 && kBlock == 128, "C2_TL_DMA: fp64, workgroups of 128 threads");
-  C2_KERNEL_BODY((tl_column_dma<F>(kernarg<TlArgs>())));
-#else
   C2_KERNEL_BODY((tl_column<F>(global_column(), kernarg<TlArgs>())));
-#endif
   C2_KERNEL_BODY(C2_WAVE_LOG_END);
 }
 
-// C2_AD_FUSED=1: one kernel runs a column's trajectory pass and then its reverse pass (waves in the bandwidth-heavy
-// forward phase and waves in the arithmetic-heavy reverse phase share the CUs); 0: two kernels in stream order;
-// 2: both are built and launches of at most kAdSplitBelow columns take the two-kernel form.  fp64: the two forms measure
-// the same at every size (both passes need one wave per SIMD's worth of registers in the fused kernel anyway).  fp32: the
-// trajectory pass alone runs six waves per SIMD instead of the fused kernel's two, which is worth 7 % when the whole
-// launch is one round of waves (160 000 columns: 1.71 -> 1.59 ms) and nothing at 1 M columns (9.09 vs 9.17 ms).
-#ifndef C2_AD_FUSED
-#if defined(CLOUDSC2_SINGLE)
-#define C2_AD_FUSED 2
-#else
-#define C2_AD_FUSED 1
-#endif
-#endif
+// CLOUDSC2AD is launched fused (ad_kernel: one kernel runs a column's trajectory pass and then its reverse pass; waves in the
+// bandwidth-heavy forward phase and waves in the arithmetic-heavy reverse phase share the CUs) or split (nl_kernel, then
+// ad_reverse_kernel, in stream order).  fp64: the two forms measure the same at every size (both passes need one wave per
+// SIMD's worth of registers in the fused kernel anyway), so it is always fused.  fp32: the trajectory pass alone runs six waves
+// per SIMD instead of the fused kernel's two, which is worth 7 % when the whole launch is one round of waves (160 000 columns:
+// 1.71 -> 1.59 ms) and nothing at 1 M columns (9.09 vs 9.17 ms), so launches of at most kAdSplitBelow columns are split.
+constexpr bool kAdSplitSmall = sizeof(real_t) == 4;
 constexpr long long kAdSplitBelow = 400000;
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
@@ -115,7 +90,7 @@ __device__ __forceinline__ void atomic_max_pos(double* addr, double v) {
   atomicMax((unsigned long long*)addr, (unsigned long long)__double_as_longlong(v));
 }
 template <unsigned F>
-__global__ void C2_BOUNDS(C2_AD_WAVES) ad_reverse_kernel(AdArgs args) {
+__global__ void __launch_bounds__(kBlock, 1) ad_reverse_kernel(AdArgs args) {
   C2_KERNEL_BODY(C2_WAVE_LOG_BEGIN);
 #if defined(__HIP_DEVICE_COMPILE__)
   if constexpr ((F & C2F_ADNORM) != 0) {  // the adjoint test's norms formed in the sweep: the wave's largest |norm3| joins the global one
@@ -128,7 +103,7 @@ __global__ void C2_BOUNDS(C2_AD_WAVES) ad_reverse_kernel(AdArgs args) {
   C2_KERNEL_BODY(C2_WAVE_LOG_END);
 }
 template <unsigned F>
-__global__ void C2_BOUNDS(C2_AD_WAVES) ad_kernel(AdArgs args) {
+__global__ void __launch_bounds__(kBlock, 1) ad_kernel(AdArgs args) {
   static_assert(!(F & C2F_VJP), "C2F_VJP is C2F_NOLIN to nl_column: the fused kernel has no vector-Jacobian form");
   C2_KERNEL_BODY(C2_WAVE_LOG_BEGIN);
   C2_KERNEL_BODY((nl_column<(F & ~C2F_ASSIGN) | C2F_CKPT>(global_column(), &kernarg<AdArgs>()->nl)));
