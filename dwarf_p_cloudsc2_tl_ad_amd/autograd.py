@@ -5,7 +5,16 @@
 
 ``inputs`` maps every name of ``binding.IN_NAMES`` to a device tensor; ``out`` is a :class:`Cloudsc2Outputs` namedtuple over
 ``binding.OUT_NAMES``.  ``torch.autograd.grad`` / ``.backward()``, ``torch.autograd.forward_ad`` and ``torch.func.jvp`` / ``vjp`` /
-``grad`` all work; double backward, vmap and gradients with respect to ``prm`` / ``ptsphy`` do not.
+``grad`` / ``vmap`` / ``jacfwd`` / ``jacrev`` all work; double backward, nested vmap, ``torch.autograd.grad(...,
+is_grads_batched=True)`` (use ``torch.func.vmap`` of the vjp function instead) and gradients with respect to ``prm`` / ``ptsphy`` do
+not.
+
+Batches.  Under ``torch.func.vmap`` the op distinguishes two cases.  Several tangents or cotangents over ONE state -- ``jacfwd``,
+``jacrev``, ``vmap(jvp)``, ``vmap(vjp_fn)`` -- are one ``cloudsc2_tl_launch_batch`` / ``cloudsc2_vjp_launch_batch`` call: the
+trajectory is read once per ``cloudsc2_batch_max()`` directions instead of once per direction, and every direction's result is the
+bits of the unbatched call.  A batch of STATES (``vmap`` of the op itself, with or without batched directions) is
+folded into the block dimension, columns being independent: one launch over ``K * nblocks`` blocks when the blocks are full, one
+launch per state when ``ngptot`` leaves a padded tail (which must stay zero, and uncomputed, in every member).
 
 Layout.  Full-level fields are ``(nblocks, nlev, nproma)``, ``paph`` and the four fluxes ``(nblocks, nlev+1, nproma)``, in the
 library's dtype (``binding.torch_real()``) on one HIP device, with column stride 1 and level stride ``nproma``: the blocked
@@ -153,9 +162,15 @@ def normalize(ts: dict, lay: Layout, groups: dict) -> dict:
 def _raw(t: torch.Tensor) -> torch.Tensor:
     """the plain tensor inside torch.func's wrappers (its transforms hand jvp / backward wrapped tensors, which have no data pointer
     of their own; the wrapper's value shares the storage)"""
-    while _functorch.is_functorch_wrapped_tensor(t):
+    while True:
+        if _functorch.is_batchedtensor(t) or _functorch.is_legacy_batchedtensor(t):
+            # a batch dimension the vmap rules below have not taken off: a nested vmap, or the legacy batching of
+            # torch.autograd.grad(..., is_grads_batched=True), which does not go through them -- its data pointer is not a field's
+            raise NotImplementedError("cloudsc2: a batched tensor reached a launcher (nested vmap and is_grads_batched=True are not "
+                                      "supported; use one level of torch.func.vmap / jacfwd / jacrev)")
+        if not _functorch.is_functorch_wrapped_tensor(t):
+            return t
         t = _functorch.get_unwrapped(t)
-    return t
 
 
 def _field(t: torch.Tensor | None, lay: Layout, name: str) -> B.Field:
@@ -174,13 +189,13 @@ def _block(kind: str, ts: dict, lay: Layout):
     return blk
 
 
-def _new(names, lay: Layout, like: torch.Tensor) -> dict:
-    """fresh contiguous arrays, padded tail zeroed (that slice only)"""
+def _new(names, lay: Layout, like: torch.Tensor, batch: int | None = None) -> dict:
+    """fresh contiguous arrays, padded tail zeroed (that slice only); batch: ``(batch, *shape)``, one member per direction"""
     out = {}
     for n in names:
-        t = torch.empty(lay.shape(n), dtype=like.dtype, device=like.device)
+        t = torch.empty(((batch,) if batch is not None else ()) + lay.shape(n), dtype=like.dtype, device=like.device)
         if lay.tail < lay.nproma:
-            t[-1, :, lay.tail:] = 0
+            t[..., -1, :, lay.tail:] = 0
         out[n] = t
     return out
 
@@ -208,8 +223,193 @@ def _evap(prm: B.Params) -> bool:
     return bool(prm.levapls2 or prm.ldrain1d)
 
 
+def _scratch_ptr(scratch: torch.Tensor) -> C.c_void_p:
+    return C.c_void_p(_raw(scratch).data_ptr() if scratch.numel() else None)
+
+
+def _zero_filled(names, ts, lay: Layout, like: torch.Tensor) -> dict:
+    """``ts`` by name with a zero plane for every None (no tangent / an output that took no part in the loss): read only, so one
+    plane per shape serves all"""
+    out, zeros = {}, {}
+    for n, t in zip(names, ts):
+        if t is None:
+            key = lay.nlevx(n)
+            if key not in zeros:
+                zeros[key] = torch.zeros(lay.shape(n), dtype=like.dtype, device=like.device)
+            t = zeros[key]
+        out[n] = t
+    return out
+
+
+# ---- what the vmap rules share --------------------------------------------------------------------------------------------------
+# torch.func.vmap hands a rule its operands with the batch level taken off and ``in_dims`` (None: not batched).  The three functions
+# below share one treatment.  ``traj`` operands batched: a batch of states (_fold).  Only direction operands batched: one batched
+# launch.  Nothing batched: the plain call.
+
+def _batch_size(in_dims, ts) -> int | None:
+    sizes = {t.shape[d] for t, d in zip(ts, in_dims) if d is not None}
+    if len(sizes) > 1:
+        raise ValueError(f"cloudsc2 under vmap: operands with different batch sizes {sorted(sizes)}")
+    return sizes.pop() if sizes else None
+
+
+def _refuse_nested(ts) -> None:
+    for t in ts:
+        if isinstance(t, torch.Tensor) and (_functorch.is_batchedtensor(_peel_grad(t)) or _functorch.is_legacy_batchedtensor(t)):
+            raise NotImplementedError("cloudsc2: nested vmap is not supported (one level of torch.func.vmap / jacfwd / jacrev is)")
+
+
+def _peel_grad(t: torch.Tensor) -> torch.Tensor:
+    while _functorch.is_gradtrackingtensor(t):
+        t = _functorch.get_unwrapped(t)
+    return t
+
+
+def _front(t: torch.Tensor, d: int | None) -> torch.Tensor:
+    return t if d is None else t.movedim(d, 0)
+
+
+def _fold(fn, lay: Layout, names, ts, in_dims, out_names):
+    """A batch of K states through ``fn(layout, tensors) -> tuple`` (the unbatched call).  Columns are independent, so with full
+    blocks the batch is folded into the block dimension -- ``(K * nblocks, nlevx, nproma)``, unbatched operands expanded -- and run
+    as one call.  With a padded tail (``ngptot < nblocks * nproma``) the tail of every member would lie in the middle of the folded
+    array, where it has to stay zero and uncomputed: then one call per state.  Returns the outputs stacked, ``(K, *shape)``;
+    members of ``out_names`` that are None name outputs without the field layout (the empty cover scratch), returned as they are."""
+    K = _batch_size(in_dims, ts)
+    ts = [_front(t, d) for t, d in zip(ts, in_dims)]
+    if lay.tail == lay.nproma:
+        folded = Layout(K * lay.nblocks, lay.nlev, lay.nproma, K * lay.nblocks * lay.nproma)
+        flat = []
+        for n, t, d in zip(names, ts, in_dims):
+            if t.dim() != 3 + (d is not None):  # (the empty cover scratch of a call without the evaporation branch)
+                flat.append(t)
+                continue
+            t = t if d is not None else t.unsqueeze(0).expand(K, *t.shape)
+            flat.append(t.reshape(K * lay.nblocks, *t.shape[2:]))
+        outs = fn(folded, flat)
+        return tuple(o if n is None else o.reshape(K, lay.nblocks, *o.shape[1:]) for n, o in zip(out_names, outs))
+    per_state = [fn(lay, [t if d is None else t[k] for t, d in zip(ts, in_dims)]) for k in range(K)]
+    return tuple(per_state[0][j] if n is None else torch.stack([r[j] for r in per_state]) for j, n in enumerate(out_names))
+
+
+def _directions(names, ts, in_dims, K: int, lay: Layout, groups: dict) -> list:
+    """K dicts name -> tensor, one per direction: member k of a batched operand, the shared tensor of an unbatched one; each
+    direction's groups normalized (all alike: the members of one batched tensor share their strides)"""
+    ts = [_front(t, d) for t, d in zip(ts, in_dims)]
+    return [normalize({n: (t if d is None else t[k]) for n, t, d in zip(names, ts, in_dims)}, lay, groups) for k in range(K)]
+
+
+def _block_array(kind: str, per_direction: list, lay: Layout):
+    typ = B.Inputs if kind == "in" else B.Outputs
+    return (typ * len(per_direction))(*[_block(kind, d, lay) for d in per_direction])
+
+
+class _Cloudsc2Tl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, *16 trajectory inputs, *16 tangents) -> 10 output tangents: the TL sweep without trajectory
+    stores.  Not differentiable (no double backward)."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, *ts):
+        x = dict(zip(B.IN_NAMES, ts[:16]))
+        like = x["pap"]
+        dev = like.device
+        dx = normalize(dict(zip(B.IN_NAMES, ts[16:])), lay, IN_GROUPS)
+        dy = _new(B.OUT_NAMES, lay, like)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                             C.byref(_block("in", x, lay)), C.byref(B.Outputs()),  # no trajectory stores
+                                             C.byref(_block("in", dx, lay)), C.byref(_block("out", dy, lay)), _stream(dev)))
+        return tuple(dy[n] for n in B.OUT_NAMES)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(*output)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, *ts):
+        _refuse_nested(ts)
+        dims = in_dims[3:]
+        K = _batch_size(dims, ts)
+        if K is None:
+            return _Cloudsc2Tl.apply(prm, ptsphy, lay, *ts), (None,) * 10
+        if any(d is not None for d in dims[:16]):  # a batch of states
+            def one(l, flat):
+                x = normalize(dict(zip(B.IN_NAMES, flat[:16])), l, IN_GROUPS)
+                return _Cloudsc2Tl.apply(prm, ptsphy, l, *(x[n] for n in B.IN_NAMES), *flat[16:])
+            return _fold(one, lay, B.IN_NAMES * 2, ts, dims, B.OUT_NAMES), (0,) * 10
+        x = dict(zip(B.IN_NAMES, ts[:16]))
+        like = x["pap"]
+        dev = like.device
+        dxs = _directions(B.IN_NAMES, ts[16:], dims[16:], K, lay, IN_GROUPS)
+        dy = _new(B.OUT_NAMES, lay, like, batch=K)
+        dys = [{n: dy[n][k] for n in B.OUT_NAMES} for k in range(K)]
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch_batch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                   C.byref(_block("in", x, lay)), K, _block_array("in", dxs, lay),
+                                                   _block_array("out", dys, lay), _stream(dev)))
+        return tuple(dy[n] for n in B.OUT_NAMES), (0,) * 10
+
+
+_VJP_TRAJ = B.IN_NAMES + ("fplsl", "fplsn", "scratch")  # the trajectory operands of _Cloudsc2Vjp
+
+
+class _Cloudsc2Vjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, *16 trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints) -> 16 input
+    adjoints: the reverse sweep in its vector-Jacobian form.  Not differentiable (no double backward)."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, *ts):
+        x = dict(zip(B.IN_NAMES, ts[:16]))
+        fplsl, fplsn, scratch = ts[16:19]
+        like = x["pap"]
+        dev = like.device
+        y = normalize(dict(zip(B.OUT_NAMES, ts[19:])), lay, OUT_GROUPS)
+        xa = _new(B.IN_NAMES, lay, like)
+        traj_out = B.Outputs()
+        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                              C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
+                                              C.byref(_block("out", y, lay)), _scratch_ptr(scratch), _stream(dev)))
+        return tuple(xa[n] for n in B.IN_NAMES)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(*output)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, *ts):
+        _refuse_nested(ts)
+        dims = in_dims[3:]
+        K = _batch_size(dims, ts)
+        if K is None:
+            return _Cloudsc2Vjp.apply(prm, ptsphy, lay, *ts), (None,) * 16
+        if any(d is not None for d in dims[:19]):  # a batch of states
+            def one(l, flat):
+                x = normalize(dict(zip(B.IN_NAMES, flat[:16])), l, IN_GROUPS)
+                fl = [t if _fits(t, l, "fplsl") and _block_stride(t, l, "fplsl") == (l.nlev + 1) * l.nproma else t.contiguous() for t in flat[16:18]]
+                sc = flat[18].contiguous()
+                return _Cloudsc2Vjp.apply(prm, ptsphy, l, *(x[n] for n in B.IN_NAMES), *fl, sc, *flat[19:])
+            return _fold(one, lay, _VJP_TRAJ + B.OUT_NAMES, ts, dims, B.IN_NAMES), (0,) * 16
+        x = dict(zip(B.IN_NAMES, ts[:16]))
+        fplsl, fplsn, scratch = ts[16:19]
+        like = x["pap"]
+        dev = like.device
+        ys = _directions(B.OUT_NAMES, ts[19:], dims[19:], K, lay, OUT_GROUPS)
+        xa = _new(B.IN_NAMES, lay, like, batch=K)
+        xas = [{n: xa[n][k] for n in B.IN_NAMES} for k in range(K)]
+        traj_out = B.Outputs()
+        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch_batch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                    C.byref(_block("in", x, lay)), C.byref(traj_out), K, _block_array("in", xas, lay),
+                                                    _block_array("out", ys, lay), _scratch_ptr(scratch), _stream(dev)))
+        return tuple(xa[n] for n in B.IN_NAMES), (0,) * 16
+
+
 class _Cloudsc2(torch.autograd.Function):
-    # forward(prm, ptsphy, layout, *16 inputs in IN_NAMES order) -> 10 outputs + the cover-checkpoint scratch (non-differentiable)
+    # forward(prm, ptsphy, layout, *16 inputs in IN_NAMES order) -> 10 outputs + the cover-checkpoint scratch (non-differentiable);
+    # its jvp and backward are the two functions above, whose vmap rules carry batched tangents and cotangents
 
     @staticmethod
     def forward(prm, ptsphy, lay, *xs):
@@ -221,7 +421,7 @@ class _Cloudsc2(torch.autograd.Function):
         with torch.cuda.device(dev):
             B.check(B.lib.cloudsc2_ad_launch_forward(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
                                                      C.byref(_block("in", x, lay)), C.byref(_block("out", out, lay)),
-                                                     C.c_void_p(_raw(scratch).data_ptr() if scratch.numel() else None), _stream(dev)))
+                                                     _scratch_ptr(scratch), _stream(dev)))
         return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
 
     @staticmethod
@@ -238,54 +438,34 @@ class _Cloudsc2(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, *grads):
         saved = ctx.saved_tensors
-        x = dict(zip(B.IN_NAMES, saved[:16]))
-        fplsl, fplsn, scratch = saved[16:]
-        lay, like = ctx.lay, x["pap"]
-        dev = like.device
+        lay, like = ctx.lay, saved[0]
         need = ctx.needs_input_grad[3:]
         if not any(need):
             return (None, None, None) + (None,) * 16
-        y = {}
-        zeros = {}
-        for n, g in zip(B.OUT_NAMES, grads[:10]):
-            if g is None:  # an output that took no part in the loss: a zero adjoint (read only, so one plane per shape serves all)
-                key = lay.nlevx(n)
-                if key not in zeros:
-                    zeros[key] = torch.zeros(lay.shape(n), dtype=like.dtype, device=dev)
-                g = zeros[key]
-            y[n] = g
-        y = normalize(y, lay, OUT_GROUPS)
-        xa = _new(B.IN_NAMES, lay, like)
-        traj_out = B.Outputs()
-        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_vjp_launch(C.byref(ctx.prm), float(ctx.ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                              C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
-                                              C.byref(_block("out", y, lay)),
-                                              C.c_void_p(_raw(scratch).data_ptr() if scratch.numel() else None), _stream(dev)))
-        return (None, None, None) + tuple(xa[n] if nd else None for n, nd in zip(B.IN_NAMES, need))
+        y = _zero_filled(B.OUT_NAMES, grads[:10], lay, like)
+        xa = _Cloudsc2Vjp.apply(ctx.prm, ctx.ptsphy, lay, *saved, *(y[n] for n in B.OUT_NAMES))
+        return (None, None, None) + tuple(a if nd else None for a, nd in zip(xa, need))
 
     @staticmethod
     def jvp(ctx, *tangents):
-        x = dict(zip(B.IN_NAMES, ctx.saved_tensors))
-        lay, like = ctx.lay, x["pap"]
-        dev = like.device
-        dx = {}
-        zeros = {}
-        for n, t in zip(B.IN_NAMES, tangents[3:]):
-            if t is None:  # no tangent: zero (read only, one plane per shape)
-                key = lay.nlevx(n)
-                if key not in zeros:
-                    zeros[key] = torch.zeros(lay.shape(n), dtype=like.dtype, device=dev)
-                t = zeros[key]
-            dx[n] = t
-        dx = normalize(dx, lay, IN_GROUPS)
-        dy = _new(B.OUT_NAMES, lay, like)
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_tl_launch(C.byref(ctx.prm), float(ctx.ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                             C.byref(_block("in", x, lay)), C.byref(B.Outputs()),  # no trajectory stores
-                                             C.byref(_block("in", dx, lay)), C.byref(_block("out", dy, lay)), _stream(dev)))
-        return tuple(dy[n] for n in B.OUT_NAMES) + (None,)
+        xs = ctx.saved_tensors
+        dx = _zero_filled(B.IN_NAMES, tangents[3:], ctx.lay, xs[0])
+        dy = _Cloudsc2Tl.apply(ctx.prm, ctx.ptsphy, ctx.lay, *xs, *(dx[n] for n in B.IN_NAMES))
+        return tuple(dy) + (None,)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, *xs):
+        _refuse_nested(xs)
+        dims = in_dims[3:]
+        if _batch_size(dims, xs) is None:
+            return _Cloudsc2.apply(prm, ptsphy, lay, *xs), (None,) * 11
+
+        def one(l, flat):
+            x = normalize(dict(zip(B.IN_NAMES, flat)), l, IN_GROUPS)
+            return _Cloudsc2.apply(prm, ptsphy, l, *(x[n] for n in B.IN_NAMES))
+        evap = _evap(prm)
+        outs = _fold(one, lay, B.IN_NAMES, xs, dims, B.OUT_NAMES + ("scratch" if evap else None,))
+        return outs, (0,) * 10 + (0 if evap else None,)
 
 
 def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None) -> Cloudsc2Outputs:

@@ -139,6 +139,15 @@ def _load() -> C.CDLL:
     lib.cloudsc2_vjp_launch.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs),
                                         C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p, C.c_void_p]
     lib.cloudsc2_vjp_launch.restype = C.c_int
+    # several directions over one trajectory: arrays of argument blocks, (Inputs * K)(...) / (Outputs * K)(...)
+    lib.cloudsc2_batch_max.argtypes = []
+    lib.cloudsc2_batch_max.restype = C.c_int
+    lib.cloudsc2_tl_launch_batch.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.c_int,
+                                             C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p]
+    lib.cloudsc2_tl_launch_batch.restype = C.c_int
+    lib.cloudsc2_vjp_launch_batch.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs), C.c_int,
+                                              C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p, C.c_void_p]
+    lib.cloudsc2_vjp_launch_batch.restype = C.c_int
     lib.cloudsc2_taylor_sums_launch.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(Outputs), C.POINTER(Outputs),
                                                 C.POINTER(Outputs), C.c_double, C.c_void_p, C.c_void_p]
     lib.cloudsc2_taylor_sweep_work_doubles.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_longlong)]
@@ -225,7 +234,7 @@ lib = _load()
 EXPORTED = ("cloudsc2_params_default", "cloudsc2_last_error", "cloudsc2_device_available", "cloudsc2_current_device", "cloudsc2_set_math_mode",
             "cloudsc2_get_math_mode", "cloudsc2_real_bytes", "cloudsc2_nl_launch",
             "cloudsc2_satur_launch", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
-            "cloudsc2_ad_launch_forward", "cloudsc2_ad_launch_reverse", "cloudsc2_vjp_launch", "cloudsc2_ad_launch_reverse_norms", "cloudsc2_taylor_sums_launch",
+            "cloudsc2_ad_launch_forward", "cloudsc2_ad_launch_reverse", "cloudsc2_vjp_launch", "cloudsc2_batch_max", "cloudsc2_tl_launch_batch", "cloudsc2_vjp_launch_batch", "cloudsc2_ad_launch_reverse_norms", "cloudsc2_taylor_sums_launch",
             "cloudsc2_taylor_sweep_work_doubles", "cloudsc2_taylor_sweep_launch", "cloudsc2_adjoint_norms_launch", "cloudsc2_nl_run", "cloudsc2_tl_taylor_run", "cloudsc2_ad_symmetry_run",
             "cloudsc2_release_workspace", "cloudsc2_taylor_verdict", "cloudsc2_adjoint_verdict",
             "cloudsc2_expand_launch", "cloudsc2_validate_workspace_doubles", "cloudsc2_validate_launch",

@@ -1004,6 +1004,317 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Batched TL and reverse sweeps: several tangents / cotangents over ONE trajectory (cloudsc2_tl_launch_batch, cloudsc2_vjp_launch_batch)
+// ---------------------------------------------------------------------------------------------------------
+// A Jacobian block, a singular-vector iteration or an ensemble of perturbations push K directions through the TL or the reverse sweep
+// over one state.  K launches read the 16 trajectory planes K times.  Here a lane reads the trajectory inputs of a level once and
+// then runs the level for each of its NB <= kBatchMax directions, each with its own carries.  NB is a COMPILE-TIME count (one
+// kernel per count, the launchers pick it): the direction loop is fully unrolled, the per-direction carries are registers (never
+// a runtime-indexed array), and the inputs of direction b + 1 are requested under the arithmetic of direction b.  Every
+// direction's results are the bits of the single-direction sweeps (tl_column without C2F_TRAJ / C2F_SELFINC,
+// ad_reverse_column<F | C2F_ASSIGN | C2F_VJP>); launder_level below says what that takes.
+constexpr int kBatchMax = 4;  // directions per launch: the fp64 kernels hold it without scratch at one wave per SIMD
+
+// (the pointer sets from the launch's direction count on are not read)
+struct TlBatchArgs {
+  Consts c; Geom g; Strides s, sp; InPtrs in; InPtrs din[kBatchMax]; OutPtrs dout[kBatchMax]; const LevelTab* tab;
+};
+// (like AdArgs: the trajectory side is the NL sweep's block; nl.out: PFPLSL5 / PFPLSN5 are read, nl.ckpt with the evaporation branch)
+struct VjpBatchArgs {
+  NlArgs nl; Strides sa; InPtrsRW ain[kBatchMax]; OutPtrs aout[kBatchMax];
+};
+typedef const C2_CONST_AS TlBatchArgs* TlBatchArgsP;
+typedef const C2_CONST_AS VjpBatchArgs* VjpBatchArgsP;
+
+// Bit-equality with the single-direction sweeps is the contract of the batched ones, and the library is compiled with the device
+// default contraction: which multiplies fuse into which adds depends on how many users a product has and on what the compiler
+// knows around it.  Measured on the MI355X, each as last-place differences from the single sweeps in the cloud levels (a few
+// hundred elements of a 100-column state), in some variants and on some states only:
+//   - level_forward evaluated once and shared by the unrolled directions: its products, and the trajectory-only products inside
+//     level_tl / level_ad that the compiler then evaluates once for all directions, have several users and fuse differently;
+//   - the same with the LevelTraj made opaque per direction: the fusions of tl_column across level_forward and level_tl are lost;
+//   - the direction loop behind a runtime guard `b < nb`: the compiler builds one level loop per count, each with its own fusions.
+// What holds in every variant and on every state tried: every direction gets the single sweep's own straight line -- level_forward
+// and level_tl / level_ad on ITS OWN opaque copy of the level's inputs, the carry and the constants' address (an empty asm
+// statement per value: no instruction) -- under a compile-time direction count.  The compiler can then neither share anything
+// between directions nor tell the copies from loaded values.  The trajectory is still READ once per launch, which is the saving:
+// the sweeps wait for HBM, not for the level's arithmetic (measured: the launch runs at the byte ratio).
+// (The host builds, compiled without contraction, need nothing.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define C2_LAUNDER_V(x) asm volatile("" : "+v"(x))
+#else
+#define C2_LAUNDER_V(x) ((void)0)
+#endif
+C2_HD void launder_level(LevelIn& x, LevelCst& k, Carry& cy) {  // (all of x but paph_surf, which is invariant over the levels)
+  C2_LAUNDER_V(x.paph_k); C2_LAUNDER_V(x.paph_k1); C2_LAUNDER_V(x.pap); C2_LAUNDER_V(x.q); C2_LAUNDER_V(x.qs); C2_LAUNDER_V(x.t);
+  C2_LAUNDER_V(x.l); C2_LAUNDER_V(x.i); C2_LAUNDER_V(x.lude); C2_LAUNDER_V(x.lu_k1); C2_LAUNDER_V(x.mfu); C2_LAUNDER_V(x.mfd);
+  C2_LAUNDER_V(x.gt); C2_LAUNDER_V(x.gq); C2_LAUNDER_V(x.gl); C2_LAUNDER_V(x.gi); C2_LAUNDER_V(x.supsat);
+  C2_LAUNDER(k.ceta); C2_LAUNDER(k.zscalm);
+  C2_LAUNDER_V(cy.rfl); C2_LAUNDER_V(cy.sfl); C2_LAUNDER_V(cy.covptot);
+}
+
+// F: C2F_QSAT (always: the batched launchers require PQSAT) | C2F_PRECISE | C2F_EVAP | C2F_OFF32; NB: the directions of the launch
+template <unsigned F, int NB>
+C2_HD void tl_batch_column(long long gcol, TlBatchArgsP a) {
+  static_assert(NB >= 1 && NB <= kBatchMax, "directions of one launch: 1..kBatchMax");
+  constexpr bool P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0, AHEAD = !EVAP;
+  static_assert((F & C2F_QSAT) && !(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32)), "flags of the batched TL sweep: QSAT, PRECISE, EVAP, OFF32");
+  typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
+  LaneOff o, op; bool active;
+  if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
+  lane_setup(&a->g, &a->sp, gcol, op, active);
+  if (!active) return;
+  const int nlev = a->g.nlev, nproma = a->g.nproma;
+  LevelTabP tab = (LevelTabP)a->tab;
+  ConstsP c = C2_CONSTS(a);
+  InPtrsP in = &a->in;
+
+  // once per column, not once per direction: the tropopause pre-scan, the critical-humidity setup, the lane offsets, the loads
+  real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->g, RC(0.0));
+  RhCrit rh;
+  rhcrit_setup(ztrpaus, rh);
+  real_t paph_surf = RC(0.0);
+  if (EVAP) paph_surf = in->paph[o.half + (long long)nlev * nproma];
+
+  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
+  Carry dcy[NB];
+  real_t dpaph_k[NB], dpaph_surf[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0);
+    dpaph_surf[b] = RC(0.0);
+    store_top(&a->dout[b], op, c);
+    const real_t* dpaph = a->din[b].paph;
+    dpaph_k[b] = dpaph[op.half];
+    if (EVAP) dpaph_surf[b] = dpaph[op.half + (long long)nlev * nproma];
+  }
+  RawLevel cur, nxt;
+  real_t paph_k = in->paph[o.half];
+  const LaneOffT<OT> ol = lane_off_as<OT>(o), opl = lane_off_as<OT>(op);  // offsets used inside the level loop
+  load_level<true>(in, ol, nproma, nlev, 0, cur);
+  Pace pace;
+  pace.begin(&a->g);
+
+  // The trajectory inputs of level jk+1 are requested at the top of level jk, as in tl_column.  The direction inputs are requested
+  // one direction ahead: those of direction 0 at the top of their own level, those of direction b + 1 under the arithmetic of
+  // direction b -- two register sets for them whatever NB is.  In the evaporation variants, the
+  // register-tightest (an earlier form of this sweep spilled 20-28 bytes per lane there with the second set), direction b > 0 asks
+  // for its inputs at its own top; not measured against the look-ahead in the present form.
+  for (int jk = 0; jk < nlev; ++jk) {
+    const bool last = (jk == nlev - 1);
+    TlBatchArgsP ap = a;
+    C2_LAUNDER(ap);
+    nxt = cur;
+    if (!last) load_level<true>(&ap->in, ol, nproma, nlev, jk + 1, nxt);
+    RawLevel dcur;
+    load_level<true>(&ap->din[0], opl, nproma, nlev, jk, dcur);
+    pace.nap();  // (with the loads in flight)
+
+    LevelCst k;
+    level_cst(tab, jk, last, k);
+    LevelIn x;
+    make_level_in(cur, paph_k, paph_surf, x);
+    Carry cy_out = cy;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      if (!AHEAD && b > 0) load_level<true>(&ap->din[b], opl, nproma, nlev, jk, dcur);
+      RawLevel dnxt = dcur;
+      if (AHEAD && b + 1 < NB) load_level<true>(&ap->din[b + 1 < NB ? b + 1 : b], opl, nproma, nlev, jk, dnxt);
+      // this direction's own straight line (launder_level says why): every direction leaves the same trajectory carry
+      LevelIn xb = x;
+      LevelCst kb = k;
+      RhCrit rhb = rh;
+      cy_out = cy;
+      launder_level(xb, kb, cy_out);
+      C2_LAUNDER_V(xb.paph_surf); C2_LAUNDER_V(rhb.zeta3); C2_LAUNDER_V(rhb.zrh2); C2_LAUNDER_V(rhb.zdeta1);
+      ConstsP cb = c;  // (and its own view of the constants: a product of two of them is shared otherwise)
+      C2_LAUNDER(cb);
+      LevelTraj tr;
+      LevelOut lo;
+      level_forward<P, EVAP>(cb, kb, rhb, xb, cy_out, tr, lo);
+      LevelIn dx;
+      make_level_in(dcur, dpaph_k[b], dpaph_surf[b], dx);
+      LevelOut dlo;
+      level_tl(cb, kb, xb, tr, dx, dcy[b], dlo);
+      C2_LAUNDER(ap);
+      store_out(&ap->dout[b], opl, nproma, jk, dlo);
+      dpaph_k[b] = dcur.paph_k1;
+      dcur = dnxt;
+    }
+    cy = cy_out;
+    paph_k = cur.paph_k1;
+    cur = nxt;
+  }
+}
+
+template <class OT>
+C2_HD void load_out_adjoint(OutPtrsP pp, const LaneOffT<OT>& oa, OT d, OT d1, LevelOut& ya) {
+  const OutPtrs pa = *pp;
+  ya.tent = ldg(pa.tent, oa.loc + d);
+  ya.tenq = ldg(pa.tenq, oa.loc + d);
+  ya.tenl = ldg(pa.tenl, oa.loc + d);
+  ya.teni = ldg(pa.teni, oa.loc + d);
+  ya.clc = ldg(pa.clc, oa.full + d);
+  ya.covptot = ldg(pa.covptot, oa.full + d);
+  ya.fplsn = ldg(pa.fplsn, oa.half + d1);
+  ya.fplsl = ldg(pa.fplsl, oa.half + d1);
+  ya.fhpsn = ldg(pa.fhpsn, oa.half + d1);
+  ya.fhpsl = ldg(pa.fhpsl, oa.half + d1);
+}
+
+// F: C2F_QSAT (always) | C2F_PRECISE | C2F_EVAP | C2F_OFF32; the form is ad_reverse_column's C2F_ASSIGN | C2F_VJP: input adjoints
+// assigned, output adjoints read only, the PSUPSAT adjoint ax.q, the PLU(1) adjoint zero, the padded tail untouched
+template <unsigned F, int NB>
+C2_HD void vjp_batch_column(long long gcol, VjpBatchArgsP a) {
+  static_assert(NB >= 1 && NB <= kBatchMax, "directions of one launch: 1..kBatchMax");
+  constexpr bool P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0, OFF32 = (F & C2F_OFF32) != 0;
+  static_assert((F & C2F_QSAT) && !(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32)), "flags of the batched reverse sweep: QSAT, PRECISE, EVAP, OFF32");
+  typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
+  LaneOff o, oa64; bool active;
+  if (!lane_setup(&a->nl.g, &a->nl.s, gcol, o, active)) return;
+  lane_setup(&a->nl.g, &a->sa, gcol, oa64, active);
+  if (!active) return;
+  const int nlev = a->nl.g.nlev, nproma = a->nl.g.nproma;
+  LevelTabP tab = (LevelTabP)a->nl.tab;
+  ConstsP c = C2_CONSTS(&a->nl);
+  InPtrsP in = &a->nl.in;
+
+  const long long osc64 = (gcol / nproma) * ((long long)nproma * nlev) + (gcol % nproma);  // scratch: (NPROMA, NLEV, NBLOCKS) contiguous
+  const LaneOffT<OT> ol = lane_off_as<OT>(o), oa = lane_off_as<OT>(oa64);
+  const OT osc = (OT)(osc64 * (OFF32 ? (long long)sizeof(real_t) : 1));
+
+  real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->nl.g, RC(0.0));
+  RhCrit rh;
+  rhcrit_setup(ztrpaus, rh);
+  const real_t paph_bottom = in->paph[o.half + (long long)nlev * nproma];
+  const real_t paph_surf = EVAP ? paph_bottom : RC(0.0);
+
+  Carry acy[NB];
+  real_t paph_pending[NB], surf_acc[NB];  // as in ad_reverse_column, per direction
+  // what is invariant over the levels is laundered per direction HERE, not per level: ad_reverse_column's compiler knows it to be
+  // invariant too, and forms what depends on it alone before the level loop
+  RhCrit rh_b[NB];
+  real_t paph_surf_b[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    acy[b].rfl = RC(0.0); acy[b].sfl = RC(0.0); acy[b].covptot = RC(0.0);
+    paph_pending[b] = RC(0.0); surf_acc[b] = RC(0.0);
+    rh_b[b] = rh; paph_surf_b[b] = paph_surf;
+    C2_LAUNDER_V(rh_b[b].zeta3); C2_LAUNDER_V(rh_b[b].zrh2); C2_LAUNDER_V(rh_b[b].zdeta1); C2_LAUNDER_V(paph_surf_b[b]);
+  }
+  real_t paph_k1 = paph_bottom;
+  // the assign form adds its results to old values that are zero (ad_load_level: xo); 0 + x is x except for x = -0, which becomes +0:
+  // the add is kept so that the bits are ad_reverse_column's
+  const real_t zero = RC(0.0);
+  Pace pace;
+  pace.begin(&a->nl.g);
+  for (int jk = nlev - 1; jk >= 0; --jk) {
+    const bool last = (jk == nlev - 1);
+    pace.nap();
+    const OT d = level_off(OT(), jk, nproma);
+    const OT d1 = d + row_off(OT(), nproma);
+    VjpBatchArgsP ap = a;
+    C2_LAUNDER(ap);
+    // the trajectory loads of the level and the first direction's output adjoints at its top, as in ad_reverse_column; the output
+    // adjoints of direction b + 1 under level_ad of direction b
+    RawLevel cur;
+    real_t paph_k;
+    Carry cy;
+    {
+      const InPtrs p = ap->nl.in;
+      paph_k = ldg(p.paph, ol.half + d);
+      cur.lu_k1 = last ? RC(0.0) : ldg(p.lu, ol.full + d1);
+      cur.pap = ldg(p.pap, ol.full + d);
+      cur.q = ldg(p.q, ol.full + d);
+      cur.t = ldg(p.t, ol.full + d);
+      cur.l = ldg(p.l, ol.clv + d);
+      cur.i = ldg(p.i, ol.clv + d);
+      cur.lude = ldg(p.lude, ol.full + d);
+      cur.mfu = ldg(p.mfu, ol.full + d);
+      cur.mfd = ldg(p.mfd, ol.full + d);
+      cur.gt = ldg(p.gt, ol.cml + d);
+      cur.gq = ldg(p.gq, ol.cml + d);
+      cur.gl = ldg(p.gl, ol.cml + d);
+      cur.gi = ldg(p.gi, ol.cml + d);
+      cur.supsat = ldg(p.supsat, ol.full + d);
+      cur.qsat = ldg(p.qsat, ol.full + d);
+      const OutPtrs po = ap->nl.out;
+      cy.rfl = ldg(po.fplsl, ol.half + d);  // ZRFL5(JK) = PFPLSL5(JK)
+      cy.sfl = ldg(po.fplsn, ol.half + d);
+      cy.covptot = EVAP ? ldg(ap->nl.ckpt, osc + d) : RC(0.0);
+    }
+    LevelOut ycur;
+    load_out_adjoint(&ap->aout[0], oa, d, d1, ycur);
+    cur.paph_k1 = paph_k1;
+
+    LevelCst k;
+    level_cst(tab, jk, last, k);
+    LevelIn x;
+    make_level_in(cur, paph_k, paph_surf, x);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      {
+        LevelOut ynxt = ycur;
+        if (b + 1 < NB) load_out_adjoint(&ap->aout[b + 1 < NB ? b + 1 : b], oa, d, d1, ynxt);
+        // this direction's own straight line (launder_level says why)
+        LevelIn xb = x;
+        LevelCst kb = k;
+        RhCrit rhb = rh_b[b];
+        Carry cyb = cy;
+        launder_level(xb, kb, cyb);
+        xb.paph_surf = paph_surf_b[b];
+        ConstsP cb = c;  // (and its own view of the constants: a product of two of them is shared otherwise)
+        C2_LAUNDER(cb);
+        LevelTraj tr;
+        LevelOut lo;
+        level_forward<P, EVAP>(cb, kb, rhb, xb, cyb, tr, lo);
+        LevelOut ya = ycur;  // enthalpy-flux adjoints folded in (cloudsc2ad.F90:914-921)
+        ya.fplsn = ya.fplsn - ya.fhpsn * cb->rlstt;
+        ya.fplsl = ya.fplsl - ya.fhpsl * cb->rlvtt;
+        LevelIn ax;
+        level_ad(cb, kb, xb, tr, ya, acy[b], ax);
+
+        C2_LAUNDER(ap);
+        const InPtrsRW px = ap->ain[b];
+        stg(px.pap, oa.full + d, zero + ax.pap);
+        stg(px.q, oa.full + d, zero + ax.q);
+        stg(px.qsat, oa.full + d, zero + ax.qs);
+        stg(px.t, oa.full + d, zero + ax.t);
+        stg(px.l, oa.clv + d, zero + ax.l);
+        stg(px.i, oa.clv + d, zero + ax.i);
+        stg(px.lude, oa.full + d, zero + ax.lude);
+        stg(px.mfu, oa.full + d, zero + ax.mfu);
+        stg(px.mfd, oa.full + d, zero + ax.mfd);
+        stg(px.gt, oa.cml + d, zero + ax.gt);
+        stg(px.gq, oa.cml + d, zero + ax.gq);
+        stg(px.gl, oa.cml + d, zero + ax.gl);
+        stg(px.gi, oa.cml + d, zero + ax.gi);
+        stg(px.supsat, oa.full + d, ax.q);  // the true derivative (C2F_VJP)
+        if (!last) stg(px.lu, oa.full + d1, zero + ax.lu_k1);
+        surf_acc[b] += ax.paph_surf;
+        if (last) {
+          surf_acc[b] += ax.paph_k1;
+        } else {
+          stg(px.paph, oa.half + d1, zero + (ax.paph_k1 + paph_pending[b]));
+        }
+        paph_pending[b] = ax.paph_k;
+        ycur = ynxt;
+      }
+    }
+    paph_k1 = paph_k;
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    {
+      const InPtrsRW px = a->ain[b];
+      px.paph[oa64.half] = paph_pending[b];
+      px.paph[oa64.half + (long long)nlev * nproma] = surf_acc[b];
+      px.lu[oa64.full] = RC(0.0);  // PLU(1) has no adjoint contribution
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Adjoint-test norms per column (cloudsc_driver_ad_mod.F90:184-195,240-264)
 // ---------------------------------------------------------------------------------------------------------
 // norm1 = <y,y>, field by field like the reference's SUMs (:185-194)

@@ -15,6 +15,8 @@
 #include "cloudsc2_kern_tl.hip"
 #include "cloudsc2_kern_ad.hip"
 #include "cloudsc2_kern_taylor.hip"
+#include "cloudsc2_kern_tl_batch.hip"
+#include "cloudsc2_kern_vjp_batch.hip"
 #endif
 
 using namespace cloudsc2;
@@ -23,7 +25,7 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------------------
 // kernels: the sweeps' __global__ wrappers and their variant tables are cloudsc2_sweep_kernels.hpp + the family units
-// cloudsc2_kern_{nl,tl,ad,taylor}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
+// cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
 // ---------------------------------------------------------------------------------------------------------
 template <bool P>
 __global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
@@ -606,6 +608,115 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// batched TL / reverse sweeps: nbatch directions over one trajectory, in chunks of at most kBatchMax per launch
+// ---------------------------------------------------------------------------------------------------------
+bool same_strides(const Strides& a, const Strides& b) {
+  return a.full == b.full && a.half == b.half && a.cml == b.cml && a.clv == b.clv && a.loc == b.loc;
+}
+
+InPtrsRW writable(const cloudsc2_inputs& x) {
+  InPtrsRW p;
+  p.paph = x.paph.ptr; p.pap = x.pap.ptr; p.q = x.q.ptr; p.qsat = x.qsat.ptr; p.t = x.t.ptr; p.l = x.l.ptr; p.i = x.i.ptr;
+  p.lude = x.lude.ptr; p.lu = x.lu.ptr; p.mfu = x.mfu.ptr; p.mfd = x.mfd.ptr; p.gt = x.gtent.ptr; p.gq = x.gtenq.ptr;
+  p.gl = x.gtenl.ptr; p.gi = x.gteni.ptr; p.supsat = x.supsat.ptr;
+  return p;
+}
+
+// Balanced chunks in stream order (5 -> 3 + 2, 9 -> 3 + 3 + 3): `launch(first, count)` once per chunk, until one fails.  A larger
+// chunk next to a small rest would leave the rest's launch with the worse ratio of trajectory to direction traffic.
+template <class Launch>
+int for_each_chunk(int nbatch, Launch launch) {
+  const int nchunks = (nbatch + kBatchMax - 1) / kBatchMax, base = nbatch / nchunks, extra = nbatch % nchunks;
+  for (int ch = 0, first = 0; ch < nchunks; ++ch) {
+    const int count = base + (ch < extra ? 1 : 0);
+    if (int rc = launch(first, count)) return rc;
+    first += count;
+  }
+  return 0;
+}
+
+// Whether the batched kernels' launches of a few partial rounds are paced like their single-direction twins': measured once at
+// 160 000 columns (profiles/EXPERIMENTS.md, "Batched tangents and cotangents")
+constexpr bool kPaceBatch = true;
+
+int tl_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                         int nbatch, const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out, void* stream) {
+  Sweep w;
+  int rc = w.begin(prm, nproma, nlev, ngptot,
+                   (!traj_in || !pert_in || !pert_out) ? "NULL argument block" : nbatch < 1 ? "nbatch >= 1 required" : nullptr);
+  if (rc) return rc;
+  if (nbatch == 1) {  // one direction: the single-direction sweep itself (it requires qsat of pert_in only, so ask here)
+    if (!traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "qsat field required");
+    const cloudsc2_outputs none = {};
+    return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_in, 0.0, pert_out, nullptr, stream);
+  }
+  if ((rc = resolve_in(*traj_in, true, w.s, w.in))) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  std::vector<InPtrs> din((size_t)nbatch);
+  std::vector<OutPtrs> dout((size_t)nbatch);
+  Strides sp = {0, 0, 0, 0, 0};
+  for (int b = 0; b < nbatch; ++b) {
+    Strides sb = {0, 0, 0, 0, 0};
+    if ((rc = resolve_in(pert_in[b], true, sb, din[b])) || (rc = resolve_out(pert_out[b], true, sb, dout[b]))) return rc;
+    if (b == 0) sp = sb;
+    else if (!same_strides(sp, sb)) return fail(CLOUDSC2_EINVAL, "batched launch: every direction must have the same block stride per layout group");
+  }
+  if ((rc = w.finish(*prm, ptsphy, true, {sp.full, sp.half, sp.cml, sp.clv, sp.loc}))) return rc;
+  TlBatchArgs args;
+  args.c = w.c; args.g = w.g; args.s = w.s; args.sp = sp; args.in = w.in; args.tab = w.tab;
+  return for_each_chunk(nbatch, [&](int first, int count) {
+    const KernelFn<TlBatchArgs> fn = tl_batch_variant(w.f, count);  // (the direction count is the kernel's compile-time one)
+    for (int b = 0; b < kBatchMax; ++b) {  // (the sets from `count` on are not read: valid pointers all the same)
+      args.din[b] = din[first + (b < count ? b : 0)];
+      args.dout[b] = dout[first + (b < count ? b : 0)];
+    }
+    schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
+    return launch_variant(fn, args, w.g.ncols_pad, (hipStream_t)stream);
+  });
+}
+
+int vjp_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                          const cloudsc2_outputs* traj_out, int nbatch, const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                          const cloudsc2_real* scratch, void* stream) {
+  Sweep w;
+  int rc = w.begin(prm, nproma, nlev, ngptot,
+                   (!traj_in || !traj_out || !adj_in || !adj_out) ? "NULL argument block" : nbatch < 1 ? "nbatch >= 1 required" : nullptr);
+  if (rc) return rc;
+  if (!traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "qsat field required");
+  if (nbatch == 1)  // one direction: the single-direction sweep itself
+    return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch), stream,
+                          AdMode{2, true, true});
+  if ((rc = w.trajectory(*traj_in, *traj_out, false))) return rc;
+  if (!w.out.fplsl || !w.out.fplsn) return fail(CLOUDSC2_EINVAL, "reverse sweep: traj_out->fplsl and ->fplsn (PFPLSL5, PFPLSN5) are required");
+  std::vector<InPtrsRW> ain((size_t)nbatch);
+  std::vector<OutPtrs> aout((size_t)nbatch);
+  Strides sa = {0, 0, 0, 0, 0};
+  for (int b = 0; b < nbatch; ++b) {
+    Strides sb = {0, 0, 0, 0, 0};
+    InPtrs checked;
+    if ((rc = resolve_in(adj_in[b], true, sb, checked)) || (rc = resolve_out(adj_out[b], true, sb, aout[b]))) return rc;
+    ain[b] = writable(adj_in[b]);
+    if (b == 0) sa = sb;
+    else if (!same_strides(sa, sb)) return fail(CLOUDSC2_EINVAL, "batched launch: every direction must have the same block stride per layout group");
+  }
+  if ((rc = w.finish(*prm, ptsphy, true, {sa.full, sa.half, sa.cml, sa.clv, sa.loc, (long long)nproma * nlev /* scratch */}))) return rc;
+  if (w.c.evap && !scratch) return fail(CLOUDSC2_EINVAL, "LEVAPLS2/LDRAIN1D: the cover-checkpoint plane `scratch` is required");
+  VjpBatchArgs args;
+  args.nl = w.nl();
+  args.nl.ckpt = const_cast<cloudsc2_real*>(scratch);
+  args.sa = sa;
+  return for_each_chunk(nbatch, [&](int first, int count) {
+    const KernelFn<VjpBatchArgs> fn = vjp_batch_variant(w.f, count);
+    for (int b = 0; b < kBatchMax; ++b) {
+      args.ain[b] = ain[first + (b < count ? b : 0)];
+      args.aout[b] = aout[first + (b < count ? b : 0)];
+    }
+    schedule(args.nl.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
+    return launch_variant(fn, args, w.g.ncols_pad, (hipStream_t)stream);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // state expansion / validation launchers
 // ---------------------------------------------------------------------------------------------------------
 int check_expand_args(const cloudsc2_real* table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
@@ -777,6 +888,21 @@ int cloudsc2_vjp_launch(const cloudsc2_params* prm, double ptsphy, int nproma, i
                         const cloudsc2_real* scratch, void* stream) {
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
                         stream, AdMode{2, true, true});
+}
+
+int cloudsc2_batch_max(void) { return kBatchMax; }
+
+int cloudsc2_tl_launch_batch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                             const cloudsc2_inputs* traj_in, int nbatch, const cloudsc2_inputs* pert_in,
+                             const cloudsc2_outputs* pert_out, void* stream) {
+  return tl_batch_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, nbatch, pert_in, pert_out, stream);
+}
+
+int cloudsc2_vjp_launch_batch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, int nbatch,
+                              const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                              const cloudsc2_real* scratch, void* stream) {
+  return vjp_batch_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, nbatch, adj_in, adj_out, scratch, stream);
 }
 
 int cloudsc2_ad_launch_reverse_norms(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,

@@ -249,6 +249,12 @@ std::vector<int> paced_kernel_occupancies() {
     add((const void*)ad_reverse_variant(f));
   }
   for (unsigned f = 64; f < 128; ++f) add((const void*)ad_reverse_variant(f));  // the vector-Jacobian forms (C2F_VJP)
+  for (unsigned f = 0; f < 64; ++f) {  // the batched sweeps
+    for (int nb = 2; nb <= kBatchMax; ++nb) {
+      add((const void*)tl_batch_variant(f, nb));
+      add((const void*)vjp_batch_variant(f, nb));
+    }
+  }
   return out;
 }
 
@@ -433,6 +439,8 @@ int cloudsc2_kernel_occupancy(int kernel, int flags, int* workgroups_per_cu) {
     case 1: fn = (const void*)tl_variant((unsigned)flags); break;
     case 2: fn = (const void*)ad_variant((unsigned)flags); break;
     case 3: fn = (const void*)ad_reverse_variant((unsigned)flags); break;
+    case 4: fn = (const void*)tl_batch_variant((unsigned)flags % 64u, flags / 64); break;  // flags + 64 x directions
+    case 5: fn = (const void*)vjp_batch_variant((unsigned)flags % 64u, flags / 64); break;
     default: break;
   }
   if (!fn) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: no such kernel variant in this build");

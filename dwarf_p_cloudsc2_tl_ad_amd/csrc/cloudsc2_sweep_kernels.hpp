@@ -1,6 +1,6 @@
 // cloudsc2_sweep_kernels.hpp -- the __global__ wrappers of the column sweeps (NL, TL, AD, the Taylor test's lambda sweep), their
 // compile-time variant tables and what they share.  The sweeps are built as one translation unit per kernel family so that an edit to
-// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor}.hip, each of which
+// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch}.hip, each of which
 // instantiates its table and exports it through one accessor (nl_variant(F) ...); the host units are listed in cloudsc2_host.hpp.
 // -DC2_SINGLE_TU puts the sweeps and their launchers into ONE code object again (cloudsc2_launch.hip then includes the family files):
 // the experiment builds of `make variant`, `make asm`, `make resources` and the -DC2_WAVE_TIMES diagnostic, whose log pointer is a
@@ -111,6 +111,27 @@ __global__ void __launch_bounds__(kBlock, 1) ad_kernel(AdArgs args) {
   C2_KERNEL_BODY(C2_WAVE_LOG_END);
 }
 
+// The batched TL and reverse sweeps (tl_batch_column, vjp_batch_column: up to kBatchMax directions over one trajectory).  One wave
+// per SIMD in fp64 like their single-direction twins, whose registers they extend by the carries of the further directions and one
+// more set of direction inputs; the fp32 builds take what they need (nothing is measured for them yet).
+// (their variant word: G = F + 64 x directions of the launch, a compile-time count -- cloudsc2_column.hpp says why)
+template <unsigned G>
+__global__ void __launch_bounds__(kBlock, 1) tl_batch_kernel(TlBatchArgs args) {
+  C2_KERNEL_BODY((tl_batch_column<G % 64u, (int)(G / 64u)>(global_column(), kernarg<TlBatchArgs>())));
+}
+template <unsigned G>
+__global__ void __launch_bounds__(kBlock, 1) vjp_batch_kernel(VjpBatchArgs args) {
+  C2_KERNEL_BODY((vjp_batch_column<G % 64u, (int)(G / 64u)>(global_column(), kernarg<VjpBatchArgs>())));
+}
+// the flag words of the batched sweeps: C2F_QSAT always, times PRECISE, EVAP, OFF32 (8 flag words per family and precision, times
+// the direction counts 2..kBatchMax)
+constexpr bool batch_variant_valid(unsigned f) {
+  return (f & C2F_QSAT) != 0 && (f & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32)) == 0;
+}
+constexpr bool batch_kernel_valid(unsigned g) {  // (one direction is tl_kernel's / ad_reverse_kernel's)
+  return batch_variant_valid(g % 64u) && g / 64u >= 2u && g / 64u <= (unsigned)kBatchMax;
+}
+
 // The ten perturbed NL runs of the Taylor test in one sweep, the lambdas on the lanes (taylor_column): the grid is over THREADS,
 // 64 per kTaylorCols columns.  A wave reads 6 columns = 48 bytes of every 128-byte line it touches, so two or three consecutive
 // waves share each line -- the one sweep whose workgroups share data.  Blocks are dealt round-robin over the 8 XCDs (b and b + 8
@@ -143,5 +164,7 @@ KernelFn<TlArgs> tl_variant(unsigned f);
 KernelFn<AdArgs> ad_variant(unsigned f);
 KernelFn<AdArgs> ad_reverse_variant(unsigned f);
 KernelFn<TaylorArgs> taylor_variant(unsigned f);
+KernelFn<TlBatchArgs> tl_batch_variant(unsigned f, int directions);
+KernelFn<VjpBatchArgs> vjp_batch_variant(unsigned f, int directions);
 
 }  // namespace cloudsc2

@@ -211,8 +211,9 @@ int cloudsc2_simd_population(long long workgroups, int cus, long long block, int
  * start-up; without it every launch simply runs unpaced (results are the same bits either way).  CLOUDSC2_PACE_VERBOSE=1 prints
  * the verdicts.  cloudsc2_dispatch_probe / cloudsc2_pace_probe run one probe and return its counts without caching anything (GPU
  * tests); cloudsc2_device_rules returns the cached verdicts of the current device (1 on, 0 off, -1 never probed);
- * cloudsc2_kernel_occupancy the workgroups per CU of one kernel variant (kernel 0 NL, 1 TL, 2 AD both sweeps, 3 AD reverse sweep;
- * flags = its C2F_* variant bits, cloudsc2_column.hpp) as the runtime reports them.
+ * cloudsc2_kernel_occupancy the workgroups per CU of one kernel variant (kernel 0 NL, 1 TL, 2 AD both sweeps, 3 AD reverse sweep,
+ * 4 batched TL, 5 batched reverse sweep; flags = its C2F_* variant bits, cloudsc2_column.hpp; for the batched sweeps, whose kernels
+ * are built per direction count, plus 64 x the directions of the launch, 2..cloudsc2_batch_max()) as the runtime reports them.
  *
  * What a caller with its own hipMalloc should expect.  The same kernel on the same data runs 0.78 or 0.92 ms (NL, 160 000 columns:
  * 0.73 vs 0.63 of the HBM peak) depending on WHERE in the HBM the state lies (profiles/r02_hbm_placement.md); cloudsc2_device_malloc*
@@ -292,6 +293,29 @@ int cloudsc2_vjp_launch(const cloudsc2_params* prm, double ptsphy, int nproma, i
                         const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
                         const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                         const cloudsc2_real* scratch, void* stream);
+
+/* Several tangents or cotangents over ONE trajectory -- a Jacobian block, a singular-vector iteration, an ensemble of perturbations.
+ * cloudsc2_tl_launch_batch replaces nbatch calls of cloudsc2_tl_launch without trajectory stores (traj_out all NULL),
+ * cloudsc2_vjp_launch_batch nbatch calls of cloudsc2_vjp_launch, over the same traj_in: every direction's results are the bits those
+ * calls give.  The trajectory planes are read once per launch instead of once per direction (bytes per column and direction, NLEV 137, fp64: 46 080 -> 28 536 + 17 544 / n for TL, 48 240 -> 28 504 + 19 736 / n
+ * for the reverse sweep, n = directions per launch).
+ *   pert_in / pert_out, adj_in / adj_out: arrays of nbatch argument blocks, one element per direction, used as by the single
+ *   launchers (adj_out read only; padded tail columns not written).  Every direction must have the same block stride per layout
+ *   group, and traj_in->qsat is required (there is no fused SATUR here): otherwise CLOUDSC2_EINVAL, as for nbatch < 1 or a NULL
+ *   field.  Without a device: CLOUDSC2_ENODEVICE.
+ * A launch carries at most cloudsc2_batch_max() directions (4 in this build: what the fp64 kernels hold in registers without
+ * scratch at one wave per SIMD); a larger nbatch is split into balanced chunks in stream order (5 -> 3 + 2, 9 -> 3 + 3 + 3), and
+ * nbatch = 1 is the single launcher itself.  Strides, pacing, stream capture and first-use behaviour are those of the other
+ * launchers: apart from the CETA table they neither allocate device memory nor synchronise. */
+int cloudsc2_batch_max(void);
+int cloudsc2_tl_launch_batch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                             const cloudsc2_inputs* traj_in, int nbatch,
+                             const cloudsc2_inputs* pert_in /* [nbatch] */, const cloudsc2_outputs* pert_out /* [nbatch] */,
+                             void* stream);
+int cloudsc2_vjp_launch_batch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, int nbatch,
+                              const cloudsc2_inputs* adj_in /* [nbatch] */, const cloudsc2_outputs* adj_out /* [nbatch], read only */,
+                              const cloudsc2_real* scratch, void* stream);
 
 /* The AD leg of the adjoint test with its norms formed in the sweep (cloudsc_driver_ad_mod.F90:198-267): the reverse sweep alone
  * in the assign form (zeroed input adjoints + CLOUDSC2AD), and for every active column norm2 = <x0, x_adj> with x0 = 0.01 * the

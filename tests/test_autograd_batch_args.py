@@ -1,0 +1,111 @@
+"""Batched tangents and cotangents, the part that needs no device: the C ABI's batch entry points fail loudly without a GPU, the
+vmap rules of the differentiable op refuse what they do not support, and the folding of a batch of states into the block dimension
+-- one call with full blocks, one call per state with a padded tail -- on CPU tensors."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests.util import B, c2
+from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
+
+NB, NLEV, NPROMA = 2, 6, 4
+
+
+def params(nlev=NLEV, **kw):
+    return c2.default_params(np.linspace(0.01, 1.0, nlev), **kw)
+
+
+def state(lay, seed):
+    g = torch.Generator().manual_seed(seed)
+    return tuple(torch.randn(lay.shape(n), generator=g, dtype=B.torch_real()) for n in B.IN_NAMES)
+
+
+def test_batch_max_is_a_small_compile_time_number():
+    assert 2 <= B.lib.cloudsc2_batch_max() <= 8
+
+
+def test_batch_launchers_fail_loudly_without_a_gpu():
+    prm = params(137)
+    one_in, one_out = (B.Inputs * 2)(), (B.Outputs * 2)()
+    i, o = B.Inputs(), B.Outputs()
+    # host pointers are never dereferenced: the device check comes first; with a GPU the empty blocks are refused instead
+    want = B.CLOUDSC2_EINVAL if c2.device_available() else B.CLOUDSC2_ENODEVICE
+    for nbatch in (1, 2):
+        assert B.lib.cloudsc2_tl_launch_batch(C.byref(prm), 3600.0, 32, 137, 64, C.byref(i), nbatch, one_in, one_out, None) == want
+        assert B.lib.cloudsc2_vjp_launch_batch(C.byref(prm), 3600.0, 32, 137, 64, C.byref(i), C.byref(o), nbatch, one_in, one_out, None,
+                                               None) == want
+        if not c2.device_available():
+            assert b"no CPU path" in B.lib.cloudsc2_last_error()
+
+
+def test_nested_vmap_is_refused_before_any_launch():
+    lay = ag.Layout(NB, NLEV, NPROMA, NB * NPROMA)
+    x = state(lay, 1)
+    prm = params()
+    f = lambda t: ag._Cloudsc2.apply(prm, 3600.0, lay, t, *x[1:])  # noqa: E731
+    with pytest.raises(NotImplementedError, match="nested vmap"):
+        torch.func.vmap(torch.func.vmap(f))(torch.zeros((2, 3) + lay.shape(B.IN_NAMES[0]), dtype=B.torch_real()))
+    for fn, n_in, n_extra in ((ag._Cloudsc2Tl, 32, 0), (ag._Cloudsc2Vjp, 16, 3)):
+        ops = list(x) + [torch.zeros(lay.shape("fplsl"), dtype=B.torch_real())] * 2 * (n_extra > 0) + [torch.zeros(0)] * (n_extra > 0)
+        ops += [torch.zeros(lay.shape(n), dtype=B.torch_real()) for n in (B.IN_NAMES if n_extra == 0 else B.OUT_NAMES)]
+        g = lambda t: fn.apply(prm, 3600.0, lay, *ops[:-1], t)  # noqa: E731,B023
+        with pytest.raises(NotImplementedError, match="nested vmap"):
+            torch.func.vmap(torch.func.vmap(g))(torch.zeros((2, 3) + tuple(ops[-1].shape), dtype=B.torch_real()))
+
+
+def test_a_batched_tensor_never_becomes_a_field():
+    lay = ag.Layout(NB, NLEV, NPROMA, NB * NPROMA)
+    with pytest.raises(NotImplementedError, match="batched tensor"):
+        torch.func.vmap(lambda t: ag._raw(t))(torch.zeros((3,) + lay.shape("t"), dtype=B.torch_real()))
+    with pytest.raises(NotImplementedError, match="batched tensor"):
+        torch.func.vmap(lambda t: ag._field(t, lay, "t").block_stride)(torch.zeros((3,) + lay.shape("t"), dtype=B.torch_real()))
+    # gradient-tracking wrappers are still unwrapped: the value shares the storage
+    t = torch.ones(lay.shape("t"), dtype=B.torch_real())
+    seen = []
+    torch.func.grad(lambda a: (seen.append(ag._raw(a).data_ptr()), a.sum())[1])(t)
+    assert seen == [t.data_ptr()]
+
+
+def test_operands_with_different_batch_sizes_are_refused():
+    a, b = torch.zeros(3, 2), torch.zeros(4, 2)
+    assert ag._batch_size((0, None, 0), (a, b, a)) == 3 and ag._batch_size((None, None), (a, b)) is None
+    with pytest.raises(ValueError, match="batch sizes"):
+        ag._batch_size((0, 0), (a, b))
+
+
+@pytest.mark.parametrize("ngptot,calls", [(NB * NPROMA, 1), (NB * NPROMA - 1, 3)])
+def test_a_batch_of_states_is_folded_into_the_block_dimension(ngptot, calls):
+    lay = ag.Layout(NB, NLEV, NPROMA, ngptot)
+    K = 3
+    batched = torch.arange(K * NB * NLEV * NPROMA, dtype=B.torch_real()).reshape(K, NB, NLEV, NPROMA)
+    moved = batched.movedim(0, 2)  # the batch dimension somewhere else: in_dim 2
+    shared = torch.full((NB, NLEV + 1, NPROMA), 7.0, dtype=B.torch_real())
+    empty = torch.zeros(0, dtype=B.torch_real())
+    seen = []
+
+    def fn(l, flat):
+        seen.append(l)
+        assert [tuple(t.shape) for t in flat[:2]] == [l.shape("t"), l.shape("paph")] and flat[2].numel() == 0
+        return flat[0] + flat[1][:, :-1], 2 * flat[1], flat[2]
+
+    out = ag._fold(fn, lay, ("t", "paph", "scratch"), (moved, shared, empty), (2, None, None), ("t", "paph", None))
+    assert len(seen) == calls
+    if calls == 1:  # full blocks: one call over K * nblocks blocks
+        assert seen[0] == ag.Layout(K * NB, NLEV, NPROMA, K * NB * NPROMA)
+    else:           # a padded tail: one call per state, each with its own ngptot
+        assert all(l == lay for l in seen)
+    assert out[0].shape == (K, NB, NLEV, NPROMA) and out[1].shape == (K, NB, NLEV + 1, NPROMA) and out[2].numel() == 0
+    assert torch.equal(out[0], batched + 7.0) and torch.equal(out[1], torch.full_like(out[1], 14.0))
+
+
+def test_new_arrays_of_a_batch_have_zero_tails():
+    lay = ag.Layout(NB, NLEV, NPROMA, NB * NPROMA - 3)
+    like = torch.zeros(1, dtype=B.torch_real())
+    for batch in (None, 3):
+        for n, t in ag._new(("t", "paph"), lay, like, batch=batch).items():
+            assert tuple(t.shape) == ((batch,) if batch else ()) + lay.shape(n)
+            assert bool(torch.all(t[..., -1, :, lay.tail:] == 0))
