@@ -1,9 +1,9 @@
 """CLOUDSC2 as a differentiable PyTorch operation: the NL sweep forward, the TL sweep as its jvp, the reverse sweep of the adjoint
 (in its vector-Jacobian form, ``cloudsc2_vjp_launch``) as its backward.
 
-    out = cloudsc2(inputs, prm, ptsphy, ngptot=None)
+    out = cloudsc2(inputs, prm, ptsphy, ngptot=None, satur=False)
 
-``inputs`` maps every name of ``binding.IN_NAMES`` to a device tensor; ``out`` is a :class:`Cloudsc2Outputs` namedtuple over
+``inputs`` maps every name of ``binding.IN_NAMES`` to a device tensor (with ``satur=True``: every name but ``qsat``); ``out`` is a :class:`Cloudsc2Outputs` namedtuple over
 ``binding.OUT_NAMES``.  ``torch.autograd.grad`` / ``.backward()``, ``torch.autograd.forward_ad`` and ``torch.func.jvp`` / ``vjp`` /
 ``grad`` / ``vmap`` / ``jacfwd`` / ``jacrev`` all work; double backward, nested vmap, ``torch.autograd.grad(...,
 is_grads_batched=True)`` (use ``torch.func.vmap`` of the vjp function instead) and gradients with respect to ``prm`` / ``ptsphy`` do
@@ -31,7 +31,16 @@ Semantics.
   * With ``prm.lregcl`` the jvp and backward are the reference's *regularised* linearisation (cloudsc2tl.F90:575,657,754,794,998),
     not the exact derivative of the forward.
   * ``qsat`` is an ordinary differentiable input, as in CLOUDSC2TL / CLOUDSC2AD.  :func:`satur` computes it from ``pap`` and ``t``
-    without a gradient: its result enters the op as a constant.
+    without a gradient by default: its result then enters the op as a constant.
+  * ``satur=True`` differentiates what the drivers compute, ``pap, t -> SATUR -> CLOUDSC2`` (cloudsc_driver_mod.F90:91): ``inputs``
+    has no ``qsat``, SATUR (satur.F90:106-123) and its two partial derivatives are evaluated inside the sweeps
+    (``cloudsc2_tl_launch_satur`` / ``cloudsc2_vjp_launch_satur``; no qsat plane is read, written or saved), and the ``pap`` / ``t``
+    gradients carry the saturation humidity's share.  The reference has no SATURTL / SATURAD: this derivative is the library's
+    own.  ``satur(pap, t, prm, differentiable=True)`` fed to the plain op is the same function unfused (three more planes, a launch
+    and torch's chain rule) for a caller who needs ``qsat`` itself; the two routes agree to 1e-11 of a field's maximum.  Batched
+    directions over one state (``jacfwd``, ``jacrev``, ``vmap(jvp)``, ``vmap(vjp_fn)``) of the ``satur=True`` op run by composition
+    -- one ``cloudsc2_satur_lin_launch``, the chain rule in torch, the batched sweeps with ``qsat`` as a plane -- so for them the
+    promise is that tolerance, not the bits of the unbatched fused call; a batch of states folds into the blocks as always.
   * The ``supsat`` gradient is the true derivative (coefficient 1 in ZQP1, cloudsc2tl.F90:345), not CLOUDSC2AD's PTSPHY*ZQP1
     (cloudsc2ad.F90:1733); every other gradient equals ``cloudsc2_ad_launch_assign``'s input adjoint bit for bit.
 
@@ -61,6 +70,9 @@ HALF_OUT = ("fplsl", "fplsn", "fhpsl", "fhpsn")
 IN_GROUPS = {"full": ("pap", "q", "qsat", "t", "lude", "lu", "mfu", "mfd", "supsat"), "half": ("paph",),
              "cml": ("gtent", "gtenq", "gtenl", "gteni"), "clv": ("l", "i")}
 OUT_GROUPS = {"loc": ("tent", "tenq", "tenl", "teni"), "full": ("clc", "covptot"), "half": HALF_OUT}
+# satur=True: SATUR is evaluated and differentiated inside the sweeps, qsat exists on no side
+SAT_NAMES = tuple(n for n in B.IN_NAMES if n != "qsat")
+SAT_GROUPS = {g: tuple(n for n in names if n != "qsat") for g, names in IN_GROUPS.items()}
 
 
 class Layout(namedtuple("Layout", "nblocks nlev nproma ngptot")):
@@ -88,14 +100,17 @@ def _fits(t: torch.Tensor, lay: Layout, name: str) -> bool:
     return (lay.nproma == 1 or t.stride(2) == 1) and t.stride(1) == lay.nproma
 
 
-def check_layout(inputs, prm: B.Params, ngptot: int | None = None) -> Layout:
+def check_layout(inputs, prm: B.Params, ngptot: int | None = None, satur: bool = False) -> Layout:
     """Every check of :func:`cloudsc2` that needs no device: names, dtype, shapes, strides, ``ngptot``, ``nlev`` and the parameters.
-    Runs on CPU or meta tensors; raises ``ValueError``."""
+    Runs on CPU or meta tensors; raises ``ValueError``.  ``satur``: the names are those of ``SAT_NAMES`` (no ``qsat``)."""
+    IN_NAMES = SAT_NAMES if satur else B.IN_NAMES
     names = set(inputs.keys()) if hasattr(inputs, "keys") else None
-    if names is None or names != set(B.IN_NAMES):
-        raise ValueError(f"inputs must map exactly the names {B.IN_NAMES}; got {sorted(names) if names is not None else type(inputs)}")
+    if satur and names is not None and "qsat" in names:
+        raise ValueError("satur=True: SATUR is evaluated and differentiated inside the op, inputs must not have a 'qsat'")
+    if names is None or names != set(IN_NAMES):
+        raise ValueError(f"inputs must map exactly the names {IN_NAMES}; got {sorted(names) if names is not None else type(inputs)}")
     dtype = B.torch_real()
-    for n in B.IN_NAMES:
+    for n in IN_NAMES:
         t = inputs[n]
         if not isinstance(t, torch.Tensor):
             raise ValueError(f"inputs[{n!r}] is not a tensor")
@@ -111,7 +126,7 @@ def check_layout(inputs, prm: B.Params, ngptot: int | None = None) -> Layout:
     lay = Layout(nb, nlev, nproma, nb * nproma if ngptot is None else int(ngptot))
     if not (nb - 1) * nproma < lay.ngptot <= nb * nproma:
         raise ValueError(f"ngptot = {lay.ngptot} does not fit {nb} blocks of nproma = {nproma} (the last block must hold 1..nproma columns)")
-    for n in B.IN_NAMES:
+    for n in IN_NAMES:
         t = inputs[n]
         if tuple(t.shape) != lay.shape(n):
             raise ValueError(f"inputs[{n!r}] has shape {tuple(t.shape)}, expected {lay.shape(n)} (from pap: nblocks, nlev, nproma)")
@@ -468,8 +483,230 @@ class _Cloudsc2(torch.autograd.Function):
         return outs, (0,) * 10 + (0 if evap else None,)
 
 
-def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None) -> Cloudsc2Outputs:
-    """SATUR-free CLOUDSC2 (``qsat`` is an input) over all blocks as a differentiable op; see the module docstring."""
+# ---- satur=True: pap, t -> SATUR -> CLOUDSC2, differentiated through SATUR inside the sweeps -------------------------------------
+
+def _satur_planes(prm, lay: Layout, pap: torch.Tensor, t: torch.Tensor, want_qsat: bool = True):
+    """``cloudsc2_satur_lin_launch``: (qsat or None, dqs/dpap, dqs/dt) as new contiguous planes, padded tail zero"""
+    dev = pap.device
+    pap, t = pap.contiguous(), t.contiguous()
+    new = _new(("qsat", "dqs_dpap", "dqs_dt") if want_qsat else ("dqs_dpap", "dqs_dt"), lay, pap)
+    with torch.cuda.device(dev):
+        B.check(B.lib.cloudsc2_satur_lin_launch(C.byref(prm), lay.nproma, lay.nlev, lay.ngptot, _field(pap, lay, "pap"), _field(t, lay, "t"),
+                                                _field(new.get("qsat"), lay, "qsat"), _field(new["dqs_dpap"], lay, "pap"),
+                                                _field(new["dqs_dt"], lay, "pap"), _stream(dev)))
+    return new.get("qsat"), new["dqs_dpap"], new["dqs_dt"]
+
+
+def _with_qsat(x15: dict, qsat) -> list:
+    return [qsat if n == "qsat" else x15[n] for n in B.IN_NAMES]
+
+
+class _Cloudsc2SaturTl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, *15 trajectory inputs, *15 tangents) -> 10 output tangents: ``cloudsc2_tl_launch_satur``.  Not
+    differentiable (no double backward)."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, *ts):
+        x = dict(zip(SAT_NAMES, ts[:15]))
+        like = x["pap"]
+        dev = like.device
+        dx = normalize(dict(zip(SAT_NAMES, ts[15:])), lay, SAT_GROUPS)
+        dy = _new(B.OUT_NAMES, lay, like)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch_satur(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                   C.byref(_block("in", x, lay)), C.byref(_block("in", dx, lay)),
+                                                   C.byref(_block("out", dy, lay)), _stream(dev)))
+        return tuple(dy[n] for n in B.OUT_NAMES)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(*output)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, *ts):
+        _refuse_nested(ts)
+        dims = in_dims[3:]
+        K = _batch_size(dims, ts)
+        if K is None:
+            return _Cloudsc2SaturTl.apply(prm, ptsphy, lay, *ts), (None,) * 10
+        if any(d is not None for d in dims[:15]):  # a batch of states
+            def one(l, flat):
+                x = normalize(dict(zip(SAT_NAMES, flat[:15])), l, SAT_GROUPS)
+                return _Cloudsc2SaturTl.apply(prm, ptsphy, l, *(x[n] for n in SAT_NAMES), *flat[15:])
+            return _fold(one, lay, SAT_NAMES * 2, ts, dims, B.OUT_NAMES), (0,) * 10
+        # K directions over one state, by composition: SATUR's partials once, the tangent of qsat of every direction in torch, the
+        # batched TL sweep with qsat as a plane
+        x = dict(zip(SAT_NAMES, ts[:15]))
+        dx = {n: _front(t, d) for n, t, d in zip(SAT_NAMES, ts[15:], dims[15:])}
+        ddim = dict(zip(SAT_NAMES, (None if d is None else 0 for d in dims[15:])))
+        qsat, dqp, dqt = _satur_planes(prm, lay, x["pap"], x["t"])
+        dx["qsat"] = dqp * dx["pap"] + dqt * dx["t"]
+        ddim["qsat"] = None if ddim["pap"] is None and ddim["t"] is None else 0
+        x16 = normalize(dict(zip(B.IN_NAMES, _with_qsat(x, qsat))), lay, IN_GROUPS)
+        return _Cloudsc2Tl.vmap(info, (None,) * 19 + tuple(ddim[n] for n in B.IN_NAMES), prm, ptsphy, lay,
+                                *(x16[n] for n in B.IN_NAMES), *(dx[n] for n in B.IN_NAMES))
+
+
+_SAT_VJP_TRAJ = SAT_NAMES + ("fplsl", "fplsn", "scratch")  # the trajectory operands of _Cloudsc2SaturVjp
+
+
+class _Cloudsc2SaturVjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, *15 trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints) -> 15 input
+    adjoints: ``cloudsc2_vjp_launch_satur``.  Not differentiable (no double backward)."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, *ts):
+        x = dict(zip(SAT_NAMES, ts[:15]))
+        fplsl, fplsn, scratch = ts[15:18]
+        like = x["pap"]
+        dev = like.device
+        y = normalize(dict(zip(B.OUT_NAMES, ts[18:])), lay, OUT_GROUPS)
+        xa = _new(SAT_NAMES, lay, like)
+        traj_out = B.Outputs()
+        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch_satur(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                    C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
+                                                    C.byref(_block("out", y, lay)), _scratch_ptr(scratch), _stream(dev)))
+        return tuple(xa[n] for n in SAT_NAMES)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(*output)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, *ts):
+        _refuse_nested(ts)
+        dims = in_dims[3:]
+        K = _batch_size(dims, ts)
+        if K is None:
+            return _Cloudsc2SaturVjp.apply(prm, ptsphy, lay, *ts), (None,) * 15
+        if any(d is not None for d in dims[:18]):  # a batch of states
+            def one(l, flat):
+                x = normalize(dict(zip(SAT_NAMES, flat[:15])), l, SAT_GROUPS)
+                fl = [t if _fits(t, l, "fplsl") and _block_stride(t, l, "fplsl") == (l.nlev + 1) * l.nproma else t.contiguous() for t in flat[15:17]]
+                sc = flat[17].contiguous()
+                return _Cloudsc2SaturVjp.apply(prm, ptsphy, l, *(x[n] for n in SAT_NAMES), *fl, sc, *flat[18:])
+            return _fold(one, lay, _SAT_VJP_TRAJ + B.OUT_NAMES, ts, dims, SAT_NAMES), (0,) * 15
+        # K cotangents over one state, by composition: the batched reverse sweep with qsat as a plane, then SATUR's transpose in torch
+        x = dict(zip(SAT_NAMES, ts[:15]))
+        qsat, dqp, dqt = _satur_planes(prm, lay, x["pap"], x["t"])
+        x16 = normalize(dict(zip(B.IN_NAMES, _with_qsat(x, qsat))), lay, IN_GROUPS)
+        xa, _ = _Cloudsc2Vjp.vmap(info, (None,) * 22 + tuple(dims[18:]), prm, ptsphy, lay, *(x16[n] for n in B.IN_NAMES), *ts[15:])
+        xa = dict(zip(B.IN_NAMES, xa))
+        xa["pap"] = xa["pap"] + dqp * xa["qsat"]
+        xa["t"] = xa["t"] + dqt * xa["qsat"]
+        return tuple(xa[n] for n in SAT_NAMES), (0,) * 15
+
+
+class _Cloudsc2Satur(torch.autograd.Function):
+    # forward(prm, ptsphy, layout, *15 inputs in SAT_NAMES order) -> 10 outputs + the cover-checkpoint scratch (non-differentiable):
+    # the NL sweep with SATUR fused; its jvp and backward are the two functions above.  One plane less than _Cloudsc2 is saved.
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, *xs):
+        x = dict(zip(SAT_NAMES, xs))
+        like = x["pap"]
+        dev = like.device
+        out = _new(B.OUT_NAMES, lay, like)
+        scratch = torch.empty((lay.nblocks, lay.nlev, lay.nproma) if _evap(prm) else (0,), dtype=like.dtype, device=dev)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_ad_launch_forward(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                     C.byref(_block("in", x, lay)), C.byref(_block("out", out, lay)),
+                                                     _scratch_ptr(scratch), _stream(dev)))
+        return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        prm, ptsphy, lay, *xs = inputs
+        out = dict(zip(B.OUT_NAMES, output[:-1]))
+        scratch = output[-1]
+        ctx.mark_non_differentiable(scratch)
+        ctx.save_for_backward(*xs, out["fplsl"], out["fplsn"], scratch)
+        ctx.save_for_forward(*xs)
+        ctx.prm, ctx.ptsphy, ctx.lay = prm, ptsphy, lay
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        lay, like = ctx.lay, saved[0]
+        need = ctx.needs_input_grad[3:]
+        if not any(need):
+            return (None, None, None) + (None,) * 15
+        y = _zero_filled(B.OUT_NAMES, grads[:10], lay, like)
+        xa = _Cloudsc2SaturVjp.apply(ctx.prm, ctx.ptsphy, lay, *saved, *(y[n] for n in B.OUT_NAMES))
+        return (None, None, None) + tuple(a if nd else None for a, nd in zip(xa, need))
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        xs = ctx.saved_tensors
+        dx = _zero_filled(SAT_NAMES, tangents[3:], ctx.lay, xs[0])
+        dy = _Cloudsc2SaturTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, *xs, *(dx[n] for n in SAT_NAMES))
+        return tuple(dy) + (None,)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, *xs):
+        _refuse_nested(xs)
+        dims = in_dims[3:]
+        if _batch_size(dims, xs) is None:
+            return _Cloudsc2Satur.apply(prm, ptsphy, lay, *xs), (None,) * 11
+
+        def one(l, flat):
+            x = normalize(dict(zip(SAT_NAMES, flat)), l, SAT_GROUPS)
+            return _Cloudsc2Satur.apply(prm, ptsphy, l, *(x[n] for n in SAT_NAMES))
+        evap = _evap(prm)
+        outs = _fold(one, lay, SAT_NAMES, xs, dims, B.OUT_NAMES + ("scratch" if evap else None,))
+        return outs, (0,) * 10 + (0 if evap else None,)
+
+
+class _Satur(torch.autograd.Function):
+    # forward(prm, layout, pap, t) -> qsat, dqs/dpap, dqs/dt (the partials non-differentiable, saved): SATUR with first-order
+    # derivatives, both elementwise products with the partial planes
+
+    @staticmethod
+    def forward(prm, lay, pap, t):
+        return _satur_planes(prm, lay, pap, t)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        _, dqp, dqt = output
+        ctx.mark_non_differentiable(dqp, dqt)
+        ctx.save_for_backward(dqp, dqt)
+        ctx.save_for_forward(dqp, dqt)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gp, _gt):
+        dqp, dqt = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return None, None, (g * dqp if need[2] else None), (g * dqt if need[3] else None)
+
+    @staticmethod
+    def jvp(ctx, _prm, _lay, dpap, dt):
+        dqp, dqt = ctx.saved_tensors
+        dq = None
+        for part, d in ((dqp, dpap), (dqt, dt)):
+            if d is not None:
+                dq = part * d if dq is None else dq + part * d
+        return dq if dq is not None else torch.zeros_like(dqp), None, None
+
+    @staticmethod
+    def vmap(info, in_dims, prm, lay, pap, t):
+        raise NotImplementedError("satur(differentiable=True): torch.func.vmap is not supported (differentiate the op with "
+                                  "satur=True, whose vmap rules carry batches)")
+
+
+def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False) -> Cloudsc2Outputs:
+    """CLOUDSC2 over all blocks as a differentiable op, SATUR-free (``qsat`` is an input) or, with ``satur=True``, with SATUR
+    evaluated and differentiated inside (``inputs`` without ``qsat``); see the module docstring."""
+    if satur:
+        lay = check_layout(inputs, prm, ngptot, satur=True)
+        dev = check_device(inputs[n] for n in SAT_NAMES)
+        _prepare(dev)
+        x = normalize({n: inputs[n] for n in SAT_NAMES}, lay, SAT_GROUPS)
+        out = _Cloudsc2Satur.apply(prm, float(ptsphy), lay, *(x[n] for n in SAT_NAMES))
+        return Cloudsc2Outputs(*out[:10])
     lay = check_layout(inputs, prm, ngptot)
     dev = check_device(inputs[n] for n in B.IN_NAMES)
     _prepare(dev)
@@ -478,10 +715,12 @@ def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None) ->
     return Cloudsc2Outputs(*out[:10])
 
 
-def satur(pap: torch.Tensor, t: torch.Tensor, prm: B.Params, ngptot: int | None = None) -> torch.Tensor:
-    """SATUR (satur.F90:106-123, the LPHYLIN branch the drivers call) into a new ``(nblocks, nlev, nproma)`` tensor, with NO
-    gradient: passed to :func:`cloudsc2` as ``qsat`` it is a constant input there (differentiate through ``qsat`` only as an input
-    of its own, as CLOUDSC2TL / CLOUDSC2AD do)."""
+def satur(pap: torch.Tensor, t: torch.Tensor, prm: B.Params, ngptot: int | None = None, differentiable: bool = False) -> torch.Tensor:
+    """SATUR (satur.F90:106-123, the LPHYLIN branch the drivers call) into a new ``(nblocks, nlev, nproma)`` tensor.  By default
+    with NO gradient: passed to :func:`cloudsc2` as ``qsat`` it is a constant input there (differentiate through ``qsat`` only as
+    an input of its own, as CLOUDSC2TL / CLOUDSC2AD do).  ``differentiable=True``: the result carries first-order derivatives with
+    respect to ``pap`` and ``t`` (``cloudsc2_satur_lin_launch``: the two partial planes are saved, backward and jvp are elementwise
+    products with them; no double backward, no vmap) -- the unfused counterpart of ``cloudsc2(..., satur=True)``."""
     for n, a in (("pap", pap), ("t", t)):
         if not isinstance(a, torch.Tensor) or a.dtype != B.torch_real() or a.dim() != 3:
             raise ValueError(f"{n} must be a 3-D {B.torch_real()} tensor")
@@ -492,6 +731,8 @@ def satur(pap: torch.Tensor, t: torch.Tensor, prm: B.Params, ngptot: int | None 
     if not (nb - 1) * nproma < lay.ngptot <= nb * nproma or not 2 <= nlev <= B.CLOUDSC2_MAX_NLEV or int(prm.nlev) != nlev:
         raise ValueError(f"satur: shape {tuple(pap.shape)}, ngptot {lay.ngptot} and prm.nlev {prm.nlev} do not fit together")
     dev = check_device((pap, t))
+    if differentiable:
+        return _Satur.apply(prm, lay, pap, t)[0]
     with torch.no_grad():
         pap, t = pap.detach().contiguous(), t.detach().contiguous()
         q = _new(("qsat",), lay, pap)["qsat"]

@@ -373,6 +373,10 @@ enum : unsigned {
                      // (cloudsc2_vjp_launch): the output adjoints are only read (not zeroed) and the PSUPSAT adjoint is the true
                      // derivative zqp1 instead of the reference's PTSPHY*zqp1 (cloudsc2ad.F90:1733 vs cloudsc2tl.F90:345).
                      // It shares its bit with NOLIN: the fused ad_kernel, which hands its flags on to nl_column, never takes it.
+  C2F_SATLIN = 128u, // TL (without TRAJ / SELFINC) and the VJP form of the reverse sweep, never with QSAT: SATUR is differentiated
+                     // inside the sweep (satur_lin_point).  The tangent of qsat is dqs/dpap dpap + dqs/dt dt instead of an input plane,
+                     // its adjoint is folded into those of pap and t instead of being stored: no qsat plane on either side
+                     // (cloudsc2_tl_launch_satur, cloudsc2_vjp_launch_satur)
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -395,6 +399,33 @@ C2_HD void satur_column(long long gcol, SaturArgsP a) {
   for (int jk = 0; jk < nlev; ++jk) {
     long long d = (long long)jk * nproma;
     stg(qsat, o.full + d, satur_point<P>(C2_CONSTS(a), ldg(pap, o.full + d), ldg(t, o.full + d)));
+  }
+}
+
+// SATUR and its two partial derivatives as planes (cloudsc2_satur_lin_launch); qsat may be NULL: partials only
+struct SaturLinArgs {
+  Consts c; Geom g; Strides s; const real_t* pap; const real_t* t; real_t* qsat; real_t* dqs_dpap; real_t* dqs_dt;
+};
+typedef const C2_CONST_AS SaturLinArgs* SaturLinArgsP;
+
+template <bool P>
+C2_HD void satur_lin_column(long long gcol, SaturLinArgsP a) {
+  LaneOff o; bool active;
+  if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
+  if (!active) return;
+  const int nlev = a->g.nlev, nproma = a->g.nproma;
+  const real_t* pap = a->pap;
+  const real_t* t = a->t;
+  real_t* qsat = a->qsat;
+  real_t* dp = a->dqs_dpap;
+  real_t* dt = a->dqs_dt;
+  for (int jk = 0; jk < nlev; ++jk) {
+    long long d = (long long)jk * nproma;
+    real_t dqp, dqt;
+    const real_t qs = satur_lin_point<P>(C2_CONSTS(a), ldg(pap, o.full + d), ldg(t, o.full + d), dqp, dqt);
+    if (qsat) stg(qsat, o.full + d, qs);
+    stg(dp, o.full + d, dqp);
+    stg(dt, o.full + d, dqt);
   }
 }
 
@@ -674,7 +705,8 @@ C2_HD void self_increment(const RawLevel& r, real_t supsat_inc, RawLevel& d) {
 template <unsigned F>
 C2_HD void tl_column(long long gcol, TlArgsP a) {
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, STORE_TRAJ = (F & C2F_TRAJ) != 0, EVAP = (F & C2F_EVAP) != 0;
-  constexpr bool SELFINC = (F & C2F_SELFINC) != 0;
+  constexpr bool SELFINC = (F & C2F_SELFINC) != 0, SATLIN = (F & C2F_SATLIN) != 0;
+  static_assert(!SATLIN || (!HAS_QSAT && !STORE_TRAJ && !SELFINC), "C2F_SATLIN: SATUR fused, no trajectory stores, increments given");
   typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
   LaneOff o, op; bool active;
   if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
@@ -710,7 +742,7 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   real_t paph_k = in->paph[o.half], dpaph_k = SELFINC ? paph_k * RC(0.01) : din->paph[op.half];
   const LaneOffT<OT> ol = lane_off_as<OT>(o), opl = lane_off_as<OT>(op);  // offsets used inside the level loop
   load_level<HAS_QSAT>(in, ol, nproma, nlev, 0, cur);
-  if (!SELFINC) load_level<true>(din, opl, nproma, nlev, 0, dcur);
+  if (!SELFINC) load_level<!SATLIN>(din, opl, nproma, nlev, 0, dcur);
   Pace pace;
   pace.begin(&a->g);
 
@@ -728,10 +760,16 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
     if (!SELFINC) dnxt = dcur;
     if (!last) {
       load_level<HAS_QSAT>(in, ol, nproma, nlev, jk + 1, nxt);
-      if (!SELFINC) load_level<true>(din, opl, nproma, nlev, jk + 1, dnxt);
+      if (!SELFINC) load_level<!SATLIN>(din, opl, nproma, nlev, jk + 1, dnxt);
     }
     pace.nap();  // (with the next level's loads in flight)
-    if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);
+    if constexpr (SATLIN) {  // the tangent of qsat from those of pap and t: no qsat plane in either input set
+      real_t dqs_dpap, dqs_dt;
+      cur.qsat = satur_lin_point<P>(c, cur.pap, cur.t, dqs_dpap, dqs_dt);
+      dcur.qsat = dqs_dpap * dcur.pap + dqs_dt * dcur.t;
+    } else if (!HAS_QSAT) {
+      cur.qsat = satur_point<P>(c, cur.pap, cur.t);
+    }
     if (SELFINC) self_increment(cur, ap->supsat_inc, dcur);
 
     LevelCst k;
@@ -856,7 +894,8 @@ template <unsigned F>
 C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| of the column with C2F_ADNORM (+inf for NaN), else 0
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0;
   constexpr bool OFF32 = (F & C2F_OFF32) != 0, ASSIGN = (F & C2F_ASSIGN) != 0, ADNORM = (F & C2F_ADNORM) != 0;
-  constexpr bool VJP = (F & C2F_VJP) != 0;
+  constexpr bool VJP = (F & C2F_VJP) != 0, SATLIN = (F & C2F_SATLIN) != 0;
+  static_assert(!SATLIN || (VJP && !HAS_QSAT), "C2F_SATLIN: the vector-Jacobian form with SATUR fused");
   static_assert(!ADNORM || ASSIGN, "the fused norms are those of the adjoint test: assign form");
   static_assert(!VJP || (ASSIGN && !ADNORM), "the vector-Jacobian product assigns its input adjoints and forms no norms");
   typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
@@ -904,7 +943,13 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     const RawLevel& xo = L.xo;
     LevelOut ya = L.ya;  // enthalpy-flux adjoints folded in below (cloudsc2ad.F90:914-921)
 
-    if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);
+    [[maybe_unused]] real_t dqs_dpap = RC(0.0), dqs_dt = RC(0.0);
+    if constexpr (SATLIN) {
+      // (PAP and PT requested one level ahead, so that SATUR runs under the level's other loads: measured, no gain -- EXPERIMENTS.md 12)
+      cur.qsat = satur_lin_point<P>(c, cur.pap, cur.t, dqs_dpap, dqs_dt);
+    } else if (!HAS_QSAT) {
+      cur.qsat = satur_point<P>(c, cur.pap, cur.t);
+    }
     LevelCst k;
     level_cst(tab, jk, last, k);
     LevelIn x;
@@ -917,6 +962,10 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     ya.fplsl = ya.fplsl - ya.fhpsl * c->rlvtt;
     LevelIn ax;
     level_ad(c, k, x, tr, ya, acy, ax);
+    if constexpr (SATLIN) {  // the adjoint of qsat goes to pap and t through SATUR's transpose; it has no plane of its own
+      ax.pap += dqs_dpap * ax.qs;
+      ax.t += dqs_dt * ax.qs;
+    }
 
     C2_LAUNDER(ap);
     const InPtrsRW px = ap->ain;
@@ -924,7 +973,7 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     // accumulate input adjoints (cloudsc2ad.F90:1723-1738; PSUPSAT assigned, :1733)
     stg(px.pap, oa.full + d, xo.pap + ax.pap);
     stg(px.q, oa.full + d, xo.q + ax.q);
-    stg(px.qsat, oa.full + d, xo.qsat + ax.qs);
+    if constexpr (!SATLIN) stg(px.qsat, oa.full + d, xo.qsat + ax.qs);
     stg(px.t, oa.full + d, xo.t + ax.t);
     stg(px.l, oa.clv + d, xo.l + ax.l);
     stg(px.i, oa.clv + d, xo.i + ax.i);

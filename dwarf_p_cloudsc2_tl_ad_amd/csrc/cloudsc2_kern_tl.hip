@@ -4,7 +4,8 @@
 
 namespace cloudsc2 {
 namespace {
-C2_VARIANT_TABLE(g_tl_kernels, tl_kernel, TlArgs, 64, true)
+// (C2F_SATLIN: SATUR differentiated in the sweep -- without QSAT, TRAJ, SELFINC: PRECISE x EVAP x OFF32)
+C2_VARIANT_TABLE(g_tl_kernels, tl_kernel, TlArgs, 256, F < 64u || (F & ~(C2F_PRECISE | C2F_EVAP | C2F_OFF32)) == C2F_SATLIN)
 }  // namespace
 KernelFn<TlArgs> tl_variant(unsigned f) { return f < g_tl_kernels.size() ? g_tl_kernels[f] : nullptr; }
 }  // namespace cloudsc2

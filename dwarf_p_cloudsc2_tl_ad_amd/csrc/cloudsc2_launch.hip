@@ -31,6 +31,10 @@ template <bool P>
 __global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
   C2_KERNEL_BODY(satur_column<P>(global_column(), kernarg<SaturArgs>()));
 }
+template <bool P>
+__global__ void __launch_bounds__(kBlock) satur_lin_kernel(SaturLinArgs args) {
+  C2_KERNEL_BODY(satur_lin_column<P>(global_column(), kernarg<SaturLinArgs>()));
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Data-format kernels either side of the path: the input file holds KLON (=100) columns,
@@ -495,9 +499,10 @@ struct Sweep {
 };
 
 // pert_in == NULL: the increments are 0.01*x of the trajectory inputs (supsat_inc * PSUPSAT for PSUPSAT), C2F_SELFINC
+// satlin: SATUR is differentiated in the sweep (C2F_SATLIN): no qsat on either input side, no trajectory stores
 int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
                    const cloudsc2_outputs* traj_out, const cloudsc2_inputs* pert_in, double supsat_inc, const cloudsc2_outputs* pert_out,
-                   double* yy, void* stream) {
+                   double* yy, void* stream, bool satlin = false) {
   Sweep w;
   int rc = w.begin(prm, nproma, nlev, ngptot, (!traj_in || !traj_out || !pert_out) ? "NULL argument block" : nullptr);
   if (rc) return rc;
@@ -506,11 +511,13 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   int nset = 0;
   for (auto f : tf) nset += f->ptr ? 1 : 0;
   if (nset != 0 && nset != 10) return fail(CLOUDSC2_EINVAL, "traj_out: give all ten trajectory outputs or none");
+  if (satlin && (traj_in->qsat.ptr || (pert_in && pert_in->qsat.ptr)))
+    return fail(CLOUDSC2_EINVAL, "SATUR differentiated in the sweep: traj_in->qsat and pert_in->qsat must be NULL");
   if ((rc = w.trajectory(*traj_in, *traj_out, false))) return rc;
   TlArgs args;
   args.sp = Strides{0, 0, 0, 0, 0};
   if (pert_in) {
-    if ((rc = resolve_in(*pert_in, true, args.sp, args.din))) return rc;
+    if ((rc = resolve_in(*pert_in, !satlin, args.sp, args.din))) return rc;
   } else {
     memset(&args.din, 0, sizeof(args.din));  // (sp: taken from the outputs by resolve_out)
   }
@@ -519,6 +526,7 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sp.full, sp.half, sp.cml, sp.clv, sp.loc}))) return rc;
   if (!pert_in) w.f |= C2F_SELFINC;
   if (nset == 10) w.f |= C2F_TRAJ;
+  if (satlin) w.f |= C2F_SATLIN;  // (its launcher passes pert_in and no trajectory outputs)
   args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.out = w.out; args.tab = w.tab;
   args.supsat_inc = (real_t)supsat_inc;
   args.yy = yy;
@@ -534,11 +542,13 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
 // What an AD launch runs.  which 0: both sweeps (the fused kernel, or the two kernels in stream order); 1: the trajectory pass
 // alone; 2: the reverse sweep alone.  assign: the input adjoints are assigned, not accumulated.  vjp: the vector-Jacobian product.
 // norms / gmax: the adjoint test's norms formed in the reverse sweep.
+// satlin: the vector-Jacobian product with SATUR differentiated in the sweep (C2F_SATLIN).
 struct AdMode {
   int which;
   bool assign, vjp;
   double* norms;
   double* gmax;
+  bool satlin = false;
 };
 
 int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
@@ -553,9 +563,11 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   if (m.which == 2 && (!w.out.fplsl || !w.out.fplsn)) return fail(CLOUDSC2_EINVAL, "reverse sweep: traj_out->fplsl and ->fplsn (PFPLSL5, PFPLSN5) are required");
   AdArgs args;
   memset(&args, 0, sizeof(args));
+  if (m.satlin && (traj_in->qsat.ptr || adj_in->qsat.ptr))
+    return fail(CLOUDSC2_EINVAL, "SATUR differentiated in the sweep: traj_in->qsat and adj_in->qsat must be NULL");
   if (m.which != 1) {
     InPtrs aip_c;
-    if ((rc = resolve_in(*adj_in, true, args.sa, aip_c))) return rc;
+    if ((rc = resolve_in(*adj_in, !m.satlin, args.sa, aip_c))) return rc;
     if ((rc = resolve_out(*adj_out, true, args.sa, args.aout))) return rc;
     InPtrsRW& aip = args.ain;
     aip.paph = adj_in->paph.ptr; aip.pap = adj_in->pap.ptr; aip.q = adj_in->q.ptr; aip.qsat = adj_in->qsat.ptr;
@@ -574,6 +586,7 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   if (m.vjp) {  // the vector-Jacobian product: reverse sweep alone, assign form, adj_out read only, true PSUPSAT adjoint
     if (m.which != 2 || !m.assign || m.norms) return fail(CLOUDSC2_EINVAL, "vector-Jacobian product: reverse sweep alone, assign form, no norms");
     f |= C2F_VJP;
+    if (m.satlin) f |= C2F_SATLIN;
   }
   if (m.norms) {  // the adjoint test's norm2 / norm3 formed in the reverse sweep
     if (m.which != 2 || !m.assign || w.c.evap || !m.gmax) return fail(CLOUDSC2_EINVAL, "fused adjoint norms: reverse sweep alone, assign form, no evaporation branch");
@@ -823,6 +836,26 @@ int cloudsc2_satur_launch(const cloudsc2_params* prm, int nproma, int nlev, int 
   return 0;
 }
 
+int cloudsc2_satur_lin_launch(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, cloudsc2_field pap, cloudsc2_field t,
+                              cloudsc2_field qsat, cloudsc2_field dqs_dpap, cloudsc2_field dqs_dt, void* stream) {
+  Geom g;
+  int rc = check_geom(prm, nproma, nlev, ngptot, g);
+  if (rc) return rc;
+  if (!pap.ptr || !t.ptr || !dqs_dpap.ptr || !dqs_dt.ptr) return fail(CLOUDSC2_EINVAL, "NULL field");
+  if (pap.block_stride != t.block_stride || pap.block_stride != dqs_dpap.block_stride || pap.block_stride != dqs_dt.block_stride ||
+      (qsat.ptr && pap.block_stride != qsat.block_stride))
+    return fail(CLOUDSC2_EINVAL, "pap, t, qsat, dqs_dpap, dqs_dt must share one block stride");
+  SaturLinArgs args;
+  args.c = make_consts(*prm, 1.0);
+  args.g = g;
+  args.s = Strides{pap.block_stride, 0, 0, 0, 0};
+  args.pap = pap.ptr; args.t = t.ptr; args.qsat = qsat.ptr; args.dqs_dpap = dqs_dpap.ptr; args.dqs_dt = dqs_dt.ptr;
+  hipLaunchKernelGGL(precise_of(prm) ? satur_lin_kernel<true> : satur_lin_kernel<false>, dim3(grid_for(g.ncols_pad, kBlock)), dim3(kBlock), 0,
+                     (hipStream_t)stream, args);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 int cloudsc2_nl_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
                        const cloudsc2_inputs* in, const cloudsc2_outputs* out, cloudsc2_field zero_plane,
                        double pert_lambda, void* stream) {
@@ -888,6 +921,22 @@ int cloudsc2_vjp_launch(const cloudsc2_params* prm, double ptsphy, int nproma, i
                         const cloudsc2_real* scratch, void* stream) {
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
                         stream, AdMode{2, true, true});
+}
+
+int cloudsc2_tl_launch_satur(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                             const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out,
+                             void* stream) {
+  if (!pert_in) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  const cloudsc2_outputs none = {};
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_in, 0.0, pert_out, nullptr, stream, true);
+}
+
+int cloudsc2_vjp_launch_satur(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                              const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                              const cloudsc2_real* scratch, void* stream) {
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
+                        stream, AdMode{2, true, true, nullptr, nullptr, true});
 }
 
 int cloudsc2_batch_max(void) { return kBatchMax; }

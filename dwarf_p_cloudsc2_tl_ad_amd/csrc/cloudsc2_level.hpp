@@ -170,7 +170,7 @@ enum { KT0_PTSPHY, KT0_RTT, KT0_R3IES, KT0_R4IES, KT0_R3LES, KT0_R4LES, KT0_R5LE
 enum { KT1_RETV, KT1_ZCONS3, KT1_RG, KT1_ZQTMST, KT1_ZCONS2, KT1_ZMELTP2, KT1_ZLCRIT_L_R2, KT1_ZLCRIT_I_R2 };
 enum { KT2_CK_L, KT2_CK_I, KT2_RLVTT, KT2_RLSTT, KT2_SPARE0, KT2_SPARE1, KT2_SPARE2, KT2_SPARE3 };
 // kf: FOEALFA
-enum { KF_RTICE, KF_RTWAT, KF_RTWAT_RTICE_R, KF_SPARE0, KF_SPARE1, KF_SPARE2, KF_SPARE3, KF_SPARE4 };
+enum { KF_RTICE, KF_RTWAT, KF_RTWAT_RTICE_R, KF_R5LES, KF_R5IES, KF_SPARE2, KF_SPARE3, KF_SPARE4 };  // (R5*: satur_lin_point)
 
 // Launch-invariant scalars: the module constants plus what CLOUDSC2 derives from them at entry
 // (cloudsc2.F90:235-244, cloudsc2tl.F90:321-332).
@@ -226,7 +226,7 @@ inline void fill_stage_blocks(Consts& c) {
   k = c.kt2.v; k[KT2_CK_L] = c.lregcl ? c.zckcodtla : c.zckcodtl; k[KT2_CK_I] = c.lregcl ? c.zckcodtia : c.zckcodti;
   k[KT2_RLVTT] = c.rlvtt; k[KT2_RLSTT] = c.rlstt; k[KT2_SPARE0] = k[KT2_SPARE1] = k[KT2_SPARE2] = k[KT2_SPARE3] = RC(0.0);
   k = c.kf.v; k[KF_RTICE] = c.rtice; k[KF_RTWAT] = c.rtwat; k[KF_RTWAT_RTICE_R] = c.rtwat_rtice_r;
-  k[KF_SPARE0] = k[KF_SPARE1] = k[KF_SPARE2] = k[KF_SPARE3] = k[KF_SPARE4] = RC(0.0);
+  k[KF_R5LES] = c.r5les; k[KF_R5IES] = c.r5ies; k[KF_SPARE2] = k[KF_SPARE3] = k[KF_SPARE4] = RC(0.0);
 }
 
 // host side: everything the kernels need besides fields and level tables, from the caller's parameter block
@@ -373,24 +373,29 @@ C2_HD real_t foealfa(ConstsP c, real_t t) {
   return fmin(RC(1.0), x * x);
 }
 
-// SATUR, LDPHYLIN branch (src/cloudsc2_nl/satur.F90:106-123)
-template <bool P>
-C2_HD real_t satur_point(ConstsP c, real_t pap, real_t t) {
+// SATUR, LDPHYLIN branch (src/cloudsc2_nl/satur.F90:106-123).  LIN: its two partial derivatives as well (satur_lin_point below); the
+// evaluation of qsat is this one text in both forms.
+template <bool P, bool LIN>
+C2_HD real_t satur_eval(ConstsP c, real_t pap, real_t t, real_t& dqs_dpap, real_t& dqs_dt) {
   StageBlock kf, ks;
   c2_block2(&c->kf, &c->ks, kf, ks);
   real_t zalfa;
+  [[maybe_unused]] real_t dzalfa = RC(0.0);
   {  // FOEALFA (fcttre.func.h:74-75)
     real_t xa = (fmax(kf.v[KF_RTICE], fmin(kf.v[KF_RTWAT], t)) - kf.v[KF_RTICE]) * kf.v[KF_RTWAT_RTICE_R];
     zalfa = fmin(RC(1.0), xa * xa);
+    if constexpr (LIN) dzalfa = (t > kf.v[KF_RTICE] && t < kf.v[KF_RTWAT]) ? RC(2.0) * xa * kf.v[KF_RTWAT_RTICE_R] : RC(0.0);
   }
   const real_t r4les = ks.v[KS_R4LES], r4ies = ks.v[KS_R4IES], rtt = ks.v[KS_RTT], r3les = ks.v[KS_R3LES],
                r3ies = ks.v[KS_R3IES], r2es = ks.v[KS_R2ES], retv = ks.v[KS_RETV];
   real_t zfoeewl, zfoeewi, zqs, zcor;
+  [[maybe_unused]] bool clamped = false;  // LIN: the ZQMAX clamp acted
   if (P) {
     zfoeewl = r2es * exp(r3les * (t - rtt) / (t - r4les));
     zfoeewi = r2es * exp(r3ies * (t - rtt) / (t - r4ies));
     real_t zfoeew = zalfa * zfoeewl + (RC(1.0) - zalfa) * zfoeewi;
     zqs = zfoeew / pap;
+    if constexpr (LIN) clamped = zqs > RC(0.5);
     if (zqs > RC(0.5)) zqs = RC(0.5);
     zcor = RC(1.0) / (RC(1.0) - retv * zqs);
   } else {
@@ -403,10 +408,43 @@ C2_HD real_t satur_point(ConstsP c, real_t pap, real_t t) {
     zfoeewi = r2es * c2_exp(r3ies * dt * ri);
     real_t zfoeew = zalfa * zfoeewl + (RC(1.0) - zalfa) * zfoeewi;
     zqs = zfoeew * rp;
+    if constexpr (LIN) clamped = zqs > RC(0.5);
     if (zqs > RC(0.5)) zqs = RC(0.5);
     zcor = c2_rcp(RC(1.0) - retv * zqs);
+    if constexpr (LIN) {  // the reciprocals and exps above serve the partials too: multiplies only
+      const real_t dfoeew = dzalfa * (zfoeewl - zfoeewi) + zalfa * (zfoeewl * (kf.v[KF_R5LES] * (rl * rl))) +
+                            (RC(1.0) - zalfa) * (zfoeewi * (kf.v[KF_R5IES] * (ri * ri)));
+      const real_t zcor2rp = zcor * zcor * rp;
+      dqs_dt = clamped ? RC(0.0) : zcor2rp * dfoeew;
+      dqs_dpap = clamped ? RC(0.0) : -(zcor2rp * zqs);
+    }
+  }
+  if constexpr (P && LIN) {
+    const real_t tl = t - r4les, ti = t - r4ies;
+    const real_t dfoeew = dzalfa * (zfoeewl - zfoeewi) + zalfa * (zfoeewl * kf.v[KF_R5LES] / (tl * tl)) +
+                          (RC(1.0) - zalfa) * (zfoeewi * kf.v[KF_R5IES] / (ti * ti));
+    dqs_dt = clamped ? RC(0.0) : zcor * zcor * dfoeew / pap;
+    dqs_dpap = clamped ? RC(0.0) : -(zcor * zcor * zqs / pap);
   }
   return zqs * zcor;
+}
+template <bool P>
+C2_HD real_t satur_point(ConstsP c, real_t pap, real_t t) {
+  real_t unused_dp, unused_dt;
+  return satur_eval<P, false>(c, pap, t, unused_dp, unused_dt);
+}
+// SATUR with its first derivatives (the dwarf ships no SATURTL / SATURAD; these are the derivatives of satur.F90:106-123 as
+// written): returns the bits of satur_point<P>, and
+//   zalfa = min(1, xa^2): dzalfa/dt = 2 xa RTWAT_RTICE_R for RTICE < t < RTWAT, else 0
+//   dfoeewl/dt = foeewl R3LES (RTT - R4LES) / (t - R4LES)^2 = foeewl R5LES / (t - R4LES)^2, likewise for ice
+//   dfoeew/dt = dzalfa (foeewl - foeewi) + zalfa dfoeewl + (1 - zalfa) dfoeewi
+//   zqs = foeew / pap;  zqs > 0.5 (the ZQMAX clamp): both partials are exactly 0;  otherwise, with zcor = 1 / (1 - RETV zqs),
+//   dqs/dt = zcor^2 dfoeew / pap,  dqs/dpap = -zcor^2 zqs / pap
+// At the kinks the value is the one-sided one these formulas give: t == RTICE and t == RTWAT take dzalfa = 0 (the cold side's
+// limit at RTICE, the warm side's at RTWAT), zqs == 0.5 exactly takes the unclamped side.
+template <bool P>
+C2_HD real_t satur_lin_point(ConstsP c, real_t pap, real_t t, real_t& dqs_dpap, real_t& dqs_dt) {
+  return satur_eval<P, true>(c, pap, t, dqs_dpap, dqs_dt);
 }
 
 // Everything level_tl / level_ad need from the trajectory of one level.  Names follow the "...5" variables of

@@ -249,6 +249,10 @@ std::vector<int> paced_kernel_occupancies() {
     add((const void*)ad_reverse_variant(f));
   }
   for (unsigned f = 64; f < 128; ++f) add((const void*)ad_reverse_variant(f));  // the vector-Jacobian forms (C2F_VJP)
+  for (unsigned f = C2F_SATLIN; f < 2u * C2F_SATLIN; ++f) {  // SATUR differentiated in the sweep (C2F_SATLIN)
+    add((const void*)tl_variant(f));
+    add((const void*)ad_reverse_variant(f));
+  }
   for (unsigned f = 0; f < 64; ++f) {  // the batched sweeps
     for (int nb = 2; nb <= kBatchMax; ++nb) {
       add((const void*)tl_batch_variant(f, nb));

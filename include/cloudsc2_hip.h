@@ -173,6 +173,16 @@ int cloudsc2_nl_launch(const cloudsc2_params* prm, double ptsphy, int nproma, in
 int cloudsc2_satur_launch(const cloudsc2_params* prm, int nproma, int nlev, int ngptot,
                           cloudsc2_field pap, cloudsc2_field t, cloudsc2_field qsat, void* stream);
 
+/* SATUR and its two partial derivatives (satur.F90:106-123, LDPHYLIN branch, differentiated as written; the reference ships no
+ * SATURTL / SATURAD, so these are this library's own derivative code): dqs_dpap, dqs_dt (NPROMA,NLEV,NBLOCKS) receive d(qsat)/d(pap)
+ * and d(qsat)/d(t), qsat the bits of cloudsc2_satur_launch (qsat.ptr may be NULL: partials only).  Where the ZQMAX clamp acts
+ * (foeew/pap > 0.5) both partials are exactly 0; at the kinks (t == RTICE, t == RTWAT, foeew/pap == 0.5) they take the one-sided
+ * value of the formulas in cloudsc2_level.hpp (satur_lin_point).  All planes share one block stride; padded tail columns are not
+ * written.  Asynchronous, no allocation, no synchronisation. */
+int cloudsc2_satur_lin_launch(const cloudsc2_params* prm, int nproma, int nlev, int ngptot,
+                              cloudsc2_field pap, cloudsc2_field t, cloudsc2_field qsat,
+                              cloudsc2_field dqs_dpap, cloudsc2_field dqs_dt, void* stream);
+
 /* CLOUDSC2TL (src/cloudsc2_tl/cloudsc2tl.F90:10-24): trajectory in -> trajectory out (give all ten traj_out
  * fields, or all NULL to skip the trajectory stores), perturbation in -> perturbation out.  traj_in->qsat NULL => fused
  * SATUR for PQS5.  pert_in must give all 16 fields.
@@ -213,7 +223,8 @@ int cloudsc2_simd_population(long long workgroups, int cus, long long block, int
  * tests); cloudsc2_device_rules returns the cached verdicts of the current device (1 on, 0 off, -1 never probed);
  * cloudsc2_kernel_occupancy the workgroups per CU of one kernel variant (kernel 0 NL, 1 TL, 2 AD both sweeps, 3 AD reverse sweep,
  * 4 batched TL, 5 batched reverse sweep; flags = its C2F_* variant bits, cloudsc2_column.hpp; for the batched sweeps, whose kernels
- * are built per direction count, plus 64 x the directions of the launch, 2..cloudsc2_batch_max()) as the runtime reports them.
+ * are built per direction count, plus 64 x the directions of the launch, 2..cloudsc2_batch_max()) as the runtime reports them
+ * (the sweeps of cloudsc2_tl_launch_satur / cloudsc2_vjp_launch_satur: kernel 1 / 3 with C2F_SATLIN = 128 among the flags).
  *
  * What a caller with its own hipMalloc should expect.  The same kernel on the same data runs 0.78 or 0.92 ms (NL, 160 000 columns:
  * 0.73 vs 0.63 of the HBM peak) depending on WHERE in the HBM the state lies (profiles/r02_hbm_placement.md); cloudsc2_device_malloc*
@@ -293,6 +304,25 @@ int cloudsc2_vjp_launch(const cloudsc2_params* prm, double ptsphy, int nproma, i
                         const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
                         const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                         const cloudsc2_real* scratch, void* stream);
+
+/* The derivative of what the drivers compute, pap, t -> SATUR -> CLOUDSC2 (cloudsc_driver_mod.F90:91), with SATUR differentiated
+ * inside the sweeps (satur.F90:106-123, see cloudsc2_satur_lin_launch; CLOUDSC2TL / CLOUDSC2AD of the reference treat PQSAT as an
+ * independent input and it has no SATURTL / SATURAD).  No qsat plane exists on any side: 2 planes per level less than
+ * cloudsc2_tl_launch / cloudsc2_vjp_launch read and write.
+ *   cloudsc2_tl_launch_satur: cloudsc2_tl_launch without trajectory stores; traj_in->qsat and pert_in->qsat must both be NULL
+ *     (else CLOUDSC2_EINVAL), the other 15 fields of each are required; the tangent of qsat is dqs/dpap dpap + dqs/dt dt.
+ *   cloudsc2_vjp_launch_satur: cloudsc2_vjp_launch (adj_out read only, true PSUPSAT derivative, padded tail not written);
+ *     traj_in->qsat and adj_in->qsat must both be NULL; adj_in->pap and adj_in->t carry SATUR's contribution
+ *     (pap += dqs/dpap qsat_adj, t += dqs/dt qsat_adj).
+ * New entry points rather than a new meaning of NULL in the existing ones, where traj_in->qsat == NULL already says "fused SATUR,
+ * independent qsat tangent / adjoint".  Strides, pacing, stream capture and first-use behaviour are those of the other launchers. */
+int cloudsc2_tl_launch_satur(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                             const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out,
+                             void* stream);
+int cloudsc2_vjp_launch_satur(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                              const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                              const cloudsc2_real* scratch, void* stream);
 
 /* Several tangents or cotangents over ONE trajectory -- a Jacobian block, a singular-vector iteration, an ensemble of perturbations.
  * cloudsc2_tl_launch_batch replaces nbatch calls of cloudsc2_tl_launch without trajectory stores (traj_out all NULL),
