@@ -1,13 +1,25 @@
 """CLOUDSC2 as a differentiable PyTorch operation: the NL sweep forward, the TL sweep as its jvp, the reverse sweep of the adjoint
 (in its vector-Jacobian form, ``cloudsc2_vjp_launch``) as its backward.
 
-    out = cloudsc2(inputs, prm, ptsphy, ngptot=None, satur=False)
+    out = cloudsc2(inputs, prm, ptsphy, ngptot=None, satur=False, params=None)
 
 ``inputs`` maps every name of ``binding.IN_NAMES`` to a device tensor (with ``satur=True``: every name but ``qsat``); ``out`` is a :class:`Cloudsc2Outputs` namedtuple over
 ``binding.OUT_NAMES``.  ``torch.autograd.grad`` / ``.backward()``, ``torch.autograd.forward_ad`` and ``torch.func.jvp`` / ``vjp`` /
 ``grad`` / ``vmap`` / ``jacfwd`` / ``jacrev`` all work; double backward, nested vmap, ``torch.autograd.grad(...,
-is_grads_batched=True)`` (use ``torch.func.vmap`` of the vjp function instead) and gradients with respect to ``prm`` / ``ptsphy`` do
-not.
+is_grads_batched=True)`` (use ``torch.func.vmap`` of the vjp function instead) and gradients with respect to ``ptsphy`` do not.
+
+Parameters.  ``params`` maps any subset of ``PARAM_NAMES`` (``rkconv``, ``rclcrit``, ``rlptrc``, ``rpecons``: the four constants of
+``prm`` that enter CLOUDSC2 smoothly) to 0-d ``float64`` tensors, on the CPU or on the inputs' device.  Their values override those
+fields of a *copy* of ``prm`` -- the forward is bit for bit ``cloudsc2(inputs, prm_with_those_values, ...)`` -- and the op is
+differentiable with respect to them: ``loss(out).backward()`` leaves a 0-d float64 ``.grad`` on each parameter's device next to the
+field gradients (which are the bits of the op without ``params``), ``torch.func.grad`` / ``vjp``, ``forward_ad`` and
+``torch.func.jvp`` work.  Backward is one ``cloudsc2_vjp_launch_par`` (the reverse sweep sums each column's contributions in four
+doubles, a second kernel folds them in a fixed order: the same bits from run to run), or today's launch when no parameter needs a
+gradient; jvp is one ``cloudsc2_tl_launch_par``.  The constants travel in the kernel-argument segment, so the parameters' values
+(and, in forward mode, their tangents) are read on the HOST: that synchronises when they live on the device, returning a gradient
+to a CPU parameter copies four doubles back, and the op refuses ``params`` while the stream is capturing.  Any ``torch.func.vmap``
+level over the op with ``params`` (so also ``jacfwd`` / ``jacrev``) raises ``NotImplementedError``: use the unbatched calls, one
+direction at a time.  With the evaporation branch ``rpecons`` must not be 0.
 
 Batches.  Under ``torch.func.vmap`` the op distinguishes two cases.  Several tangents or cotangents over ONE state -- ``jacfwd``,
 ``jacrev``, ``vmap(jvp)``, ``vmap(vjp_fn)`` -- are one ``cloudsc2_tl_launch_batch`` / ``cloudsc2_vjp_launch_batch`` call: the
@@ -30,6 +42,11 @@ Semantics.
     refused, because the forward would then not be the function its derivatives belong to.
   * With ``prm.lregcl`` the jvp and backward are the reference's *regularised* linearisation (cloudsc2tl.F90:575,657,754,794,998),
     not the exact derivative of the forward.
+  * The parameter derivative is the library's own (the reference has none).  Its local partials are exact derivatives of the
+    forward; the resulting perturbation travels down the column through the same linearisation as the field tangents.  So with
+    ``prm.lregcl`` it is regularised exactly where CLOUDSC2TL is and is not the exact derivative; with ``lregcl = 0`` it is.
+    ``d zfwat / d rlptrc = -d zfwat / dT`` at cold points, 0 elsewhere.  Exact zeros: ``clc`` and ``covptot`` depend on none of the
+    four; without the evaporation branch nothing depends on ``rpecons``; with it ``teni`` does not depend on ``rclcrit``.
   * ``qsat`` is an ordinary differentiable input, as in CLOUDSC2TL / CLOUDSC2AD.  :func:`satur` computes it from ``pap`` and ``t``
     without a gradient by default: its result then enters the op as a constant.
   * ``satur=True`` differentiates what the drivers compute, ``pap, t -> SATUR -> CLOUDSC2`` (cloudsc_driver_mod.F90:91): ``inputs``
@@ -51,6 +68,7 @@ capture.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import threading
 from collections import namedtuple
@@ -73,6 +91,7 @@ OUT_GROUPS = {"loc": ("tent", "tenq", "tenl", "teni"), "full": ("clc", "covptot"
 # satur=True: SATUR is evaluated and differentiated inside the sweeps, qsat exists on no side
 SAT_NAMES = tuple(n for n in B.IN_NAMES if n != "qsat")
 SAT_GROUPS = {g: tuple(n for n in names if n != "qsat") for g, names in IN_GROUPS.items()}
+PARAM_NAMES = B.PARAM_NAMES  # the constants of prm that cloudsc2(..., params=...) differentiates
 
 
 class Layout(namedtuple("Layout", "nblocks nlev nproma ngptot")):
@@ -697,9 +716,224 @@ class _Satur(torch.autograd.Function):
                                   "satur=True, whose vmap rules carry batches)")
 
 
-def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False) -> Cloudsc2Outputs:
+# ---- params=...: the derivative with respect to the tunable parameters next to the one with respect to the fields ----------------
+
+_NO_VMAP = ("cloudsc2 with params: torch.func.vmap, jacfwd and jacrev are not supported (batched parameter directions are not built); "
+            "use .backward() / torch.autograd.grad / torch.func.grad / torch.func.vjp, or torch.autograd.forward_ad / torch.func.jvp, "
+            "one direction at a time")
+
+
+def check_params(params, prm: B.Params) -> tuple:
+    """The checks of ``cloudsc2(..., params=...)`` that need no device; returns the given names in ``PARAM_NAMES`` order.  Runs on CPU
+    tensors; raises ``ValueError``."""
+    if not hasattr(params, "keys"):
+        raise ValueError(f"params must map names of {PARAM_NAMES} to 0-d float64 tensors; got {type(params)}")
+    unknown = sorted(set(params.keys()) - set(PARAM_NAMES))
+    if unknown:
+        raise ValueError(f"params: unknown name(s) {unknown}; the differentiable parameters are {PARAM_NAMES}")
+    for n in params.keys():
+        p = params[n]
+        if not isinstance(p, torch.Tensor):
+            raise ValueError(f"params[{n!r}] is not a tensor")
+        if p.dtype != torch.float64:
+            raise ValueError(f"params[{n!r}] has dtype {p.dtype}; parameters are float64 in both builds (the constants of cloudsc2_params are C doubles)")
+        if p.dim() != 0:
+            raise ValueError(f"params[{n!r}] must be a 0-d tensor; got shape {tuple(p.shape)}")
+    if not prm.lphylin:
+        raise ValueError("params with prm.lphylin = 0: the parameter derivative belongs to the LPHYLIN form of the scheme")
+    return tuple(n for n in PARAM_NAMES if n in params.keys())
+
+
+def _batched_inside(t) -> bool:
+    """a vmap level anywhere under torch.func's wrappers (jacfwd hands the op a dual whose primal has been batched with its tangent)"""
+    while isinstance(t, torch.Tensor):
+        if _functorch.is_batchedtensor(t) or _functorch.is_legacy_batchedtensor(t):
+            return True
+        if not _functorch.is_functorch_wrapped_tensor(t):
+            return False
+        t = _functorch.get_unwrapped(t)
+    return False
+
+
+def _refuse_batched(ts) -> None:
+    if any(_batched_inside(t) for t in ts):
+        raise NotImplementedError(_NO_VMAP)
+
+
+def _host_value(t: torch.Tensor | None) -> float:
+    return 0.0 if t is None else float(_raw(t).detach())
+
+
+def _names(satur: bool):
+    return (SAT_NAMES, SAT_GROUPS) if satur else (B.IN_NAMES, IN_GROUPS)
+
+
+class _Cloudsc2ParTl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, (4 parameter tangents), *n trajectory inputs, *n tangents) -> 10 output tangents:
+    ``cloudsc2_tl_launch_par`` (n = 16, or 15 with satur).  Not differentiable."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, dpar, *ts):
+        names, groups = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        like = x["pap"]
+        dev = like.device
+        dx = normalize(dict(zip(names, ts[n:])), lay, groups)
+        dy = _new(B.OUT_NAMES, lay, like)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch_par(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
+                                                 C.byref(_block("in", x, lay)), C.byref(_block("in", dx, lay)),
+                                                 (C.c_double * len(PARAM_NAMES))(*dpar), C.byref(_block("out", dy, lay)), _stream(dev)))
+        return tuple(dy[k] for k in B.OUT_NAMES)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(*output)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP)
+
+
+class _Cloudsc2ParVjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints) -> n input
+    adjoints and the 4 parameter adjoints (device float64): ``cloudsc2_vjp_launch_par``.  Not differentiable."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, *ts):
+        names, _ = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        fplsl, fplsn, scratch = ts[n:n + 3]
+        like = x["pap"]
+        dev = like.device
+        y = normalize(dict(zip(B.OUT_NAMES, ts[n + 3:])), lay, OUT_GROUPS)
+        xa = _new(names, lay, like)
+        traj_out = B.Outputs()
+        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
+        nwork = C.c_longlong()
+        B.check(B.lib.cloudsc2_par_work_doubles(lay.nproma, lay.ngptot, C.byref(nwork)))
+        work = torch.empty(nwork.value, dtype=torch.float64, device=dev)
+        par_adj = torch.empty(len(PARAM_NAMES), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch_par(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
+                                                  C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
+                                                  C.byref(_block("out", y, lay)), _scratch_ptr(scratch), C.c_void_p(work.data_ptr()),
+                                                  C.c_void_p(par_adj.data_ptr()), _stream(dev)))
+        return tuple(xa[k] for k in names) + (par_adj,)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(*output)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP)
+
+
+class _Cloudsc2Par(torch.autograd.Function):
+    # forward(prm, ptsphy, layout, satur, parameter names, *their 0-d tensors, *n inputs) -> 10 outputs + the cover-checkpoint scratch:
+    # prm already holds the parameters' values, so the forward is the NL sweep of _Cloudsc2 / _Cloudsc2Satur; the tensors are operands
+    # for autograd's sake.  backward: one cloudsc2_vjp_launch_par (today's launch when no parameter needs a gradient); jvp: one
+    # cloudsc2_tl_launch_par.
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, pnames, *ts):
+        names, _ = _names(satur)
+        x = dict(zip(names, ts[len(pnames):]))
+        like = x["pap"]
+        dev = like.device
+        out = _new(B.OUT_NAMES, lay, like)
+        scratch = torch.empty((lay.nblocks, lay.nlev, lay.nproma) if _evap(prm) else (0,), dtype=like.dtype, device=dev)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_ad_launch_forward(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                     C.byref(_block("in", x, lay)), C.byref(_block("out", out, lay)),
+                                                     _scratch_ptr(scratch), _stream(dev)))
+        return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        prm, ptsphy, lay, satur, pnames, *ts = inputs
+        xs = ts[len(pnames):]
+        out = dict(zip(B.OUT_NAMES, output[:-1]))
+        scratch = output[-1]
+        ctx.mark_non_differentiable(scratch)
+        ctx.save_for_backward(*xs, out["fplsl"], out["fplsn"], scratch)
+        ctx.save_for_forward(*xs)
+        ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.pnames = prm, ptsphy, lay, satur, pnames
+        ctx.pdevs = tuple(p.device for p in ts[:len(pnames)])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        _refuse_batched(grads)
+        saved = ctx.saved_tensors
+        lay, like, P = ctx.lay, saved[0], len(ctx.pnames)
+        need_p, need_x = ctx.needs_input_grad[5:5 + P], ctx.needs_input_grad[5 + P:]
+        if not any(need_p) and not any(need_x):
+            return (None,) * (5 + P + len(need_x))
+        y = _zero_filled(B.OUT_NAMES, grads[:10], lay, like)
+        if not any(need_p):  # the field gradients alone: today's launch
+            vjp = _Cloudsc2SaturVjp if ctx.satur else _Cloudsc2Vjp
+            xa = vjp.apply(ctx.prm, ctx.ptsphy, lay, *saved, *(y[n] for n in B.OUT_NAMES))
+            return (None,) * (5 + P) + tuple(a if nd else None for a, nd in zip(xa, need_x))
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("cloudsc2 with params: the backward cannot run while the stream is capturing")
+        *xa, par_adj = _Cloudsc2ParVjp.apply(ctx.prm, ctx.ptsphy, lay, ctx.satur, *saved, *(y[n] for n in B.OUT_NAMES))
+        gp = tuple(par_adj[PARAM_NAMES.index(n)].to(d) if nd else None for n, d, nd in zip(ctx.pnames, ctx.pdevs, need_p))
+        return (None,) * 5 + gp + tuple(a if nd else None for a, nd in zip(xa, need_x))
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        _refuse_batched(tangents)
+        names, _ = _names(ctx.satur)
+        P = len(ctx.pnames)
+        xs = ctx.saved_tensors
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("cloudsc2 with params: the parameter tangents are read on the host, which cannot happen while the stream is capturing")
+        dpar = [0.0] * len(PARAM_NAMES)
+        for n, t in zip(ctx.pnames, tangents[5:5 + P]):
+            dpar[PARAM_NAMES.index(n)] = _host_value(t)
+        dx = _zero_filled(names, tangents[5 + P:], ctx.lay, xs[0])
+        dy = _Cloudsc2ParTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, tuple(dpar), *xs, *(dx[n] for n in names))
+        return tuple(dy) + (None,)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP)
+
+
+def _cloudsc2_par(inputs, prm: B.Params, ptsphy: float, ngptot, satur: bool, params) -> Cloudsc2Outputs:
+    names, groups = _names(satur)
+    lay = check_layout(inputs, prm, ngptot, satur=satur)
+    pnames = check_params(params, prm)
+    dev = check_device(inputs[n] for n in names)
+    ps = tuple(params[n] for n in pnames)
+    _refuse_batched(ps + tuple(inputs[n] for n in names))
+    for n, p in zip(pnames, ps):
+        if p.device.type != "cpu" and p.device != dev:
+            raise ValueError(f"params[{n!r}] is on {p.device}: parameters live on the CPU or on the inputs' device {dev}")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("cloudsc2 with params: the parameters' values are read on the host (they travel in the kernel-argument "
+                           "segment), which cannot happen while the stream is capturing")
+    _prepare(dev)
+    prm = copy.copy(prm)  # (a ctypes structure: a copy of its bytes)
+    for n, p in zip(pnames, ps):
+        setattr(prm, n, _host_value(p))  # synchronises when the parameter lives on the device
+    if _evap(prm) and prm.rpecons == 0.0:
+        raise ValueError("params with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
+    x = normalize({n: inputs[n] for n in names}, lay, groups)
+    out = _Cloudsc2Par.apply(prm, float(ptsphy), lay, bool(satur), pnames, *ps, *(x[n] for n in names))
+    return Cloudsc2Outputs(*out[:10])
+
+
+def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None) -> Cloudsc2Outputs:
     """CLOUDSC2 over all blocks as a differentiable op, SATUR-free (``qsat`` is an input) or, with ``satur=True``, with SATUR
-    evaluated and differentiated inside (``inputs`` without ``qsat``); see the module docstring."""
+    evaluated and differentiated inside (``inputs`` without ``qsat``); ``params``: a mapping of names of ``PARAM_NAMES`` to 0-d
+    float64 tensors that override those constants of (a copy of) ``prm`` and are differentiated too; see the module docstring."""
+    if params is not None:
+        return _cloudsc2_par(inputs, prm, ptsphy, ngptot, satur, params)
     if satur:
         lay = check_layout(inputs, prm, ngptot, satur=True)
         dev = check_device(inputs[n] for n in SAT_NAMES)

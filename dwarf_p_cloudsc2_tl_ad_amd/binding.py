@@ -75,6 +75,8 @@ class Field(C.Structure):
 IN_NAMES = ("paph", "pap", "q", "qsat", "t", "l", "i", "lude", "lu", "mfu", "mfd", "gtent", "gtenq", "gtenl",
             "gteni", "supsat")
 OUT_NAMES = ("tent", "tenq", "tenl", "teni", "clc", "fplsl", "fplsn", "fhpsl", "fhpsn", "covptot")
+# the tunable constants of struct cloudsc2_params the sweeps differentiate, in the order of CLOUDSC2_NPAR (include/cloudsc2_hip.h)
+PARAM_NAMES = ("rkconv", "rclcrit", "rlptrc", "rpecons")
 
 
 class Inputs(C.Structure):
@@ -147,6 +149,16 @@ def _load() -> C.CDLL:
     lib.cloudsc2_tl_launch_satur.restype = C.c_int
     lib.cloudsc2_vjp_launch_satur.argtypes = lib.cloudsc2_vjp_launch.argtypes
     lib.cloudsc2_vjp_launch_satur.restype = C.c_int
+    # the derivative with respect to the tunable parameters (order: PARAM_NAMES): dpar is a host array of CLOUDSC2_NPAR doubles,
+    # work / par_adj are device pointers
+    lib.cloudsc2_par_work_doubles.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_longlong)]
+    lib.cloudsc2_par_work_doubles.restype = C.c_int
+    lib.cloudsc2_tl_launch_par.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Inputs),
+                                           C.POINTER(C.c_double), C.POINTER(Outputs), C.c_void_p]
+    lib.cloudsc2_tl_launch_par.restype = C.c_int
+    lib.cloudsc2_vjp_launch_par.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs),
+                                            C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cloudsc2_vjp_launch_par.restype = C.c_int
     # several directions over one trajectory: arrays of argument blocks, (Inputs * K)(...) / (Outputs * K)(...)
     lib.cloudsc2_batch_max.argtypes = []
     lib.cloudsc2_batch_max.restype = C.c_int
@@ -241,7 +253,7 @@ lib = _load()
 # every symbol include/cloudsc2_hip.h declares
 EXPORTED = ("cloudsc2_params_default", "cloudsc2_last_error", "cloudsc2_device_available", "cloudsc2_current_device", "cloudsc2_set_math_mode",
             "cloudsc2_get_math_mode", "cloudsc2_real_bytes", "cloudsc2_nl_launch",
-            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
+            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
             "cloudsc2_ad_launch_forward", "cloudsc2_ad_launch_reverse", "cloudsc2_vjp_launch", "cloudsc2_batch_max", "cloudsc2_tl_launch_batch", "cloudsc2_vjp_launch_batch", "cloudsc2_ad_launch_reverse_norms", "cloudsc2_taylor_sums_launch",
             "cloudsc2_taylor_sweep_work_doubles", "cloudsc2_taylor_sweep_launch", "cloudsc2_adjoint_norms_launch", "cloudsc2_nl_run", "cloudsc2_tl_taylor_run", "cloudsc2_ad_symmetry_run",
             "cloudsc2_release_workspace", "cloudsc2_taylor_verdict", "cloudsc2_adjoint_verdict",

@@ -70,9 +70,19 @@ struct AdArgs {
   double* norms;  // C2F_ADNORM: (3, ncols_pad) doubles: norm1 (read), norm2 and norm3 (written)
   double* gmax;   // C2F_ADNORM: one double, raised to the largest |norm3| (the kernel's wave maxima, atomically)
 };
+// C2F_PARLIN: the sweep's own block first (tl_column / ad_reverse_column take a pointer to it and step on to what follows)
+struct TlParArgs {
+  TlArgs a; ParLin par;
+};
+struct AdParArgs {
+  AdArgs a; ParLin par;
+  double* work;  // (PAR_COUNT, ncols_pad) doubles: every active lane's parameter adjoints (the padded tail is not written)
+};
 typedef const C2_CONST_AS NlArgs* NlArgsP;
 typedef const C2_CONST_AS TlArgs* TlArgsP;
 typedef const C2_CONST_AS AdArgs* AdArgsP;
+typedef const C2_CONST_AS TlParArgs* TlParArgsP;
+typedef const C2_CONST_AS AdParArgs* AdParArgsP;
 typedef const C2_CONST_AS InPtrs* InPtrsP;
 typedef const C2_CONST_AS OutPtrs* OutPtrsP;
 typedef const C2_CONST_AS InPtrsRW* InPtrsRWP;
@@ -377,6 +387,11 @@ enum : unsigned {
                      // inside the sweep (satur_lin_point).  The tangent of qsat is dqs/dpap dpap + dqs/dt dt instead of an input plane,
                      // its adjoint is folded into those of pap and t instead of being stored: no qsat plane on either side
                      // (cloudsc2_tl_launch_satur, cloudsc2_vjp_launch_satur)
+  C2F_PARLIN = 256u, // TL (without TRAJ / SELFINC) and the VJP form of the reverse sweep, each with QSAT or with SATLIN: the derivative
+                     // with respect to RKCONV, RCLCRIT, RLPTRC, RPECONS (struct ParLin).  The argument block is TlParArgs / AdParArgs.
+                     // TL: four parameter tangents add their source terms.  Reverse sweep: the lane sums its column's contributions
+                     // in four doubles and stores them to the launch's workspace, which a second kernel folds in a fixed order
+                     // (cloudsc2_tl_launch_par, cloudsc2_vjp_launch_par; kernels: cloudsc2_kern_{tl,vjp}_par.hip)
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -705,8 +720,9 @@ C2_HD void self_increment(const RawLevel& r, real_t supsat_inc, RawLevel& d) {
 template <unsigned F>
 C2_HD void tl_column(long long gcol, TlArgsP a) {
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, STORE_TRAJ = (F & C2F_TRAJ) != 0, EVAP = (F & C2F_EVAP) != 0;
-  constexpr bool SELFINC = (F & C2F_SELFINC) != 0, SATLIN = (F & C2F_SATLIN) != 0;
+  constexpr bool SELFINC = (F & C2F_SELFINC) != 0, SATLIN = (F & C2F_SATLIN) != 0, PARLIN = (F & C2F_PARLIN) != 0;
   static_assert(!SATLIN || (!HAS_QSAT && !STORE_TRAJ && !SELFINC), "C2F_SATLIN: SATUR fused, no trajectory stores, increments given");
+  static_assert(!PARLIN || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC), "C2F_PARLIN: QSAT or SATLIN, no trajectory stores, increments given");
   typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
   LaneOff o, op; bool active;
   if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
@@ -780,7 +796,8 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
     LevelTraj tr;
     LevelOut lo, dlo;
     level_forward<P, EVAP>(c, k, rh, x, cy, tr, lo);
-    level_tl(c, k, x, tr, dx, dcy, dlo);
+    if constexpr (PARLIN) level_tl<true>(c, k, x, tr, dx, dcy, dlo, &((TlParArgsP)ap)->par);  // (a is the head of a TlParArgs)
+    else level_tl(c, k, x, tr, dx, dcy, dlo);
     C2_LAUNDER(ap);
     out = &ap->out; dout = &ap->dout;
     if (STORE_TRAJ) store_out(out, ol, nproma, jk, lo);
@@ -894,8 +911,9 @@ template <unsigned F>
 C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| of the column with C2F_ADNORM (+inf for NaN), else 0
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0;
   constexpr bool OFF32 = (F & C2F_OFF32) != 0, ASSIGN = (F & C2F_ASSIGN) != 0, ADNORM = (F & C2F_ADNORM) != 0;
-  constexpr bool VJP = (F & C2F_VJP) != 0, SATLIN = (F & C2F_SATLIN) != 0;
+  constexpr bool VJP = (F & C2F_VJP) != 0, SATLIN = (F & C2F_SATLIN) != 0, PARLIN = (F & C2F_PARLIN) != 0;
   static_assert(!SATLIN || (VJP && !HAS_QSAT), "C2F_SATLIN: the vector-Jacobian form with SATUR fused");
+  static_assert(!PARLIN || (VJP && (HAS_QSAT != SATLIN)), "C2F_PARLIN: the vector-Jacobian form, QSAT or SATLIN");
   static_assert(!ADNORM || ASSIGN, "the fused norms are those of the adjoint test: assign form");
   static_assert(!VJP || (ASSIGN && !ADNORM), "the vector-Jacobian product assigns its input adjoints and forms no norms");
   typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
@@ -926,6 +944,7 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   real_t paph_k1 = paph_bottom;
   double n2 = 0.0;  // ADNORM: <x0, x_adj>, x0 = 0.01 * trajectory inputs, ZSUPSAT0 = 0 (cloudsc_driver_ad_mod.F90:139,240-256)
   AdLevelLoads L;
+  [[maybe_unused]] ParAcc pacc = {{0.0, 0.0, 0.0, 0.0}};  // PARLIN
   Pace pace;
   pace.begin(&a->nl.g);
   for (int jk = nlev - 1; jk >= 0; --jk) {
@@ -961,7 +980,8 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     ya.fplsn = ya.fplsn - ya.fhpsn * c->rlstt;
     ya.fplsl = ya.fplsl - ya.fhpsl * c->rlvtt;
     LevelIn ax;
-    level_ad(c, k, x, tr, ya, acy, ax);
+    if constexpr (PARLIN) level_ad<true>(c, k, x, tr, ya, acy, ax, &((AdParArgsP)ap)->par, &pacc);  // (a is the head of an AdParArgs)
+    else level_ad(c, k, x, tr, ya, acy, ax);
     if constexpr (SATLIN) {  // the adjoint of qsat goes to pap and t through SATUR's transpose; it has no plane of its own
       ax.pap += dqs_dpap * ax.qs;
       ax.t += dqs_dt * ax.qs;
@@ -1028,6 +1048,12 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   } else {
     ain->paph[oa64.half] += paph_pending;
     ain->paph[oa64.half + (long long)nlev * nproma] += surf_acc;
+  }
+  if constexpr (PARLIN) {  // the lane's four sums: consecutive lanes, consecutive doubles of each row (gcol < ncols_pad: lane_setup)
+    double* work = ((AdParArgsP)a)->work;
+    const long long np = a->nl.g.ncols_pad;
+#pragma unroll
+    for (int i = 0; i < PAR_COUNT; ++i) work[i * np + gcol] = pacc.v[i];
   }
   // the adjoint of the (constant zero) top fluxes is discarded (cloudsc2ad.F90:1678-1679,917-919)
   if constexpr (!VJP) {

@@ -17,6 +17,8 @@
 #include "cloudsc2_kern_taylor.hip"
 #include "cloudsc2_kern_tl_batch.hip"
 #include "cloudsc2_kern_vjp_batch.hip"
+#include "cloudsc2_kern_tl_par.hip"
+#include "cloudsc2_kern_vjp_par.hip"
 #endif
 
 using namespace cloudsc2;
@@ -34,6 +36,25 @@ __global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
 template <bool P>
 __global__ void __launch_bounds__(kBlock) satur_lin_kernel(SaturLinArgs args) {
   C2_KERNEL_BODY(satur_lin_column<P>(global_column(), kernarg<SaturLinArgs>()));
+}
+
+// The second kernel of cloudsc2_vjp_launch_par: row blockIdx.x of the reverse sweep's workspace (the active columns' sums of one
+// parameter) folded into one double in a fixed order -- thread t adds columns t, t + 1024, ... in turn, then a fixed tree over the
+// threads -- so the result is the same bits from run to run.  Columns from ngptot on (the padded tail) were not written and are not read.
+constexpr int kParFoldBlock = 1024;
+__global__ void __launch_bounds__(kParFoldBlock)
+par_fold_kernel(const double* __restrict__ work, long long ncols_pad, long long ngptot, double* __restrict__ par_adj) {
+  __shared__ double red[kParFoldBlock];
+  const double* row = work + (long long)blockIdx.x * ncols_pad;
+  double v = 0.0;
+  for (long long g = threadIdx.x; g < ngptot; g += kParFoldBlock) v += row[g];
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int off = kParFoldBlock / 2; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) par_adj[blockIdx.x] = red[0];
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -502,7 +523,7 @@ struct Sweep {
 // satlin: SATUR is differentiated in the sweep (C2F_SATLIN): no qsat on either input side, no trajectory stores
 int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
                    const cloudsc2_outputs* traj_out, const cloudsc2_inputs* pert_in, double supsat_inc, const cloudsc2_outputs* pert_out,
-                   double* yy, void* stream, bool satlin = false) {
+                   double* yy, void* stream, bool satlin = false, const double* dpar = nullptr) {
   Sweep w;
   int rc = w.begin(prm, nproma, nlev, ngptot, (!traj_in || !traj_out || !pert_out) ? "NULL argument block" : nullptr);
   if (rc) return rc;
@@ -533,9 +554,16 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   // the fp32 TL variants that run three waves per SIMD (tl_kernel's launch bounds) share their SIMDs like the NL kernel does:
   // -3.7 % at 160 000 columns with the waves kept abreast; the fp64 TL and both adjoints run one wave per SIMD and lose 1-5 %
   // (profiles/r03_wave_times.txt); they are paced instead
-  const void* tl = (const void*)tl_variant(w.f);
+  if (dpar) w.f |= C2F_PARLIN;  // (its launcher passes pert_in and no trajectory outputs)
+  const void* tl = dpar ? (const void*)tl_par_variant(w.f) : (const void*)tl_variant(w.f);
   const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);
   schedule(args.g, abreast ? tl : nullptr, false, abreast ? nullptr : tl);
+  if (dpar) {
+    TlParArgs pargs;
+    pargs.a = args;
+    pargs.par = make_parlin(w.c, dpar);
+    return launch_variant(tl_par_variant(w.f), pargs, w.g.ncols_pad, (hipStream_t)stream);
+  }
   return launch_variant(tl_variant(w.f), args, w.g.ncols_pad, (hipStream_t)stream);
 }
 
@@ -549,6 +577,8 @@ struct AdMode {
   double* norms;
   double* gmax;
   bool satlin = false;
+  double* par_work = nullptr;  // the vector-Jacobian product with the parameter adjoints (C2F_PARLIN): the workspace and the result
+  double* par_adj = nullptr;
 };
 
 int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
@@ -605,6 +635,19 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
     schedule(args.nl.g, fwd, false, nullptr);
     return launch_variant(nl_variant(f_fwd), args.nl, n, st);
   }
+  if (m.par_work) {  // the reverse sweep with the parameter sums, then their fold
+    if (!m.vjp || !m.par_adj) return fail(CLOUDSC2_EINVAL, "parameter adjoints: the vector-Jacobian product, with workspace and result");
+    f |= C2F_PARLIN;
+    schedule(args.nl.g, nullptr, false, (const void*)vjp_par_variant(f));
+    AdParArgs pargs;
+    pargs.a = args;
+    pargs.par = make_parlin(w.c, nullptr);
+    pargs.work = m.par_work;
+    if ((rc = launch_variant(vjp_par_variant(f), pargs, n, st))) return rc;
+    hipLaunchKernelGGL(par_fold_kernel, dim3(PAR_COUNT), dim3(kParFoldBlock), 0, st, (const double*)m.par_work, n, (long long)w.g.ngptot, m.par_adj);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
   if (m.which == 2) {
     schedule(args.nl.g, nullptr, false, rev);
     return launch_variant(ad_reverse_variant(f), args, n, st);
@@ -618,6 +661,15 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   schedule(args.nl.g, fwd, false, rev);
   if ((rc = launch_variant(nl_variant(f_fwd), args.nl, n, st))) return rc;
   return launch_variant(ad_reverse_variant(f), args, n, st);
+}
+
+// what the two parameter launchers check before their parents' checks
+int check_par(const cloudsc2_params* prm, int satur) {
+  if (satur != 0 && satur != 1) return fail(CLOUDSC2_EINVAL, "satur must be 0 (qsat given) or 1 (SATUR differentiated in the sweep)");
+  if (int rc = require_device()) return rc;
+  if (prm && (prm->levapls2 || prm->ldrain1d) && prm->rpecons == 0.0)
+    return fail(CLOUDSC2_EINVAL, "parameter derivative with the evaporation branch: rpecons must not be 0");
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -937,6 +989,35 @@ int cloudsc2_vjp_launch_satur(const cloudsc2_params* prm, double ptsphy, int npr
                               const cloudsc2_real* scratch, void* stream) {
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
                         stream, AdMode{2, true, true, nullptr, nullptr, true});
+}
+
+static_assert(CLOUDSC2_NPAR == PAR_COUNT, "the header's parameter count is the level functions'");
+
+int cloudsc2_par_work_doubles(int nproma, int ngptot, long long* n) {
+  if (nproma < 1 || ngptot < 1 || !n) return fail(CLOUDSC2_EINVAL, "nproma >= 1, ngptot >= 1 and a result pointer required");
+  *n = (long long)PAR_COUNT * ((((long long)ngptot + nproma - 1) / nproma) * nproma);
+  return 0;
+}
+
+int cloudsc2_tl_launch_par(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                           const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const double* dpar,
+                           const cloudsc2_outputs* pert_out, void* stream) {
+  if (int rc = check_par(prm, satur)) return rc;
+  if (!pert_in || !dpar) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
+  const cloudsc2_outputs none = {};
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_in, 0.0, pert_out, nullptr, stream, satur != 0, dpar);
+}
+
+int cloudsc2_vjp_launch_par(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                            const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                            const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                            const cloudsc2_real* scratch, double* work, double* par_adj, void* stream) {
+  if (int rc = check_par(prm, satur)) return rc;
+  if (!work || !par_adj) return fail(CLOUDSC2_EINVAL, "the parameter workspace and result are required");
+  if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
+                        stream, AdMode{2, true, true, nullptr, nullptr, satur != 0, work, par_adj});
 }
 
 int cloudsc2_batch_max(void) { return kBatchMax; }

@@ -266,6 +266,43 @@ inline Consts make_consts(const cloudsc2_params& p, double ptsphy) {
   return c;
 }
 
+// The four tunable constants that enter CLOUDSC2 smoothly, in the order of CLOUDSC2_NPAR, and what the parameter forms of level_tl /
+// level_ad (template argument PAR; C2F_PARLIN in cloudsc2_column.hpp) need besides Consts.  The local partials are exact
+// derivatives of level_forward's statements:
+//   RKCONV   ZCKCODTL = 2 RKCONV PTSPHY, ZCKCODTI = 5 RKCONV PTSPHY (cloudsc2.F90:235-236):
+//            d zdl = dck_l (1 - zexp3),  d zdi = dck_i zexp1 (1 - zexp2)
+//   RCLCRIT  ZLCRIT (cloudsc2.F90:505-509,522-526), with q = zcld / ZLCRIT and zexp = exp(-q^2):
+//            d zdl = -2 ZCKCODTL zexp3 zcldl^2 / ZLCRIT^3 dZLCRIT = crc_l zexp3 zcldl^2, likewise for ice (crc_i = 0 with the evaporation
+//            branch, whose ice threshold is the constant 1e-4)
+//   RLPTRC   ZOEALFAW = 0.545 (tanh(0.17 (T - RLPTRC)) + 1) (cloudsc2.F90:350): d zfwat / d RLPTRC = -d zfwat / dT at cold points
+//   RPECONS  ZBETA = RG RPECONS (...)^0.5777 (cloudsc2.F90:566): d zbeta = zbeta / RPECONS
+// The true ZCKCODTL / ZCKCODTI enter the partials also under LREGCL (the regularised coefficients of cloudsc2tl.F90:754,794 belong to the
+// propagation of a perturbation of zcld, which the parameter perturbation goes through at the levels below like any other).
+enum { PAR_RKCONV, PAR_RCLCRIT, PAR_RLPTRC, PAR_RPECONS, PAR_COUNT };
+struct ParLin {
+  real_t dpar[PAR_COUNT];  // TL: the parameter tangents (not read by the reverse sweep)
+  real_t dck_l, dck_i;     // d ZCKCODTL / d RKCONV, d ZCKCODTI / d RKCONV
+  real_t crc_l, crc_i;     // -2 ZCKCODT{L,I} / ZLCRIT_{L,I}^3 * d ZLCRIT_{L,I} / d RCLCRIT
+  real_t rpecons_r;        // 1 / RPECONS (0 without the evaporation branch, where nothing reads it)
+  real_t spare[3];
+};
+typedef const C2_CONST_AS ParLin* ParLinP;
+struct ParAcc { double v[PAR_COUNT]; };  // one lane's parameter adjoints, summed over its column's levels (double in both builds)
+
+// host side; dpar may be NULL (reverse sweep)
+inline ParLin make_parlin(const Consts& c, const double* dpar) {
+  ParLin p;
+  for (int i = 0; i < PAR_COUNT; ++i) p.dpar[i] = dpar ? (real_t)dpar[i] : RC(0.0);
+  p.dck_l = RC(2.0) * c.ptsphy;
+  p.dck_i = RC(5.0) * c.ptsphy;
+  const real_t dlc_l = c.evap ? RC(1.9) : RC(2.0), dlc_i = c.evap ? RC(0.0) : RC(2.0);
+  p.crc_l = -RC(2.0) * c.zckcodtl * dlc_l * (c.zlcrit_l_r * c.zlcrit_l_r * c.zlcrit_l_r);
+  p.crc_i = -RC(2.0) * c.zckcodti * dlc_i * (c.zlcrit_i_r * c.zlcrit_i_r * c.zlcrit_i_r);
+  p.rpecons_r = c.evap ? RC(1.0) / c.rpecons : RC(0.0);
+  p.spare[0] = p.spare[1] = p.spare[2] = RC(0.0);
+  return p;
+}
+
 // Raw inputs of one level (dummy arguments of CLOUDSC2 at (JL,JK); cloudsc2.F90:124-143).
 struct LevelIn {
   real_t paph_k, paph_k1;  // PAPHP1(JK), PAPHP1(JK+1)
@@ -940,8 +977,10 @@ C2_HD real_t regcl_factor(real_t zqpd5, real_t zqcd5, real_t zscalm) {
 // Tangent-linear of one level about LevelTraj.  cloudsc2tl.F90:343-373 (first guess) + :457-1099,
 // CUADJTQSTL KCALL=0 (cuadjtqstl.F90:333-405).  dx = perturbation inputs, dcy = perturbation carries.
 // ---------------------------------------------------------------------------------------------------------
+// PAR: the four parameter tangents pl->dpar add their source terms at the parameters' use sites (struct ParLin).
+template <bool PAR = false>
 C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelTraj& t, const LevelIn& dx,
-                    Carry& dcy, LevelOut& dout) {
+                    Carry& dcy, LevelOut& dout, [[maybe_unused]] ParLinP pl = nullptr) {
   // constants of this function from three 64-byte blocks (one scalar-cache wait)
   StageBlock kt0, kt1, kt2;
   c2_block3(&c->kt0, &c->kt1, &c->kt2, kt0, kt1, kt2);
@@ -970,6 +1009,9 @@ C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
   real_t zfwat, z3es, z4es, r4;
   if (t.cold) { zfwat = RC(0.545) * RC(0.17) * ztp1 * t.zcosh2r; z3es = r3ies; z4es = r4ies; r4 = t.ri; }
   else        { zfwat = RC(0.0);                            z3es = r3les; z4es = r4les; r4 = t.rl; }
+  if constexpr (PAR) {  // d zfwat / d RLPTRC = -d zfwat / dT
+    if (t.cold) zfwat = RC(0.545) * RC(0.17) * (ztp1 - pl->dpar[PAR_RLPTRC]) * t.zcosh2r;
+  }
   const real_t rp = t.zqp;
   real_t zfoeew = z3es * (rtt - z4es) * ztp1 * t.zfoeew * (r4 * r4);
   real_t zesdp = zfoeew * rp - dx.pap * t.zfoeew * (rp * rp);
@@ -1063,6 +1105,8 @@ C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
     real_t zcldl = zqlwc * t.rclc - t.zqlwc1 * pclc * rclc2;
     real_t ck = ck_l;
     real_t zd = (RC(2.0) * ck * zlcrit_l_r2) * t.zexp3 * t.zcldl * zcldl;
+    if constexpr (PAR)
+      zd += pl->dck_l * pl->dpar[PAR_RKCONV] * (RC(1.0) - t.zexp3) + pl->crc_l * pl->dpar[PAR_RCLCRIT] * t.zexp3 * (t.zcldl * t.zcldl);
     real_t zlnew = t.zcldl * t.zexpdl * pclc + t.clc * t.zexpdl * zcldl - t.clc * t.zcldl * t.zexpdl * zd;
     zprr = zqlwc - zlnew;
     zqlwc = zqlwc - zprr;
@@ -1071,6 +1115,8 @@ C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
     real_t cki = ck_i;
     real_t zdi = cki * t.zexp1 *
                  (t.zexp2 * (RC(2.0) * t.zcldi * zcldi * zlcrit_i_r2 - RC(0.025) * ztp1) + RC(0.025) * ztp1);
+    if constexpr (PAR)
+      zdi += t.zexp1 * (pl->dck_i * pl->dpar[PAR_RKCONV] * (RC(1.0) - t.zexp2) + pl->crc_i * pl->dpar[PAR_RCLCRIT] * t.zexp2 * (t.zcldi * t.zcldi));
     real_t zinew = t.zcldi * t.zexpdi * pclc + t.clc * t.zexpdi * zcldi - t.clc * t.zcldi * t.zexpdi * zdi;
     zprs = zqiwc - zinew;
     zqiwc = zqiwc - zprs;
@@ -1099,6 +1145,7 @@ C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
                  RC(2.0) * (x.qs - t.zqlim) * t.covpclr * pclc * (r_omc2 * r_omc);
     real_t zbeta = RC(0.5777) * t.zbeta * (zpreclr * (t.covptot1 * r_prtot * r_clr) + RC(0.5) * dx.pap * t.zqp -
                                            RC(0.5) * dx.paph_surf * r_psurf - zcovpclr * r_clr);
+    if constexpr (PAR) zbeta += t.zbeta * (pl->rpecons_r * pl->dpar[PAR_RPECONS]);
     real_t zb = ptsphy * ((x.qs - t.zqe) * zbeta + t.zbeta * dx.qs - t.zbeta * zqe) * r_den -
                 (ptsphy * ptsphy) * t.zbeta * (x.qs - t.zqe) * (t.zbeta * zcorqs + t.zcorqs * zbeta) * (r_den * r_den);
     real_t zdtgdp = -ptsphy * rg * (dx.paph_k1 - dx.paph_k) * rdp2;
@@ -1200,8 +1247,18 @@ C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
 //   ax   : adjoint increments of the level's inputs (to be added to the input-adjoint arrays);
 //          ax.paph_k / ax.paph_k1 / ax.lu_k1 / ax.paph_surf are contributions to neighbouring indices.
 // ---------------------------------------------------------------------------------------------------------
+// PAR: the level's contributions to the four parameter adjoints are added to `pacc` (the transposes of level_tl<true>'s source terms).
+// They are formed from opaque copies of the adjoint and trajectory values they read (C2_PAR_COPY), so that no product of the level
+// gains a user: the field adjoints keep the bits of the form without parameters (cloudsc2_column.hpp, launder_level, says what the
+// device's contraction otherwise does).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define C2_PAR_COPY(name, x) real_t name = (x); asm volatile("" : "+v"(name))
+#else
+#define C2_PAR_COPY(name, x) const real_t name = (x)
+#endif
+template <bool PAR = false>
 C2_HD void level_ad(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelTraj& t, const LevelOut& ya,
-                    Carry& acy, LevelIn& ax) {
+                    Carry& acy, LevelIn& ax, [[maybe_unused]] ParLinP pl = nullptr, [[maybe_unused]] ParAcc* pacc = nullptr) {
   // constants of this function from three 64-byte blocks (one scalar-cache wait)
   StageBlock kt0, kt1, kt2;
   c2_block3(&c->kt0, &c->kt1, &c->kt2, kt0, kt1, kt2);
@@ -1372,6 +1429,10 @@ C2_HD void level_ad(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
     a_corqs -= p2 * t.zbeta;
     zbeta -= p2 * t.zcorqs;
     // zbeta
+    if constexpr (PAR) {
+      C2_PAR_COPY(p_zbeta, zbeta); C2_PAR_COPY(p_tzbeta, t.zbeta);
+      pacc->v[PAR_RPECONS] += (double)(p_zbeta * (p_tzbeta * pl->rpecons_r));
+    }
     const real_t w = RC(0.5777) * t.zbeta * zbeta;
     zpreclr += w * (t.covptot1 * r_prtot * r_clr);
     a_pap += RC(0.5) * w * t.zqp;
@@ -1413,6 +1474,12 @@ C2_HD void level_ad(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
       real_t zcldi = zinew * t.clc * t.zexpdi;
       real_t zdi = -zinew * t.clc * t.zcldi * t.zexpdi;
       real_t cki = ck_i;
+      if constexpr (PAR) {
+        C2_PAR_COPY(p_zdi, zdi); C2_PAR_COPY(p_e1, t.zexp1); C2_PAR_COPY(p_e2, t.zexp2); C2_PAR_COPY(p_cld, t.zcldi);
+        const real_t g = p_zdi * p_e1;
+        pacc->v[PAR_RKCONV] += (double)(g * (pl->dck_i * (RC(1.0) - p_e2)));
+        pacc->v[PAR_RCLCRIT] += (double)(g * (pl->crc_i * p_e2 * (p_cld * p_cld)));
+      }
       a_tp1 += cki * t.zexp1 * (RC(1.0) - t.zexp2) * RC(0.025) * zdi;
       zcldi += (cki * t.zexp1 * t.zexp2 * RC(2.0) * t.zcldi * zlcrit_i_r2) * zdi;
       a_qiwc += zcldi * t.rclc;
@@ -1425,6 +1492,11 @@ C2_HD void level_ad(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
       real_t zcldl = zlnew * t.clc * t.zexpdl;
       real_t zdl = -zlnew * t.clc * t.zcldl * t.zexpdl;
       real_t ck = ck_l;
+      if constexpr (PAR) {
+        C2_PAR_COPY(p_zdl, zdl); C2_PAR_COPY(p_e3, t.zexp3); C2_PAR_COPY(p_cld, t.zcldl);
+        pacc->v[PAR_RKCONV] += (double)(p_zdl * (pl->dck_l * (RC(1.0) - p_e3)));
+        pacc->v[PAR_RCLCRIT] += (double)(p_zdl * (pl->crc_l * p_e3 * (p_cld * p_cld)));
+      }
       zcldl += (RC(2.0) * ck * zlcrit_l_r2) * t.zexp3 * t.zcldl * zdl;
       a_qlwc += zcldl * t.rclc;
       a_clc -= t.zqlwc1 * zcldl * (t.rclc * t.rclc);
@@ -1570,6 +1642,10 @@ C2_HD void level_ad(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
     else        { z3es = r3les; z4es = r4les; r4 = t.rl; }
     a_tp1 += z3es * (rtt - z4es) * a_foeew * t.zfoeew * (r4 * r4);
     if (t.cold) a_tp1 += RC(0.545) * RC(0.17) * a_fwat * t.zcosh2r;
+    if constexpr (PAR) {  // (t.zcosh2r is 0 at warm points)
+      C2_PAR_COPY(p_fwat, a_fwat); C2_PAR_COPY(p_ch, t.zcosh2r);
+      pacc->v[PAR_RLPTRC] -= (double)(RC(0.545) * RC(0.17) * p_fwat * (t.cold ? p_ch : RC(0.0)));
+    }
   }
 
   // thermodynamic constants and first guess (cloudsc2ad.F90:1701-1738)

@@ -1,6 +1,6 @@
 // cloudsc2_sweep_kernels.hpp -- the __global__ wrappers of the column sweeps (NL, TL, AD, the Taylor test's lambda sweep), their
 // compile-time variant tables and what they share.  The sweeps are built as one translation unit per kernel family so that an edit to
-// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch}.hip, each of which
+// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par}.hip, each of which
 // instantiates its table and exports it through one accessor (nl_variant(F) ...); the host units are listed in cloudsc2_host.hpp.
 // -DC2_SINGLE_TU puts the sweeps and their launchers into ONE code object again (cloudsc2_launch.hip then includes the family files):
 // the experiment builds of `make variant`, `make asm`, `make resources` and the -DC2_WAVE_TIMES diagnostic, whose log pointer is a
@@ -111,6 +111,23 @@ __global__ void __launch_bounds__(kBlock, 1) ad_kernel(AdArgs args) {
   C2_KERNEL_BODY(C2_WAVE_LOG_END);
 }
 
+// The parameter forms (C2F_PARLIN; units cloudsc2_kern_tl_par.hip, cloudsc2_kern_vjp_par.hip): the same columns over the larger argument
+// blocks, under their parents' launch bounds.
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, (sizeof(real_t) == 4 && (F & C2F_OFF32) && !(F & C2F_EVAP)) ? 3 : 1)
+tl_par_kernel(TlParArgs args) {
+  C2_KERNEL_BODY((tl_column<F>(global_column(), &kernarg<TlParArgs>()->a)));
+}
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) vjp_par_kernel(AdParArgs args) {
+  C2_KERNEL_BODY((ad_reverse_column<F>(global_column(), &kernarg<AdParArgs>()->a)));
+}
+// their flag words: PARLIN with QSAT or with SATLIN (the reverse sweep: | ASSIGN | VJP), times PRECISE, EVAP, OFF32
+constexpr bool par_variant_valid(unsigned f, unsigned form) {
+  const unsigned rest = f & ~(C2F_PRECISE | C2F_EVAP | C2F_OFF32);
+  return rest == (C2F_PARLIN | form | C2F_QSAT) || rest == (C2F_PARLIN | form | C2F_SATLIN);
+}
+
 // The batched TL and reverse sweeps (tl_batch_column, vjp_batch_column: up to kBatchMax directions over one trajectory).  One wave
 // per SIMD in fp64 like their single-direction twins, whose registers they extend by the carries of the further directions and one
 // more set of direction inputs; the fp32 builds take what they need (nothing is measured for them yet).
@@ -164,6 +181,8 @@ KernelFn<TlArgs> tl_variant(unsigned f);
 KernelFn<AdArgs> ad_variant(unsigned f);
 KernelFn<AdArgs> ad_reverse_variant(unsigned f);
 KernelFn<TaylorArgs> taylor_variant(unsigned f);
+KernelFn<TlParArgs> tl_par_variant(unsigned f);
+KernelFn<AdParArgs> vjp_par_variant(unsigned f);
 KernelFn<TlBatchArgs> tl_batch_variant(unsigned f, int directions);
 KernelFn<VjpBatchArgs> vjp_batch_variant(unsigned f, int directions);
 

@@ -324,6 +324,40 @@ int cloudsc2_vjp_launch_satur(const cloudsc2_params* prm, double ptsphy, int npr
                               const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                               const cloudsc2_real* scratch, void* stream);
 
+/* The derivative with respect to the scheme's tunable parameters, next to the derivative with respect to its fields.  Four constants
+ * of cloudsc2_params enter CLOUDSC2 smoothly, in this order (CLOUDSC2_NPAR):
+ *   rkconv   the autoconversion rate, ZCKCODTL = 2 RKCONV PTSPHY, ZCKCODTI = 5 RKCONV PTSPHY (cloudsc2.F90:235-236)
+ *   rclcrit  the autoconversion threshold, ZLCRIT = 2 RCLCRIT; with LEVAPLS2 .OR. LDRAIN1D 1.9 RCLCRIT for liquid and the constant 1e-4 for
+ *            ice, which then does not depend on it (:505-509,522-526)
+ *   rlptrc   the mixed-phase fraction ZOEALFAW = 0.545 (tanh(0.17 (T - RLPTRC)) + 1) at cold points (:350)
+ *   rpecons  the evaporation of precipitation, ZBETA = RG RPECONS (...)^0.5777, with LEVAPLS2 .OR. LDRAIN1D only (:566)
+ * (rlmin enters a comparison only; the thermodynamic constants and ptsphy are not tunables.  None of the four enters SATUR.)  The
+ * reference has no parameter derivative; this one is the library's own.  The local partials are exact derivatives of the NL sweep's
+ * statements; the resulting perturbation travels down the column through the same linearisation as the field tangents.  So with
+ * prm->lregcl the parameter derivative is regularised exactly where CLOUDSC2TL is (cloudsc2tl.F90:575,657,754,794,998) and is not the
+ * exact derivative; with lregcl = 0 it is.  Exact zeros: clc and covptot depend on none of the four; without the evaporation branch
+ * nothing depends on rpecons; with it teni does not depend on rclcrit.
+ *   satur = 0: traj_in->qsat (and pert_in->qsat / adj_in->qsat) required, as for cloudsc2_tl_launch / cloudsc2_vjp_launch;
+ *   satur = 1: every qsat field NULL, SATUR differentiated in the sweep, as for the _satur pair.  Any other value: CLOUDSC2_EINVAL.
+ *   With the evaporation branch rpecons must not be 0 (its partial is formed as ZBETA / RPECONS): CLOUDSC2_EINVAL.
+ * cloudsc2_tl_launch_par: cloudsc2_tl_launch without trajectory stores (cloudsc2_tl_launch_satur), plus the source terms of the four
+ *   parameter tangents dpar (host doubles, read during the call: they travel in the kernel-argument segment like every constant).
+ * cloudsc2_vjp_launch_par: cloudsc2_vjp_launch (cloudsc2_vjp_launch_satur): the field adjoints it writes are the bits the plain launcher
+ *   writes.  Every active column's four sums over its levels go to `work` (device, cloudsc2_par_work_doubles() doubles, the caller's;
+ *   formed in double in both builds), and a second kernel folds them in a fixed order into par_adj (device, CLOUDSC2_NPAR doubles,
+ *   assigned): no floating-point atomics, the same bits from run to run.  Padded tail columns write nothing and are not summed.
+ * Like every launcher they take the caller's stream and one block stride per layout group, neither allocate nor synchronise (apart from
+ * the CETA table of a grid's first use), are plain kernel nodes under stream capture (one, and a pair), and are paced like their parents. */
+#define CLOUDSC2_NPAR 4
+int cloudsc2_par_work_doubles(int nproma, int ngptot, long long* n);
+int cloudsc2_tl_launch_par(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                           const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const double* dpar /* [CLOUDSC2_NPAR], host */,
+                           const cloudsc2_outputs* pert_out, void* stream);
+int cloudsc2_vjp_launch_par(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                            const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                            const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out /* read only */,
+                            const cloudsc2_real* scratch, double* work, double* par_adj /* device, [CLOUDSC2_NPAR] */, void* stream);
+
 /* Several tangents or cotangents over ONE trajectory -- a Jacobian block, a singular-vector iteration, an ensemble of perturbations.
  * cloudsc2_tl_launch_batch replaces nbatch calls of cloudsc2_tl_launch without trajectory stores (traj_out all NULL),
  * cloudsc2_vjp_launch_batch nbatch calls of cloudsc2_vjp_launch, over the same traj_in: every direction's results are the bits those
