@@ -19,7 +19,10 @@ gradient; jvp is one ``cloudsc2_tl_launch_par``.  The constants travel in the ke
 (and, in forward mode, their tangents) are read on the HOST: that synchronises when they live on the device, returning a gradient
 to a CPU parameter copies four doubles back, and the op refuses ``params`` while the stream is capturing.  Any ``torch.func.vmap``
 level over the op with ``params`` (so also ``jacfwd`` / ``jacrev``) raises ``NotImplementedError``: use the unbatched calls, one
-direction at a time.  With the evaporation branch ``rpecons`` must not be 0.
+direction at a time.  With the evaporation branch ``rpecons`` must not be 0.  The whole parameter Jacobian -- ``d out / d p`` for
+all four parameters, what a Gauss-Newton or Levenberg-Marquardt calibration needs -- is :func:`param_jacobian`: one
+``cloudsc2_tl_launch_parjac``, the trajectory read once and no tangent plane read, every entry the ``torch.func.jvp`` of the op
+with a unit tangent on that parameter.
 
 Batches.  Under ``torch.func.vmap`` the op distinguishes two cases.  Several tangents or cotangents over ONE state -- ``jacfwd``,
 ``jacrev``, ``vmap(jvp)``, ``vmap(vjp_fn)`` -- are one ``cloudsc2_tl_launch_batch`` / ``cloudsc2_vjp_launch_batch`` call: the
@@ -947,6 +950,48 @@ def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, sa
     x = normalize({n: inputs[n] for n in B.IN_NAMES}, lay, IN_GROUPS)
     out = _Cloudsc2.apply(prm, float(ptsphy), lay, *(x[n] for n in B.IN_NAMES))
     return Cloudsc2Outputs(*out[:10])
+
+
+def param_jacobian(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None) -> dict:
+    """The whole parameter Jacobian of :func:`cloudsc2` at one state: a dict ``name -> Cloudsc2Outputs`` holding ``d out / d name``
+    for every name of ``PARAM_NAMES`` (``params=None``: at ``prm``'s values), or for the names of ``params`` (a mapping as for
+    ``cloudsc2(..., params=...)``, whose values override a copy of ``prm``).  One ``cloudsc2_tl_launch_parjac``: the trajectory is
+    read once and no tangent plane exists, where ``torch.func.jvp`` of the op with a unit tangent on one parameter is a launch per
+    parameter over zero-filled tangent planes; every entry is that jvp's result.  ``inputs`` as for :func:`cloudsc2` (without ``qsat``
+    when ``satur=True``: SATUR is then evaluated in the sweep; none of the parameters enters it).  The result is plain contiguous
+    tensors without a graph, padded tails zero; without the evaporation branch the ``rpecons`` entry is zero tensors."""
+    names, groups = _names(satur)
+    lay = check_layout(inputs, prm, ngptot, satur=satur)
+    pnames = PARAM_NAMES if params is None else check_params(params, prm)
+    dev = check_device(inputs[n] for n in names)
+    ps = () if params is None else tuple(params[n] for n in pnames)
+    if any(_batched_inside(t) for t in ps + tuple(inputs[n] for n in names)):
+        raise NotImplementedError("param_jacobian: batched (vmap-wrapped) operands are not supported; call it once per state")
+    for n, p in zip(pnames, ps):
+        if p.device.type != "cpu" and p.device != dev:
+            raise ValueError(f"params[{n!r}] is on {p.device}: parameters live on the CPU or on the inputs' device {dev}")
+    if any(p.device.type != "cpu" for p in ps) and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("param_jacobian: the parameters' values are read on the host (they travel in the kernel-argument segment), "
+                           "which cannot happen for device tensors while the stream is capturing")
+    _prepare(dev)
+    prm = copy.copy(prm)  # (a ctypes structure: a copy of its bytes)
+    for n, p in zip(pnames, ps):
+        setattr(prm, n, _host_value(p))  # synchronises when the parameter lives on the device
+    evap = _evap(prm)
+    if evap and prm.rpecons == 0.0:
+        raise ValueError("param_jacobian with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
+    with torch.no_grad():
+        x = normalize({n: _raw(inputs[n]).detach() for n in names}, lay, groups)
+        like = x["pap"]
+        ran = PARAM_NAMES if evap else PARAM_NAMES[:-1]  # (nothing depends on rpecons without the evaporation branch: not run)
+        dy = {n: _new(B.OUT_NAMES, lay, like) for n in ran}
+        if any(n in ran for n in pnames):
+            blocks = (B.Outputs * len(PARAM_NAMES))(*(_block("out", dy[n], lay) for n in ran))
+            with torch.cuda.device(dev):
+                B.check(B.lib.cloudsc2_tl_launch_parjac(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                        C.byref(_block("in", x, lay)), blocks, _stream(dev)))
+        return {n: Cloudsc2Outputs(*(dy[n][k] if n in ran else torch.zeros(lay.shape(k), dtype=like.dtype, device=dev) for k in B.OUT_NAMES))
+                for n in pnames}
 
 
 def satur(pap: torch.Tensor, t: torch.Tensor, prm: B.Params, ngptot: int | None = None, differentiable: bool = False) -> torch.Tensor:

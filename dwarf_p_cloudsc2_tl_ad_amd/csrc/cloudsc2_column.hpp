@@ -1222,6 +1222,118 @@ C2_HD void tl_batch_column(long long gcol, TlBatchArgsP a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The parameter Jacobian in one sweep: d out / d rkconv ... rpecons over ONE trajectory (cloudsc2_tl_launch_parjac)
+// ---------------------------------------------------------------------------------------------------------
+// A calibration of the tunable parameters by Gauss-Newton needs every column of d out / d p, which forward mode gives as one
+// tl_column<F | C2F_PARLIN> launch per parameter with a unit tangent -- each reading the 16 trajectory planes and 16 tangent planes
+// that hold nothing but zeros.  The parameter directions are special: the field tangents are identically zero and there are at most
+// kBatchMax of them.  This sweep is tl_batch_column with the direction inputs replaced by zeros in registers: the trajectory is read
+// once, no tangent plane is read, and direction b runs level_tl<true> with its own ParLin par[b] (the host's make_parlin of the unit
+// tangent of parameter b).  Every direction is the bits of tl_column<F | C2F_PARLIN> on zero-filled planes: its own straight line as in
+// tl_batch_column (launder_level), and zeros the compiler cannot tell from loaded values (an empty asm statement on each).
+// The direction count belongs to the flag word: without the evaporation branch nothing depends on rpecons and its direction is not run.
+constexpr int parjac_directions(unsigned f) { return (f & C2F_EVAP) ? PAR_COUNT : PAR_COUNT - 1; }
+static_assert(PAR_COUNT <= kBatchMax && PAR_RPECONS == PAR_COUNT - 1, "the parameter directions fit one launch, rpecons last");
+
+// (dout and par from the launch's direction count on are not read)
+struct TlParJacArgs {
+  Consts c; Geom g; Strides s, sp; InPtrs in; OutPtrs dout[kBatchMax]; ParLin par[kBatchMax]; const LevelTab* tab;
+};
+typedef const C2_CONST_AS TlParJacArgs* TlParJacArgsP;
+
+// the zero field tangents of one level, opaque (tl_column reads them from its tangent planes; without the evaporation branch its
+// surface-pressure tangent is the literal zero it is here)
+template <bool EVAP>
+C2_HD void zero_level_in(LevelIn& dx) {
+  dx.paph_k = dx.paph_k1 = dx.pap = dx.q = dx.qs = dx.t = dx.l = dx.i = dx.lude = dx.lu_k1 = dx.mfu = dx.mfd = dx.gt = dx.gq = dx.gl =
+      dx.gi = dx.supsat = dx.paph_surf = RC(0.0);
+  C2_LAUNDER_V(dx.paph_k); C2_LAUNDER_V(dx.paph_k1); C2_LAUNDER_V(dx.pap); C2_LAUNDER_V(dx.q); C2_LAUNDER_V(dx.qs); C2_LAUNDER_V(dx.t);
+  C2_LAUNDER_V(dx.l); C2_LAUNDER_V(dx.i); C2_LAUNDER_V(dx.lude); C2_LAUNDER_V(dx.lu_k1); C2_LAUNDER_V(dx.mfu); C2_LAUNDER_V(dx.mfd);
+  C2_LAUNDER_V(dx.gt); C2_LAUNDER_V(dx.gq); C2_LAUNDER_V(dx.gl); C2_LAUNDER_V(dx.gi); C2_LAUNDER_V(dx.supsat);
+  if (EVAP) C2_LAUNDER_V(dx.paph_surf);
+}
+
+// F: C2F_QSAT (otherwise the trajectory's SATUR is evaluated in the sweep) | C2F_PRECISE | C2F_EVAP | C2F_OFF32
+template <unsigned F>
+C2_HD void tl_parjac_column(long long gcol, TlParJacArgsP a) {
+  constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0;
+  constexpr int NP = parjac_directions(F);
+  static_assert(!(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32)), "flags of the parameter-Jacobian sweep: QSAT, PRECISE, EVAP, OFF32");
+  typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
+  LaneOff o, op; bool active;
+  if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
+  lane_setup(&a->g, &a->sp, gcol, op, active);
+  if (!active) return;
+  const int nlev = a->g.nlev, nproma = a->g.nproma;
+  LevelTabP tab = (LevelTabP)a->tab;
+  ConstsP c = C2_CONSTS(a);
+  InPtrsP in = &a->in;
+
+  // once per column, not once per direction: the tropopause pre-scan, the critical-humidity setup, the lane offsets, the loads
+  real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->g, RC(0.0));
+  RhCrit rh;
+  rhcrit_setup(ztrpaus, rh);
+  real_t paph_surf = RC(0.0);
+  if (EVAP) paph_surf = in->paph[o.half + (long long)nlev * nproma];
+
+  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
+  Carry dcy[NP];
+#pragma unroll
+  for (int b = 0; b < NP; ++b) {
+    dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0);
+    store_top(&a->dout[b], op, c);
+  }
+  RawLevel cur, nxt;
+  real_t paph_k = in->paph[o.half];
+  const LaneOffT<OT> ol = lane_off_as<OT>(o), opl = lane_off_as<OT>(op);  // offsets used inside the level loop
+  load_level<HAS_QSAT>(in, ol, nproma, nlev, 0, cur);
+  Pace pace;
+  pace.begin(&a->g);
+
+  // The trajectory inputs of level jk+1 are requested at the top of level jk, as in tl_column; nothing else is read.
+  for (int jk = 0; jk < nlev; ++jk) {
+    const bool last = (jk == nlev - 1);
+    TlParJacArgsP ap = a;
+    C2_LAUNDER(ap);
+    nxt = cur;
+    if (!last) load_level<HAS_QSAT>(&ap->in, ol, nproma, nlev, jk + 1, nxt);
+    pace.nap();  // (with the loads in flight)
+    if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);  // (once per level: every direction gets its own opaque copy)
+
+    LevelCst k;
+    level_cst(tab, jk, last, k);
+    LevelIn x;
+    make_level_in(cur, paph_k, paph_surf, x);
+    Carry cy_out = cy;
+#pragma unroll
+    for (int b = 0; b < NP; ++b) {
+      // this direction's own straight line (launder_level says why): every direction leaves the same trajectory carry
+      LevelIn xb = x;
+      LevelCst kb = k;
+      RhCrit rhb = rh;
+      cy_out = cy;
+      launder_level(xb, kb, cy_out);
+      C2_LAUNDER_V(xb.paph_surf); C2_LAUNDER_V(rhb.zeta3); C2_LAUNDER_V(rhb.zrh2); C2_LAUNDER_V(rhb.zdeta1);
+      ConstsP cb = c;  // (and its own view of the constants: a product of two of them is shared otherwise)
+      C2_LAUNDER(cb);
+      LevelTraj tr;
+      LevelOut lo;
+      level_forward<P, EVAP>(cb, kb, rhb, xb, cy_out, tr, lo);
+      LevelIn dx;
+      zero_level_in<EVAP>(dx);
+      LevelOut dlo;
+      C2_LAUNDER(ap);
+      level_tl<true>(cb, kb, xb, tr, dx, dcy[b], dlo, &ap->par[b]);
+      C2_LAUNDER(ap);
+      store_out(&ap->dout[b], opl, nproma, jk, dlo);
+    }
+    cy = cy_out;
+    paph_k = cur.paph_k1;
+    cur = nxt;
+  }
+}
+
 template <class OT>
 C2_HD void load_out_adjoint(OutPtrsP pp, const LaneOffT<OT>& oa, OT d, OT d1, LevelOut& ya) {
   const OutPtrs pa = *pp;

@@ -19,6 +19,7 @@
 #include "cloudsc2_kern_vjp_batch.hip"
 #include "cloudsc2_kern_tl_par.hip"
 #include "cloudsc2_kern_vjp_par.hip"
+#include "cloudsc2_kern_tl_parjac.hip"
 #endif
 
 using namespace cloudsc2;
@@ -27,7 +28,7 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------------------
 // kernels: the sweeps' __global__ wrappers and their variant tables are cloudsc2_sweep_kernels.hpp + the family units
-// cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
+// cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
 // ---------------------------------------------------------------------------------------------------------
 template <bool P>
 __global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
@@ -740,6 +741,43 @@ int tl_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, 
   });
 }
 
+// The parameter Jacobian: the sensitivities of the ten outputs to the tunable parameters in ONE sweep over the trajectory
+// (tl_parjac_column: no tangent planes; direction k runs with make_parlin of the unit tangent of parameter k).  Without the evaporation
+// branch the kernel runs CLOUDSC2_NPAR - 1 directions and pert_out[PAR_RPECONS] is not looked at.
+int tl_parjac_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                          const cloudsc2_outputs* pert_out, void* stream) {
+  // (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
+  if (!prm || !traj_in || !pert_out) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "parameter Jacobian: CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
+  const bool evap = prm->levapls2 || prm->ldrain1d;
+  if (evap && prm->rpecons == 0.0) return fail(CLOUDSC2_EINVAL, "parameter derivative with the evaporation branch: rpecons must not be 0");
+  const int np = evap ? (int)PAR_COUNT : (int)PAR_COUNT - 1;
+  Sweep w;
+  int rc = resolve_in(*traj_in, false, w.s, w.in);
+  if (rc) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  TlParJacArgs args;
+  Strides sp = {0, 0, 0, 0, 0};
+  for (int b = 0; b < np; ++b) {
+    Strides sb = {0, 0, 0, 0, 0};
+    if ((rc = resolve_out(pert_out[b], true, sb, args.dout[b]))) return rc;
+    if (b == 0) sp = sb;
+    else if (!same_strides(sp, sb)) return fail(CLOUDSC2_EINVAL, "parameter Jacobian: every block must have the same block stride per layout group");
+  }
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sp.full, sp.half, sp.loc}))) return rc;
+  args.c = w.c; args.g = w.g; args.s = w.s; args.sp = sp; args.in = w.in; args.tab = w.tab;
+  for (int b = 0; b < kBatchMax; ++b) {  // (the sets from `np` on are not read: valid contents all the same)
+    double e[PAR_COUNT] = {};
+    e[b < np ? b : 0] = 1.0;
+    args.par[b] = make_parlin(w.c, e);
+    if (b >= np) args.dout[b] = args.dout[0];
+  }
+  const KernelFn<TlParJacArgs> fn = tl_parjac_variant(w.f);
+  schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
+  return launch_variant(fn, args, w.g.ncols_pad, (hipStream_t)stream);
+}
+
 int vjp_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
                           const cloudsc2_outputs* traj_out, int nbatch, const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                           const cloudsc2_real* scratch, void* stream) {
@@ -1033,6 +1071,11 @@ int cloudsc2_vjp_launch_batch(const cloudsc2_params* prm, double ptsphy, int npr
                               const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                               const cloudsc2_real* scratch, void* stream) {
   return vjp_batch_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, nbatch, adj_in, adj_out, scratch, stream);
+}
+
+int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* pert_out, void* stream) {
+  return tl_parjac_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, pert_out, stream);
 }
 
 int cloudsc2_ad_launch_reverse_norms(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,

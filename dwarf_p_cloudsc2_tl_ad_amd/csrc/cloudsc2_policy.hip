@@ -258,6 +258,7 @@ std::vector<int> paced_kernel_occupancies() {
       add((const void*)tl_batch_variant(f, nb));
       add((const void*)vjp_batch_variant(f, nb));
     }
+    add((const void*)tl_parjac_variant(f));  // the parameter Jacobian's sweep
   }
   return out;
 }
@@ -445,6 +446,7 @@ int cloudsc2_kernel_occupancy(int kernel, int flags, int* workgroups_per_cu) {
     case 3: fn = (const void*)ad_reverse_variant((unsigned)flags); break;
     case 4: fn = (const void*)tl_batch_variant((unsigned)flags % 64u, flags / 64); break;  // flags + 64 x directions
     case 5: fn = (const void*)vjp_batch_variant((unsigned)flags % 64u, flags / 64); break;
+    case 6: fn = (const void*)tl_parjac_variant((unsigned)flags); break;
     default: break;
   }
   if (!fn) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: no such kernel variant in this build");

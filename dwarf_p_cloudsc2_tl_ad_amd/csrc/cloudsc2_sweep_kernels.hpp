@@ -1,6 +1,6 @@
 // cloudsc2_sweep_kernels.hpp -- the __global__ wrappers of the column sweeps (NL, TL, AD, the Taylor test's lambda sweep), their
 // compile-time variant tables and what they share.  The sweeps are built as one translation unit per kernel family so that an edit to
-// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par}.hip, each of which
+// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac}.hip, each of which
 // instantiates its table and exports it through one accessor (nl_variant(F) ...); the host units are listed in cloudsc2_host.hpp.
 // -DC2_SINGLE_TU puts the sweeps and their launchers into ONE code object again (cloudsc2_launch.hip then includes the family files):
 // the experiment builds of `make variant`, `make asm`, `make resources` and the -DC2_WAVE_TIMES diagnostic, whose log pointer is a
@@ -149,6 +149,15 @@ constexpr bool batch_kernel_valid(unsigned g) {  // (one direction is tl_kernel'
   return batch_variant_valid(g % 64u) && g / 64u >= 2u && g / 64u <= (unsigned)kBatchMax;
 }
 
+// The parameter Jacobian in one sweep (tl_parjac_column; unit cloudsc2_kern_tl_parjac.hip): the batched TL sweep's structure and launch
+// bounds, the direction count (3, or 4 with the evaporation branch) fixed by the flag word.  Flag words: PRECISE, EVAP, OFF32 times
+// QSAT or SATUR evaluated in the sweep -- 16 kernels per precision.
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) tl_parjac_kernel(TlParJacArgs args) {
+  C2_KERNEL_BODY((tl_parjac_column<F>(global_column(), kernarg<TlParJacArgs>())));
+}
+constexpr bool parjac_variant_valid(unsigned f) { return (f & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32)) == 0; }
+
 // The ten perturbed NL runs of the Taylor test in one sweep, the lambdas on the lanes (taylor_column): the grid is over THREADS,
 // 64 per kTaylorCols columns.  A wave reads 6 columns = 48 bytes of every 128-byte line it touches, so two or three consecutive
 // waves share each line -- the one sweep whose workgroups share data.  Blocks are dealt round-robin over the 8 XCDs (b and b + 8
@@ -185,5 +194,6 @@ KernelFn<TlParArgs> tl_par_variant(unsigned f);
 KernelFn<AdParArgs> vjp_par_variant(unsigned f);
 KernelFn<TlBatchArgs> tl_batch_variant(unsigned f, int directions);
 KernelFn<VjpBatchArgs> vjp_batch_variant(unsigned f, int directions);
+KernelFn<TlParJacArgs> tl_parjac_variant(unsigned f);
 
 }  // namespace cloudsc2

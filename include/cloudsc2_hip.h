@@ -222,7 +222,7 @@ int cloudsc2_simd_population(long long workgroups, int cus, long long block, int
  * the verdicts.  cloudsc2_dispatch_probe / cloudsc2_pace_probe run one probe and return its counts without caching anything (GPU
  * tests); cloudsc2_device_rules returns the cached verdicts of the current device (1 on, 0 off, -1 never probed);
  * cloudsc2_kernel_occupancy the workgroups per CU of one kernel variant (kernel 0 NL, 1 TL, 2 AD both sweeps, 3 AD reverse sweep,
- * 4 batched TL, 5 batched reverse sweep; flags = its C2F_* variant bits, cloudsc2_column.hpp; for the batched sweeps, whose kernels
+ * 4 batched TL, 5 batched reverse sweep, 6 the parameter Jacobian's sweep; flags = its C2F_* variant bits, cloudsc2_column.hpp; for the batched sweeps, whose kernels
  * are built per direction count, plus 64 x the directions of the launch, 2..cloudsc2_batch_max()) as the runtime reports them
  * (the sweeps of cloudsc2_tl_launch_satur / cloudsc2_vjp_launch_satur: kernel 1 / 3 with C2F_SATLIN = 128 among the flags).
  *
@@ -357,6 +357,22 @@ int cloudsc2_vjp_launch_par(const cloudsc2_params* prm, double ptsphy, int nprom
                             const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
                             const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out /* read only */,
                             const cloudsc2_real* scratch, double* work, double* par_adj /* device, [CLOUDSC2_NPAR] */, void* stream);
+
+/* The whole parameter Jacobian in one sweep -- what a Gauss-Newton or Levenberg-Marquardt calibration of the four parameters needs.
+ * cloudsc2_tl_launch_parjac replaces one cloudsc2_tl_launch_par call per parameter, each with all-zero tangent planes and the unit
+ * tangent e_k as dpar: pert_out[k] receives d out / d p_k, k in CLOUDSC2_NPAR order, and every block is the bits that call gives
+ * (satur = 0).  The trajectory planes are read once, no tangent plane is read (bytes per column, NLEV 137, fp64:
+ * NP x 46 080 -> 17 544 + NP x 10 992, NP = the directions run).
+ *   traj_in->qsat may be NULL: SATUR is then evaluated in the sweep (none of the four enters SATUR and the field tangents are zero,
+ *   so the tangent of qsat is zero either way); the other 15 fields are required.
+ *   With LEVAPLS2 .OR. LDRAIN1D all four blocks are required and rpecons must not be 0 (CLOUDSC2_EINVAL).  Without the evaporation
+ *   branch nothing depends on rpecons: three directions are run, and pert_out[3] is neither read nor written (its fields may be NULL).
+ *   A NULL field elsewhere, prm->lphylin = 0, bad shapes, or blocks whose strides per layout group differ: CLOUDSC2_EINVAL (reported
+ *   before the device is looked for).  Without a device: CLOUDSC2_ENODEVICE.  Padded tail columns are not written.
+ * Like every launcher it takes the caller's stream and one block stride per layout group, neither allocates nor synchronises (apart from
+ * the CETA table of a grid's first use), is one plain kernel node under stream capture, and is paced like the batched sweeps. */
+int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* pert_out /* [CLOUDSC2_NPAR] */, void* stream);
 
 /* Several tangents or cotangents over ONE trajectory -- a Jacobian block, a singular-vector iteration, an ensemble of perturbations.
  * cloudsc2_tl_launch_batch replaces nbatch calls of cloudsc2_tl_launch without trajectory stores (traj_out all NULL),
