@@ -225,6 +225,13 @@ def _load() -> C.CDLL:
     lib.cloudsc2_device_rules.restype = C.c_int
     lib.cloudsc2_kernel_occupancy.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
     lib.cloudsc2_kernel_occupancy.restype = C.c_int
+    # debug: which kernel variants exist, and which the calling thread's launcher calls have enqueued (include/cloudsc2_hip.h)
+    lib.cloudsc2_variant_built.argtypes = [C.c_int, C.c_uint]
+    lib.cloudsc2_variant_built.restype = C.c_int
+    lib.cloudsc2_debug_launch_log_reset.argtypes = []
+    lib.cloudsc2_debug_launch_log_reset.restype = None
+    lib.cloudsc2_debug_launch_log.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_uint), C.c_int]
+    lib.cloudsc2_debug_launch_log.restype = C.c_int
     lib.cloudsc2_device_probe.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, dp]
     lib.cloudsc2_device_probe.restype = C.c_int
     lib.cloudsc2_device_malloc_state.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.c_int]
@@ -265,7 +272,8 @@ EXPORTED = ("cloudsc2_params_default", "cloudsc2_last_error", "cloudsc2_device_a
             "cloudsc2_device_malloc", "cloudsc2_device_free", "cloudsc2_device_malloc_info", "cloudsc2_device_malloc_counts", "cloudsc2_pace_plan", "cloudsc2_simd_population", "cloudsc2_dispatch_probe", "cloudsc2_pace_probe", "cloudsc2_device_prepare", "cloudsc2_device_rules", "cloudsc2_kernel_occupancy", "cloudsc2_device_probe", "cloudsc2_device_malloc_state",
             "cloudsc2_state_create", "cloudsc2_state_destroy", "cloudsc2_state_field", "cloudsc2_state_blocking", "cloudsc2_state_expand",
             "cloudsc2_state_upload", "cloudsc2_state_download", "cloudsc2_state_nl", "cloudsc2_state_tl_taylor",
-            "cloudsc2_state_ad_symmetry", "cloudsc2_state_validate", "cloudsc2_synthetic_table")
+            "cloudsc2_state_ad_symmetry", "cloudsc2_state_validate", "cloudsc2_synthetic_table",
+            "cloudsc2_variant_built", "cloudsc2_debug_launch_log_reset", "cloudsc2_debug_launch_log")
 
 # field ids of the resident-state API (enum in include/cloudsc2_hip.h)
 F_FULL = {"PT": 0, "PQ": 1, "PAP": 2, "PAPH": 3, "PLU": 4, "PLUDE": 5, "PMFU": 6, "PMFD": 7, "PA": 8, "PSUPSAT": 9, "PCOVPTOT": 10,
@@ -296,6 +304,26 @@ class DeviceBuffer:
         if getattr(self, "ptr", 0):
             lib.cloudsc2_device_free(C.c_void_p(self.ptr))
             self.ptr = 0
+
+
+LAUNCH_LOG_MAX = 64  # entries the launch log keeps (cloudsc2_debug_launch_log)
+FAMILIES = ("nl", "tl", "ad", "ad_reverse", "tl_batch", "vjp_batch", "tl_parjac", "tl_par", "vjp_par", "taylor")
+
+
+def launch_log_reset() -> None:
+    lib.cloudsc2_debug_launch_log_reset()
+
+
+def launch_log() -> list:
+    """[(family, word), ...] of the sweep kernels this thread's launcher calls have enqueued since launch_log_reset(), in order; raises
+    if there were more than the log keeps."""
+    fam, word = (C.c_int * LAUNCH_LOG_MAX)(), (C.c_uint * LAUNCH_LOG_MAX)()
+    n = lib.cloudsc2_debug_launch_log(fam, word, LAUNCH_LOG_MAX)
+    if n < 0:
+        check(n)
+    if n > LAUNCH_LOG_MAX:
+        raise Cloudsc2Error(CLOUDSC2_EINVAL, f"launch log overflow: {n} launches since the reset, {LAUNCH_LOG_MAX} recorded")
+    return [(fam[i], word[i]) for i in range(n)]
 
 
 def device_probe(ptr: int, nbytes: int, kind: int = 0, rounds: int = 5) -> float:

@@ -61,12 +61,24 @@ int validate_launch_impl(const cloudsc2_real* table, int klon, int period, long 
 
 inline unsigned grid_for(long long ncols, int block) { return (unsigned)((ncols + block - 1) / block); }
 
+// The kernel families of the sweeps, as cloudsc2_kernel_occupancy, cloudsc2_variant_built and the launch log number them
+enum SweepFamily {
+  kFamNl = 0, kFamTl = 1, kFamAd = 2, kFamAdReverse = 3, kFamTlBatch = 4, kFamVjpBatch = 5, kFamTlParjac = 6, kFamTlPar = 7,
+  kFamVjpPar = 8, kFamTaylor = 9, kFamCount = 10
+};
+// the variant's entry point (nullptr: not built); the batched families' word is flags + 64 x directions (cloudsc2_policy.hip)
+const void* variant_entry(int family, unsigned word);
+// The calling thread's launch log (cloudsc2_debug_launch_log): a thread-local array of plain integers, no device call -- harmless
+// during stream capture.  Every sweep launch passes launch_variant, which records the kernel it has enqueued.
+void log_launch(int family, unsigned word);
+
 template <class Args>
-int launch_variant(KernelFn<Args> fn, const Args& args, long long ncols, hipStream_t st) {
+int launch_variant(SweepFamily family, unsigned word, KernelFn<Args> fn, const Args& args, long long ncols, hipStream_t st) {
   if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   Args a = args;
   void* argv[] = {&a};
   HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(ncols, kBlock)), dim3(kBlock), argv, 0, st));
+  log_launch(family, word);
   return 0;
 }
 

@@ -313,6 +313,24 @@ bool device_ok() {
 
 int no_device() { return fail(CLOUDSC2_ENODEVICE, "no HIP device available (this library has no CPU path)"); }
 
+// The calling thread's launch log (cloudsc2_debug_launch_log): the first kLaunchLogMax sweep kernels enqueued since the reset, and how
+// many there were in all.  Plain thread-local integers: no allocation, no lock, no device call.
+namespace {
+constexpr int kLaunchLogMax = 64;
+struct LaunchLog {
+  long long count;
+  int family[kLaunchLogMax];
+  unsigned word[kLaunchLogMax];
+};
+thread_local LaunchLog g_launch_log = {};
+}  // namespace
+
+void log_launch(int family, unsigned word) {
+  LaunchLog& l = g_launch_log;
+  if (l.count < kLaunchLogMax) { l.family[l.count] = family; l.word[l.count] = word; }
+  if (l.count < 0x7fffffff) ++l.count;
+}
+
 // 0 = fast math (shared reciprocals, branch-free exp), 1 = precise (IEEE division, libm exp/tanh, reference order)
 namespace {
 int initial_math_mode() {
@@ -563,9 +581,9 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
     TlParArgs pargs;
     pargs.a = args;
     pargs.par = make_parlin(w.c, dpar);
-    return launch_variant(tl_par_variant(w.f), pargs, w.g.ncols_pad, (hipStream_t)stream);
+    return launch_variant(kFamTlPar, w.f, tl_par_variant(w.f), pargs, w.g.ncols_pad, (hipStream_t)stream);
   }
-  return launch_variant(tl_variant(w.f), args, w.g.ncols_pad, (hipStream_t)stream);
+  return launch_variant(kFamTl, w.f, tl_variant(w.f), args, w.g.ncols_pad, (hipStream_t)stream);
 }
 
 // What an AD launch runs.  which 0: both sweeps (the fused kernel, or the two kernels in stream order); 1: the trajectory pass
@@ -634,7 +652,7 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   const void* rev = (const void*)ad_reverse_variant(f);
   if (m.which == 1) {
     schedule(args.nl.g, fwd, false, nullptr);
-    return launch_variant(nl_variant(f_fwd), args.nl, n, st);
+    return launch_variant(kFamNl, f_fwd, nl_variant(f_fwd), args.nl, n, st);
   }
   if (m.par_work) {  // the reverse sweep with the parameter sums, then their fold
     if (!m.vjp || !m.par_adj) return fail(CLOUDSC2_EINVAL, "parameter adjoints: the vector-Jacobian product, with workspace and result");
@@ -644,24 +662,24 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
     pargs.a = args;
     pargs.par = make_parlin(w.c, nullptr);
     pargs.work = m.par_work;
-    if ((rc = launch_variant(vjp_par_variant(f), pargs, n, st))) return rc;
+    if ((rc = launch_variant(kFamVjpPar, f, vjp_par_variant(f), pargs, n, st))) return rc;
     hipLaunchKernelGGL(par_fold_kernel, dim3(PAR_COUNT), dim3(kParFoldBlock), 0, st, (const double*)m.par_work, n, (long long)w.g.ngptot, m.par_adj);
     HIP_TRY(hipGetLastError());
     return 0;
   }
   if (m.which == 2) {
     schedule(args.nl.g, nullptr, false, rev);
-    return launch_variant(ad_reverse_variant(f), args, n, st);
+    return launch_variant(kFamAdReverse, f, ad_reverse_variant(f), args, n, st);
   }
   if (!kAdSplitSmall || n > kAdSplitBelow) {
     schedule(args.nl.g, nullptr, false, (const void*)ad_variant(f));
-    return launch_variant(ad_variant(f), args, n, st);
+    return launch_variant(kFamAd, f, ad_variant(f), args, n, st);
   }
   // trajectory pass, then the reverse pass, in stream order: one Geom carries the NL kernel's `fair` and the reverse kernel's pacing
   // (the NL kernel does not look at the pacing fields unless fair & 4)
   schedule(args.nl.g, fwd, false, rev);
-  if ((rc = launch_variant(nl_variant(f_fwd), args.nl, n, st))) return rc;
-  return launch_variant(ad_reverse_variant(f), args, n, st);
+  if ((rc = launch_variant(kFamNl, f_fwd, nl_variant(f_fwd), args.nl, n, st))) return rc;
+  return launch_variant(kFamAdReverse, f, ad_reverse_variant(f), args, n, st);
 }
 
 // what the two parameter launchers check before their parents' checks
@@ -737,7 +755,7 @@ int tl_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, 
       args.dout[b] = dout[first + (b < count ? b : 0)];
     }
     schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
-    return launch_variant(fn, args, w.g.ncols_pad, (hipStream_t)stream);
+    return launch_variant(kFamTlBatch, w.f + 64u * (unsigned)count, fn, args, w.g.ncols_pad, (hipStream_t)stream);
   });
 }
 
@@ -775,7 +793,7 @@ int tl_parjac_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
   }
   const KernelFn<TlParJacArgs> fn = tl_parjac_variant(w.f);
   schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
-  return launch_variant(fn, args, w.g.ncols_pad, (hipStream_t)stream);
+  return launch_variant(kFamTlParjac, w.f, fn, args, w.g.ncols_pad, (hipStream_t)stream);
 }
 
 int vjp_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
@@ -815,7 +833,7 @@ int vjp_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
       args.aout[b] = aout[first + (b < count ? b : 0)];
     }
     schedule(args.nl.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
-    return launch_variant(fn, args, w.g.ncols_pad, (hipStream_t)stream);
+    return launch_variant(kFamVjpBatch, w.f + 64u * (unsigned)count, fn, args, w.g.ncols_pad, (hipStream_t)stream);
   });
 }
 
@@ -904,6 +922,14 @@ int cloudsc2_debug_wave_log(unsigned long long* host_buf, long long nwaves) {
 }
 #endif
 
+void cloudsc2_debug_launch_log_reset(void) { g_launch_log.count = 0; }
+int cloudsc2_debug_launch_log(int* families, unsigned* flags, int max) {
+  if (max < 0 || (max > 0 && (!families || !flags))) return fail(CLOUDSC2_EINVAL, "cloudsc2_debug_launch_log: max >= 0 and, with max > 0, both arrays required");
+  const LaunchLog& l = g_launch_log;
+  for (int i = 0; i < max && i < kLaunchLogMax && i < l.count; ++i) { families[i] = l.family[i]; flags[i] = l.word[i]; }
+  return (int)l.count;
+}
+
 void cloudsc2_set_math_mode(int precise) { g_precise.store(precise ? 1 : 0); }
 int cloudsc2_get_math_mode(void) { return g_precise.load(); }
 
@@ -961,7 +987,7 @@ int cloudsc2_nl_launch(const cloudsc2_params* prm, double ptsphy, int nproma, in
   NlArgs args = w.nl();
   args.zero_plane = zero_plane.ptr; args.zero_stride = zero_plane.block_stride; args.lam = pert_lambda;
   schedule(args.g, (const void*)nl_variant(w.f), true, nullptr);
-  return launch_variant(nl_variant(w.f), args, w.g.ncols_pad, (hipStream_t)stream);
+  return launch_variant(kFamNl, w.f, nl_variant(w.f), args, w.g.ncols_pad, (hipStream_t)stream);
 }
 
 int cloudsc2_tl_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
@@ -1151,7 +1177,7 @@ int cloudsc2_taylor_sweep_launch(const cloudsc2_params* prm, double ptsphy, int 
   const Geom& g = w.g;
   const long long nwaves = (g.ncols_pad + kTaylorCols - 1) / kTaylorCols;
   const long long per8 = 8LL * kBlock;  // the kernel's XCD mapping wants a multiple of 8 blocks
-  if ((rc = launch_variant(taylor_variant(w.f), args, (nwaves * 64 + per8 - 1) / per8 * per8, (hipStream_t)stream))) return rc;
+  if ((rc = launch_variant(kFamTaylor, w.f, taylor_variant(w.f), args, (nwaves * 64 + per8 - 1) / per8 * per8, (hipStream_t)stream))) return rc;
   const long long nblocks_stat = ((long long)ngptot + nproma_stat - 1) / nproma_stat;
   if (nproma_stat <= 512) {
     hipLaunchKernelGGL(taylor_reduce_kernel, dim3((unsigned)nblocks_stat), dim3(128), 0, (hipStream_t)stream, nproma_stat, ngptot,

@@ -391,6 +391,23 @@ int device_prepare() {
   return 0;
 }
 
+// one lookup for cloudsc2_kernel_occupancy and cloudsc2_variant_built (pure host: the tables of the family units)
+const void* variant_entry(int family, unsigned word) {
+  switch (family) {
+    case kFamNl: return (const void*)nl_variant(word);
+    case kFamTl: return (const void*)tl_variant(word);
+    case kFamAd: return (const void*)ad_variant(word);
+    case kFamAdReverse: return (const void*)ad_reverse_variant(word);
+    case kFamTlBatch: return (const void*)tl_batch_variant(word % 64u, (int)(word / 64u));  // flags + 64 x directions
+    case kFamVjpBatch: return (const void*)vjp_batch_variant(word % 64u, (int)(word / 64u));
+    case kFamTlParjac: return (const void*)tl_parjac_variant(word);
+    case kFamTlPar: return (const void*)tl_par_variant(word);
+    case kFamVjpPar: return (const void*)vjp_par_variant(word);
+    case kFamTaylor: return (const void*)taylor_variant(word);
+    default: return nullptr;
+  }
+}
+
 }  // namespace cloudsc2
 
 extern "C" {
@@ -438,22 +455,17 @@ int cloudsc2_device_rules(int workgroups_per_cu, int* nl_nap, int* pacing) {
 int cloudsc2_kernel_occupancy(int kernel, int flags, int* workgroups_per_cu) {
   if (!workgroups_per_cu) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: NULL argument");
   if (int rc = require_device()) return rc;
-  const void* fn = nullptr;
-  switch (kernel) {
-    case 0: fn = (const void*)nl_variant((unsigned)flags); break;
-    case 1: fn = (const void*)tl_variant((unsigned)flags); break;
-    case 2: fn = (const void*)ad_variant((unsigned)flags); break;
-    case 3: fn = (const void*)ad_reverse_variant((unsigned)flags); break;
-    case 4: fn = (const void*)tl_batch_variant((unsigned)flags % 64u, flags / 64); break;  // flags + 64 x directions
-    case 5: fn = (const void*)vjp_batch_variant((unsigned)flags % 64u, flags / 64); break;
-    case 6: fn = (const void*)tl_parjac_variant((unsigned)flags); break;
-    default: break;
-  }
+  const void* fn = kernel >= kFamNl && kernel <= kFamTlParjac ? variant_entry(kernel, (unsigned)flags) : nullptr;
   if (!fn) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: no such kernel variant in this build");
   Occupancy o;
   HIP_TRY(occupancy(fn, &o));
   *workgroups_per_cu = o.per_cu;
   return 0;
+}
+
+int cloudsc2_variant_built(int family, unsigned flags) {
+  if (family < 0 || family >= kFamCount) return fail(CLOUDSC2_EINVAL, "cloudsc2_variant_built: family must be 0..9");
+  return variant_entry(family, flags) ? 1 : 0;
 }
 
 int cloudsc2_pace_plan(long long workgroups, long long slots, int* whole_rounds, int* fast_first, int* nap_recip_q16) {

@@ -589,6 +589,26 @@ int cloudsc2_validate_format(const char* name, int ndim, const double stats[5], 
 /* The header line CLOUDSC2_ARRAY_STATE_VALIDATE prints first (cloudsc2_array_state_mod.F90:226-229). */
 int cloudsc2_validate_header(char* buf, int buflen);
 
+/* --------------------------------------------------------------------------------------------------
+ * Debug: what the tests use to see which kernel variant a launch ran (host code only; the -DC2_WAVE_TIMES diagnostic build adds
+ * cloudsc2_debug_wave_log, tools/wave_times.py).
+ *
+ * cloudsc2_variant_built  1 if the kernel variant exists in this build, 0 if not; CLOUDSC2_EINVAL for an unknown family.  No device
+ *   needed.  family 0..6 as cloudsc2_kernel_occupancy's `kernel` (0 NL, 1 TL, 2 AD both sweeps, 3 AD reverse sweep, 4 batched TL,
+ *   5 batched reverse sweep, 6 the parameter Jacobian's sweep), 7 TL with the parameter tangents, 8 reverse sweep with the parameter
+ *   adjoints, 9 the Taylor sweep; flags = the variant's C2F_* word (cloudsc2_column.hpp), for families 4 and 5 plus 64 x directions.
+ * cloudsc2_debug_launch_log  the sweep kernels the CALLING THREAD's launcher calls have enqueued since its last
+ *   cloudsc2_debug_launch_log_reset, in order: returns their number and writes the (family, word) pairs of the first min(max, 64) of
+ *   them.  The log keeps 64 entries; further launches are counted but not recorded, so a return value above 64 says that the record
+ *   is incomplete.  Only a launch the runtime accepted is logged: a launcher that returns an argument error or
+ *   CLOUDSC2_ENODEVICE logs nothing.  The log is a thread-local array of integers: it makes no device call, costs nothing
+ *   measurable, and is harmless during stream capture (what is logged then is the kernel captured).  max < 0, or max > 0 with a
+ *   NULL array: CLOUDSC2_EINVAL.  The small kernels around the sweeps (SATUR, the folds and sums) are not logged.
+ * ------------------------------------------------------------------------------------------------ */
+int cloudsc2_variant_built(int family, unsigned flags);
+void cloudsc2_debug_launch_log_reset(void);
+int cloudsc2_debug_launch_log(int* families, unsigned* flags, int max);
+
 #ifdef __cplusplus
 }
 #endif

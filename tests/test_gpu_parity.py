@@ -688,7 +688,11 @@ def test_math_mode_is_per_call():
 def test_offset_variants_give_the_same_bits(tmp_path):
     """The launchers pick 32-bit byte offsets (C2F_OFF32) whenever every buffer is below 4 GiB, i.e. in every other test
     of this file; CLOUDSC2_OFF32=0 forces the 64-bit variants that large states use.  Both must produce identical bits
-    (the choice is read once per process, hence the two child processes)."""
+    (the choice is read once per process, hence the two child processes).
+
+    This test covers NL, TL and AD with default flags.  tests/test_gpu_offset_variants.py holds every public sweep launcher, the
+    evaporation branch and both arithmetics to the same contract, reads from the launch log which variant each child really ran,
+    and launches over spans that really reach 4 GiB."""
     import os
     import subprocess
     import sys
