@@ -12,4 +12,4 @@ from .state import (Cloudsc2State, bytes_per_column, ceta_from_table, column_ran
                     state_from_table, synthetic_table, validate_l1)
 from .driver import (DeviceState, FlatFields, ResidentState, cloudsc_driver, cloudsc_driver_ad, cloudsc_driver_tl,  # noqa: F401
                      run_state)
-from .autograd import PARAM_NAMES, Cloudsc2Outputs, cloudsc2, param_jacobian, satur  # noqa: F401,E402
+from .autograd import PARAM_NAMES, Cloudsc2Outputs, NormalEquations, cloudsc2, param_jacobian, param_normal_equations, satur  # noqa: F401,E402

@@ -22,7 +22,8 @@ level over the op with ``params`` (so also ``jacfwd`` / ``jacrev``) raises ``Not
 direction at a time.  With the evaporation branch ``rpecons`` must not be 0.  The whole parameter Jacobian -- ``d out / d p`` for
 all four parameters, what a Gauss-Newton or Levenberg-Marquardt calibration needs -- is :func:`param_jacobian`: one
 ``cloudsc2_tl_launch_parjac``, the trajectory read once and no tangent plane read, every entry the ``torch.func.jvp`` of the op
-with a unit tangent on that parameter.
+with a unit tangent on that parameter.  Such a step itself needs only ``J^T W J`` and ``J^T W r``: :func:`param_normal_equations` forms
+them in one ``cloudsc2_parnormal_launch`` without the Jacobian ever being written.
 
 Batches.  Under ``torch.func.vmap`` the op distinguishes two cases.  Several tangents or cotangents over ONE state -- ``jacfwd``,
 ``jacrev``, ``vmap(jvp)``, ``vmap(vjp_fn)`` -- are one ``cloudsc2_tl_launch_batch`` / ``cloudsc2_vjp_launch_batch`` call: the
@@ -992,6 +993,109 @@ def param_jacobian(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = No
                                                         C.byref(_block("in", x, lay)), blocks, _stream(dev)))
         return {n: Cloudsc2Outputs(*(dy[n][k] if n in ran else torch.zeros(lay.shape(k), dtype=like.dtype, device=dev) for k in B.OUT_NAMES))
                 for n in pnames}
+
+
+NormalEquations = namedtuple("NormalEquations", "names jtj jtr")
+
+
+def normal_row(a: int, b: int) -> int:
+    """where ``cloudsc2_parnormal_launch`` leaves ``(J^T W J)[a][b]``: the upper triangle row by row in ``PARAM_NAMES`` order"""
+    a, b = min(a, b), max(a, b)
+    return a * len(PARAM_NAMES) - a * (a - 1) // 2 + (b - a)
+
+
+def check_residual(residual, weights, lay: Layout) -> tuple:
+    """The checks of :func:`param_normal_equations` on its residuals and weights that need no device; raises ``ValueError``.
+    ``residual``: a non-empty mapping of names of ``binding.OUT_NAMES`` (the observed outputs) to tensors of that output's shape in the
+    library's dtype; ``weights``: ``None`` or a mapping over a subset of ``residual``'s names with the same shapes (a missing name is
+    weight 1).  Returns ``(residual, weights)`` as dicts the launcher can take: it wants one block stride per layout group, the same
+    for residuals and weights, so a group that does not fit is copied contiguous (:func:`normalize`)."""
+    if not hasattr(residual, "keys") or (weights is not None and not hasattr(weights, "keys")):
+        raise ValueError(f"residual (and weights, if given) must map names of {B.OUT_NAMES} to tensors; got {type(residual)}, {type(weights)}")
+    if len(residual.keys()) == 0:
+        raise ValueError("residual is empty: at least one output must be observed")
+    weights = {} if weights is None else weights
+    for what, d in (("residual", residual), ("weights", weights)):
+        unknown = sorted(set(d.keys()) - set(B.OUT_NAMES), key=str)
+        if unknown:
+            raise ValueError(f"{what}: unknown name(s) {unknown}; the outputs are {B.OUT_NAMES}")
+    unobserved = sorted(set(weights.keys()) - set(residual.keys()))
+    if unobserved:
+        raise ValueError(f"weights given for output(s) {unobserved} that are not observed (no residual)")
+    dtype = B.torch_real()
+    for what, d in (("residual", residual), ("weights", weights)):
+        for n, t in d.items():
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what}[{n!r}] is not a tensor")
+            if t.dtype != dtype:
+                raise ValueError(f"{what}[{n!r}] has dtype {t.dtype}; this library works on {dtype} (CLOUDSC2_PRECISION)")
+            if tuple(t.shape) != lay.shape(n):
+                raise ValueError(f"{what}[{n!r}] has shape {tuple(t.shape)}, expected {lay.shape(n)}")
+    r = {n: residual[n] for n in B.OUT_NAMES if n in residual.keys()}
+    w = {n: weights[n] for n in B.OUT_NAMES if n in weights.keys()}
+    # (group keys other than "full" / "half": any common stride will do, not only that of contiguous arrays)
+    r = normalize(r, lay, {"r_" + g: tuple(n for n in names if n in r) for g, names in OUT_GROUPS.items()})
+    w = normalize(w, lay, {"w_" + g: tuple(n for n in names if n in w) for g, names in OUT_GROUPS.items()})
+    for names in OUT_GROUPS.values():
+        rn, wn = [n for n in names if n in r], [n for n in names if n in w]
+        if wn and _block_stride(r[rn[0]], lay, rn[0]) != _block_stride(w[wn[0]], lay, wn[0]):
+            for n in rn:
+                r[n] = r[n].contiguous()
+            for n in wn:
+                w[n] = w[n].contiguous()
+    return r, w
+
+
+def param_normal_equations(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, residual=None, weights=None,
+                           satur: bool = False, params=None) -> NormalEquations:
+    """The Gauss-Newton normal equations of the parameters at one state: ``NormalEquations(names, jtj, jtr)`` with ``jtj = J^T W J``
+    (``(len(names), len(names))`` float64, symmetric: the upper triangle mirrored bit for bit) and ``jtr = J^T W r``
+    (``(len(names),)`` float64) on the inputs' device, where ``J = d out / d names`` is :func:`param_jacobian`'s, ``r`` the
+    ``residual`` (model - observation; a mapping of the observed outputs' names to tensors of their shape) and ``W`` the diagonal
+    ``weights`` (``None``, or a mapping over a subset of ``residual``'s names; a missing name is weight 1).  The sums run over every
+    active column, level and observed output.  One ``cloudsc2_parnormal_launch``: the sensitivities never exist in memory, the sums
+    are formed in double in a fixed order and are the same bits from run to run.  ``names`` is ``PARAM_NAMES`` (``params=None``: at
+    ``prm``'s values) or the names of ``params`` in that order (a mapping as for ``cloudsc2(..., params=...)``, whose values override
+    a copy of ``prm``); the rules for ``params``, ``satur``, batched operands and ``rpecons`` are :func:`param_jacobian`'s.  Without
+    the evaporation branch every entry with ``rpecons`` is exactly zero.  The result is plain tensors without a graph.  With
+    ``params=None`` or CPU parameters the call can be captured in ``torch.cuda.graph`` after one eager call."""
+    names, groups = _names(satur)
+    lay = check_layout(inputs, prm, ngptot, satur=satur)
+    pnames = PARAM_NAMES if params is None else check_params(params, prm)
+    r, w = check_residual(residual, weights, lay)
+    dev = check_device([inputs[n] for n in names] + list(r.values()) + list(w.values()))
+    ps = () if params is None else tuple(params[n] for n in pnames)
+    if any(_batched_inside(t) for t in ps + tuple(inputs[n] for n in names) + tuple(r.values()) + tuple(w.values())):
+        raise NotImplementedError("param_normal_equations: batched (vmap-wrapped) operands are not supported; call it once per state")
+    for n, p in zip(pnames, ps):
+        if p.device.type != "cpu" and p.device != dev:
+            raise ValueError(f"params[{n!r}] is on {p.device}: parameters live on the CPU or on the inputs' device {dev}")
+    if any(p.device.type != "cpu" for p in ps) and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("param_normal_equations: the parameters' values are read on the host (they travel in the kernel-argument "
+                           "segment), which cannot happen for device tensors while the stream is capturing")
+    _prepare(dev)
+    prm = copy.copy(prm)  # (a ctypes structure: a copy of its bytes)
+    for n, p in zip(pnames, ps):
+        setattr(prm, n, _host_value(p))  # synchronises when the parameter lives on the device
+    if _evap(prm) and prm.rpecons == 0.0:
+        raise ValueError("param_normal_equations with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
+    with torch.no_grad():
+        if not pnames:
+            return NormalEquations((), torch.zeros((0, 0), dtype=torch.float64, device=dev), torch.zeros((0,), dtype=torch.float64, device=dev))
+        x = normalize({n: _raw(inputs[n]).detach() for n in names}, lay, groups)
+        r = {n: _raw(t).detach() for n, t in r.items()}
+        w = {n: _raw(t).detach() for n, t in w.items()}
+        work = torch.empty(B.NNORMAL * lay.nblocks * lay.nproma, dtype=torch.float64, device=dev)
+        normal = torch.empty(B.NNORMAL, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_parnormal_launch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                    C.byref(_block("in", x, lay)), C.byref(_block("out", r, lay)),
+                                                    C.byref(_block("out", w, lay)) if w else None, C.c_void_p(work.data_ptr()),
+                                                    C.c_void_p(normal.data_ptr()), _stream(dev)))
+        idx = [PARAM_NAMES.index(n) for n in pnames]
+        jtj = torch.stack([normal[normal_row(a, b)] for a in idx for b in idx]).reshape(len(idx), len(idx))
+        jtr = torch.stack([normal[B.NNORMAL - len(PARAM_NAMES) + a] for a in idx])
+        return NormalEquations(tuple(pnames), jtj, jtr)
 
 
 def satur(pap: torch.Tensor, t: torch.Tensor, prm: B.Params, ngptot: int | None = None, differentiable: bool = False) -> torch.Tensor:

@@ -77,6 +77,8 @@ IN_NAMES = ("paph", "pap", "q", "qsat", "t", "l", "i", "lude", "lu", "mfu", "mfd
 OUT_NAMES = ("tent", "tenq", "tenl", "teni", "clc", "fplsl", "fplsn", "fhpsl", "fhpsn", "covptot")
 # the tunable constants of struct cloudsc2_params the sweeps differentiate, in the order of CLOUDSC2_NPAR (include/cloudsc2_hip.h)
 PARAM_NAMES = ("rkconv", "rclcrit", "rlptrc", "rpecons")
+# doubles of cloudsc2_parnormal_launch's result (CLOUDSC2_NNORMAL): the upper triangle of J^T W J row by row, then J^T W r
+NNORMAL = len(PARAM_NAMES) * (len(PARAM_NAMES) + 1) // 2 + len(PARAM_NAMES)
 
 
 class Inputs(C.Structure):
@@ -162,6 +164,13 @@ def _load() -> C.CDLL:
     # the sensitivities of the outputs to all parameters in one sweep: (Outputs * CLOUDSC2_NPAR)(...), no tangent planes
     lib.cloudsc2_tl_launch_parjac.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p]
     lib.cloudsc2_tl_launch_parjac.restype = C.c_int
+    # the Gauss-Newton normal equations of the parameters in one sweep: residual and weight blocks (NULL fields: not observed / weight 1),
+    # work / normal are device pointers
+    lib.cloudsc2_parnormal_work_doubles.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_longlong)]
+    lib.cloudsc2_parnormal_work_doubles.restype = C.c_int
+    lib.cloudsc2_parnormal_launch.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs),
+                                              C.POINTER(Outputs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cloudsc2_parnormal_launch.restype = C.c_int
     # several directions over one trajectory: arrays of argument blocks, (Inputs * K)(...) / (Outputs * K)(...)
     lib.cloudsc2_batch_max.argtypes = []
     lib.cloudsc2_batch_max.restype = C.c_int
@@ -263,7 +272,7 @@ lib = _load()
 # every symbol include/cloudsc2_hip.h declares
 EXPORTED = ("cloudsc2_params_default", "cloudsc2_last_error", "cloudsc2_device_available", "cloudsc2_current_device", "cloudsc2_set_math_mode",
             "cloudsc2_get_math_mode", "cloudsc2_real_bytes", "cloudsc2_nl_launch",
-            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch_parjac", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
+            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch_parjac", "cloudsc2_parnormal_work_doubles", "cloudsc2_parnormal_launch", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
             "cloudsc2_ad_launch_forward", "cloudsc2_ad_launch_reverse", "cloudsc2_vjp_launch", "cloudsc2_batch_max", "cloudsc2_tl_launch_batch", "cloudsc2_vjp_launch_batch", "cloudsc2_ad_launch_reverse_norms", "cloudsc2_taylor_sums_launch",
             "cloudsc2_taylor_sweep_work_doubles", "cloudsc2_taylor_sweep_launch", "cloudsc2_adjoint_norms_launch", "cloudsc2_nl_run", "cloudsc2_tl_taylor_run", "cloudsc2_ad_symmetry_run",
             "cloudsc2_release_workspace", "cloudsc2_taylor_verdict", "cloudsc2_adjoint_verdict",

@@ -1334,6 +1334,199 @@ C2_HD void tl_parjac_column(long long gcol, TlParJacArgsP a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The Gauss-Newton normal equations of the parameters in one sweep: H = J^T W J and g = J^T W r (cloudsc2_parnormal_launch)
+// ---------------------------------------------------------------------------------------------------------
+// A Gauss-Newton or Levenberg-Marquardt step needs the 4 x 4 matrix H and the 4-vector g, never J = d out / d p itself.  This sweep
+// is tl_parjac_column with the stores replaced by sums: the NP sensitivities of a level stay in registers, the level's residual r
+// (model - observation) and diagonal weight w of every observed output are read, and the lane accumulates, in double in both
+// builds, H[a][b] += (w J_a) J_b for a <= b and g[a] += (w J_a) r.  The order of every sum is fixed -- levels outermost, outputs in
+// the order of struct cloudsc2_outputs -- and a lane's sums go to row `normal_row` of `work`, which a second kernel folds over the
+// columns in a fixed order (par_fold_kernel's): the same bits from run to run, no atomics.
+// An output is observed when its residual pointer is not NULL; a NULL weight pointer is weight 1.  Both are wave-uniform run-time
+// branches on the argument block, not variants.  clc and covptot depend on none of the parameters: their sensitivities are exact
+// zeros, so their planes are not read at all.  Half level 0 of the four fluxes is the zero flux of the model top (store_top): its
+// sensitivity is zero and its residual and weight are not read either.
+constexpr int normal_sums(int np) { return np * (np + 1) / 2 + np; }
+// row of H[a][b] (a <= b) and of g[a] in `work` and in the result: the upper triangle of the PAR_COUNT x PAR_COUNT matrix row by row,
+// then g -- whatever the sweep's direction count, so that without the evaporation branch the rows with rpecons are simply not written
+constexpr int normal_row_h(int a, int b) { return a * PAR_COUNT - a * (a - 1) / 2 + (b - a); }
+constexpr int normal_row_g(int a) { return PAR_COUNT * (PAR_COUNT + 1) / 2 + a; }
+constexpr int kNormalObs = 8;  // the outputs that depend on a parameter: tent tenq tenl teni fplsl fplsn fhpsl fhpsn
+
+// (par from the launch's direction count on is not read; resid / weight: read only, NULL members as above; sr: their block strides)
+struct ParNormalArgs {
+  Consts c; Geom g; Strides s, sr; InPtrs in; OutPtrs resid, weight; ParLin par[kBatchMax]; const LevelTab* tab;
+  double* work;  // (normal_sums(PAR_COUNT), ncols_pad) doubles: every active lane's sums (the padded tail is not written)
+};
+typedef const C2_CONST_AS ParNormalArgs* ParNormalArgsP;
+
+// residual and weight of one level, in the order of kNormalObs; an unobserved output's pair is not read
+struct ObsLevel {
+  real_t r[kNormalObs], w[kNormalObs];
+};
+C2_HD void load_obs_one(const real_t* r, const real_t* w, long long i, real_t& rv, real_t& wv) {
+  rv = RC(0.0);
+  wv = RC(1.0);
+  if (r) {
+    rv = ldg(r, i);
+    if (w) wv = ldg(w, i);
+  }
+}
+C2_HD void load_obs(ParNormalArgsP ap, const LaneOff& o, int nproma, int jk, ObsLevel& v) {
+  const OutPtrs r = ap->resid, w = ap->weight;
+  const long long d = level_off(0LL, jk, nproma), d1 = d + row_off(0LL, nproma);
+  load_obs_one(r.tent, w.tent, o.loc + d, v.r[0], v.w[0]);
+  load_obs_one(r.tenq, w.tenq, o.loc + d, v.r[1], v.w[1]);
+  load_obs_one(r.tenl, w.tenl, o.loc + d, v.r[2], v.w[2]);
+  load_obs_one(r.teni, w.teni, o.loc + d, v.r[3], v.w[3]);
+  load_obs_one(r.fplsl, w.fplsl, o.half + d1, v.r[4], v.w[4]);
+  load_obs_one(r.fplsn, w.fplsn, o.half + d1, v.r[5], v.w[5]);
+  load_obs_one(r.fhpsl, w.fhpsl, o.half + d1, v.r[6], v.w[6]);
+  load_obs_one(r.fhpsn, w.fhpsn, o.half + d1, v.r[7], v.w[7]);
+}
+
+// one lane's sums: the upper triangle of its NP x NP block row by row, and g
+template <int NP>
+struct NormalAcc {
+  double h[NP * (NP + 1) / 2], g[NP];
+};
+// one output of one level: j[a] = its sensitivity to parameter a.  The operands are converted before the products (fp32 build).
+template <int NP>
+C2_HD void normal_add(NormalAcc<NP>& acc, const real_t (&j)[NP], real_t r, real_t w) {
+  double jd[NP];
+#pragma unroll
+  for (int a = 0; a < NP; ++a) jd[a] = (double)j[a];
+  const double rd = (double)r, wd = (double)w;
+#pragma unroll
+  for (int a = 0; a < NP; ++a) {
+    const double wj = wd * jd[a];
+#pragma unroll
+    for (int b = a; b < NP; ++b) acc.h[a * NP - a * (a - 1) / 2 + (b - a)] += wj * jd[b];
+    acc.g[a] += wj * rd;
+  }
+}
+
+// The sensitivities of one direction, opaque: the empty asm statements are ordered among themselves, so a direction's eight results
+// exist before the next direction's inputs are laundered.  Without this the compiler interleaves the NP straight lines, which have no
+// store between them here, and holds their intermediate values all at once (fp64: scratch in six of the eight forms).
+C2_HD void launder_sens(LevelOut& v) {
+  C2_LAUNDER_V(v.tent); C2_LAUNDER_V(v.tenq); C2_LAUNDER_V(v.tenl); C2_LAUNDER_V(v.teni);
+  C2_LAUNDER_V(v.fplsl); C2_LAUNDER_V(v.fplsn); C2_LAUNDER_V(v.fhpsl); C2_LAUNDER_V(v.fhpsn);
+}
+
+// F: C2F_QSAT (otherwise the trajectory's SATUR is evaluated in the sweep) | C2F_PRECISE | C2F_EVAP; 64-bit offsets always
+template <unsigned F>
+C2_HD void parnormal_column(long long gcol, ParNormalArgsP a) {
+  constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0;
+  constexpr int NP = parjac_directions(F);
+  static_assert(!(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP)), "flags of the normal-equations sweep: QSAT, PRECISE, EVAP");
+  LaneOff o, orw; bool active;
+  if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
+  lane_setup(&a->g, &a->sr, gcol, orw, active);
+  if (!active) return;
+  const int nlev = a->g.nlev, nproma = a->g.nproma;
+  LevelTabP tab = (LevelTabP)a->tab;
+  ConstsP c = C2_CONSTS(a);
+  InPtrsP in = &a->in;
+
+  // once per column, not once per direction: the tropopause pre-scan, the critical-humidity setup, the lane offsets, the loads
+  real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->g, RC(0.0));
+  RhCrit rh;
+  rhcrit_setup(ztrpaus, rh);
+  real_t paph_surf = RC(0.0);
+  if (EVAP) paph_surf = in->paph[o.half + (long long)nlev * nproma];
+  // which outputs are observed (wave-uniform: the pointers are the argument block's)
+  unsigned obs;
+  {
+    const OutPtrs r = a->resid;
+    obs = (r.tent ? 1u : 0u) | (r.tenq ? 2u : 0u) | (r.tenl ? 4u : 0u) | (r.teni ? 8u : 0u) | (r.fplsl ? 16u : 0u) |
+          (r.fplsn ? 32u : 0u) | (r.fhpsl ? 64u : 0u) | (r.fhpsn ? 128u : 0u);
+  }
+
+  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
+  Carry dcy[NP];
+  NormalAcc<NP> acc;
+#pragma unroll
+  for (int b = 0; b < NP; ++b) {
+    dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0);
+    acc.g[b] = 0.0;
+  }
+#pragma unroll
+  for (int i = 0; i < NP * (NP + 1) / 2; ++i) acc.h[i] = 0.0;
+  RawLevel cur, nxt;
+  real_t paph_k = in->paph[o.half];
+  load_level<HAS_QSAT>(in, o, nproma, nlev, 0, cur);
+
+  // The trajectory inputs of level jk+1 are requested at the top of level jk, as in tl_parjac_column, and with them the residuals and
+  // weights of level jk itself: they are used after the level's NP directions and are in flight under that arithmetic.
+  for (int jk = 0; jk < nlev; ++jk) {
+    const bool last = (jk == nlev - 1);
+    ParNormalArgsP ap = a;
+    C2_LAUNDER(ap);
+    nxt = cur;
+    if (!last) load_level<HAS_QSAT>(&ap->in, o, nproma, nlev, jk + 1, nxt);
+    ObsLevel ob;
+    load_obs(ap, orw, nproma, jk, ob);
+    if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);  // (once per level: every direction gets its own opaque copy)
+
+    LevelCst k;
+    level_cst(tab, jk, last, k);
+    LevelIn x;
+    make_level_in(cur, paph_k, paph_surf, x);
+    Carry cy_out = cy;
+    LevelOut dlo[NP];
+#pragma unroll
+    for (int b = 0; b < NP; ++b) {
+      // this direction's own straight line (launder_level says why): every direction leaves the same trajectory carry
+      LevelIn xb = x;
+      LevelCst kb = k;
+      RhCrit rhb = rh;
+      cy_out = cy;
+      launder_level(xb, kb, cy_out);
+      C2_LAUNDER_V(xb.paph_surf); C2_LAUNDER_V(rhb.zeta3); C2_LAUNDER_V(rhb.zrh2); C2_LAUNDER_V(rhb.zdeta1);
+      ConstsP cb = c;  // (and its own view of the constants: a product of two of them is shared otherwise)
+      C2_LAUNDER(cb);
+      LevelTraj tr;
+      LevelOut lo;
+      level_forward<P, EVAP>(cb, kb, rhb, xb, cy_out, tr, lo);
+      LevelIn dx;
+      zero_level_in<EVAP>(dx);
+      C2_LAUNDER(ap);
+      level_tl<true>(cb, kb, xb, tr, dx, dcy[b], dlo[b], &ap->par[b]);
+      launder_sens(dlo[b]);
+    }
+    // the level's contributions, output by output in the order of struct cloudsc2_outputs (clc and covptot: exact zeros, skipped)
+#define C2_NORMAL_ADD(bit, field)                          \
+  if (obs & (1u << (bit))) {                               \
+    real_t j[NP];                                          \
+    _Pragma("unroll") for (int b = 0; b < NP; ++b) j[b] = dlo[b].field; \
+    normal_add<NP>(acc, j, ob.r[bit], ob.w[bit]);          \
+  }
+    C2_NORMAL_ADD(0, tent)
+    C2_NORMAL_ADD(1, tenq)
+    C2_NORMAL_ADD(2, tenl)
+    C2_NORMAL_ADD(3, teni)
+    C2_NORMAL_ADD(4, fplsl)
+    C2_NORMAL_ADD(5, fplsn)
+    C2_NORMAL_ADD(6, fhpsl)
+    C2_NORMAL_ADD(7, fhpsn)
+#undef C2_NORMAL_ADD
+    cy = cy_out;
+    paph_k = cur.paph_k1;
+    cur = nxt;
+  }
+  // the lane's sums: consecutive lanes, consecutive doubles of each row (gcol < ngptot <= ncols_pad)
+  double* work = a->work;
+  const long long np = a->g.ncols_pad;
+#pragma unroll
+  for (int ia = 0; ia < NP; ++ia) {
+#pragma unroll
+    for (int ib = ia; ib < NP; ++ib) work[normal_row_h(ia, ib) * np + gcol] = acc.h[ia * NP - ia * (ia - 1) / 2 + (ib - ia)];
+    work[normal_row_g(ia) * np + gcol] = acc.g[ia];
+  }
+}
+
 template <class OT>
 C2_HD void load_out_adjoint(OutPtrsP pp, const LaneOffT<OT>& oa, OT d, OT d1, LevelOut& ya) {
   const OutPtrs pa = *pp;

@@ -20,6 +20,7 @@
 #include "cloudsc2_kern_tl_par.hip"
 #include "cloudsc2_kern_vjp_par.hip"
 #include "cloudsc2_kern_tl_parjac.hip"
+#include "cloudsc2_kern_parnormal.hip"
 #endif
 
 using namespace cloudsc2;
@@ -28,7 +29,7 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------------------
 // kernels: the sweeps' __global__ wrappers and their variant tables are cloudsc2_sweep_kernels.hpp + the family units
-// cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
+// cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
 // ---------------------------------------------------------------------------------------------------------
 template <bool P>
 __global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
@@ -43,8 +44,7 @@ __global__ void __launch_bounds__(kBlock) satur_lin_kernel(SaturLinArgs args) {
 // parameter) folded into one double in a fixed order -- thread t adds columns t, t + 1024, ... in turn, then a fixed tree over the
 // threads -- so the result is the same bits from run to run.  Columns from ngptot on (the padded tail) were not written and are not read.
 constexpr int kParFoldBlock = 1024;
-__global__ void __launch_bounds__(kParFoldBlock)
-par_fold_kernel(const double* __restrict__ work, long long ncols_pad, long long ngptot, double* __restrict__ par_adj) {
+__device__ __forceinline__ void fold_row(const double* __restrict__ work, long long ncols_pad, long long ngptot, double* __restrict__ sums) {
   __shared__ double red[kParFoldBlock];
   const double* row = work + (long long)blockIdx.x * ncols_pad;
   double v = 0.0;
@@ -55,7 +55,21 @@ par_fold_kernel(const double* __restrict__ work, long long ncols_pad, long long 
     if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
     __syncthreads();
   }
-  if (threadIdx.x == 0) par_adj[blockIdx.x] = red[0];
+  if (threadIdx.x == 0) sums[blockIdx.x] = red[0];
+}
+__global__ void __launch_bounds__(kParFoldBlock)
+par_fold_kernel(const double* __restrict__ work, long long ncols_pad, long long ngptot, double* __restrict__ par_adj) {
+  fold_row(work, ncols_pad, ngptot, par_adj);
+}
+// Its sibling for a workspace some of whose rows were not written (cloudsc2_parnormal_launch without the evaporation branch: the rows
+// with rpecons): a row whose bit is set in `unwritten` is not read and its sum is stored as the exact zero it stands for.
+__global__ void __launch_bounds__(kParFoldBlock)
+par_fold_rows_kernel(const double* __restrict__ work, long long ncols_pad, long long ngptot, unsigned unwritten, double* __restrict__ sums) {
+  if ((unwritten >> blockIdx.x) & 1u) {  // (block-uniform)
+    if (threadIdx.x == 0) sums[blockIdx.x] = 0.0;
+    return;
+  }
+  fold_row(work, ncols_pad, ngptot, sums);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -796,6 +810,69 @@ int tl_parjac_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
   return launch_variant(kFamTlParjac, w.f, fn, args, w.g.ncols_pad, (hipStream_t)stream);
 }
 
+// The Gauss-Newton normal equations of the parameters: J^T W J and J^T W r over every active column, level and observed output, without
+// J ever existing in memory (parnormal_column sums each column in registers; the fold of cloudsc2_vjp_launch_par adds the columns).
+// Two kernel nodes, both launched directly: this is not a sweep family (no family number, no pacing, no launch-log entry).
+static_assert(CLOUDSC2_NNORMAL == normal_sums(PAR_COUNT) && CLOUDSC2_NNORMAL <= 32, "rows of the workspace: one bit each in the fold's mask");
+int parnormal_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                          const cloudsc2_outputs* resid, const cloudsc2_outputs* weight, double* work, double* normal, void* stream) {
+  // (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
+  if (!prm || !traj_in || !resid || !work || !normal) return fail(CLOUDSC2_EINVAL, "NULL argument block, workspace or result");
+  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "normal equations: CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
+  const bool evap = prm->levapls2 || prm->ldrain1d;
+  if (evap && prm->rpecons == 0.0) return fail(CLOUDSC2_EINVAL, "parameter derivative with the evaporation branch: rpecons must not be 0");
+  Sweep w;
+  int rc = resolve_in(*traj_in, false, w.s, w.in);
+  if (rc) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  const cloudsc2_outputs none = {};
+  const cloudsc2_outputs& wt = weight ? *weight : none;
+  const cloudsc2_field* rf[10] = {&resid->tent, &resid->tenq, &resid->tenl, &resid->teni, &resid->clc,
+                                  &resid->fplsl, &resid->fplsn, &resid->fhpsl, &resid->fhpsn, &resid->covptot};
+  const cloudsc2_field* wf[10] = {&wt.tent, &wt.tenq, &wt.tenl, &wt.teni, &wt.clc, &wt.fplsl, &wt.fplsn, &wt.fhpsl, &wt.fhpsn, &wt.covptot};
+  const int group[10] = {0, 0, 0, 0, 1, 2, 2, 2, 2, 1};  // loc, full, half
+  bool weighted[3] = {false, false, false};
+  int nobs = 0;
+  for (int i = 0; i < 10; ++i) {
+    if (rf[i]->ptr) ++nobs;
+    else if (wf[i]->ptr) return fail(CLOUDSC2_EINVAL, "normal equations: a weight is given for an output that is not observed (its residual is NULL)");
+    if (wf[i]->ptr) weighted[group[i]] = true;
+  }
+  if (!nobs) return fail(CLOUDSC2_EINVAL, "normal equations: no output is observed (every residual field is NULL)");
+  ParNormalArgs args;
+  Strides sr = {0, 0, 0, 0, 0}, sw = {0, 0, 0, 0, 0};
+  if ((rc = resolve_out(*resid, false, sr, args.resid)) || (rc = resolve_out(wt, false, sw, args.weight))) return rc;
+  if ((weighted[0] && sw.loc != sr.loc) || (weighted[1] && sw.full != sr.full) || (weighted[2] && sw.half != sr.half))
+    return fail(CLOUDSC2_EINVAL, "normal equations: residuals and weights must have the same block stride per layout group");
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sr.full, sr.half, sr.loc}))) return rc;
+  const unsigned f = w.f & ~C2F_OFF32;  // (64-bit offsets always: a 32-bit form is not built)
+  args.c = w.c; args.g = w.g; args.s = w.s; args.sr = sr; args.in = w.in; args.tab = w.tab; args.work = work;
+  const int np = evap ? (int)PAR_COUNT : (int)PAR_COUNT - 1;
+  for (int b = 0; b < kBatchMax; ++b) {  // (the sets from `np` on are not read: valid contents all the same)
+    double e[PAR_COUNT] = {};
+    e[b < np ? b : 0] = 1.0;
+    args.par[b] = make_parlin(w.c, e);
+  }
+  const KernelFn<ParNormalArgs> fn = parnormal_variant(f);
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  schedule(args.g, nullptr, false, nullptr);
+  const hipStream_t st = (hipStream_t)stream;
+  const long long n = w.g.ncols_pad;
+  void* argv[] = {&args};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(n, kBlock)), dim3(kBlock), argv, 0, st));
+  if (evap) {
+    hipLaunchKernelGGL(par_fold_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)w.g.ngptot, normal);
+  } else {  // the rows with rpecons were not written: not read, stored as zeros
+    unsigned unwritten = 1u << normal_row_g(PAR_RPECONS);
+    for (int a = 0; a < PAR_COUNT; ++a) unwritten |= 1u << normal_row_h(a, PAR_RPECONS);
+    hipLaunchKernelGGL(par_fold_rows_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)w.g.ngptot,
+                       unwritten, normal);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 int vjp_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
                           const cloudsc2_outputs* traj_out, int nbatch, const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                           const cloudsc2_real* scratch, void* stream) {
@@ -1102,6 +1179,18 @@ int cloudsc2_vjp_launch_batch(const cloudsc2_params* prm, double ptsphy, int npr
 int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* pert_out, void* stream) {
   return tl_parjac_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, pert_out, stream);
+}
+
+int cloudsc2_parnormal_work_doubles(int nproma, int ngptot, long long* n) {
+  if (nproma < 1 || ngptot < 1 || !n) return fail(CLOUDSC2_EINVAL, "nproma >= 1, ngptot >= 1 and a result pointer required");
+  *n = (long long)CLOUDSC2_NNORMAL * ((((long long)ngptot + nproma - 1) / nproma) * nproma);
+  return 0;
+}
+
+int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* resid, const cloudsc2_outputs* weight,
+                              double* work, double* normal, void* stream) {
+  return parnormal_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, resid, weight, work, normal, stream);
 }
 
 int cloudsc2_ad_launch_reverse_norms(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,

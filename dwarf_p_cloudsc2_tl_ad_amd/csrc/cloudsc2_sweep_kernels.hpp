@@ -1,6 +1,6 @@
 // cloudsc2_sweep_kernels.hpp -- the __global__ wrappers of the column sweeps (NL, TL, AD, the Taylor test's lambda sweep), their
 // compile-time variant tables and what they share.  The sweeps are built as one translation unit per kernel family so that an edit to
-// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac}.hip, each of which
+// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal}.hip, each of which
 // instantiates its table and exports it through one accessor (nl_variant(F) ...); the host units are listed in cloudsc2_host.hpp.
 // -DC2_SINGLE_TU puts the sweeps and their launchers into ONE code object again (cloudsc2_launch.hip then includes the family files):
 // the experiment builds of `make variant`, `make asm`, `make resources` and the -DC2_WAVE_TIMES diagnostic, whose log pointer is a
@@ -158,6 +158,14 @@ __global__ void __launch_bounds__(kBlock, 1) tl_parjac_kernel(TlParJacArgs args)
 }
 constexpr bool parjac_variant_valid(unsigned f) { return (f & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32)) == 0; }
 
+// The normal equations of the parameters in one sweep (parnormal_column; unit cloudsc2_kern_parnormal.hip): tl_parjac_kernel's launch
+// bounds.  Flag words: QSAT, PRECISE, EVAP -- 8 kernels per precision, 64-bit offsets.  Not a sweep family: it has no family number, is
+// not paced and is not in the launch log; cloudsc2_parnormal_launch launches it directly, like the fold that follows it.
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) parnormal_kernel(ParNormalArgs args) {
+  C2_KERNEL_BODY((parnormal_column<F>(global_column(), kernarg<ParNormalArgs>())));
+}
+
 // The ten perturbed NL runs of the Taylor test in one sweep, the lambdas on the lanes (taylor_column): the grid is over THREADS,
 // 64 per kTaylorCols columns.  A wave reads 6 columns = 48 bytes of every 128-byte line it touches, so two or three consecutive
 // waves share each line -- the one sweep whose workgroups share data.  Blocks are dealt round-robin over the 8 XCDs (b and b + 8
@@ -195,5 +203,6 @@ KernelFn<AdParArgs> vjp_par_variant(unsigned f);
 KernelFn<TlBatchArgs> tl_batch_variant(unsigned f, int directions);
 KernelFn<VjpBatchArgs> vjp_batch_variant(unsigned f, int directions);
 KernelFn<TlParJacArgs> tl_parjac_variant(unsigned f);
+KernelFn<ParNormalArgs> parnormal_variant(unsigned f);
 
 }  // namespace cloudsc2

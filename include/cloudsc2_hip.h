@@ -374,6 +374,33 @@ int cloudsc2_vjp_launch_par(const cloudsc2_params* prm, double ptsphy, int nprom
 int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* pert_out /* [CLOUDSC2_NPAR] */, void* stream);
 
+/* The Gauss-Newton normal equations of the four parameters in one sweep.  A Gauss-Newton or Levenberg-Marquardt step needs
+ * H = J^T W J (CLOUDSC2_NPAR x CLOUDSC2_NPAR) and g = J^T W r, never J = d out / d p itself: r = model - observation, W a diagonal weight,
+ * the sums over every active column, level and observed output.  cloudsc2_parnormal_launch forms them without a sensitivity plane
+ * ever being written: the sweep of cloudsc2_tl_launch_parjac keeps a level's sensitivities in registers, reads that level's residuals
+ * and weights and sums the products per column in double (both builds); a second kernel folds the columns' sums in a fixed order
+ * (that of cloudsc2_vjp_launch_par): no atomics, the same bits from run to run.  Bytes per column (NLEV 137, fp64, ten outputs observed
+ * and weighted): 17 544 + 2 x 10 992 + 14 x 8 = 39 640, where cloudsc2_tl_launch_parjac alone writes 17 544 + 4 x 10 992 = 61 512.
+ *   traj_in  as for cloudsc2_tl_launch_parjac (qsat may be NULL: SATUR evaluated in the sweep).
+ *   resid    read only.  A field with a NULL pointer is an output that is not observed; at least one must be given.
+ *   weight   read only; may be NULL.  A NULL field is weight 1; a field given for an output that is not observed is an error.
+ *            clc and covptot depend on none of the parameters: observed, they contribute exact zeros and their planes are not read.
+ *            Half level 0 of the four fluxes (the zero flux at the model top) is not read either, nor any value of a padded tail column.
+ *   work     device, cloudsc2_parnormal_work_doubles() doubles (CLOUDSC2_NNORMAL x the padded column count), the caller's.
+ *   normal   device, CLOUDSC2_NNORMAL doubles, assigned: the upper triangle of H row by row in CLOUDSC2_NPAR order (10), then g (4).
+ *   Without LEVAPLS2 .OR. LDRAIN1D three directions run and every entry that involves rpecons is assigned exactly 0.0.
+ * CLOUDSC2_EINVAL (reported before the device is looked for): a NULL prm, traj_in, resid, work or normal; prm->lphylin = 0; the evaporation
+ * branch with rpecons = 0; no observed output; a weight for an unobserved output; residual or weight fields whose block strides per
+ * layout group differ, among themselves or from each other; bad shapes.  Without a device: CLOUDSC2_ENODEVICE.
+ * It takes the caller's stream, neither allocates nor synchronises (apart from the CETA table of a grid's first use) and is two plain
+ * kernel nodes in a chain under stream capture.  It is not paced, has 64-bit offsets only, and is no kernel family of
+ * cloudsc2_variant_built / cloudsc2_kernel_occupancy / the launch log. */
+#define CLOUDSC2_NNORMAL (CLOUDSC2_NPAR * (CLOUDSC2_NPAR + 1) / 2 + CLOUDSC2_NPAR) /* 14 */
+int cloudsc2_parnormal_work_doubles(int nproma, int ngptot, long long* n);
+int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* resid, const cloudsc2_outputs* weight,
+                              double* work, double* normal /* device, [CLOUDSC2_NNORMAL] */, void* stream);
+
 /* Several tangents or cotangents over ONE trajectory -- a Jacobian block, a singular-vector iteration, an ensemble of perturbations.
  * cloudsc2_tl_launch_batch replaces nbatch calls of cloudsc2_tl_launch without trajectory stores (traj_out all NULL),
  * cloudsc2_vjp_launch_batch nbatch calls of cloudsc2_vjp_launch, over the same traj_in: every direction's results are the bits those
