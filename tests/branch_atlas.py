@@ -1,0 +1,469 @@
+"""Branch atlas (test helpers): the census of level_forward's branch outcomes, an atmosphere that reaches every one of them, and
+the per-class error metric with bounds measured on the reference alone.
+
+* ``census``       one signature word per cell from tests/hostcheck/hostcheck_census.hip (the predicates LevelTraj records);
+* ``atlas_table``  random_table plus directed column groups;
+* ``Classes``      class = the active cells that share one outcome of one signature bit; threshold cells taken out;
+* ``Bounds``       floor(f, c): the reference's own response to a one-ulp perturbation of every input, per field and class;
+                   K = the accepted whole-field tolerance over the largest whole-field floor; bound(f, c) = K floor(f, c), never
+                   looser than the whole-field bound.
+
+Nothing here is imported by the package.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+
+from tests.util import B, HOSTCHECK_DIR, ROOT, c2, hfld, host_traj_blocks, hostcheck, increments_of, make_params, refcall, set_lib_params
+
+NL_TOL = 1e-12    # the whole-field bounds the project accepts (tests/test_gpu_parity.py)
+TLAD_TOL = 1e-11
+MIN_CELLS = 32    # every class, before and after the exclusion of threshold cells
+MAX_EXCLUDED = 0.05
+
+CENSUS_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_census_sp.so" if B.SINGLE else "libhostcheck_census.so")
+
+# name -> bit of the signature word (hostcheck_census.hip); "regime" is the two-bit field at 4
+BITS = {"cold": 0, "esdp_clip": 1, "qlim_is_qs": 2, "below_rtice": 3, "llo1": 6, "llo3": 7, "newmax": 8, "melt": 9, "warm2": 10,
+        "melt_all": 11, "cloudy": 12, "frz1": 13, "llo2": 14, "dpr_clip": 15, "warm_adj": 16, "a_clip0": 17, "a_clip1": 18,
+        "dq_pos": 19, "frz2": 20, "last": 21, "partial_melt": 22, "regcl_capped": 23, "a_clip0&dq_pos": 24, "a_clip1&dq_pos": 25,
+        "esdp_clip&cloud": 26, "llo2&dpr_clip": 27}
+SIG_ACTIVE = np.uint32(1 << 31)
+# a bit that is only defined where another holds: its two outcomes are classes inside that domain (level_forward sets warm2 and
+# melt_all under `melt`, dpr_clip under `llo2`; regcl_factor is evaluated in the partial-cover regime only)
+DOMAIN = {"warm2": "melt", "melt_all": "melt", "partial_melt": "melt", "dpr_clip": "llo2", "regcl_capped": "regime=2"}
+# bits that do not exist without the evaporation branch: with EVAP = false t.llo2 is a compile-time false (level_forward stage J)
+EVAP_ONLY = ("llo2", "dpr_clip", "llo2&dpr_clip")
+# `last` is true on the bottom level only: it cannot be spread over two levels
+ONE_LEVEL = ("last=1",)
+
+
+def build_census() -> str:
+    src = os.path.join(HOSTCHECK_DIR, "hostcheck_census.hip")
+    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
+        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
+    if (not os.path.exists(CENSUS_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(CENSUS_LIB) for d in deps):
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
+                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", CENSUS_LIB, src])
+    return CENSUS_LIB
+
+
+_lib = None
+
+
+def census_lib():
+    global _lib
+    if _lib is None:
+        lib = C.CDLL(build_census())
+        lib.hostcheck_census.argtypes = [C.POINTER(B.Params), C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs),
+                                         C.POINTER(B.Outputs), C.c_void_p]
+        lib.hostcheck_census.restype = C.c_longlong
+        lib.hostcheck_satur.argtypes = [C.POINTER(B.Params), C.c_int, C.c_int, C.c_int, B.Field, B.Field, B.Field]
+        _lib = lib
+    return _lib
+
+
+def census(prm, st, qsat: np.ndarray | None = None, precise: int = 0):
+    """Signature words (NBLOCKS, NLEV, NPROMA) of a state (0 in the padded tail), the state the walk left (its outputs are the
+    walk's LevelOut) and the number of cells where dpr_clip and reset differ."""
+    lib = census_lib()
+    got = st.copy()
+    i, o = host_traj_blocks(got, qsat)
+    sig = np.zeros((st.nblocks, st.nlev, st.nproma), dtype=np.uint32)
+    lib.hostcheck_set_precise(int(precise))
+    try:
+        differ = lib.hostcheck_census(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(i), C.byref(o), sig.ctypes.data)
+    finally:
+        lib.hostcheck_set_precise(0)
+    assert differ >= 0
+    return sig, got, int(differ)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the atmosphere
+# ---------------------------------------------------------------------------------------------------------------------
+def atlas_table(nlev: int, ncol: int, seed: int) -> dict:
+    """random_table plus directed groups of columns, interleaved (column j belongs to group j mod 8) so that every group has
+    columns in every NPROMA block:
+
+    0 A   hot, thin air aloft (PAP < 2000 Pa, +20..120 K), half of those cells moist with a little cloud water: the saturation
+          pressure over p passes the 0.5 cap in stage A (esdp_clip) and in the saturation adjustment (a_clip), with condensation;
+    1 A'  as A, warmer still and always moist;
+    2 B   +5..20 K at all levels: a deep melting layer (warm2, melt_all), and F on top of it;
+    3 B'  first-guess temperature a fraction of a kelvin above RTT + 2 through the layer where it lies between RTT and 292 K: the
+          snow from above melts a little on each of those levels (partial melt);
+    4 C   PQ x 1.0..1.6: overcast and supersaturated cells;
+    5 E   total water set just below saturation in the troposphere: partial cover with regcl_factor under its cap;
+    6 F   below the 262 K level the first-guess temperature alternates between 271..272.5 K and 279..289 K from level to level: the
+          cold levels make snow, the warm ones melt all of it (melt_all, far more often than the residues that a complete
+          evaporation leaves in the snow flux, which are threshold cells);
+    7 D   the unchanged random_table.
+    """
+    tab = c2.random_table(nlev, ncol, seed=seed)
+    rng = np.random.default_rng(seed + 1000)
+    grp = np.arange(ncol) % 8
+    u = lambda a, b, shape=(nlev, ncol): rng.uniform(a, b, size=shape)  # noqa: E731
+    pap = tab["PAP"]
+    col = lambda g: np.broadcast_to(grp == g, (nlev, ncol))  # noqa: E731
+
+    top = pap < 2000.0
+    hot = top & (col(0) | col(1))
+    tab["PT"] = np.where(hot, tab["PT"] + np.where(col(1), u(60.0, 140.0), u(20.0, 120.0)), tab["PT"])
+    wet = hot & (col(1) | (u(0.0, 1.0) < 0.5))
+    tab["PQ"] = np.where(wet, u(0.3, 0.95), tab["PQ"])
+    tab["PCLV_QL"] = np.where(wet, u(0.0, 1e-4), tab["PCLV_QL"])
+    # A': convective detrainment into those cells, the one source of condensate where the critical relative humidity is 1
+    tab["PLUDE"] = np.where(wet & col(1), u(0.0, 2.0e-6), tab["PLUDE"])
+    tab["PLU"] = np.where(col(1) & (pap < 2500.0), u(1.0e-5, 1.0e-3), tab["PLU"])
+
+    tab["PT"] = tab["PT"] + np.where(col(2), u(5.0, 20.0, (1, ncol)), 0.0)
+    ptsphy = float(tab["PTSPHY"])
+    ztp2 = tab["PT"] + ptsphy * tab["TENDENCY_CML_T"]  # the first guess of level_forward
+    thaw = col(3) & (ztp2 > 273.16) & (ztp2 < 292.0)
+    tab["PT"] = np.where(thaw, 275.16 + 10.0 ** u(-4.5, -1.5) - ptsphy * tab["TENDENCY_CML_T"], tab["PT"])
+
+    # B and F: freezing and warm levels in turn below the 262 K level: the cold ones make snow, the warm ones melt all of it
+    ztp2 = tab["PT"] + ptsphy * tab["TENDENCY_CML_T"]
+    low = (col(2) | col(6)) & (ztp2 > 262.0)
+    odd = np.broadcast_to((np.arange(nlev) % 2 == 1)[:, None], (nlev, ncol))
+    tab["PT"] = np.where(low, np.where(odd, 279.0 + u(0.0, 10.0), 271.0 + u(0.0, 1.5)) - ptsphy * tab["TENDENCY_CML_T"], tab["PT"])
+
+    tab["PQ"] = np.where(col(4), tab["PQ"] * u(1.0, 1.6), tab["PQ"])
+
+    # E: first-guess total water (ZQP2 + ZL + ZI of level_forward) a little below ZQSAT = qsat(PAP, PT) * ZSUPSAT
+    ztp2 = tab["PT"] + ptsphy * tab["TENDENCY_CML_T"]
+    zqsat = _host_qsat(tab) * np.where(ztp2 < 250.16, 1.8 - 3.0e-3 * ztp2, 1.0)  # RTICE = RTT - 23
+    rest = (ptsphy * tab["TENDENCY_CML_Q"] + tab["PSUPSAT"] + tab["PCLV_QL"] + ptsphy * tab["TENDENCY_CML_QL"] + tab["PCLV_QI"] +
+            ptsphy * tab["TENDENCY_CML_QI"])
+    pq = zqsat * u(0.95, 0.99995) - rest
+    tab["PQ"] = np.where(col(5) & (pap > 1.0e4) & (pq > 0.0), pq, tab["PQ"])
+    return tab
+
+
+def _host_qsat(tab: dict) -> np.ndarray:
+    """SATUR of the host build on a table's (PAP, PT): an input recipe needs it, not a reference."""
+    pap, t = np.ascontiguousarray(tab["PAP"], dtype=B.REAL), np.ascontiguousarray(tab["PT"], dtype=B.REAL)
+    nlev, ncol = pap.shape
+    qsat = np.zeros_like(pap)
+    prm = c2.default_params(np.full(nlev, 0.5))
+    f = lambda a: B.Field(a.ctypes.data, a.size)  # noqa: E731
+    hc = census_lib()  # (its own copy of hostcheck.hip: the arithmetic mode set here is not the one the tests set on hostcheck())
+    hc.hostcheck_set_precise(1)
+    try:
+        assert hc.hostcheck_satur(C.byref(prm), ncol, nlev, ncol, f(pap), f(t), f(qsat)) == 0
+    finally:
+        hc.hostcheck_set_precise(0)
+    return qsat.astype(np.float64)
+
+
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# layout: the reference works on (NLEVx, columns) matrices, the sweeps on (NBLOCKS, NLEVx, NPROMA) blocks
+# ---------------------------------------------------------------------------------------------------------------------
+def active_cols(a: np.ndarray, ngptot: int) -> np.ndarray:
+    """(NBLOCKS, NLEVx, NPROMA) -> (NLEVx, ngptot): the active columns in global order (blocks are contiguous)."""
+    nb, nlevx, nproma = a.shape
+    return np.ascontiguousarray(a.transpose(1, 0, 2)).reshape(nlevx, nb * nproma)[:, :ngptot]
+
+
+def to_blocks(m: np.ndarray, nproma: int, fill: float = 0.0) -> np.ndarray:
+    """(NLEVx, ngptot) -> (NBLOCKS, NLEVx, NPROMA), the padded tail filled with `fill`."""
+    nlevx, ngptot = m.shape
+    nb = (ngptot + nproma - 1) // nproma
+    out = np.full((nlevx, nb * nproma), fill, dtype=m.dtype)
+    out[:, :ngptot] = m
+    return np.ascontiguousarray(out.reshape(nlevx, nb, nproma).transpose(1, 0, 2))
+
+
+TABLE_FIELDS = ("PT", "PQ", "PAP", "PAPH", "PLU", "PLUDE", "PMFU", "PMFD", "PCLV_QL", "PCLV_QI", "TENDENCY_CML_T", "TENDENCY_CML_Q",
+                "TENDENCY_CML_QL", "TENDENCY_CML_QI", "PSUPSAT")
+
+
+def one_ulp(a: np.ndarray, rng) -> np.ndarray:
+    """Every element times 1 + 2^-52 or 1 - 2^-52, the sign drawn from rng."""
+    return a * (1.0 + np.where(rng.integers(0, 2, size=a.shape) == 1, 1.0, -1.0) * 2.0 ** -52)
+
+
+def perturbed_table(tab: dict, seed: int = 77) -> dict:
+    rng = np.random.default_rng(seed)
+    out = dict(tab)
+    for n in TABLE_FIELDS:
+        out[n] = one_ulp(tab[n], rng)
+    return out
+
+
+def checker():
+    """The reference itself where it was built, else its plain-C restatement."""
+    return refcall.RefLib() if refcall.have_ref() else refcall.OracleLib()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# classes
+# ---------------------------------------------------------------------------------------------------------------------
+def outcome_masks(sig: np.ndarray, evap: bool) -> dict:
+    """name -> boolean mask over the cells of `sig` (any shape): one entry per outcome of every signature bit.  A bit with a
+    domain (DOMAIN) has its outcomes inside the domain only."""
+    act = (sig & SIG_ACTIVE) != 0
+    bit = lambda n: ((sig >> np.uint32(BITS[n])) & np.uint32(1)) != 0  # noqa: E731
+    reg = (sig >> np.uint32(4)) & np.uint32(3)
+    out = {f"regime={r}": act & (reg == r) for r in range(3)}
+    for n in BITS:
+        if n in EVAP_ONLY and not evap:
+            continue
+        dom, tag = act, ""
+        if n in DOMAIN:
+            d = DOMAIN[n]
+            dom, tag = act & (out[d] if d.startswith("regime") else bit(d)), "|" + d
+        out[f"{n}=0{tag}"] = dom & ~bit(n)
+        out[f"{n}=1{tag}"] = dom & bit(n)
+    return out
+
+
+def census_counts(sig: np.ndarray, evap: bool) -> dict:
+    return {n: int(m.sum()) for n, m in outcome_masks(sig, evap).items()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# one case: an atmosphere, a flag set, the reference's results on it, its classes and the bounds
+# ---------------------------------------------------------------------------------------------------------------------
+FLAG_SETS = {"plain": dict(), "lregcl": dict(lregcl=True), "levapls2": dict(levapls2=True),
+             "levapls2+lregcl": dict(levapls2=True, lregcl=True)}
+NPROMA, NGPTOT, NCOL, SEED = 32, 90, 96, 3
+DRAWS = 6  # sign patterns of the one-ulp perturbation
+FLUX = ("fplsl", "fplsn", "fhpsl", "fhpsn")
+
+
+def _inputs_of(tab: dict, ngptot: int) -> dict:
+    st = c2.state_from_table(tab, ngptot, ngptot, real=np.float64)
+    return refcall.block_inputs(st, 0, None)
+
+
+class Case:
+    """Everything the per-class comparison of one (levels, flag set) needs; built once (see `case`)."""
+
+    def __init__(self, nlev: int, flagset: str):
+        self.nlev, self.flagset = nlev, flagset
+        self.flags = FLAG_SETS[flagset]
+        self.evap = bool(self.flags.get("levapls2"))
+        self.tab = atlas_table(nlev, NCOL, SEED)
+        self.prm = make_params(self.tab, **self.flags)
+        self.st = c2.state_from_table(self.tab, NPROMA, NGPTOT)
+        self.ptsphy = self.st.ptsphy
+        self.chk = checker()
+        set_lib_params(self.chk, self.prm)
+        # the reference on the state ...
+        self.inp = _inputs_of(self.tab, NGPTOT)
+        self.inp["qsat"] = self.chk.satur(self.inp["pap"], self.inp["t"])
+        self.qsat = to_blocks(self.inp["qsat"], NPROMA)  # what a sweep with QSAT fed reads
+        self.dinp = {n: np.ascontiguousarray(a * 0.01) for n, a in self.inp.items()}  # the test drivers' increments
+        self.ref = self._reference(self.inp, self.dinp, None)
+        # ... and on the state with every input one ulp off, DRAWS sign patterns: the floor is the largest response of the
+        # reference over them (one pattern alone can cancel inside a small class)
+        self.tab_p, refs_p = [], []
+        for k in range(DRAWS):
+            rng = np.random.default_rng(78 + k)
+            tab_p = perturbed_table(self.tab, seed=177 + k)
+            inp_p = _inputs_of(tab_p, NGPTOT)
+            inp_p["qsat"] = one_ulp(self.inp["qsat"], rng)  # QSAT is an input of CLOUDSC2 like the others
+            dinp_p = {n: one_ulp(a, rng) for n, a in self.dinp.items()}
+            refs_p.append(self._reference(inp_p, dinp_p, rng))
+            self.tab_p.append(tab_p)
+        self._refs_p = refs_p
+        self._classes()
+        self._bounds()
+
+    # -- reference ----------------------------------------------------------------------------------------------------
+    def _reference(self, inp, dinp, rng):
+        """NL, TL (about inp, increments dinp) and AD (output adjoints = the TL outputs, one ulp off if rng) of the checker."""
+        chk, nlev, ncol = self.chk, self.nlev, NGPTOT
+        cp = lambda d: {n: a.copy() for n, a in d.items()}  # noqa: E731
+        nl = chk.cloudsc2(self.ptsphy, cp(inp))
+        traj, tl = chk.cloudsc2tl(self.ptsphy, cp(inp), cp(dinp))
+        y = {n: (one_ulp(a, rng) if rng is not None else a.copy()) for n, a in tl.items()}
+        x = refcall.new_inputs(nlev, ncol)
+        chk.cloudsc2ad(self.ptsphy, cp(inp), x, cp(y))
+        return dict(nl=nl, traj=traj, tl=tl, ad=x, y=y)
+
+    def reference_ad(self, x0: dict) -> dict:
+        """The checker's adjoint accumulated on the background x0 (PSUPSAT's is assigned, cloudsc2ad.F90:1733)."""
+        set_lib_params(self.chk, self.prm)
+        x = {n: a.copy() for n, a in x0.items()}
+        self.chk.cloudsc2ad(self.ptsphy, {n: a.copy() for n, a in self.inp.items()}, x, {n: a.copy() for n, a in self.ref["y"].items()})
+        return x
+
+    # -- classes ------------------------------------------------------------------------------------------------------
+    def _classes(self):
+        sigs, differ = [], 0
+        for st in [self.st] + [c2.state_from_table(t, NPROMA, NGPTOT) for t in self.tab_p]:
+            for qs in (self.qsat, None):
+                for precise in (0, 1):
+                    s, _, d = census(self.prm, st, qs, precise)
+                    sigs.append(active_cols(s, NGPTOT))
+                    differ += d
+        self.dpr_clip_ne_reset = differ
+        self.sig = sigs[0]
+        # threshold cells: the signature depends on the arithmetic mode, on where QSAT comes from or on one ulp of the inputs
+        self.excluded = np.zeros(self.sig.shape, dtype=bool)
+        for s in sigs[1:]:
+            self.excluded |= s != self.sig
+        self.full_classes = outcome_masks(self.sig, self.evap)
+        self.classes = {n: m & ~self.excluded for n, m in self.full_classes.items()}
+
+    # -- bounds -------------------------------------------------------------------------------------------------------
+    def class_rows(self, f: str, a: np.ndarray, mask: np.ndarray):
+        """The values of field f that belong to the cells of a class.  Full-level fields: the cell's own.  Half-level fields (the
+        fluxes; the adjoint of PAPH): the half level below the cell, where its rain and snow arrive and whose pressure closes its
+        layer.  The adjoint of PLU: level jk reads PLU(JK+1) and nothing else does (cloudsc2.F90:435), so the value at jk+1 is
+        the work of cell jk.  The top row of those fields belongs to no cell and stays under the whole-field bound."""
+        if a.shape[0] == self.nlev + 1:
+            return a[1:][mask]
+        if f == "lu":
+            return a[1:][mask[:-1]]
+        return a[mask]
+
+    def _bounds(self):
+        refs_p = self._refs_p
+        self.floor_abs, self.floor_field, self.scale = {}, {}, {}
+        for kind in ("nl", "traj", "tl", "ad"):
+            for f, r in self.ref[kind].items():
+                d = np.max([np.abs(rp[kind][f] - r) for rp in refs_p], axis=0)
+                m = float(np.abs(r).max())
+                self.scale[kind, f] = m
+                self.floor_field[kind, f] = float(d.max()) / m if m > 0.0 else 0.0
+                for cn, mask in self.classes.items():
+                    v = self.class_rows(f, d, mask)
+                    self.floor_abs[kind, f, cn] = float(v.max()) if v.size else 0.0
+        worst = lambda kinds: max(v for (k, f), v in self.floor_field.items() if k in kinds)  # noqa: E731
+        self.K_NL = NL_TOL / worst(("nl",))
+        self.K_TLAD = TLAD_TOL / worst(("tl", "ad"))
+
+    def columns(self, cols: np.ndarray) -> "Case":
+        """The same case with the field cut down to some columns: references, classes, floors, scales and K are those of the
+        subset (compare() then takes results cut down alike)."""
+        import copy
+
+        v = copy.copy(self)
+        cut = lambda d: {n: np.ascontiguousarray(a[:, cols]) for n, a in d.items()}  # noqa: E731
+        v.ref = {k: cut(d) for k, d in self.ref.items()}
+        v._refs_p = [{k: cut(d) for k, d in rp.items()} for rp in self._refs_p]
+        v.classes = cut(self.classes)
+        v.full_classes = cut(self.full_classes)
+        v._bounds()
+        return v
+
+    def tol(self, kind: str) -> float:
+        return NL_TOL if kind in ("nl", "traj") else TLAD_TOL
+
+    def K(self, kind: str) -> float:
+        return self.K_NL if kind in ("nl", "traj") else self.K_TLAD
+
+    def bound_abs(self, kind: str, f: str, cn: str) -> float:
+        """K floor(f, c) as an absolute error, never looser than the whole-field bound; 0: the numbers must be equal."""
+        return min(self.K(kind) * self.floor_abs[kind, f, cn], self.tol(kind) * self.scale[kind, f])
+
+    def compare(self, kind: str, got: dict, ref: dict | None = None):
+        """got: name -> (NLEVx, NGPTOT).  Returns (violations, worst err / bound, its place): every field under the whole-field
+        bound, every (field, class) under its class bound."""
+        ref = ref if ref is not None else self.ref[kind]
+        bad, worst, where = [], 0.0, None
+        for f, r in ref.items():
+            g = got[f]
+            assert g.shape == r.shape, (f, g.shape, r.shape)
+            if not np.all(np.isfinite(g)):
+                bad.append((kind, f, "not finite"))
+                continue
+            d = np.abs(g - r)
+            if float(d.max()) > self.tol(kind) * self.scale[kind, f]:
+                bad.append((kind, f, "field", float(d.max()) / max(self.scale[kind, f], 1e-300), self.tol(kind)))
+            for cn, mask in self.classes.items():
+                v = self.class_rows(f, d, mask)
+                if not v.size:
+                    continue
+                e, b = float(v.max()), self.bound_abs(kind, f, cn)
+                if b == 0.0:
+                    if e != 0.0:
+                        bad.append((kind, f, cn, e, "reference does not move: the numbers must be equal"))
+                    continue
+                if e / b > worst:
+                    worst, where = e / b, (kind, f, cn)
+                if e > b:
+                    bad.append((kind, f, cn, e, b))
+        return bad, worst, where
+
+
+@functools.lru_cache(maxsize=None)
+def case(nlev: int, flagset: str) -> Case:
+    return Case(nlev, flagset)
+
+
+def class_err(ref: np.ndarray, got: np.ndarray, mask: np.ndarray) -> float:
+    """err(f, c) = max_c |got - ref| / max_c |ref| (0 if both vanish, infinite if only the reference does)."""
+    d, m = float(np.abs(got - ref)[mask].max()), float(np.abs(ref)[mask].max())
+    if m == 0.0:
+        return 0.0 if d == 0.0 else np.inf
+    return d / m
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the host build of the sweeps on a case (tests/hostcheck): results as (NLEVx, NGPTOT) matrices, like the reference's
+# ---------------------------------------------------------------------------------------------------------------------
+def state_outputs(st) -> dict:
+    out = {"tent": st.B_LOC[:, 0], "tenq": st.B_LOC[:, 2], "tenl": st.B_LOC[:, 3], "teni": st.B_LOC[:, 4], "clc": st.PA,
+           "fplsl": st.PFPLSL, "fplsn": st.PFPLSN, "fhpsl": st.PFHPSL, "fhpsn": st.PFHPSN, "covptot": st.PCOVPTOT}
+    return {n: active_cols(np.ascontiguousarray(a), st.ngptot) for n, a in out.items()}
+
+
+def blocks_of(d: dict, fill: float = 0.0) -> dict:
+    return {n: to_blocks(a, NPROMA, fill) for n, a in d.items()}
+
+
+def cols_of(d: dict) -> dict:
+    return {n: active_cols(a, NGPTOT) for n, a in d.items()}
+
+
+def _flat(kind: str, arrays: dict):
+    blk = B.Inputs() if kind == "in" else B.Outputs()
+    for n, a in arrays.items():
+        setattr(blk, n, hfld(a))
+    return blk
+
+
+def host_nl(c: Case, satur: bool) -> dict:
+    """satur: SATUR in the sweep (no QSAT plane), else QSAT fed from the reference's SATUR."""
+    got = c.st.copy()
+    i, o = host_traj_blocks(got, None if satur else c.qsat)
+    assert hostcheck().hostcheck_nl(C.byref(c.prm), c.ptsphy, NPROMA, c.nlev, NGPTOT, C.byref(i), C.byref(o), B.Field(), 0.0) == 0
+    return state_outputs(got)
+
+
+def host_tl(c: Case, satur: bool):
+    """(trajectory outputs, tangent outputs) of hostcheck_tl with the reference's increments."""
+    got = c.st.copy()
+    i, o = host_traj_blocks(got, None if satur else c.qsat)
+    inc = blocks_of(c.dinp)
+    tl = {n: np.zeros((c.st.nblocks, c.nlev + (1 if n in refcall.HALF else 0), NPROMA), dtype=B.REAL) for n in B.OUT_NAMES}
+    assert hostcheck().hostcheck_tl(C.byref(c.prm), c.ptsphy, NPROMA, c.nlev, NGPTOT, C.byref(i), C.byref(o),
+                                    C.byref(_flat("in", inc)), C.byref(_flat("out", tl))) == 0
+    return state_outputs(got), cols_of(tl)
+
+
+def host_ad(c: Case, satur: bool, x0: dict, assign: bool) -> dict:
+    """hostcheck_ad (both sweeps) with the output adjoints of the case; the input adjoints start from x0 (NGPTOT matrices)."""
+    hc = hostcheck()
+    got = c.st.copy()
+    i, o = host_traj_blocks(got, None if satur else c.qsat)
+    x, y = blocks_of(x0), blocks_of(c.ref["y"])
+    scratch = np.zeros((c.st.nblocks, c.nlev, NPROMA), dtype=B.REAL)
+    hc.hostcheck_set_assign(int(assign))
+    try:
+        assert hc.hostcheck_ad(C.byref(c.prm), c.ptsphy, NPROMA, c.nlev, NGPTOT, C.byref(i), C.byref(o), C.byref(_flat("in", x)),
+                               C.byref(_flat("out", y)), scratch.ctypes.data) == 0
+    finally:
+        hc.hostcheck_set_assign(0)
+    return cols_of(x)
