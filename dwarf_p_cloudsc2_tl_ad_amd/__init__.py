@@ -12,4 +12,5 @@ from .state import (Cloudsc2State, bytes_per_column, ceta_from_table, column_ran
                     state_from_table, synthetic_table, validate_l1)
 from .driver import (DeviceState, FlatFields, ResidentState, cloudsc_driver, cloudsc_driver_ad, cloudsc_driver_tl,  # noqa: F401
                      run_state)
-from .autograd import PARAM_NAMES, Cloudsc2Outputs, NormalEquations, cloudsc2, param_jacobian, param_normal_equations, satur  # noqa: F401,E402
+from .autograd import (PARAM_NAMES, Cloudsc2Outputs, NormalEquations, check_ensemble, cloudsc2, cloudsc2_ensemble, param_jacobian,  # noqa: F401,E402
+                       param_normal_equations, satur)

@@ -25,6 +25,15 @@ all four parameters, what a Gauss-Newton or Levenberg-Marquardt calibration need
 with a unit tangent on that parameter.  Such a step itself needs only ``J^T W J`` and ``J^T W r``: :func:`param_normal_equations` forms
 them in one ``cloudsc2_parnormal_launch`` without the Jacobian ever being written.
 
+Ensembles.  ``cloudsc2_ensemble(inputs, prm, ptsphy, ngptot, satur, params={name: (K,) device tensor})`` runs K parameter sets -- a
+perturbed-parameter ensemble, over one shared state or over one 4-D state per member -- in one launch per sweep and reads the
+parameters ON THE DEVICE: each member has an argument block of its own in device memory, whose constants a small kernel derives from
+the member's row of a ``(K, 4)`` table (``cloudsc2_nl_launch_ens`` / ``cloudsc2_tl_launch_ens`` / ``cloudsc2_vjp_launch_ens``).  So it
+neither synchronises nor refuses stream capture, and the ensemble is the batch that ``vmap`` over ``params`` does not give; every
+member is the bits of the 0-d ``params`` call with its row.  The 0-d ``params`` path above keeps its host read on purpose: it is
+the one launch whose constants sit in the kernel-argument segment, its bits, launch log and refusals are what callers and tests rely
+on, and a single parameter set has no table to derive on the device.
+
 Batches.  Under ``torch.func.vmap`` the op distinguishes two cases.  Several tangents or cotangents over ONE state -- ``jacfwd``,
 ``jacrev``, ``vmap(jvp)``, ``vmap(vjp_fn)`` -- are one ``cloudsc2_tl_launch_batch`` / ``cloudsc2_vjp_launch_batch`` call: the
 trajectory is read once per ``cloudsc2_batch_max()`` directions instead of once per direction, and every direction's result is the
@@ -1096,6 +1105,298 @@ def param_normal_equations(inputs, prm: B.Params, ptsphy: float, ngptot: int | N
         jtj = torch.stack([normal[normal_row(a, b)] for a in idx for b in idx]).reshape(len(idx), len(idx))
         jtr = torch.stack([normal[B.NNORMAL - len(PARAM_NAMES) + a] for a in idx])
         return NormalEquations(tuple(pnames), jtj, jtr)
+
+
+# ---- cloudsc2_ensemble: K parameter sets in one launch, the parameters read on the device -------------------------------------------
+
+_NO_VMAP_ENS = ("cloudsc2_ensemble: torch.func.vmap, jacfwd and jacrev are not supported (the ensemble is the batch: give the members' "
+                "parameters as (K,) tensors and per-member states as 4-D inputs); use .backward() / torch.autograd.grad / "
+                "torch.func.grad / torch.func.vjp, or torch.autograd.forward_ad / torch.func.jvp")
+
+
+_NO_SECOND_ENS = ("cloudsc2_ensemble: double backward (and forward-over-reverse, reverse-over-forward) is not supported: the sweeps are "
+                  "first-order derivatives of CLOUDSC2")
+
+
+def check_ensemble(inputs, prm: B.Params, ngptot: int | None = None, satur: bool = False, params=None) -> tuple:
+    """Every check of :func:`cloudsc2_ensemble` that needs no device; returns ``(layout, K, the given names in PARAM_NAMES order)``.
+    Runs on CPU tensors; raises ``ValueError``."""
+    if not hasattr(params, "keys"):
+        raise ValueError(f"params must map names of {PARAM_NAMES} to 1-d float64 tensors of one length K; got {type(params)}")
+    if len(params.keys()) == 0:
+        raise ValueError(f"params is empty: an ensemble varies at least one of {PARAM_NAMES}")
+    unknown = sorted(set(params.keys()) - set(PARAM_NAMES), key=str)
+    if unknown:
+        raise ValueError(f"params: unknown name(s) {unknown}; the differentiable parameters are {PARAM_NAMES}")
+    pnames = tuple(n for n in PARAM_NAMES if n in params.keys())
+    K = None
+    for n in pnames:
+        p = params[n]
+        if not isinstance(p, torch.Tensor):
+            raise ValueError(f"params[{n!r}] is not a tensor")
+        if p.dtype != torch.float64:
+            raise ValueError(f"params[{n!r}] has dtype {p.dtype}; parameters are float64 in both builds (the constants of cloudsc2_params are C doubles)")
+        if p.dim() != 1 or p.shape[0] < 1:
+            raise ValueError(f"params[{n!r}] must be a 1-d tensor with one value per member (K >= 1); got shape {tuple(p.shape)}")
+        if K is None:
+            K = int(p.shape[0])
+        elif int(p.shape[0]) != K:
+            raise ValueError(f"params[{n!r}] has {p.shape[0]} members, params[{pnames[0]!r}] has {K}: one common length K is required")
+    IN_NAMES = SAT_NAMES if satur else B.IN_NAMES
+    names = set(inputs.keys()) if hasattr(inputs, "keys") else None
+    if satur and names is not None and "qsat" in names:
+        raise ValueError("satur=True: SATUR is evaluated and differentiated inside the op, inputs must not have a 'qsat'")
+    if names is None or names != set(IN_NAMES):
+        raise ValueError(f"inputs must map exactly the names {IN_NAMES}; got {sorted(names) if names is not None else type(inputs)}")
+    member0 = {}
+    for n in IN_NAMES:
+        t = inputs[n]
+        if isinstance(t, torch.Tensor) and t.dim() == 4:
+            if int(t.shape[0]) != K:
+                raise ValueError(f"inputs[{n!r}] is 4-D with leading size {t.shape[0]}: a per-member input has one state for each of the K = {K} members")
+            t = t[0]
+        elif isinstance(t, torch.Tensor) and t.dim() != 3:
+            raise ValueError(f"inputs[{n!r}] must be 3-D (shared by all members) or 4-D (K, nblocks, nlev{'+1' if n in HALF_IN else ''}, nproma); "
+                             f"got shape {tuple(t.shape)}")
+        member0[n] = t
+    return check_layout(member0, prm, ngptot, satur=satur), K, pnames
+
+
+def _member0(t: torch.Tensor) -> torch.Tensor:
+    return t[0] if t.dim() == 4 else t
+
+
+def _normalize_ens(ts: dict, lay: Layout, groups: dict) -> dict:
+    """:func:`normalize` for tensors that are 3-D (shared) or 4-D (one per member): the launchers take one block stride per layout
+    group and any member stride per field"""
+    out = dict(ts)
+    for g, names in groups.items():
+        want = lay.nlev * lay.nproma if g == "full" else (lay.nlev + 1) * lay.nproma if g == "half" else None
+        if not _group_fits({n: _member0(out[n]) for n in names}, lay, names, want):
+            for n in names:
+                out[n] = out[n].contiguous()
+    return out
+
+
+def _ens_block(kind: str, ts: dict, lay: Layout, K: int):
+    """member 0's argument block and the member strides (elements; 0: shared) of ``ts``: name -> 3-D or 4-D tensor"""
+    blk, names = (B.Inputs(), B.IN_NAMES) if kind == "in" else (B.Outputs(), B.OUT_NAMES)
+    ms = (C.c_longlong * len(names))()
+    for n, t in ts.items():
+        t = _raw(t)
+        setattr(blk, n, _field(_member0(t), lay, n))
+        ms[names.index(n)] = t.stride(0) if t.dim() == 4 and K > 1 else 0
+    return blk, ms
+
+
+def _ens_workspace(K: int, lay: Layout, dev: torch.device) -> torch.Tensor:
+    nbytes = B.lib.cloudsc2_ens_workspace_bytes(K, lay.nproma, lay.nlev, lay.ngptot)
+    if nbytes < 0:
+        B.check(int(nbytes))
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+
+
+def _ptr(t: torch.Tensor) -> C.c_void_p:
+    return C.c_void_p(_raw(t).data_ptr())
+
+
+def _table(t: torch.Tensor) -> torch.Tensor:
+    """a (K, 4) parameter table as the launchers read it: plain, contiguous"""
+    return _raw(t).detach().contiguous()
+
+
+def _refuse_batched_ens(ts) -> None:
+    if any(_batched_inside(t) for t in ts):
+        raise NotImplementedError(_NO_VMAP_ENS)
+
+
+class _Cloudsc2EnsTl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, K, (K, 4) parameters, (K, 4) parameter tangents, *n trajectory inputs, *n tangents) -> 10
+    output tangents ``(K, ...)``: ``cloudsc2_tl_launch_ens``.  Inputs and tangents are 3-D (shared) or 4-D.  Differentiating it again
+    raises ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, K, ptab, dptab, *ts):
+        names, groups = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        like = x["pap"]
+        dev = like.device
+        dx = _normalize_ens(dict(zip(names, ts[n:])), lay, groups)
+        dy = _new(B.OUT_NAMES, lay, like, batch=K)
+        ptab, dptab = _table(ptab), _table(dptab)
+        work = _ens_workspace(K, lay, dev)
+        (xb, xm), (db, dm), (yb, ym) = _ens_block("in", x, lay, K), _ens_block("in", dx, lay, K), _ens_block("out", dy, lay, K)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch_ens(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur), K, _ptr(ptab),
+                                                 _ptr(dptab), C.byref(xb), xm, C.byref(db), dm, C.byref(yb), ym, _ptr(work), _stream(dev)))
+        return tuple(dy[k] for k in B.OUT_NAMES)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError(_NO_SECOND_ENS)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        raise NotImplementedError(_NO_SECOND_ENS)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP_ENS)
+
+
+class _Cloudsc2EnsVjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, K, (K, 4) parameters, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output
+    adjoints) -> n input adjoints ``(K, ...)`` and the ``(K, 4)`` parameter adjoints: ``cloudsc2_vjp_launch_ens``.  Differentiating it
+    again (double backward) raises ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, K, ptab, *ts):
+        names, _ = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        fplsl, fplsn, scratch = ts[n:n + 3]
+        like = x["pap"]
+        dev = like.device
+        y = _normalize_ens(dict(zip(B.OUT_NAMES, ts[n + 3:])), lay, OUT_GROUPS)
+        xa = _new(names, lay, like, batch=K)
+        ptab = _table(ptab)
+        work = _ens_workspace(K, lay, dev)
+        par_adj = torch.empty((K, len(PARAM_NAMES)), dtype=torch.float64, device=dev)
+        (xb, xm), (ab, am), (yb, ym) = _ens_block("in", x, lay, K), _ens_block("in", xa, lay, K), _ens_block("out", y, lay, K)
+        tb, tm = _ens_block("out", {"fplsl": fplsl, "fplsn": fplsn}, lay, K)
+        sc = _raw(scratch)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch_ens(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur), K, _ptr(ptab),
+                                                  C.byref(xb), xm, C.byref(tb), tm, C.byref(ab), am, C.byref(yb), ym, _scratch_ptr(scratch),
+                                                  sc.stride(0) if sc.dim() == 4 and K > 1 else 0, _ptr(work), _ptr(par_adj), _stream(dev)))
+        return tuple(xa[k] for k in names) + (par_adj,)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError(_NO_SECOND_ENS)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        raise NotImplementedError(_NO_SECOND_ENS)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP_ENS)
+
+
+class _Cloudsc2Ens(torch.autograd.Function):
+    # forward(prm, ptsphy, layout, satur, K, the (K, 4) parameter table, *n inputs, 3-D or 4-D) -> 10 outputs (K, ...) + the members'
+    # cover-checkpoint scratch: cloudsc2_nl_launch_ens.  prm holds the values of the parameters that are not given; the table is a device
+    # tensor nobody reads on the host.  backward: one cloudsc2_vjp_launch_ens; jvp: one cloudsc2_tl_launch_ens.
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, K, ptab, *xs):
+        names, _ = _names(satur)
+        x = dict(zip(names, xs))
+        like = x["pap"]
+        dev = like.device
+        out = _new(B.OUT_NAMES, lay, like, batch=K)
+        evap = _evap(prm)
+        scratch = torch.empty((K, lay.nblocks, lay.nlev, lay.nproma) if evap else (0,), dtype=like.dtype, device=dev)
+        ptab = _table(ptab)
+        work = _ens_workspace(K, lay, dev)
+        (xb, xm), (ob, om) = _ens_block("in", x, lay, K), _ens_block("out", out, lay, K)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_nl_launch_ens(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, K, _ptr(ptab), C.byref(xb), xm,
+                                                 C.byref(ob), om, _scratch_ptr(scratch), scratch.stride(0) if evap and K > 1 else 0,
+                                                 _ptr(work), _stream(dev)))
+        return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        prm, ptsphy, lay, satur, K, ptab, *xs = inputs
+        out = dict(zip(B.OUT_NAMES, output[:-1]))
+        scratch = output[-1]
+        ctx.mark_non_differentiable(scratch)
+        ctx.save_for_backward(ptab, *xs, out["fplsl"], out["fplsn"], scratch)
+        ctx.save_for_forward(ptab, *xs)
+        ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.K = prm, ptsphy, lay, satur, K
+
+    @staticmethod
+    def backward(ctx, *grads):
+        _refuse_batched_ens(grads)
+        ptab, *saved = ctx.saved_tensors
+        lay, like = ctx.lay, saved[0]
+        need_p, need_x = ctx.needs_input_grad[5], ctx.needs_input_grad[6:]
+        if not need_p and not any(need_x):
+            return (None,) * (6 + len(need_x))
+        y = _zero_filled(B.OUT_NAMES, grads[:10], lay, like)  # (an output that took no part: one shared zero plane)
+        *xa, par_adj = _Cloudsc2EnsVjp.apply(ctx.prm, ctx.ptsphy, lay, ctx.satur, ctx.K, ptab, *saved, *(y[n] for n in B.OUT_NAMES))
+        # a per-member input gets its members' gradients, a shared one their sum
+        gx = tuple((a if x.dim() == 4 else a.sum(0)) if nd else None for a, x, nd in zip(xa, saved, need_x))
+        return (None,) * 5 + (par_adj if need_p else None,) + gx
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        _refuse_batched_ens(tangents)
+        names, _ = _names(ctx.satur)
+        ptab, *xs = ctx.saved_tensors
+        dptab = tangents[5] if tangents[5] is not None else torch.zeros_like(ptab)
+        dx = _zero_filled(names, tangents[6:], ctx.lay, xs[0])  # (no tangent: one shared zero plane)
+        dy = _Cloudsc2EnsTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.K, ptab, dptab, *xs, *(dx[n] for n in names))
+        return tuple(dy) + (None,)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP_ENS)
+
+
+def cloudsc2_ensemble(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None) -> Cloudsc2Outputs:
+    """A perturbed-parameter ensemble of CLOUDSC2 in one launch: K parameter sets over one state, or over one state each.
+
+    ``params`` maps a non-empty subset of ``PARAM_NAMES`` to 1-d ``float64`` tensors of one common length K >= 1 ON THE INPUTS' DEVICE;
+    a name that is not given keeps ``prm``'s value in every member.  Nothing is read on the host: the ``(K, 4)`` table is assembled
+    with torch ops and a small kernel derives every member's constants from its row on the device, so the call does not synchronise,
+    and after one eager call with the same CETA the forward and ``torch.autograd.grad`` of it can be captured in ``torch.cuda.graph`` --
+    a replay after ``params[name].copy_(new)`` computes with the new values.
+
+    ``inputs``: the names of :func:`cloudsc2` (without ``qsat`` when ``satur=True``); each tensor is 3-D in that op's layout and
+    shared by all members, or 4-D ``(K, nblocks, nlevx, nproma)`` with one state per member and any member stride ``t.stride(0)``.
+    The in-block layout rules are :func:`cloudsc2`'s: one block stride per layout group, a group that does not fit is copied contiguous.
+
+    Returns a :class:`Cloudsc2Outputs` of ``(K, nblocks, nlevx, nproma)`` tensors, the padded tail zero in every member.
+    ``.backward()``, ``torch.autograd.grad``, ``torch.func.grad`` / ``vjp``, ``forward_ad`` and ``torch.func.jvp`` differentiate with
+    respect to the ``(K,)`` parameters (gradient ``(K,)``, float64, on the device) and the fields (a 4-D input gets per-member
+    gradients, a 3-D shared input the sum over the members); ``torch.func.vmap`` / ``jacfwd`` / ``jacrev`` raise
+    ``NotImplementedError``, and so does double backward (differentiating a gradient made with ``create_graph=True``, or a tangent).  ``prm.lphylin = 0`` is refused.  With the
+    evaporation branch (``levapls2`` / ``ldrain1d``) every member's ``rpecons`` must be non-zero: a value given in ``params`` lives on
+    the device and is NOT checked (a zero gives non-finite ``rpecons`` derivatives); ``prm``'s own value is checked when it is used.
+
+    Promise: member k of every output, every per-member field gradient, every output tangent and every parameter gradient is bit for
+    bit what ``cloudsc2(inputs_k, prm, ptsphy, ngptot, satur=..., params={the four 0-d values of row k})`` gives forward, in
+    ``backward`` and in ``jvp``.  The gradient of a shared input is the members' sum (``xa.sum(0)``): equal to the sum of those
+    calls' gradients up to the order of summation, not to the bit."""
+    names, groups = _names(satur)
+    lay, K, pnames = check_ensemble(inputs, prm, ngptot, satur, params)
+    dev = check_device(inputs[n] for n in names)
+    ps = tuple(params[n] for n in pnames)
+    _refuse_batched_ens(ps + tuple(inputs[n] for n in names))
+    for n, p in zip(pnames, ps):
+        if p.device != dev:
+            raise ValueError(f"params[{n!r}] is on {p.device}: the parameters of an ensemble live on the inputs' device {dev} (they are read there)")
+    if _evap(prm) and "rpecons" not in pnames and prm.rpecons == 0.0:
+        raise ValueError("cloudsc2_ensemble with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
+    _prepare(dev)
+    given = dict(zip(pnames, ps))
+    ptab = torch.stack([given[n] if n in given else torch.full((K,), float(getattr(prm, n)), dtype=torch.float64, device=dev)
+                        for n in PARAM_NAMES], dim=1)
+    x = _normalize_ens({n: inputs[n] for n in names}, lay, groups)
+    out = _Cloudsc2Ens.apply(prm, float(ptsphy), lay, bool(satur), K, ptab, *(x[n] for n in names))
+    return Cloudsc2Outputs(*out[:10])
 
 
 def satur(pap: torch.Tensor, t: torch.Tensor, prm: B.Params, ngptot: int | None = None, differentiable: bool = False) -> torch.Tensor:

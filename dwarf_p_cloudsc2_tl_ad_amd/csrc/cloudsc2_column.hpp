@@ -90,6 +90,62 @@ typedef const C2_CONST_AS LevelTab* LevelTabP;
 typedef const C2_CONST_AS Geom* GeomP;
 typedef const C2_CONST_AS Strides* StridesP;
 
+// Perturbed-parameter ensembles (cloudsc2_{nl,tl,vjp}_launch_ens): K members, each with an argument block of its own in DEVICE
+// MEMORY -- NlArgs, TlParArgs or AdParArgs, the column functions read it through the same constant-address-space pointer -- which
+// ens_args_kernel derives from one template block (the host's, built from the caller's parameter block with the base pointers): every
+// pointer advanced by member x that field's member stride (elements; 0: the members share the field), the constants from the member's
+// row of the (K, 4) parameter array (ens_consts).
+struct EnsStrides {
+  long long in[16], out[10];    // the trajectory's inputs and outputs, in the order of InPtrs / OutPtrs
+  long long in2[16], out2[10];  // TL: the input and output tangents; reverse sweep: the input and output adjoints
+  long long ckpt;               // the cover-checkpoint plane
+};
+static_assert(sizeof(InPtrs) == 16 * sizeof(void*) && sizeof(InPtrsRW) == sizeof(InPtrs) && sizeof(OutPtrs) == 10 * sizeof(void*),
+              "the pointer blocks are arrays of 16 / 10 pointers");
+template <class Ptrs>
+C2_HD void ens_advance_ptrs(Ptrs& p, const long long* stride, long long member) {
+  real_t** q = (real_t**)&p;
+  for (int i = 0; i < (int)(sizeof(Ptrs) / sizeof(void*)); ++i)
+    if (q[i]) q[i] += member * stride[i];
+}
+C2_HD void ens_advance(NlArgs& a, const EnsStrides& m, long long member) {
+  ens_advance_ptrs(a.in, m.in, member);
+  ens_advance_ptrs(a.out, m.out, member);
+  if (a.ckpt) a.ckpt += member * m.ckpt;
+}
+C2_HD void ens_advance(TlParArgs& a, const EnsStrides& m, long long member) {
+  ens_advance_ptrs(a.a.in, m.in, member);
+  ens_advance_ptrs(a.a.din, m.in2, member);
+  ens_advance_ptrs(a.a.dout, m.out2, member);
+}
+C2_HD void ens_advance(AdParArgs& a, const EnsStrides& m, long long member) {  // (work: one (PAR_COUNT, ncols_pad) slab per member)
+  ens_advance(a.a.nl, m, member);
+  ens_advance_ptrs(a.a.ain, m.in2, member);
+  ens_advance_ptrs(a.a.aout, m.out2, member);
+  a.work += member * (long long)PAR_COUNT * a.a.nl.g.ncols_pad;
+}
+C2_HD Consts& ens_consts_of(NlArgs& a) { return a.c; }
+C2_HD Consts& ens_consts_of(TlParArgs& a) { return a.a.c; }
+C2_HD Consts& ens_consts_of(AdParArgs& a) { return a.a.nl.c; }
+C2_HD ParLin* ens_parlin_of(NlArgs&) { return nullptr; }
+C2_HD ParLin* ens_parlin_of(TlParArgs& a) { return &a.par; }
+C2_HD ParLin* ens_parlin_of(AdParArgs& a) { return &a.par; }
+// member `member`'s block from the template: what thread `member` of ens_args_kernel stores (dpar: the member's four parameter
+// tangents, or NULL)
+template <class Args>
+C2_HD void ens_member_args(Args& a, const Args& tmpl, const EnsStrides& m, double ptsphy, long long member, const double* par,
+                           const double* dpar) {
+  a = tmpl;
+  ens_advance(a, m, member);
+  ens_consts(ens_consts_of(a), ptsphy, par, dpar, ens_parlin_of(a));
+}
+// The ensemble sweeps' grid is members x wgs_per_member workgroups of `block` threads: workgroup b works for member b / wgs_per_member
+// on that member's columns from (b mod wgs_per_member) x block on (a member's last workgroup may be partly idle; no wave spans two members).
+C2_HD void ens_locate(unsigned wg, unsigned wgs_per_member, unsigned thread, unsigned block, unsigned& member, long long& column) {
+  member = wg / wgs_per_member;
+  column = (long long)(wg - member * wgs_per_member) * block + thread;
+}
+
 // Per-lane offsets of the column inside each layout group.  LaneOff: element offsets (64 bit).  LaneOff32: BYTE offsets
 // in 32 bits, usable when every buffer is smaller than 4 GiB (C2F_OFF32): the accesses then take the
 // `global_load v, v_off32, s[base]` form -- no 64-bit address arithmetic per access, half the offset registers.

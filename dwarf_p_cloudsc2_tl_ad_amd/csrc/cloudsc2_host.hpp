@@ -8,7 +8,7 @@
 //   cloudsc2_driver.hip   the host-array drivers and the resident state
 //   cloudsc2_helpers.hip  host-only helpers of the C ABI (default parameters, offsets, validation text, the synthetic table, verdicts)
 //
-// The sweeps' kernels are in cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal}.hip (cloudsc2_sweep_kernels.hpp).  A __global__ kernel stays in the unit
+// The sweeps' kernels are in cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal,nl_ens,tl_ens,vjp_ens}.hip (cloudsc2_sweep_kernels.hpp).  A __global__ kernel stays in the unit
 // that launches it: without relocatable device code a kernel cannot be launched by name from another unit's code object.  Everything
 // here has external linkage inside namespace cloudsc2; the link's version script (cloudsc2_hip.map) keeps it out of the dynamic symbol
 // table, where only the C ABI appears.

@@ -21,6 +21,9 @@
 #include "cloudsc2_kern_vjp_par.hip"
 #include "cloudsc2_kern_tl_parjac.hip"
 #include "cloudsc2_kern_parnormal.hip"
+#include "cloudsc2_kern_nl_ens.hip"
+#include "cloudsc2_kern_tl_ens.hip"
+#include "cloudsc2_kern_vjp_ens.hip"
 #endif
 
 using namespace cloudsc2;
@@ -29,7 +32,7 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------------------
 // kernels: the sweeps' __global__ wrappers and their variant tables are cloudsc2_sweep_kernels.hpp + the family units
-// cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
+// cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal,nl_ens,tl_ens,vjp_ens}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
 // ---------------------------------------------------------------------------------------------------------
 template <bool P>
 __global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
@@ -71,6 +74,25 @@ par_fold_rows_kernel(const double* __restrict__ work, long long ncols_pad, long 
   }
   fold_row(work, ncols_pad, ngptot, sums);
 }
+// The fold of cloudsc2_vjp_launch_ens: grid (PAR_COUNT, members), member blockIdx.y's rows folded like par_fold_kernel folds them.
+__global__ void __launch_bounds__(kParFoldBlock)
+par_fold_ens_kernel(const double* __restrict__ work, long long ncols_pad, long long ngptot, double* __restrict__ par_adj) {
+  fold_row(work + (long long)blockIdx.y * PAR_COUNT * ncols_pad, ncols_pad, ngptot, par_adj + (long long)blockIdx.y * PAR_COUNT);
+}
+
+// The first kernel of every ensemble launcher: thread k writes member k's argument block to the workspace (ens_member_args: the template
+// block with its pointers advanced and its constants derived from row k of `params`, and of `dparams` if given; plain stores).
+constexpr int kEnsArgsBlock = 64;
+template <class Args>
+__global__ void __launch_bounds__(kEnsArgsBlock)
+ens_args_kernel(Args tmpl, EnsStrides ms, double ptsphy, int members, const double* __restrict__ params,
+                const double* __restrict__ dparams, Args* __restrict__ blocks) {
+  const long long k = (long long)blockIdx.x * kEnsArgsBlock + threadIdx.x;
+  if (k >= members) return;
+  ens_member_args(blocks[k], tmpl, ms, ptsphy, k, params + k * PAR_COUNT, dparams ? dparams + k * PAR_COUNT : nullptr);
+}
+static_assert(sizeof(AdParArgs) + sizeof(EnsStrides) + 64 <= 4096 && sizeof(TlParArgs) + sizeof(EnsStrides) + 64 <= 4096,
+              "ens_args_kernel's arguments fit the kernel-argument segment");
 
 // ---------------------------------------------------------------------------------------------------------
 // Data-format kernels either side of the path: the input file holds KLON (=100) columns,
@@ -552,11 +574,45 @@ struct Sweep {
   }
 };
 
+// What an ensemble launcher hands its parent's implementation: the parent checks the call and builds the argument block exactly as for
+// its own launch (from the caller's parameter block: the template), then ens_launch runs it for `members` members instead.
+struct EnsSpec {
+  int members;
+  const double* params;   // device, (members, PAR_COUNT)
+  const double* dparams;  // device, (members, PAR_COUNT): the parameter tangents (TL), else NULL
+  EnsStrides ms;
+  void* workspace;        // device, cloudsc2_ens_workspace_bytes()
+  double* par_adj;        // device, (members, PAR_COUNT): the parameter adjoints (reverse sweep), else NULL
+};
+const Geom& geom_of(const NlArgs& a) { return a.g; }
+const Geom& geom_of(const TlParArgs& a) { return a.a.g; }
+const Geom& geom_of(const AdParArgs& a) { return a.a.nl.g; }
+constexpr size_t kEnsBlockBytes = std::max({sizeof(NlArgs), sizeof(TlParArgs), sizeof(AdParArgs)});
+size_t ens_blocks_bytes(int members) { return ((size_t)members * kEnsBlockBytes + 255) / 256 * 256; }
+
+// Two launches, neither paced nor logged: the members' argument blocks, then the sweep over members x ceil(ncols_pad / kBlock) workgroups.
+template <class Args>
+int ens_launch(KernelFn<EnsArgs<Args>> fn, const Args& tmpl, double ptsphy, const EnsSpec& e, hipStream_t st) {
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  const Geom& g = geom_of(tmpl);
+  const unsigned wgs = grid_for(g.ncols_pad, kBlock);
+  if ((long long)wgs * e.members > 0x7fffffffLL) return fail(CLOUDSC2_EINVAL, "ensemble: members x workgroups per member exceeds the grid limit");
+  Args* blocks = (Args*)e.workspace;
+  hipLaunchKernelGGL(ens_args_kernel<Args>, dim3(grid_for(e.members, kEnsArgsBlock)), dim3(kEnsArgsBlock), 0, st, tmpl, e.ms, ptsphy, e.members,
+                     e.params, e.dparams, blocks);
+  HIP_TRY(hipGetLastError());
+  EnsArgs<Args> a;
+  a.blocks = blocks; a.wgs_per_member = wgs;
+  void* argv[] = {&a};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(wgs * (unsigned)e.members), dim3(kBlock), argv, 0, st));
+  return 0;
+}
+
 // pert_in == NULL: the increments are 0.01*x of the trajectory inputs (supsat_inc * PSUPSAT for PSUPSAT), C2F_SELFINC
 // satlin: SATUR is differentiated in the sweep (C2F_SATLIN): no qsat on either input side, no trajectory stores
 int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
                    const cloudsc2_outputs* traj_out, const cloudsc2_inputs* pert_in, double supsat_inc, const cloudsc2_outputs* pert_out,
-                   double* yy, void* stream, bool satlin = false, const double* dpar = nullptr) {
+                   double* yy, void* stream, bool satlin = false, const double* dpar = nullptr, const EnsSpec* ens = nullptr) {
   Sweep w;
   int rc = w.begin(prm, nproma, nlev, ngptot, (!traj_in || !traj_out || !pert_out) ? "NULL argument block" : nullptr);
   if (rc) return rc;
@@ -588,6 +644,12 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   // -3.7 % at 160 000 columns with the waves kept abreast; the fp64 TL and both adjoints run one wave per SIMD and lose 1-5 %
   // (profiles/r03_wave_times.txt); they are paced instead
   if (dpar) w.f |= C2F_PARLIN;  // (its launcher passes pert_in and no trajectory outputs)
+  if (ens) {  // (with dpar, which the members' rows replace: the template's ParLin is overwritten whole)
+    TlParArgs pargs;
+    pargs.a = args;
+    pargs.par = make_parlin(w.c, dpar);
+    return ens_launch(tl_ens_variant(w.f), pargs, ptsphy, *ens, (hipStream_t)stream);
+  }
   const void* tl = dpar ? (const void*)tl_par_variant(w.f) : (const void*)tl_variant(w.f);
   const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);
   schedule(args.g, abreast ? tl : nullptr, false, abreast ? nullptr : tl);
@@ -612,6 +674,7 @@ struct AdMode {
   bool satlin = false;
   double* par_work = nullptr;  // the vector-Jacobian product with the parameter adjoints (C2F_PARLIN): the workspace and the result
   double* par_adj = nullptr;
+  const EnsSpec* ens = nullptr;  // the launch runs for the members of an ensemble (which 1, or the parameter form of which 2)
 };
 
 int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
@@ -664,6 +727,8 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   const unsigned f_fwd = (f & ~C2F_ASSIGN) | (w.c.evap ? C2F_CKPT : 0u);
   const void* fwd = (const void*)nl_variant(f_fwd);
   const void* rev = (const void*)ad_reverse_variant(f);
+  if (m.ens && m.which == 1) return ens_launch(nl_ens_variant(f_fwd), args.nl, ptsphy, *m.ens, st);
+  if (m.ens && !m.par_work) return fail(CLOUDSC2_EINVAL, "ensemble: the trajectory pass or the parameter form of the reverse sweep");
   if (m.which == 1) {
     schedule(args.nl.g, fwd, false, nullptr);
     return launch_variant(kFamNl, f_fwd, nl_variant(f_fwd), args.nl, n, st);
@@ -671,6 +736,17 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   if (m.par_work) {  // the reverse sweep with the parameter sums, then their fold
     if (!m.vjp || !m.par_adj) return fail(CLOUDSC2_EINVAL, "parameter adjoints: the vector-Jacobian product, with workspace and result");
     f |= C2F_PARLIN;
+    if (m.ens) {  // (par_work: the first member's slab)
+      AdParArgs pargs;
+      pargs.a = args;
+      pargs.par = make_parlin(w.c, nullptr);
+      pargs.work = m.par_work;
+      if ((rc = ens_launch(vjp_ens_variant(f), pargs, ptsphy, *m.ens, st))) return rc;
+      hipLaunchKernelGGL(par_fold_ens_kernel, dim3(PAR_COUNT, (unsigned)m.ens->members), dim3(kParFoldBlock), 0, st, (const double*)m.par_work, n,
+                         (long long)w.g.ngptot, m.par_adj);
+      HIP_TRY(hipGetLastError());
+      return 0;
+    }
     schedule(args.nl.g, nullptr, false, (const void*)vjp_par_variant(f));
     AdParArgs pargs;
     pargs.a = args;
@@ -1159,6 +1235,87 @@ int cloudsc2_vjp_launch_par(const cloudsc2_params* prm, double ptsphy, int nprom
   if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
                         stream, AdMode{2, true, true, nullptr, nullptr, satur != 0, work, par_adj});
+}
+
+// ---- perturbed-parameter ensembles: the three launchers above for `members` members, the parameters read on the device ----------------
+namespace {
+int check_ens(const cloudsc2_params* prm, int satur, int members, const double* params_dev, const void* workspace) {
+  if (satur != 0 && satur != 1) return fail(CLOUDSC2_EINVAL, "satur must be 0 (qsat given) or 1 (SATUR differentiated in the sweep)");
+  if (members < 1 || members > 65535) return fail(CLOUDSC2_EINVAL, "ensemble: 1 <= members <= 65535 required");
+  if (!params_dev || !workspace) return fail(CLOUDSC2_EINVAL, "ensemble: the parameter array and the workspace are required");
+  if (prm && !prm->lphylin) return fail(CLOUDSC2_EINVAL, "ensemble: CLOUDSC2TL / CLOUDSC2AD linearise the LPHYLIN form only (prm->lphylin = 0)");
+  return 0;
+}
+// a block the members WRITE (n fields from `first` on): with more than one member no field may be shared (member stride 0), the
+// members would write over each other; then the device check, as in check_par
+static_assert(sizeof(cloudsc2_inputs) == 16 * sizeof(cloudsc2_field) && sizeof(cloudsc2_outputs) == 10 * sizeof(cloudsc2_field), "blocks of fields");
+int check_ens_written(const cloudsc2_field* first, int n, const long long* mstride, int members) {
+  for (int i = 0; first && members > 1 && i < n; ++i)
+    if (first[i].ptr && (!mstride || mstride[i] == 0))
+      return fail(CLOUDSC2_EINVAL, "ensemble: a field the members write has member stride 0 (every member needs its own)");
+  return require_device();
+}
+void ens_copy(long long* dst, const long long* src, int n) {
+  for (int i = 0; i < n; ++i) dst[i] = src ? src[i] : 0;
+}
+}  // namespace
+
+long long cloudsc2_ens_workspace_bytes(int members, int nproma, int nlev, int ngptot) {
+  if (members < 1 || members > 65535 || nproma < 1 || nlev < 2 || nlev > CLOUDSC2_MAX_NLEV || ngptot < 1)
+    return fail(CLOUDSC2_EINVAL, "1 <= members <= 65535, nproma >= 1, 2 <= nlev <= CLOUDSC2_MAX_NLEV, ngptot >= 1 required");
+  const long long ncols_pad = (((long long)ngptot + nproma - 1) / nproma) * nproma;
+  return (long long)ens_blocks_bytes(members) + (long long)members * PAR_COUNT * ncols_pad * (long long)sizeof(double);
+}
+
+int cloudsc2_nl_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int members, const double* params_dev,
+                           const cloudsc2_inputs* traj_in, const long long* traj_in_mstride, const cloudsc2_outputs* traj_out,
+                           const long long* traj_out_mstride, cloudsc2_real* scratch, long long scratch_mstride, void* workspace,
+                           void* stream) {
+  if (int rc = check_ens(prm, 0, members, params_dev, workspace)) return rc;
+  if (scratch && members > 1 && scratch_mstride == 0) return fail(CLOUDSC2_EINVAL, "ensemble: the cover-checkpoint plane has member stride 0");
+  if (int rc = check_ens_written(traj_out ? &traj_out->tent : nullptr, 10, traj_out_mstride, members)) return rc;
+  EnsSpec e = {members, params_dev, nullptr, {}, workspace, nullptr};
+  ens_copy(e.ms.in, traj_in_mstride, 16); ens_copy(e.ms.out, traj_out_mstride, 10);
+  ens_copy(e.ms.in2, nullptr, 16); ens_copy(e.ms.out2, nullptr, 10);
+  e.ms.ckpt = scratch_mstride;
+  AdMode m{1, false, false};
+  m.ens = &e;
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, nullptr, nullptr, scratch, stream, m);
+}
+
+int cloudsc2_tl_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
+                           const double* params_dev, const double* dparams_dev, const cloudsc2_inputs* traj_in,
+                           const long long* traj_in_mstride, const cloudsc2_inputs* pert_in, const long long* pert_in_mstride,
+                           const cloudsc2_outputs* pert_out, const long long* pert_out_mstride, void* workspace, void* stream) {
+  if (int rc = check_ens(prm, satur, members, params_dev, workspace)) return rc;
+  if (int rc = check_ens_written(pert_out ? &pert_out->tent : nullptr, 10, pert_out_mstride, members)) return rc;
+  if (!pert_in || !dparams_dev) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
+  EnsSpec e = {members, params_dev, dparams_dev, {}, workspace, nullptr};
+  ens_copy(e.ms.in, traj_in_mstride, 16); ens_copy(e.ms.out, nullptr, 10);
+  ens_copy(e.ms.in2, pert_in_mstride, 16); ens_copy(e.ms.out2, pert_out_mstride, 10);
+  e.ms.ckpt = 0;
+  const cloudsc2_outputs none = {};
+  const double no_tangent[PAR_COUNT] = {};  // (the template's; every member's come from dparams_dev)
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_in, 0.0, pert_out, nullptr, stream, satur != 0, no_tangent, &e);
+}
+
+int cloudsc2_vjp_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
+                            const double* params_dev, const cloudsc2_inputs* traj_in, const long long* traj_in_mstride,
+                            const cloudsc2_outputs* traj_out, const long long* traj_out_mstride, const cloudsc2_inputs* adj_in,
+                            const long long* adj_in_mstride, const cloudsc2_outputs* adj_out, const long long* adj_out_mstride,
+                            const cloudsc2_real* scratch, long long scratch_mstride, void* workspace, double* par_adj, void* stream) {
+  if (int rc = check_ens(prm, satur, members, params_dev, workspace)) return rc;
+  if (int rc = check_ens_written(adj_in ? &adj_in->paph : nullptr, 16, adj_in_mstride, members)) return rc;
+  if (!par_adj) return fail(CLOUDSC2_EINVAL, "the parameter adjoints' array is required");
+  if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
+  EnsSpec e = {members, params_dev, nullptr, {}, workspace, par_adj};
+  ens_copy(e.ms.in, traj_in_mstride, 16); ens_copy(e.ms.out, traj_out_mstride, 10);
+  ens_copy(e.ms.in2, adj_in_mstride, 16); ens_copy(e.ms.out2, adj_out_mstride, 10);
+  e.ms.ckpt = scratch_mstride;
+  AdMode m{2, true, true, nullptr, nullptr, satur != 0, (double*)((char*)workspace + ens_blocks_bytes(members)), par_adj};
+  m.ens = &e;
+  return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch), stream, m);
 }
 
 int cloudsc2_batch_max(void) { return kBatchMax; }

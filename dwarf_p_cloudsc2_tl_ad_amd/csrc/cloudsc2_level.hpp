@@ -303,6 +303,42 @@ inline ParLin make_parlin(const Consts& c, const double* dpar) {
   return p;
 }
 
+// The ensemble launchers' counterpart of the three host functions above, for the device (and the host, which tests it): `c` is a Consts
+// built by make_consts from the caller's parameter block; every member that depends on RKCONV, RCLCRIT, RLPTRC or RPECONS is rewritten
+// from par[] (PAR_* order) -- the expressions of make_consts and fill_stage_blocks in their order, so that the bytes are those the host
+// builds for a parameter block holding these four values -- and *pl, if given, is make_parlin(c, dpar) (dpar may be NULL).  `ptsphy` is
+// the double make_consts was given (c.ptsphy is its real_t rounding).
+C2_HD void ens_consts(Consts& c, double ptsphy, const double* par, const double* dpar, ParLin* pl) {
+  const double rkconv = par[PAR_RKCONV], rclcrit = par[PAR_RCLCRIT];
+  c.rpecons = par[PAR_RPECONS]; c.rlptrc = par[PAR_RLPTRC];
+  c.zckcodtl = RC(2.0) * rkconv * ptsphy;
+  c.zckcodti = RC(5.0) * rkconv * ptsphy;
+  c.zckcodtla = c.zckcodtl / RC(100.0);
+  c.zckcodtia = c.zckcodti / RC(100.0);
+  c.zlcrit_l = c.evap ? RC(1.9) * rclcrit : rclcrit * RC(2.0);
+  c.zlcrit_i = c.evap ? RC(1.e-04) : rclcrit * RC(2.0);
+  c.zlcrit_l_r = RC(1.0) / c.zlcrit_l;
+  c.zlcrit_i_r = RC(1.0) / c.zlcrit_i;
+  c.k0.v[K0_RLPTRC] = c.rlptrc;
+  real_t* k = c.k3.v;
+  k[K3_ZLCRIT_L_R] = c.zlcrit_l_r; k[K3_ZCKCODTL] = c.zckcodtl; k[K3_ZLCRIT_I_R] = c.zlcrit_i_r; k[K3_ZCKCODTI] = c.zckcodti;
+  k[K3_ZLCRIT_L] = c.zlcrit_l; k[K3_ZLCRIT_I] = c.zlcrit_i;
+  c.kt1.v[KT1_ZLCRIT_L_R2] = c.zlcrit_l_r * c.zlcrit_l_r;
+  c.kt1.v[KT1_ZLCRIT_I_R2] = c.zlcrit_i_r * c.zlcrit_i_r;
+  c.kt2.v[KT2_CK_L] = c.lregcl ? c.zckcodtla : c.zckcodtl;
+  c.kt2.v[KT2_CK_I] = c.lregcl ? c.zckcodtia : c.zckcodti;
+  if (!pl) return;
+  ParLin& p = *pl;
+  for (int i = 0; i < PAR_COUNT; ++i) p.dpar[i] = dpar ? (real_t)dpar[i] : RC(0.0);
+  p.dck_l = RC(2.0) * c.ptsphy;
+  p.dck_i = RC(5.0) * c.ptsphy;
+  const real_t dlc_l = c.evap ? RC(1.9) : RC(2.0), dlc_i = c.evap ? RC(0.0) : RC(2.0);
+  p.crc_l = -RC(2.0) * c.zckcodtl * dlc_l * (c.zlcrit_l_r * c.zlcrit_l_r * c.zlcrit_l_r);
+  p.crc_i = -RC(2.0) * c.zckcodti * dlc_i * (c.zlcrit_i_r * c.zlcrit_i_r * c.zlcrit_i_r);
+  p.rpecons_r = c.evap ? RC(1.0) / c.rpecons : RC(0.0);
+  p.spare[0] = p.spare[1] = p.spare[2] = RC(0.0);
+}
+
 // Raw inputs of one level (dummy arguments of CLOUDSC2 at (JL,JK); cloudsc2.F90:124-143).
 struct LevelIn {
   real_t paph_k, paph_k1;  // PAPHP1(JK), PAPHP1(JK+1)

@@ -1,6 +1,6 @@
 // cloudsc2_sweep_kernels.hpp -- the __global__ wrappers of the column sweeps (NL, TL, AD, the Taylor test's lambda sweep), their
 // compile-time variant tables and what they share.  The sweeps are built as one translation unit per kernel family so that an edit to
-// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal}.hip, each of which
+// one sweep does not rebuild every variant table (448 slots, ~70 s as one unit): cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal,nl_ens,tl_ens,vjp_ens}.hip, each of which
 // instantiates its table and exports it through one accessor (nl_variant(F) ...); the host units are listed in cloudsc2_host.hpp.
 // -DC2_SINGLE_TU puts the sweeps and their launchers into ONE code object again (cloudsc2_launch.hip then includes the family files):
 // the experiment builds of `make variant`, `make asm`, `make resources` and the -DC2_WAVE_TIMES diagnostic, whose log pointer is a
@@ -128,6 +128,57 @@ constexpr bool par_variant_valid(unsigned f, unsigned form) {
   return rest == (C2F_PARLIN | form | C2F_QSAT) || rest == (C2F_PARLIN | form | C2F_SATLIN);
 }
 
+// The ensemble forms (units cloudsc2_kern_{nl,tl,vjp}_ens.hip): the same columns again, under their parents' launch bounds, over an
+// argument block that lives in device memory -- one per member, written by ens_args_kernel (cloudsc2_launch.hip) in the launch before.
+// The block's address comes from blockIdx and the kernel arguments alone (ens_locate), so it is workgroup-uniform and the constants
+// are scalar loads as before: through the scalar cache from memory instead of from the kernel-argument segment.  Not sweep families:
+// no family number, no pacing (fair = 0, pace_* = 0 in every block), no launch-log entry; launched directly, like parnormal_kernel.
+template <class Args>
+struct EnsArgs {
+  const Args* blocks;        // [members]
+  unsigned wgs_per_member;   // ceil(ncols_pad / kBlock)
+};
+typedef EnsArgs<NlArgs> NlEnsArgs;
+typedef EnsArgs<TlParArgs> TlEnsArgs;
+typedef EnsArgs<AdParArgs> VjpEnsArgs;
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class Args>
+__device__ __forceinline__ const C2_CONST_AS Args* ens_block(const C2_CONST_AS EnsArgs<Args>* e, long long& column) {
+  unsigned member;
+  ens_locate(blockIdx.x, e->wgs_per_member, threadIdx.x, blockDim.x, member, column);
+  return (const C2_CONST_AS Args*)(e->blocks + member);
+}
+#endif
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, (F & C2F_EVAP) ? 1 : 3) nl_ens_kernel(NlEnsArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  long long column;
+  const C2_CONST_AS NlArgs* a = ens_block(kernarg<NlEnsArgs>(), column);
+  nl_column<F>(column, a);
+#endif
+}
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, (sizeof(real_t) == 4 && (F & C2F_OFF32) && !(F & C2F_EVAP)) ? 3 : 1)
+tl_ens_kernel(TlEnsArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  long long column;
+  const C2_CONST_AS TlParArgs* a = ens_block(kernarg<TlEnsArgs>(), column);
+  tl_column<F>(column, &a->a);
+#endif
+}
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) vjp_ens_kernel(VjpEnsArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  long long column;
+  const C2_CONST_AS AdParArgs* a = ens_block(kernarg<VjpEnsArgs>(), column);
+  ad_reverse_column<F>(column, &a->a);
+#endif
+}
+// the NL words cloudsc2_ad_launch_forward can produce: QSAT, PRECISE, OFF32 free, the cover checkpoint exactly with the evaporation branch
+constexpr bool nl_ens_variant_valid(unsigned f) {
+  return (f & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_CKPT | C2F_OFF32)) == 0 && ((f & C2F_CKPT) != 0) == ((f & C2F_EVAP) != 0);
+}
+
 // The batched TL and reverse sweeps (tl_batch_column, vjp_batch_column: up to kBatchMax directions over one trajectory).  One wave
 // per SIMD in fp64 like their single-direction twins, whose registers they extend by the carries of the further directions and one
 // more set of direction inputs; the fp32 builds take what they need (nothing is measured for them yet).
@@ -204,5 +255,8 @@ KernelFn<TlBatchArgs> tl_batch_variant(unsigned f, int directions);
 KernelFn<VjpBatchArgs> vjp_batch_variant(unsigned f, int directions);
 KernelFn<TlParJacArgs> tl_parjac_variant(unsigned f);
 KernelFn<ParNormalArgs> parnormal_variant(unsigned f);
+KernelFn<NlEnsArgs> nl_ens_variant(unsigned f);
+KernelFn<TlEnsArgs> tl_ens_variant(unsigned f);
+KernelFn<VjpEnsArgs> vjp_ens_variant(unsigned f);
 
 }  // namespace cloudsc2

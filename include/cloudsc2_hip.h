@@ -401,6 +401,45 @@ int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int npr
                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* resid, const cloudsc2_outputs* weight,
                               double* work, double* normal /* device, [CLOUDSC2_NNORMAL] */, void* stream);
 
+/* Perturbed-parameter ensembles: `members` parameter sets over one state (or one state each) in ONE call, the four parameters read on the
+ * DEVICE.  The launchers above carry the parameters inside the constants of the kernel-argument segment, so the host must know their
+ * values; these three put one argument block per member into device memory instead: a first kernel derives member k's block from the
+ * template the host builds from prm (pointers advanced by k x the field's member stride, constants from row k of params_dev, the
+ * expressions of the host's derivation in their order), the sweep then runs members x ceil(ncols_pad / 128) workgroups, workgroup b for
+ * member b / ceil(ncols_pad / 128).  Member k's results are the bits the parent launcher gives for a prm holding row k's values:
+ *   cloudsc2_nl_launch_ens   cloudsc2_ad_launch_forward (the NL sweep, with the cover checkpoint when LEVAPLS2 .OR. LDRAIN1D),
+ *   cloudsc2_tl_launch_ens   cloudsc2_tl_launch_par, the parameter tangents row k of dparams_dev,
+ *   cloudsc2_vjp_launch_ens  cloudsc2_vjp_launch_par, the parameter adjoints assigned to row k of par_adj; its fold runs once per member
+ *                            in cloudsc2_vjp_launch_par's order.
+ *   params_dev, dparams_dev, par_adj   device, (members, CLOUDSC2_NPAR) doubles in CLOUDSC2_NPAR order; read / written by the kernels only.
+ *   *_mstride   per argument block an array of member strides in ELEMENTS, one per field in the order of the block's struct (16 for
+ *               cloudsc2_inputs, 10 for cloudsc2_outputs); 0: all members share the field; NULL: all zero.  The block itself holds
+ *               member 0's pointers and the block strides, which all members share.  A field the members write (traj_out and scratch of the NL
+ *               sweep, pert_out, adj_in) must not be shared by more than one member: CLOUDSC2_EINVAL.
+ *   scratch, scratch_mstride   the cover-checkpoint plane(s), as for the parents (required with the evaporation branch).
+ *   workspace   device, cloudsc2_ens_workspace_bytes() bytes, the caller's, 256-byte aligned: the members' argument blocks and, for
+ *               the reverse sweep, members x CLOUDSC2_NPAR x the padded column count doubles.  One query serves all three.
+ *   With the evaporation branch every member's rpecons must not be 0; the values live on the device, so this is NOT checked.
+ * 1 <= members <= 65535 and members x ceil(ncols_pad / 128) < 2^31, else CLOUDSC2_EINVAL; prm->lphylin = 0: CLOUDSC2_EINVAL; the other
+ * errors are the parents'.  No launcher allocates, copies or synchronises (apart from the CETA table of a grid's first use); each is two
+ * plain kernel nodes in a chain under stream capture, the reverse sweep three.  They are not paced (fair = 0, no pacing fields), are no
+ * kernel family of cloudsc2_variant_built / cloudsc2_kernel_occupancy and do not appear in the launch log. */
+long long cloudsc2_ens_workspace_bytes(int members, int nproma, int nlev, int ngptot); /* < 0: CLOUDSC2_EINVAL */
+int cloudsc2_nl_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int members,
+                           const double* params_dev, const cloudsc2_inputs* traj_in, const long long* traj_in_mstride,
+                           const cloudsc2_outputs* traj_out, const long long* traj_out_mstride, cloudsc2_real* scratch,
+                           long long scratch_mstride, void* workspace, void* stream);
+int cloudsc2_tl_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
+                           const double* params_dev, const double* dparams_dev, const cloudsc2_inputs* traj_in,
+                           const long long* traj_in_mstride, const cloudsc2_inputs* pert_in, const long long* pert_in_mstride,
+                           const cloudsc2_outputs* pert_out, const long long* pert_out_mstride, void* workspace, void* stream);
+int cloudsc2_vjp_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
+                            const double* params_dev, const cloudsc2_inputs* traj_in, const long long* traj_in_mstride,
+                            const cloudsc2_outputs* traj_out, const long long* traj_out_mstride, const cloudsc2_inputs* adj_in,
+                            const long long* adj_in_mstride, const cloudsc2_outputs* adj_out /* read only */,
+                            const long long* adj_out_mstride, const cloudsc2_real* scratch, long long scratch_mstride, void* workspace,
+                            double* par_adj, void* stream);
+
 /* Several tangents or cotangents over ONE trajectory -- a Jacobian block, a singular-vector iteration, an ensemble of perturbations.
  * cloudsc2_tl_launch_batch replaces nbatch calls of cloudsc2_tl_launch without trajectory stores (traj_out all NULL),
  * cloudsc2_vjp_launch_batch nbatch calls of cloudsc2_vjp_launch, over the same traj_in: every direction's results are the bits those
