@@ -6,13 +6,17 @@ the per-class error metric with bounds measured on the reference alone.
 * ``Classes``      class = the active cells that share one outcome of one signature bit; threshold cells taken out;
 * ``Bounds``       floor(f, c): the reference's own response to a one-ulp perturbation of every input, per field and class;
                    K = the accepted whole-field tolerance over the largest whole-field floor; bound(f, c) = K floor(f, c), never
-                   looser than the whole-field bound.
+                   looser than the whole-field bound.  In an fp32 process (B.SINGLE): E(f, c) = the larger of the error of the
+                   reference's -DSINGLE build against the fp64 reference on the same values and its response to one fp32 ulp of
+                   every input; bound(f, c) = ERR_FACTOR E(f, c) on |ours - fp64 reference| (Case._init_single).
 
 Nothing here is imported by the package.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
+import dataclasses
 import functools
 import os
 import subprocess
@@ -26,7 +30,11 @@ TLAD_TOL = 1e-11
 MIN_CELLS = 32    # every class, before and after the exclusion of threshold cells
 MAX_EXCLUDED = 0.05
 
-CENSUS_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_census_sp.so" if B.SINGLE else "libhostcheck_census.so")
+# the census in both precisions, side by side: an fp32 process also asks the fp64 build about the same (fp32-rounded) inputs
+CENSUS_LIBS = {False: os.path.join(HOSTCHECK_DIR, "libhostcheck_census.so"), True: os.path.join(HOSTCHECK_DIR, "libhostcheck_census_sp.so")}
+CENSUS_LIB = CENSUS_LIBS[B.SINGLE]
+if B.SINGLE:
+    from tests.single_checks import ERR_FACTOR  # the project's "as accurate as the reference's -DSINGLE" factor (4)
 
 # name -> bit of the signature word (hostcheck_census.hip); "regime" is the two-bit field at 4
 BITS = {"cold": 0, "esdp_clip": 1, "qlim_is_qs": 2, "below_rtice": 3, "llo1": 6, "llo3": 7, "newmax": 8, "melt": 9, "warm2": 10,
@@ -43,37 +51,40 @@ EVAP_ONLY = ("llo2", "dpr_clip", "llo2&dpr_clip")
 ONE_LEVEL = ("last=1",)
 
 
-def build_census() -> str:
+def build_census(single: bool = B.SINGLE) -> str:
+    lib = CENSUS_LIBS[single]
     src = os.path.join(HOSTCHECK_DIR, "hostcheck_census.hip")
     deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
         os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(CENSUS_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(CENSUS_LIB) for d in deps):
+    if (not os.path.exists(lib)) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", CENSUS_LIB, src])
-    return CENSUS_LIB
+                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if single else []) + ["-o", lib, src])
+    return lib
 
 
-_lib = None
+_libs = {}
 
 
-def census_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_census())
+def census_lib(single: bool = B.SINGLE):
+    """The census of the process's own precision; `single` given: of that precision (its field blocks then hold elements of that
+    size, see `census`)."""
+    if single not in _libs:
+        lib = C.CDLL(build_census(single))
         lib.hostcheck_census.argtypes = [C.POINTER(B.Params), C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs),
                                          C.POINTER(B.Outputs), C.c_void_p]
         lib.hostcheck_census.restype = C.c_longlong
         lib.hostcheck_satur.argtypes = [C.POINTER(B.Params), C.c_int, C.c_int, C.c_int, B.Field, B.Field, B.Field]
-        _lib = lib
-    return _lib
+        _libs[single] = lib
+    return _libs[single]
 
 
-def census(prm, st, qsat: np.ndarray | None = None, precise: int = 0):
+def census(prm, st, qsat: np.ndarray | None = None, precise: int = 0, single: bool = B.SINGLE):
     """Signature words (NBLOCKS, NLEV, NPROMA) of a state (0 in the padded tail), the state the walk left (its outputs are the
-    walk's LevelOut) and the number of cells where dpr_clip and reset differ."""
-    lib = census_lib()
+    walk's LevelOut) and the number of cells where dpr_clip and reset differ.  `single`: the precision of the census build; the
+    state and qsat hold elements of that precision."""
+    lib = census_lib(single)
     got = st.copy()
-    i, o = host_traj_blocks(got, qsat)
+    i, o = host_traj_blocks(got, qsat, real=np.float32 if single else np.float64)
     sig = np.zeros((st.nblocks, st.nlev, st.nproma), dtype=np.uint32)
     lib.hostcheck_set_precise(int(precise))
     try:
@@ -125,7 +136,10 @@ def atlas_table(nlev: int, ncol: int, seed: int) -> dict:
     ptsphy = float(tab["PTSPHY"])
     ztp2 = tab["PT"] + ptsphy * tab["TENDENCY_CML_T"]  # the first guess of level_forward
     thaw = col(3) & (ztp2 > 273.16) & (ztp2 < 292.0)
-    tab["PT"] = np.where(thaw, 275.16 + 10.0 ** u(-4.5, -1.5) - ptsphy * tab["TENDENCY_CML_T"], tab["PT"])
+    # (fp32: one ulp at 275 K is 3e-5 K, and an excess below 1e-3 K makes partial melt a threshold outcome in a tenth of its cells;
+    # the same number of draws, so the random stream of everything after it is the fp64 recipe's)
+    lo = -3.0 if B.SINGLE else -4.5
+    tab["PT"] = np.where(thaw, 275.16 + 10.0 ** u(lo, -1.5) - ptsphy * tab["TENDENCY_CML_T"], tab["PT"])
 
     # B and F: freezing and warm levels in turn below the 262 K level: the cold ones make snow, the warm ones melt all of it
     ztp2 = tab["PT"] + ptsphy * tab["TENDENCY_CML_T"]
@@ -185,16 +199,19 @@ TABLE_FIELDS = ("PT", "PQ", "PAP", "PAPH", "PLU", "PLUDE", "PMFU", "PMFD", "PCLV
                 "TENDENCY_CML_QL", "TENDENCY_CML_QI", "PSUPSAT")
 
 
+ULP = 2.0 ** -23 if B.SINGLE else 2.0 ** -52
+
+
 def one_ulp(a: np.ndarray, rng) -> np.ndarray:
-    """Every element times 1 + 2^-52 or 1 - 2^-52, the sign drawn from rng."""
-    return a * (1.0 + np.where(rng.integers(0, 2, size=a.shape) == 1, 1.0, -1.0) * 2.0 ** -52)
+    """Every element times 1 + ULP or 1 - ULP (2^-52; 2^-23 in an fp32 process, rounded to fp32), the sign drawn from rng."""
+    return (a * (1.0 + np.where(rng.integers(0, 2, size=a.shape) == 1, 1.0, -1.0) * ULP)).astype(a.dtype, copy=False)
 
 
 def perturbed_table(tab: dict, seed: int = 77) -> dict:
     rng = np.random.default_rng(seed)
     out = dict(tab)
     for n in TABLE_FIELDS:
-        out[n] = one_ulp(tab[n], rng)
+        out[n] = one_ulp(np.asarray(tab[n], dtype=B.REAL), rng).astype(np.float64)  # (fp32: one ulp of the value the state holds)
     return out
 
 
@@ -236,11 +253,12 @@ FLAG_SETS = {"plain": dict(), "lregcl": dict(lregcl=True), "levapls2": dict(leva
              "levapls2+lregcl": dict(levapls2=True, lregcl=True)}
 NPROMA, NGPTOT, NCOL, SEED = 32, 90, 96, 3
 DRAWS = 6  # sign patterns of the one-ulp perturbation
+F64 = np.float64
 FLUX = ("fplsl", "fplsn", "fhpsl", "fhpsn")
 
 
 def _inputs_of(tab: dict, ngptot: int) -> dict:
-    st = c2.state_from_table(tab, ngptot, ngptot, real=np.float64)
+    st = c2.state_from_table(tab, ngptot, ngptot, real=B.REAL)
     return refcall.block_inputs(st, 0, None)
 
 
@@ -255,6 +273,9 @@ class Case:
         self.prm = make_params(self.tab, **self.flags)
         self.st = c2.state_from_table(self.tab, NPROMA, NGPTOT)
         self.ptsphy = self.st.ptsphy
+        if B.SINGLE:
+            self._init_single()
+            return
         self.chk = checker()
         set_lib_params(self.chk, self.prm)
         # the reference on the state ...
@@ -290,12 +311,128 @@ class Case:
         chk.cloudsc2ad(self.ptsphy, cp(inp), x, cp(y))
         return dict(nl=nl, traj=traj, tl=tl, ad=x, y=y)
 
-    def reference_ad(self, x0: dict) -> dict:
-        """The checker's adjoint accumulated on the background x0 (PSUPSAT's is assigned, cloudsc2ad.F90:1733)."""
+    def reference_ad(self, x0: dict, satur: bool = False) -> dict:
+        """The checker's adjoint accumulated on the background x0 (PSUPSAT's is assigned, cloudsc2ad.F90:1733).  fp32: the fp64
+        reference's, with the yardstick E of the adjoint taken from both references' runs on the same x0 (RefWithError)."""
+        if B.SINGLE:
+            return self._reference_ad_single(x0, satur)
         set_lib_params(self.chk, self.prm)
         x = {n: a.copy() for n, a in x0.items()}
         self.chk.cloudsc2ad(self.ptsphy, {n: a.copy() for n, a in self.inp.items()}, x, {n: a.copy() for n, a in self.ref["y"].items()})
         return x
+
+    # -- fp32: two references, the fp64 one is the truth ------------------------------------------------------------------------
+    def _init_single(self):
+        """No golden fp32 data exists: the fp64 reference on the same fp32 values is the truth, and the yardstick is the error the
+        reference's own -DSINGLE build makes against it (P) or its response to one fp32 ulp of every input (U), whichever is
+        larger, over the state and DRAWS perturbed states.  Two sets: QSAT fed (the fp32 reference's SATUR, upcast for the fp64
+        run) and SATUR in the sweep (each reference its own SATUR)."""
+        self.chk32, self.chk64 = refcall.RefLib(single=True), refcall.RefLib()
+        self.chk = self.chk64
+        self._set_params()
+        self.inp = _inputs_of(self.tab, NGPTOT)
+        assert self.inp["pap"].dtype == np.float32
+        self.inp["qsat"] = self.chk32.satur(self.inp["pap"], self.inp["t"])
+        self.qsat = to_blocks(self.inp["qsat"], NPROMA)
+        self.dinp = {n: np.ascontiguousarray(a * B.REAL(0.01)) for n, a in self.inp.items()}
+        samples = [(self.inp, self.dinp, None)]
+        self.tab_p = []
+        for k in range(DRAWS):
+            rng = np.random.default_rng(78 + k)
+            tab_p = perturbed_table(self.tab, seed=177 + k)
+            inp_p = _inputs_of(tab_p, NGPTOT)
+            inp_p["qsat"] = one_ulp(self.inp["qsat"], rng)
+            dinp_p = {n: one_ulp(a, rng) for n, a in self.dinp.items()}
+            samples.append((inp_p, dinp_p, rng))
+            self.tab_p.append(tab_p)
+        self._runs, self.sets = {}, {}
+        for satur in (False, True):
+            runs = []
+            for inp, dinp, rng in samples:
+                # (the same sign patterns of the output adjoints in both sets)
+                runs.append(self._pair(inp, dinp, copy.deepcopy(rng), satur))
+            self._runs[satur] = runs
+            ref = dict(runs[0]["r64"], y=runs[0]["y"])
+            E = {(kind, f): self._error_of([r["r32"][kind][f] for r in runs], [r["r64"][kind][f] for r in runs])
+                 for kind in ("nl", "traj", "tl", "ad") for f in ref[kind]}
+            self.sets[satur] = dict(ref=ref, E=E)
+        self.ref = self.sets[False]["ref"]
+        self._classes()
+
+    def _set_params(self):
+        for chk in (self.chk32, self.chk64):
+            set_lib_params(chk, self.prm)
+
+    def _pair(self, inp, dinp, rng, satur: bool, x0: dict | None = None, y: dict | None = None) -> dict:
+        """Both references on identical values (satur: except QSAT, each its own SATUR's).  The output adjoints are the fp32
+        reference's TL outputs (one ulp off if rng), the same for both.  With x0 and y: the adjoint alone, accumulated on x0."""
+        up = lambda d: {n: np.ascontiguousarray(a, dtype=F64) for n, a in d.items()}  # noqa: E731
+        cp = lambda d: {n: a.copy() for n, a in d.items()}  # noqa: E731
+        c32, c64, pt = self.chk32, self.chk64, self.ptsphy
+        i32, i64 = cp(inp), up(inp)
+        if satur:
+            i32["qsat"], i64["qsat"] = c32.satur(i32["pap"], i32["t"]), c64.satur(i64["pap"], i64["t"])
+        r32, r64 = {}, {}
+        if y is None:
+            r32["nl"], r64["nl"] = c32.cloudsc2(pt, cp(i32)), c64.cloudsc2(pt, cp(i64))
+            (r32["traj"], r32["tl"]), (r64["traj"], r64["tl"]) = c32.cloudsc2tl(pt, cp(i32), cp(dinp)), c64.cloudsc2tl(pt, cp(i64), up(dinp))
+            y = {n: (one_ulp(a, rng) if rng is not None else a.copy()) for n, a in r32["tl"].items()}
+        x32 = ({n: np.ascontiguousarray(a, dtype=np.float32) for n, a in x0.items()} if x0 is not None
+               else refcall.new_inputs(self.nlev, NGPTOT, dtype=np.float32))
+        x64 = up(x32)
+        c32.cloudsc2ad(pt, cp(i32), x32, cp(y))
+        c64.cloudsc2ad(pt, cp(i64), x64, up(y))
+        r32["ad"], r64["ad"] = x32, x64
+        return dict(r32={k: up(d) for k, d in r32.items()}, r64=r64, y=y, inp=inp)
+
+    @staticmethod
+    def _error_of(s32: list, s64: list) -> np.ndarray:
+        """E per element: the larger of P = max over the samples |ref32 - ref64| and U = max over the draws |ref32(draw) -
+        ref32(state)|."""
+        p = np.max([np.abs(a - b) for a, b in zip(s32, s64)], axis=0)
+        u = np.max([np.abs(a - s32[0]) for a in s32[1:]], axis=0)
+        return np.maximum(p, u)
+
+    def _reference_ad_single(self, x0: dict, satur: bool) -> dict:
+        self._set_params()
+        runs = [self._pair(r["inp"], None, None, satur, x0=x0, y=r["y"]) for r in self._runs[bool(satur)]]
+        ref = RefWithError(runs[0]["r64"]["ad"])
+        ref.E = {f: self._error_of([r["r32"]["ad"][f] for r in runs], [r["r64"]["ad"][f] for r in runs]) for f in ref}
+        return ref
+
+    def refset(self, satur: bool = False) -> dict:
+        """The references a sweep is compared with and takes its output adjoints (`y`) from: one set in fp64; in fp32 the set
+        that matches where the sweep's QSAT comes from."""
+        return self.sets[bool(satur)]["ref"] if B.SINGLE else self.ref
+
+    def _compare_single(self, kind: str, got: dict, ref: dict | None, satur: bool):
+        """|got - ref64(state)| under ERR_FACTOR x E: over all cells of a field, and over the cells of every class."""
+        s = self.sets[bool(satur)]
+        ref = ref if ref is not None else s["ref"][kind]
+        E = ref.E if isinstance(ref, RefWithError) else {f: s["E"][kind, f] for f in ref}
+        bad, worst, where = [], 0.0, None
+        for f, r in ref.items():
+            g = np.asarray(got[f], dtype=F64)
+            assert g.shape == r.shape, (f, g.shape, r.shape)
+            if not np.all(np.isfinite(g)):
+                bad.append((kind, f, "not finite"))
+                continue
+            d = np.abs(g - r)
+            cells = [("field", float(d.max()), ERR_FACTOR * float(E[f].max()))]
+            for cn, mask in self.classes.items():
+                v = self.class_rows(f, d, mask)
+                if v.size:
+                    cells.append((cn, float(v.max()), ERR_FACTOR * float(self.class_rows(f, E[f], mask).max())))
+            for cn, e, b in cells:
+                if b == 0.0:
+                    if e != 0.0:
+                        bad.append((kind, f, cn, e, "both references agree and do not move: the numbers must be equal"))
+                    continue
+                if e / b > worst:
+                    worst, where = e / b, (kind, f, cn)
+                if e > b:
+                    bad.append((kind, f, cn, e, b))
+        return bad, worst, where
 
     # -- classes ------------------------------------------------------------------------------------------------------
     def _classes(self):
@@ -306,6 +443,10 @@ class Case:
                     s, _, d = census(self.prm, st, qs, precise)
                     sigs.append(active_cols(s, NGPTOT))
                     differ += d
+                    if B.SINGLE:  # the fp64 host census of the same fp32 values: a cell on whose branch the precisions differ
+                        s, _, d = census(self.prm, upcast_state(st), None if qs is None else qs.astype(F64), precise, single=False)
+                        sigs.append(active_cols(s, NGPTOT))
+                        differ += d
         self.dpr_clip_ne_reset = differ
         self.sig = sigs[0]
         # threshold cells: the signature depends on the arithmetic mode, on where QSAT comes from or on one ulp of the inputs
@@ -346,8 +487,7 @@ class Case:
     def columns(self, cols: np.ndarray) -> "Case":
         """The same case with the field cut down to some columns: references, classes, floors, scales and K are those of the
         subset (compare() then takes results cut down alike)."""
-        import copy
-
+        assert not B.SINGLE, "the fp32 yardstick is not cut down to columns"
         v = copy.copy(self)
         cut = lambda d: {n: np.ascontiguousarray(a[:, cols]) for n, a in d.items()}  # noqa: E731
         v.ref = {k: cut(d) for k, d in self.ref.items()}
@@ -367,9 +507,11 @@ class Case:
         """K floor(f, c) as an absolute error, never looser than the whole-field bound; 0: the numbers must be equal."""
         return min(self.K(kind) * self.floor_abs[kind, f, cn], self.tol(kind) * self.scale[kind, f])
 
-    def compare(self, kind: str, got: dict, ref: dict | None = None):
+    def compare(self, kind: str, got: dict, ref: dict | None = None, satur: bool = False):
         """got: name -> (NLEVx, NGPTOT).  Returns (violations, worst err / bound, its place): every field under the whole-field
-        bound, every (field, class) under its class bound."""
+        bound, every (field, class) under its class bound.  satur (fp32 only): the sweep evaluated SATUR itself."""
+        if B.SINGLE:
+            return self._compare_single(kind, got, ref, satur)
         ref = ref if ref is not None else self.ref[kind]
         bad, worst, where = [], 0.0, None
         for f, r in ref.items():
@@ -397,9 +539,37 @@ class Case:
         return bad, worst, where
 
 
+class RefWithError(dict):
+    """A reference result (field -> matrix) that carries its own yardstick E (field -> matrix)."""
+
+    E: dict
+
+
+def upcast_state(st):
+    """The same values in fp64 arrays."""
+    return dataclasses.replace(st, **{f.name: getattr(st, f.name).astype(F64) for f in dataclasses.fields(st)
+                                      if isinstance(getattr(st, f.name), np.ndarray)})
+
+
 @functools.lru_cache(maxsize=None)
 def case(nlev: int, flagset: str) -> Case:
     return Case(nlev, flagset)
+
+
+_ref_ad = {}
+
+
+def reference_ad(c: Case, x0: dict, satur: bool = False) -> dict:
+    """c.reference_ad(x0, satur), computed once per (case, set, background): the tests of both arithmetic modes share it."""
+    import hashlib
+
+    h = hashlib.sha1()
+    for n in sorted(x0):
+        h.update(np.ascontiguousarray(x0[n]).tobytes())
+    key = (c.nlev, c.flagset, bool(satur) and B.SINGLE, h.hexdigest())
+    if key not in _ref_ad:
+        _ref_ad[key] = c.reference_ad(x0, satur)
+    return _ref_ad[key]
 
 
 def class_err(ref: np.ndarray, got: np.ndarray, mask: np.ndarray) -> float:
@@ -458,7 +628,7 @@ def host_ad(c: Case, satur: bool, x0: dict, assign: bool) -> dict:
     hc = hostcheck()
     got = c.st.copy()
     i, o = host_traj_blocks(got, None if satur else c.qsat)
-    x, y = blocks_of(x0), blocks_of(c.ref["y"])
+    x, y = blocks_of(x0), blocks_of(c.refset(satur)["y"])
     scratch = np.zeros((c.st.nblocks, c.nlev, NPROMA), dtype=B.REAL)
     hc.hostcheck_set_assign(int(assign))
     try:

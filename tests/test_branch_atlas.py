@@ -6,6 +6,10 @@ Why: the older atmospheres (synthetic_table, random_table) never take some branc
 the branch changes, and tests/util.relerr divides by the maximum of a whole field, so a statement that is wrong on a rare branch
 passes.  Here a class is the set of cells with one outcome of one predicate, and the error inside a class is measured against the
 class's own magnitude and bounded by the reference's own conditioning inside that class (see branch_atlas.Case).
+
+In an fp32 process (CLOUDSC2_PRECISION=single; tests/test_single.py starts one) the same tests hold the fp32 host build to
+ERR_FACTOR x the error of the reference's own -DSINGLE build inside every class, the fp64 reference on the same fp32 values being
+the truth (branch_atlas.Case._init_single).
 """
 from __future__ import annotations
 
@@ -18,7 +22,7 @@ from tests import branch_atlas as A
 from tests.test_hostcheck_vjp import vjp_lib
 from tests.util import B, c2, host_traj_blocks, hostcheck, make_params, relerr
 
-pytestmark = pytest.mark.skipif(B.SINGLE, reason="the bounds are fp64 statements; the fp32 library is not covered (DESIGN.md)")
+BITS_VIEW = np.int32 if B.SINGLE else np.int64  # the integer of an element's size: bits are compared through it
 
 # Outcomes the atlas cannot reach: name -> the reason, argued from level_forward.  None is left: `esdp_clip&cloud=1`, the one
 # candidate, needs condensate where e_s(T)/p > 0.5, i.e. in thin hot air above the tropopause, where the critical relative
@@ -56,9 +60,9 @@ def test_census_walk_is_the_nl_sweep(precise, nproma, ngptot, levapls2, satur):
     assert hostcheck().hostcheck_nl(C.byref(prm), st.ptsphy, nproma, st.nlev, ngptot, C.byref(i), C.byref(o), B.Field(), 0.0) == 0
     for n in ("B_LOC", "PA", "PFPLSL", "PFPLSN", "PFHPSL", "PFHPSN"):
         a, b = getattr(walked, n), getattr(got, n)
-        assert np.array_equal(a.view(np.int64), b.view(np.int64)), n
+        assert np.array_equal(a.view(BITS_VIEW), b.view(BITS_VIEW)), n
     # (PCOVPTOT: the sweep also zeroes the padded tail, the walk leaves it alone)
-    assert np.array_equal(A.active_cols(walked.PCOVPTOT, ngptot).view(np.int64), A.active_cols(got.PCOVPTOT, ngptot).view(np.int64))
+    assert np.array_equal(A.active_cols(walked.PCOVPTOT, ngptot).view(BITS_VIEW), A.active_cols(got.PCOVPTOT, ngptot).view(BITS_VIEW))
     act = A.active_cols(sig, ngptot)
     assert np.all(act & A.SIG_ACTIVE) and np.count_nonzero(sig & A.SIG_ACTIVE) == st.nlev * ngptot
     assert differ == 0, "dpr_clip and reset are one predicate (hostcheck_census.hip)"
@@ -134,10 +138,19 @@ def test_threshold_cells_are_few(nlev, flagset):
     class comparison (they stay under the whole-field bound): at most 5 % of any class, and 32 cells are left in every class."""
     c = A.case(nlev, flagset)
     assert c.dpr_clip_ne_reset == 0
+    share, smallest = (0.0, ""), (c.sig.size, "")
     for name, full in c.full_classes.items():
         kept = c.classes[name]
+        share = max(share, ((full.sum() - kept.sum()) / full.sum(), name))
+        smallest = min(smallest, (int(kept.sum()), name))
         assert kept.sum() >= A.MIN_CELLS, (name, int(kept.sum()))
         assert full.sum() - kept.sum() <= A.MAX_EXCLUDED * full.sum(), (name, int(full.sum()), int(kept.sum()))
+    if B.SINGLE:  # (fp32: also the cells on whose branch the fp32 and the fp64 host census of the same values differ)
+        print(f"\n{nlev} levels, {flagset}: {int(c.excluded.sum())} threshold cells of {c.sig.size}; largest excluded share "
+              f"{100.0 * share[0]:.1f} % ({share[1]}); smallest kept class {smallest[0]} ({smallest[1]}); DRAWS = {A.DRAWS}")
+        for kind in ("nl", "tl", "ad"):
+            print("  E / max|ref|", kind, " ".join(f"{f}={c.sets[False]['E'][kind, f].max() / max(np.abs(r).max(), 1e-300):.1e}" for f, r in c.ref[kind].items()))
+        return
     print(f"\n{nlev} levels, {flagset}: {int(c.excluded.sum())} threshold cells of {c.sig.size}; K_NL = {c.K_NL:.2f}, K_TLAD = {c.K_TLAD:.2f}")
     for kind in ("nl", "tl", "ad"):
         print("  floor", kind, " ".join(f"{f}={c.floor_field[kind, f]:.1e}" for f in c.ref[kind]))
@@ -147,6 +160,8 @@ def test_threshold_cells_are_few(nlev, flagset):
 def test_class_metric_sees_what_the_field_norm_does_not(nlev):
     """An error of 1e-9 relative, confined to the cells of a class whose values lie three orders below the field's maximum,
     passes relerr <= NL_TOL over the field and must fail the class bound."""
+    if B.SINGLE:
+        return _class_metric_single(nlev)
     c = A.case(nlev, "plain").columns(np.arange(A.NGPTOT)[np.arange(A.NGPTOT) % 8 == 7])  # group D: the unchanged random_table
     ref = c.ref["nl"]
     tried = 0
@@ -169,6 +184,40 @@ def test_class_metric_sees_what_the_field_norm_does_not(nlev):
     assert not bad and worst == 0.0
 
 
+def _class_metric_single(nlev):
+    """fp32: a relative error inside a rare class that is 8 x the class bound at the class's largest value and still inside the
+    whole-field bound (so the class's E is at most 1/8 of the field's): both sizes come from E, the yardstick measured on the two
+    references."""
+    c = A.case(nlev, "plain")
+    ref = c.ref["nl"]
+    tried = 0
+    for f in ("tent", "tenq", "tenl", "teni", "fplsl", "fplsn"):
+        r, e = ref[f], c.sets[False]["E"]["nl", f]
+        half = r.shape[0] == nlev + 1
+        rows = r[1:] if half else r
+        field_bound = A.ERR_FACTOR * float(e.max())
+        for cn, mask in c.classes.items():
+            if not mask.any():
+                continue
+            class_bound = A.ERR_FACTOR * float(c.class_rows(f, e, mask).max())
+            top = float(np.abs(rows[mask]).max())
+            if not (0.0 < 8.0 * class_bound <= field_bound) or top == 0.0:
+                continue
+            rel = 8.0 * class_bound / top
+            got = {n: a.copy() for n, a in ref.items()}
+            g = got[f][1:] if half else got[f]
+            g[mask] *= 1.0 + rel
+            assert float(np.abs(got[f] - r).max()) <= field_bound, (f, cn)
+            bad, _, _ = c.compare("nl", got)
+            assert not any(b[1] == f and b[2] == "field" for b in bad), (f, cn, "the planted error does not pass the whole-field bound")
+            assert any(b[1] == f and b[2] == cn for b in bad), (f, cn, "the class metric did not see it")
+            tried += 1
+    print(f"\n{nlev} levels: the class metric caught {tried} planted errors that pass the whole-field bound")
+    assert tried >= 3, "no rare class to try the metric on"
+    bad, worst, _ = c.compare("nl", ref)
+    assert not bad and worst == 0.0
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. the host build against the reference, per class
 # ---------------------------------------------------------------------------------------------------------------------
@@ -180,8 +229,8 @@ def host_vjp(c, satur: bool) -> dict:
     scratch = np.zeros((c.st.nblocks, c.nlev, A.NPROMA), dtype=B.REAL)
     assert hv.hostcheck_vjp_sweep(C.byref(c.prm), c.ptsphy, A.NPROMA, c.nlev, A.NGPTOT, C.byref(i), C.byref(o), None, None,
                                   scratch.ctypes.data, 1, 0) == 0
-    x = A.blocks_of({n: np.full_like(a, np.nan) for n, a in c.ref["ad"].items()}, fill=np.nan)
-    y = A.blocks_of(c.ref["y"])
+    x = A.blocks_of({n: np.full(a.shape, np.nan, dtype=B.REAL) for n, a in c.ref["ad"].items()}, fill=np.nan)
+    y = A.blocks_of(c.refset(satur)["y"])
     assert hv.hostcheck_vjp_sweep(C.byref(c.prm), c.ptsphy, A.NPROMA, c.nlev, A.NGPTOT, C.byref(i), C.byref(o),
                                   C.byref(A._flat("in", x)), C.byref(A._flat("out", y)), scratch.ctypes.data, 2, 1) == 0
     return A.cols_of(x)
@@ -197,7 +246,7 @@ def vjp_as_adjoint(c, x: dict) -> dict:
 def background(c) -> dict:
     """A non-zero background for the accumulating adjoint, of the size of the result cell by cell."""
     rng = np.random.default_rng(5)
-    return {n: a * rng.uniform(-1.0, 1.0, size=a.shape) for n, a in c.ref["ad"].items()}
+    return {n: (a * rng.uniform(-1.0, 1.0, size=a.shape)).astype(B.REAL) for n, a in c.ref["ad"].items()}
 
 
 WORST = {}
@@ -209,14 +258,15 @@ WORST = {}
 def test_host_build_within_the_class_bounds(precise, nlev, flagset, satur):
     c = A.case(nlev, flagset)
     results = {}
-    results["nl"] = c.compare("nl", A.host_nl(c, satur))
+    # (satur: in fp32 the references that ran their own SATUR; fp64 has one set and ignores it)
+    results["nl"] = c.compare("nl", A.host_nl(c, satur), satur=satur)
     traj, tl = A.host_tl(c, satur)
-    results["traj"] = c.compare("traj", traj)
-    results["tl"] = c.compare("tl", tl)
+    results["traj"] = c.compare("traj", traj, satur=satur)
+    results["tl"] = c.compare("tl", tl, satur=satur)
     x0 = background(c)
-    results["ad accumulate"] = c.compare("ad", A.host_ad(c, satur, x0, assign=False), c.reference_ad(x0))
-    results["ad assign"] = c.compare("ad", A.host_ad(c, satur, {n: np.full_like(a, 7.25) for n, a in x0.items()}, assign=True))
-    results["vjp"] = c.compare("ad", vjp_as_adjoint(c, host_vjp(c, satur)))
+    results["ad accumulate"] = c.compare("ad", A.host_ad(c, satur, x0, assign=False), A.reference_ad(c, x0, satur), satur=satur)
+    results["ad assign"] = c.compare("ad", A.host_ad(c, satur, {n: np.full_like(a, 7.25) for n, a in x0.items()}, assign=True), satur=satur)
+    results["vjp"] = c.compare("ad", vjp_as_adjoint(c, host_vjp(c, satur)), satur=satur)
     failures = []
     for what, (bad, worst, where) in results.items():
         print(f"{what:14s} worst err/bound {worst:.3f} at {where}")

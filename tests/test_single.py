@@ -51,6 +51,49 @@ def test_single_kernels_on_gpu():
     assert "driver-level NL == kernel-level NL" in out and "fp32 criterion OK" in out
 
 
+FAULT_CODES = (124, 134, 137, 139)  # time limit, abort, kill, segmentation fault (tests/test_gpu_offset_variants.py); or negative
+_atlas_trouble = []
+
+
+def _atlas_child(module: str, *args: str, timeout: int):
+    """tests/test_branch_atlas.py or tests/test_gpu_branch_atlas.py in an fp32 process: one child, one time limit, no retry.  A child
+    that faulted, aborted or ran into its limit fails the test, and nothing more is started from this module's atlas tests."""
+    if _atlas_trouble:
+        pytest.fail(f"not started: {_atlas_trouble[0]}")
+    env = dict(os.environ, CLOUDSC2_PRECISION="single")
+    try:
+        p = subprocess.run([sys.executable, "-m", "pytest", os.path.join("tests", module), "-q", "-s", "-p", "no:cacheprovider", *args],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
+        rc, text, err = p.returncode, p.stdout, p.stderr
+    except subprocess.TimeoutExpired as e:
+        rc, text, err = 124, f"time limit: {e}", ""
+    lines = text.splitlines()
+    print("\n".join(ln for ln in lines if "worst err/bound" in ln or "threshold cells" in ln))
+    print("\n".join(lines[-15:]))
+    if rc in FAULT_CODES or rc < 0:
+        _atlas_trouble.append(f"tests/{module} under CLOUDSC2_PRECISION=single ended with {rc}")
+    assert rc == 0, (rc, text[-6000:], err[-2000:])
+    last = lines[-1] if lines else ""
+    assert " passed" in last and "failed" not in last and "error" not in last, last
+    return text
+
+
+@pytest.mark.skipif(not refcall.have_ref(single=True), reason="oracle/_ref/libcloudsc2_ref_sp.so not built")
+def test_single_branch_atlas_on_host():
+    """The branch atlas in an fp32 process: the fp32 host build inside every class bound."""
+    out = _atlas_child("test_branch_atlas.py", timeout=900)
+    assert out.count("worst err/bound") >= 6 * 2 * 2 * 4 * 2  # six sweeps, both modes, both QSAT sources, four flag sets, two heights
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(not refcall.have_ref(single=True), reason="oracle/_ref/libcloudsc2_ref_sp.so not built")
+def test_single_branch_atlas_on_gpu():
+    """The kernels of libcloudsc2_hip_sp.so inside every class bound: NL (driver, SATUR in the sweep), TL, trajectory, AD, VJP."""
+    out = _atlas_child("test_gpu_branch_atlas.py", "-m", "gpu", timeout=300)
+    assert "skipped" in out.splitlines()[-1], "the two sweep-against-sweep tests are fp64-only"
+    assert out.count("worst err/bound") >= 2 * 2 * 2 * 2 + 4 * 2 * 2 * 4  # NL driver and kernel; TL, trajectory, AD, VJP
+
+
 @pytest.mark.gpu
 def test_single_fortran_mains(tmp_path):
     """fortran/build_sp: the drivers with the reference's signatures compiled with -DSINGLE (JPRB = fp32) against

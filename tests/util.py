@@ -57,31 +57,34 @@ def hostcheck():
     return _hc
 
 
-def hfld(a: np.ndarray, offset: int = 0, stride: int | None = None) -> B.Field:
-    assert a.dtype == B.REAL and a.flags["C_CONTIGUOUS"]
+def hfld(a: np.ndarray, offset: int = 0, stride: int | None = None, real=None) -> B.Field:
+    """real: the element type of a host build of the other precision (tests/branch_atlas.py), else the process's own"""
+    real = np.dtype(real or B.REAL)
+    assert a.dtype == real and a.flags["C_CONTIGUOUS"]
     f = B.Field()
-    f.ptr = a.ctypes.data + B.REAL_BYTES * offset
+    f.ptr = a.ctypes.data + real.itemsize * offset
     f.block_stride = stride if stride is not None else int(np.prod(a.shape[1:]))
     return f
 
 
-def host_traj_blocks(st: c2.Cloudsc2State, qsat: np.ndarray | None = None):
+def host_traj_blocks(st: c2.Cloudsc2State, qsat: np.ndarray | None = None, real=None):
     """Inputs/Outputs blocks with HOST pointers into a Cloudsc2State (same mapping as DeviceState)."""
     S = st.nproma * st.nlev
+    fld = lambda a, offset=0, stride=None: hfld(a, offset, stride, real)  # noqa: E731
     i = B.Inputs()
-    i.paph = hfld(st.PAPH); i.pap = hfld(st.PAP); i.q = hfld(st.PQ)
-    i.qsat = hfld(qsat) if qsat is not None else B.Field()
-    i.t = hfld(st.PT)
-    i.l = hfld(st.PCLV, 0 * S, 5 * S); i.i = hfld(st.PCLV, 1 * S, 5 * S)
-    i.lude = hfld(st.PLUDE); i.lu = hfld(st.PLU); i.mfu = hfld(st.PMFU); i.mfd = hfld(st.PMFD)
-    i.gtent = hfld(st.B_CML, 0 * S, 8 * S); i.gtenq = hfld(st.B_CML, 2 * S, 8 * S)
-    i.gtenl = hfld(st.B_CML, 3 * S, 8 * S); i.gteni = hfld(st.B_CML, 4 * S, 8 * S)
-    i.supsat = hfld(st.PSUPSAT)
+    i.paph = fld(st.PAPH); i.pap = fld(st.PAP); i.q = fld(st.PQ)
+    i.qsat = fld(qsat) if qsat is not None else B.Field()
+    i.t = fld(st.PT)
+    i.l = fld(st.PCLV, 0 * S, 5 * S); i.i = fld(st.PCLV, 1 * S, 5 * S)
+    i.lude = fld(st.PLUDE); i.lu = fld(st.PLU); i.mfu = fld(st.PMFU); i.mfd = fld(st.PMFD)
+    i.gtent = fld(st.B_CML, 0 * S, 8 * S); i.gtenq = fld(st.B_CML, 2 * S, 8 * S)
+    i.gtenl = fld(st.B_CML, 3 * S, 8 * S); i.gteni = fld(st.B_CML, 4 * S, 8 * S)
+    i.supsat = fld(st.PSUPSAT)
     o = B.Outputs()
-    o.tent = hfld(st.B_LOC, 0 * S, 8 * S); o.tenq = hfld(st.B_LOC, 2 * S, 8 * S)
-    o.tenl = hfld(st.B_LOC, 3 * S, 8 * S); o.teni = hfld(st.B_LOC, 4 * S, 8 * S)
-    o.clc = hfld(st.PA); o.covptot = hfld(st.PCOVPTOT)
-    o.fplsl = hfld(st.PFPLSL); o.fplsn = hfld(st.PFPLSN); o.fhpsl = hfld(st.PFHPSL); o.fhpsn = hfld(st.PFHPSN)
+    o.tent = fld(st.B_LOC, 0 * S, 8 * S); o.tenq = fld(st.B_LOC, 2 * S, 8 * S)
+    o.tenl = fld(st.B_LOC, 3 * S, 8 * S); o.teni = fld(st.B_LOC, 4 * S, 8 * S)
+    o.clc = fld(st.PA); o.covptot = fld(st.PCOVPTOT)
+    o.fplsl = fld(st.PFPLSL); o.fplsn = fld(st.PFPLSN); o.fhpsl = fld(st.PFHPSL); o.fhpsn = fld(st.PFHPSN)
     return i, o
 
 
