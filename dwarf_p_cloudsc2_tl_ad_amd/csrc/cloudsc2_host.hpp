@@ -8,7 +8,7 @@
 //   cloudsc2_driver.hip   the host-array drivers and the resident state
 //   cloudsc2_helpers.hip  host-only helpers of the C ABI (default parameters, offsets, validation text, the synthetic table, verdicts)
 //
-// The sweeps' kernels are in cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal,nl_ens,tl_ens,vjp_ens}.hip (cloudsc2_sweep_kernels.hpp).  A __global__ kernel stays in the unit
+// The sweeps' kernels are in the family units cloudsc2_kern_<family>.hip, one per name of the Makefile's FAMILIES (cloudsc2_sweep_kernels.hpp).  A __global__ kernel stays in the unit
 // that launches it: without relocatable device code a kernel cannot be launched by name from another unit's code object.  Everything
 // here has external linkage inside namespace cloudsc2; the link's version script (cloudsc2_hip.map) keeps it out of the dynamic symbol
 // table, where only the C ABI appears.
@@ -30,12 +30,13 @@
 
 #include "../../include/cloudsc2_hip.h"
 #include "cloudsc2_sweep_kernels.hpp"
+#include "cloudsc2_fields.hpp"  // the field table: resolve_in / resolve_out, writable, outputs_given, ncols_pad
 
 namespace cloudsc2 {
 
 // ---- error state (cloudsc2_launch.hip) ---------------------------------------------------------------------------------------------
 extern thread_local std::string g_err;  // cloudsc2_last_error()
-int fail(int code, const char* msg);
+int fail(int code, const char* msg);  // (declared by cloudsc2_fields.hpp too, which is built without this header by its test)
 
 #define HIP_TRY(expr)                                                                     \
   do {                                                                                    \
@@ -53,8 +54,6 @@ inline int require_device() { return device_ok() ? 0 : no_device(); }
 // ---- argument checks and launch helpers (cloudsc2_launch.hip) -----------------------------------------------------------------------
 bool precise_of(const cloudsc2_params* prm);  // the arithmetic of one call: its own request, else the process default
 int check_geom(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, Geom& g);
-int resolve_in(const cloudsc2_inputs& in, bool need_qsat, Strides& s, InPtrs& p);
-int resolve_out(const cloudsc2_outputs& out, bool all_required, Strides& s, OutPtrs& p);
 int get_tables(const cloudsc2_params& p, const LevelTab** dev, int* kb0, int* kb1);
 int validate_launch_impl(const cloudsc2_real* table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
                          long long ngptot, cloudsc2_field field, double* workspace, double* stats, void* stream, long long ncols_minmax);

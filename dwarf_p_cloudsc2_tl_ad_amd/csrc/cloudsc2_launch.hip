@@ -32,7 +32,7 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------------------
 // kernels: the sweeps' __global__ wrappers and their variant tables are cloudsc2_sweep_kernels.hpp + the family units
-// cloudsc2_kern_{nl,tl,ad,taylor,tl_batch,vjp_batch,tl_par,vjp_par,tl_parjac,parnormal,nl_ens,tl_ens,vjp_ens}.hip; here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
+// cloudsc2_kern_<family>.hip (the Makefile's FAMILIES); here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
 // ---------------------------------------------------------------------------------------------------------
 template <bool P>
 __global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
@@ -461,62 +461,6 @@ int get_tables(const cloudsc2_params& p, const LevelTab** dev, int* kb0, int* kb
   *dev = e.dev; *kb0 = e.kb0; *kb1 = e.kb1;
   return 0;
 }
-namespace {
-struct GroupStride {
-  long long v;
-  bool set;
-  bool ok;
-  GroupStride() : v(0), set(false), ok(true) {}
-  void add(const cloudsc2_field& f) {
-    if (!f.ptr) return;
-    if (!set) { v = f.block_stride; set = true; }
-    else if (v != f.block_stride) ok = false;
-  }
-};
-}  // namespace
-
-int resolve_in(const cloudsc2_inputs& in, bool need_qsat, Strides& s, InPtrs& p) {
-  const cloudsc2_field* req[] = {&in.paph, &in.pap, &in.q, &in.t, &in.l, &in.i, &in.lude, &in.lu,
-                                 &in.mfu,  &in.mfd, &in.gtent, &in.gtenq, &in.gtenl, &in.gteni, &in.supsat};
-  for (auto f : req)
-    if (!f->ptr) return fail(CLOUDSC2_EINVAL, "a required input field has a NULL pointer");
-  if (need_qsat && !in.qsat.ptr) return fail(CLOUDSC2_EINVAL, "qsat field required");
-  GroupStride full, half, cml, clv;
-  full.add(in.pap); full.add(in.q); full.add(in.qsat); full.add(in.t); full.add(in.lude); full.add(in.lu);
-  full.add(in.mfu); full.add(in.mfd); full.add(in.supsat);
-  half.add(in.paph);
-  cml.add(in.gtent); cml.add(in.gtenq); cml.add(in.gtenl); cml.add(in.gteni);
-  clv.add(in.l); clv.add(in.i);
-  if (!full.ok || !half.ok || !cml.ok || !clv.ok)
-    return fail(CLOUDSC2_EINVAL, "fields of one layout group (full-level / PGTEN* / PL,PI) must share one block stride");
-  s.full = full.v; s.half = half.v; s.cml = cml.v; s.clv = clv.v;
-  p.paph = in.paph.ptr; p.pap = in.pap.ptr; p.q = in.q.ptr; p.qsat = in.qsat.ptr; p.t = in.t.ptr; p.l = in.l.ptr;
-  p.i = in.i.ptr; p.lude = in.lude.ptr; p.lu = in.lu.ptr; p.mfu = in.mfu.ptr; p.mfd = in.mfd.ptr;
-  p.gt = in.gtent.ptr; p.gq = in.gtenq.ptr; p.gl = in.gtenl.ptr; p.gi = in.gteni.ptr; p.supsat = in.supsat.ptr;
-  return 0;
-}
-
-int resolve_out(const cloudsc2_outputs& out, bool all_required, Strides& s, OutPtrs& p) {
-  const cloudsc2_field* all[] = {&out.tent, &out.tenq, &out.tenl, &out.teni, &out.clc,
-                                 &out.fplsl, &out.fplsn, &out.fhpsl, &out.fhpsn, &out.covptot};
-  if (all_required)
-    for (auto f : all)
-      if (!f->ptr) return fail(CLOUDSC2_EINVAL, "a required output field has a NULL pointer");
-  GroupStride full, half, loc;
-  full.add(out.clc); full.add(out.covptot);
-  half.add(out.fplsl); half.add(out.fplsn); half.add(out.fhpsl); half.add(out.fhpsn);
-  loc.add(out.tent); loc.add(out.tenq); loc.add(out.tenl); loc.add(out.teni);
-  if (!full.ok || !half.ok || !loc.ok)
-    return fail(CLOUDSC2_EINVAL, "output fields of one layout group must share one block stride");
-  if (full.set) { if (s.full && s.full != full.v) return fail(CLOUDSC2_EINVAL, "PCLC/PCOVPTOT stride differs from the input full-level stride"); s.full = full.v; }
-  if (half.set) { if (s.half && s.half != half.v) return fail(CLOUDSC2_EINVAL, "flux stride differs from the PAPH stride"); s.half = half.v; }
-  s.loc = loc.v;
-  p.tent = out.tent.ptr; p.tenq = out.tenq.ptr; p.tenl = out.tenl.ptr; p.teni = out.teni.ptr; p.clc = out.clc.ptr;
-  p.fplsl = out.fplsl.ptr; p.fplsn = out.fplsn.ptr; p.fhpsl = out.fhpsl.ptr; p.fhpsn = out.fhpsn.ptr;
-  p.covptot = out.covptot.ptr;
-  return 0;
-}
-
 int check_geom(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, Geom& g) {
   if (!prm) return fail(CLOUDSC2_EINVAL, "params is NULL");
   if (nproma < 1 || nlev < 2 || ngptot < 1) return fail(CLOUDSC2_EINVAL, "nproma >= 1, nlev >= 2, ngptot >= 1 required");
@@ -524,8 +468,7 @@ int check_geom(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, Geo
   if (prm->nlev != nlev) return fail(CLOUDSC2_EINVAL, "params.nlev does not match nlev");
   if (prm->math_mode < 0 || prm->math_mode > 2) return fail(CLOUDSC2_EINVAL, "params.math_mode must be 0 (default), 1 (fast) or 2 (precise)");
   if (!device_ok()) return no_device();
-  long long nblocks = ((long long)ngptot + nproma - 1) / nproma;
-  g.nproma = nproma; g.nlev = nlev; g.ngptot = ngptot; g.ncols_pad = nblocks * nproma;
+  g.nproma = nproma; g.nlev = nlev; g.ngptot = ngptot; g.ncols_pad = ncols_pad(nproma, ngptot);
   g.kb0 = 0; g.kb1 = 0; g.fair = 0;
   return 0;
 }
@@ -608,26 +551,32 @@ int ens_launch(KernelFn<EnsArgs<Args>> fn, const Args& tmpl, double ptsphy, cons
   return 0;
 }
 
-// pert_in == NULL: the increments are 0.01*x of the trajectory inputs (supsat_inc * PSUPSAT for PSUPSAT), C2F_SELFINC
-// satlin: SATUR is differentiated in the sweep (C2F_SATLIN): no qsat on either input side, no trajectory stores
+// What a TL launch runs.  pert_in NULL: the increments are 0.01*x of the trajectory inputs (C2F_SELFINC), supsat_inc * PSUPSAT for PSUPSAT,
+// and yy, if given, receives <y,y> of every column's outputs.  The other forms are given pert_in and no trajectory outputs.
+struct TlMode {
+  const cloudsc2_inputs* pert_in = nullptr;
+  double supsat_inc = 0.0;
+  double* yy = nullptr;
+  bool satlin = false;           // SATUR is differentiated in the sweep (C2F_SATLIN): no qsat on either input side
+  const double* dpar = nullptr;  // the parameter tangents (C2F_PARLIN)
+  const EnsSpec* ens = nullptr;  // the launch runs for the members of an ensemble (needs dpar, which the members' rows replace)
+};
+
 int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
-                   const cloudsc2_outputs* traj_out, const cloudsc2_inputs* pert_in, double supsat_inc, const cloudsc2_outputs* pert_out,
-                   double* yy, void* stream, bool satlin = false, const double* dpar = nullptr, const EnsSpec* ens = nullptr) {
+                   const cloudsc2_outputs* traj_out, const cloudsc2_outputs* pert_out, void* stream, const TlMode& m) {
+  const cloudsc2_inputs* pert_in = m.pert_in;
   Sweep w;
   int rc = w.begin(prm, nproma, nlev, ngptot, (!traj_in || !traj_out || !pert_out) ? "NULL argument block" : nullptr);
   if (rc) return rc;
-  const cloudsc2_field* tf[10] = {&traj_out->tent, &traj_out->tenq, &traj_out->tenl, &traj_out->teni, &traj_out->clc,
-                                  &traj_out->fplsl, &traj_out->fplsn, &traj_out->fhpsl, &traj_out->fhpsn, &traj_out->covptot};
-  int nset = 0;
-  for (auto f : tf) nset += f->ptr ? 1 : 0;
-  if (nset != 0 && nset != 10) return fail(CLOUDSC2_EINVAL, "traj_out: give all ten trajectory outputs or none");
-  if (satlin && (traj_in->qsat.ptr || (pert_in && pert_in->qsat.ptr)))
+  const int nset = outputs_given(*traj_out);
+  if (nset != 0 && nset != kNumOut) return fail(CLOUDSC2_EINVAL, "traj_out: give all ten trajectory outputs or none");
+  if (m.satlin && (traj_in->qsat.ptr || (pert_in && pert_in->qsat.ptr)))
     return fail(CLOUDSC2_EINVAL, "SATUR differentiated in the sweep: traj_in->qsat and pert_in->qsat must be NULL");
   if ((rc = w.trajectory(*traj_in, *traj_out, false))) return rc;
   TlArgs args;
   args.sp = Strides{0, 0, 0, 0, 0};
   if (pert_in) {
-    if ((rc = resolve_in(*pert_in, !satlin, args.sp, args.din))) return rc;
+    if ((rc = resolve_in(*pert_in, !m.satlin, args.sp, args.din))) return rc;
   } else {
     memset(&args.din, 0, sizeof(args.din));  // (sp: taken from the outputs by resolve_out)
   }
@@ -635,31 +584,30 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   const Strides& sp = args.sp;
   if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sp.full, sp.half, sp.cml, sp.clv, sp.loc}))) return rc;
   if (!pert_in) w.f |= C2F_SELFINC;
-  if (nset == 10) w.f |= C2F_TRAJ;
-  if (satlin) w.f |= C2F_SATLIN;  // (its launcher passes pert_in and no trajectory outputs)
+  if (nset == kNumOut) w.f |= C2F_TRAJ;
+  if (m.satlin) w.f |= C2F_SATLIN;
   args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.out = w.out; args.tab = w.tab;
-  args.supsat_inc = (real_t)supsat_inc;
-  args.yy = yy;
+  args.supsat_inc = (real_t)m.supsat_inc;
+  args.yy = m.yy;
+  const hipStream_t st = (hipStream_t)stream;
   // the fp32 TL variants that run three waves per SIMD (tl_kernel's launch bounds) share their SIMDs like the NL kernel does:
   // -3.7 % at 160 000 columns with the waves kept abreast; the fp64 TL and both adjoints run one wave per SIMD and lose 1-5 %
   // (profiles/r03_wave_times.txt); they are paced instead
-  if (dpar) w.f |= C2F_PARLIN;  // (its launcher passes pert_in and no trajectory outputs)
-  if (ens) {  // (with dpar, which the members' rows replace: the template's ParLin is overwritten whole)
-    TlParArgs pargs;
-    pargs.a = args;
-    pargs.par = make_parlin(w.c, dpar);
-    return ens_launch(tl_ens_variant(w.f), pargs, ptsphy, *ens, (hipStream_t)stream);
-  }
-  const void* tl = dpar ? (const void*)tl_par_variant(w.f) : (const void*)tl_variant(w.f);
   const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);
-  schedule(args.g, abreast ? tl : nullptr, false, abreast ? nullptr : tl);
-  if (dpar) {
-    TlParArgs pargs;
-    pargs.a = args;
-    pargs.par = make_parlin(w.c, dpar);
-    return launch_variant(kFamTlPar, w.f, tl_par_variant(w.f), pargs, w.g.ncols_pad, (hipStream_t)stream);
+  if (!m.dpar) {
+    if (m.ens) return fail(CLOUDSC2_EINVAL, "ensemble: the parameter form of the TL sweep (dpar) is required");
+    const void* tl = (const void*)tl_variant(w.f);
+    schedule(args.g, abreast ? tl : nullptr, false, abreast ? nullptr : tl);
+    return launch_variant(kFamTl, w.f, tl_variant(w.f), args, w.g.ncols_pad, st);
   }
-  return launch_variant(kFamTl, w.f, tl_variant(w.f), args, w.g.ncols_pad, (hipStream_t)stream);
+  w.f |= C2F_PARLIN;
+  TlParArgs pargs;
+  pargs.a = args;
+  pargs.par = make_parlin(w.c, m.dpar);  // (an ensemble's template: overwritten whole by every member's row)
+  if (m.ens) return ens_launch(tl_ens_variant(w.f), pargs, ptsphy, *m.ens, st);
+  const void* tl = (const void*)tl_par_variant(w.f);
+  schedule(pargs.a.g, abreast ? tl : nullptr, false, abreast ? nullptr : tl);
+  return launch_variant(kFamTlPar, w.f, tl_par_variant(w.f), pargs, w.g.ncols_pad, st);
 }
 
 // What an AD launch runs.  which 0: both sweeps (the fused kernel, or the two kernels in stream order); 1: the trajectory pass
@@ -695,11 +643,7 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
     InPtrs aip_c;
     if ((rc = resolve_in(*adj_in, !m.satlin, args.sa, aip_c))) return rc;
     if ((rc = resolve_out(*adj_out, true, args.sa, args.aout))) return rc;
-    InPtrsRW& aip = args.ain;
-    aip.paph = adj_in->paph.ptr; aip.pap = adj_in->pap.ptr; aip.q = adj_in->q.ptr; aip.qsat = adj_in->qsat.ptr;
-    aip.t = adj_in->t.ptr; aip.l = adj_in->l.ptr; aip.i = adj_in->i.ptr; aip.lude = adj_in->lude.ptr;
-    aip.lu = adj_in->lu.ptr; aip.mfu = adj_in->mfu.ptr; aip.mfd = adj_in->mfd.ptr; aip.gt = adj_in->gtent.ptr;
-    aip.gq = adj_in->gtenq.ptr; aip.gl = adj_in->gtenl.ptr; aip.gi = adj_in->gteni.ptr; aip.supsat = adj_in->supsat.ptr;
+    args.ain = writable(*adj_in);
   }
   const Strides& sa = args.sa;
   if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sa.full, sa.half, sa.cml, sa.clv, sa.loc, (long long)nproma * nlev /* scratch */})))
@@ -736,24 +680,19 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   if (m.par_work) {  // the reverse sweep with the parameter sums, then their fold
     if (!m.vjp || !m.par_adj) return fail(CLOUDSC2_EINVAL, "parameter adjoints: the vector-Jacobian product, with workspace and result");
     f |= C2F_PARLIN;
-    if (m.ens) {  // (par_work: the first member's slab)
-      AdParArgs pargs;
-      pargs.a = args;
-      pargs.par = make_parlin(w.c, nullptr);
-      pargs.work = m.par_work;
-      if ((rc = ens_launch(vjp_ens_variant(f), pargs, ptsphy, *m.ens, st))) return rc;
-      hipLaunchKernelGGL(par_fold_ens_kernel, dim3(PAR_COUNT, (unsigned)m.ens->members), dim3(kParFoldBlock), 0, st, (const double*)m.par_work, n,
-                         (long long)w.g.ngptot, m.par_adj);
-      HIP_TRY(hipGetLastError());
-      return 0;
-    }
-    schedule(args.nl.g, nullptr, false, (const void*)vjp_par_variant(f));
     AdParArgs pargs;
     pargs.a = args;
     pargs.par = make_parlin(w.c, nullptr);
-    pargs.work = m.par_work;
-    if ((rc = launch_variant(kFamVjpPar, f, vjp_par_variant(f), pargs, n, st))) return rc;
-    hipLaunchKernelGGL(par_fold_kernel, dim3(PAR_COUNT), dim3(kParFoldBlock), 0, st, (const double*)m.par_work, n, (long long)w.g.ngptot, m.par_adj);
+    pargs.work = m.par_work;  // (of an ensemble: the first member's slab)
+    if (m.ens) {
+      if ((rc = ens_launch(vjp_ens_variant(f), pargs, ptsphy, *m.ens, st))) return rc;
+      hipLaunchKernelGGL(par_fold_ens_kernel, dim3(PAR_COUNT, (unsigned)m.ens->members), dim3(kParFoldBlock), 0, st, (const double*)m.par_work, n,
+                         (long long)w.g.ngptot, m.par_adj);
+    } else {
+      schedule(pargs.a.nl.g, nullptr, false, (const void*)vjp_par_variant(f));
+      if ((rc = launch_variant(kFamVjpPar, f, vjp_par_variant(f), pargs, n, st))) return rc;
+      hipLaunchKernelGGL(par_fold_kernel, dim3(PAR_COUNT), dim3(kParFoldBlock), 0, st, (const double*)m.par_work, n, (long long)w.g.ngptot, m.par_adj);
+    }
     HIP_TRY(hipGetLastError());
     return 0;
   }
@@ -772,13 +711,62 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   return launch_variant(kFamAdReverse, f, ad_reverse_variant(f), args, n, st);
 }
 
+// refusals several launchers share (each entry point keeps its own order of them)
+int check_satur(int satur) {
+  return satur == 0 || satur == 1 ? 0 : fail(CLOUDSC2_EINVAL, "satur must be 0 (qsat given) or 1 (SATUR differentiated in the sweep)");
+}
+int check_rpecons(const cloudsc2_params* prm) {  // (its partial is formed as ZBETA / RPECONS)
+  return prm && (prm->levapls2 || prm->ldrain1d) && prm->rpecons == 0.0
+             ? fail(CLOUDSC2_EINVAL, "parameter derivative with the evaporation branch: rpecons must not be 0") : 0;
+}
+int require_qsat(int satur, const cloudsc2_inputs* traj_in) {
+  return !satur && traj_in && !traj_in->qsat.ptr ? fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required") : 0;
+}
 // what the two parameter launchers check before their parents' checks
 int check_par(const cloudsc2_params* prm, int satur) {
-  if (satur != 0 && satur != 1) return fail(CLOUDSC2_EINVAL, "satur must be 0 (qsat given) or 1 (SATUR differentiated in the sweep)");
+  if (int rc = check_satur(satur)) return rc;
   if (int rc = require_device()) return rc;
-  if (prm && (prm->levapls2 || prm->ldrain1d) && prm->rpecons == 0.0)
-    return fail(CLOUDSC2_EINVAL, "parameter derivative with the evaporation branch: rpecons must not be 0");
+  return check_rpecons(prm);
+}
+// direction b of a parameter sweep runs with the unit tangent of parameter b (the sets from `np` on are not read: valid contents all the same)
+void unit_parlins(ParLin* par, const Consts& c, int np) {
+  for (int b = 0; b < kBatchMax; ++b) {
+    double e[PAR_COUNT] = {};
+    e[b < np ? b : 0] = 1.0;
+    par[b] = make_parlin(c, e);
+  }
+}
+
+int work_doubles(int rows, int nproma, int ngptot, long long* n) {  // rows x the padded column count
+  if (nproma < 1 || ngptot < 1 || !n) return fail(CLOUDSC2_EINVAL, "nproma >= 1, ngptot >= 1 and a result pointer required");
+  *n = (long long)rows * ncols_pad(nproma, ngptot);
   return 0;
+}
+
+// what the ensemble launchers check before their parents' checks
+int check_ens(const cloudsc2_params* prm, int satur, int members, const double* params_dev, const void* workspace) {
+  if (int rc = check_satur(satur)) return rc;
+  if (members < 1 || members > 65535) return fail(CLOUDSC2_EINVAL, "ensemble: 1 <= members <= 65535 required");
+  if (!params_dev || !workspace) return fail(CLOUDSC2_EINVAL, "ensemble: the parameter array and the workspace are required");
+  if (prm && !prm->lphylin) return fail(CLOUDSC2_EINVAL, "ensemble: CLOUDSC2TL / CLOUDSC2AD linearise the LPHYLIN form only (prm->lphylin = 0)");
+  return 0;
+}
+// a block the members WRITE: with more than one member no field may be shared (member stride 0), the
+// members would write over each other; then the device check, as in check_par
+template <class Block>
+int check_ens_written(const Block* b, const long long* mstride, int members) {
+  for (int i = 0; b && members > 1 && i < (int)(sizeof(Block) / sizeof(cloudsc2_field)); ++i)
+    if (fields_of(*b)[i].ptr && (!mstride || mstride[i] == 0))
+      return fail(CLOUDSC2_EINVAL, "ensemble: a field the members write has member stride 0 (every member needs its own)");
+  return require_device();
+}
+// the member strides of a launch's four blocks and its checkpoint plane (NULL: all members share the block's fields)
+EnsStrides ens_strides(const long long* in, const long long* out, const long long* in2, const long long* out2, long long ckpt) {
+  EnsStrides ms;
+  for (int i = 0; i < kNumIn; ++i) { ms.in[i] = in ? in[i] : 0; ms.in2[i] = in2 ? in2[i] : 0; }
+  for (int i = 0; i < kNumOut; ++i) { ms.out[i] = out ? out[i] : 0; ms.out2[i] = out2 ? out2[i] : 0; }
+  ms.ckpt = ckpt;
+  return ms;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -786,14 +774,6 @@ int check_par(const cloudsc2_params* prm, int satur) {
 // ---------------------------------------------------------------------------------------------------------
 bool same_strides(const Strides& a, const Strides& b) {
   return a.full == b.full && a.half == b.half && a.cml == b.cml && a.clv == b.clv && a.loc == b.loc;
-}
-
-InPtrsRW writable(const cloudsc2_inputs& x) {
-  InPtrsRW p;
-  p.paph = x.paph.ptr; p.pap = x.pap.ptr; p.q = x.q.ptr; p.qsat = x.qsat.ptr; p.t = x.t.ptr; p.l = x.l.ptr; p.i = x.i.ptr;
-  p.lude = x.lude.ptr; p.lu = x.lu.ptr; p.mfu = x.mfu.ptr; p.mfd = x.mfd.ptr; p.gt = x.gtent.ptr; p.gq = x.gtenq.ptr;
-  p.gl = x.gtenl.ptr; p.gi = x.gteni.ptr; p.supsat = x.supsat.ptr;
-  return p;
 }
 
 // Balanced chunks in stream order (5 -> 3 + 2, 9 -> 3 + 3 + 3): `launch(first, count)` once per chunk, until one fails.  A larger
@@ -813,183 +793,6 @@ int for_each_chunk(int nbatch, Launch launch) {
 // 160 000 columns (profiles/EXPERIMENTS.md, "Batched tangents and cotangents")
 constexpr bool kPaceBatch = true;
 
-int tl_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
-                         int nbatch, const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out, void* stream) {
-  Sweep w;
-  int rc = w.begin(prm, nproma, nlev, ngptot,
-                   (!traj_in || !pert_in || !pert_out) ? "NULL argument block" : nbatch < 1 ? "nbatch >= 1 required" : nullptr);
-  if (rc) return rc;
-  if (nbatch == 1) {  // one direction: the single-direction sweep itself (it requires qsat of pert_in only, so ask here)
-    if (!traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "qsat field required");
-    const cloudsc2_outputs none = {};
-    return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_in, 0.0, pert_out, nullptr, stream);
-  }
-  if ((rc = resolve_in(*traj_in, true, w.s, w.in))) return rc;
-  memset(&w.out, 0, sizeof(w.out));
-  std::vector<InPtrs> din((size_t)nbatch);
-  std::vector<OutPtrs> dout((size_t)nbatch);
-  Strides sp = {0, 0, 0, 0, 0};
-  for (int b = 0; b < nbatch; ++b) {
-    Strides sb = {0, 0, 0, 0, 0};
-    if ((rc = resolve_in(pert_in[b], true, sb, din[b])) || (rc = resolve_out(pert_out[b], true, sb, dout[b]))) return rc;
-    if (b == 0) sp = sb;
-    else if (!same_strides(sp, sb)) return fail(CLOUDSC2_EINVAL, "batched launch: every direction must have the same block stride per layout group");
-  }
-  if ((rc = w.finish(*prm, ptsphy, true, {sp.full, sp.half, sp.cml, sp.clv, sp.loc}))) return rc;
-  TlBatchArgs args;
-  args.c = w.c; args.g = w.g; args.s = w.s; args.sp = sp; args.in = w.in; args.tab = w.tab;
-  return for_each_chunk(nbatch, [&](int first, int count) {
-    const KernelFn<TlBatchArgs> fn = tl_batch_variant(w.f, count);  // (the direction count is the kernel's compile-time one)
-    for (int b = 0; b < kBatchMax; ++b) {  // (the sets from `count` on are not read: valid pointers all the same)
-      args.din[b] = din[first + (b < count ? b : 0)];
-      args.dout[b] = dout[first + (b < count ? b : 0)];
-    }
-    schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
-    return launch_variant(kFamTlBatch, w.f + 64u * (unsigned)count, fn, args, w.g.ncols_pad, (hipStream_t)stream);
-  });
-}
-
-// The parameter Jacobian: the sensitivities of the ten outputs to the tunable parameters in ONE sweep over the trajectory
-// (tl_parjac_column: no tangent planes; direction k runs with make_parlin of the unit tangent of parameter k).  Without the evaporation
-// branch the kernel runs CLOUDSC2_NPAR - 1 directions and pert_out[PAR_RPECONS] is not looked at.
-int tl_parjac_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
-                          const cloudsc2_outputs* pert_out, void* stream) {
-  // (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
-  if (!prm || !traj_in || !pert_out) return fail(CLOUDSC2_EINVAL, "NULL argument block");
-  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "parameter Jacobian: CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
-  const bool evap = prm->levapls2 || prm->ldrain1d;
-  if (evap && prm->rpecons == 0.0) return fail(CLOUDSC2_EINVAL, "parameter derivative with the evaporation branch: rpecons must not be 0");
-  const int np = evap ? (int)PAR_COUNT : (int)PAR_COUNT - 1;
-  Sweep w;
-  int rc = resolve_in(*traj_in, false, w.s, w.in);
-  if (rc) return rc;
-  memset(&w.out, 0, sizeof(w.out));
-  TlParJacArgs args;
-  Strides sp = {0, 0, 0, 0, 0};
-  for (int b = 0; b < np; ++b) {
-    Strides sb = {0, 0, 0, 0, 0};
-    if ((rc = resolve_out(pert_out[b], true, sb, args.dout[b]))) return rc;
-    if (b == 0) sp = sb;
-    else if (!same_strides(sp, sb)) return fail(CLOUDSC2_EINVAL, "parameter Jacobian: every block must have the same block stride per layout group");
-  }
-  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
-  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sp.full, sp.half, sp.loc}))) return rc;
-  args.c = w.c; args.g = w.g; args.s = w.s; args.sp = sp; args.in = w.in; args.tab = w.tab;
-  for (int b = 0; b < kBatchMax; ++b) {  // (the sets from `np` on are not read: valid contents all the same)
-    double e[PAR_COUNT] = {};
-    e[b < np ? b : 0] = 1.0;
-    args.par[b] = make_parlin(w.c, e);
-    if (b >= np) args.dout[b] = args.dout[0];
-  }
-  const KernelFn<TlParJacArgs> fn = tl_parjac_variant(w.f);
-  schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
-  return launch_variant(kFamTlParjac, w.f, fn, args, w.g.ncols_pad, (hipStream_t)stream);
-}
-
-// The Gauss-Newton normal equations of the parameters: J^T W J and J^T W r over every active column, level and observed output, without
-// J ever existing in memory (parnormal_column sums each column in registers; the fold of cloudsc2_vjp_launch_par adds the columns).
-// Two kernel nodes, both launched directly: this is not a sweep family (no family number, no pacing, no launch-log entry).
-static_assert(CLOUDSC2_NNORMAL == normal_sums(PAR_COUNT) && CLOUDSC2_NNORMAL <= 32, "rows of the workspace: one bit each in the fold's mask");
-int parnormal_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
-                          const cloudsc2_outputs* resid, const cloudsc2_outputs* weight, double* work, double* normal, void* stream) {
-  // (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
-  if (!prm || !traj_in || !resid || !work || !normal) return fail(CLOUDSC2_EINVAL, "NULL argument block, workspace or result");
-  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "normal equations: CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
-  const bool evap = prm->levapls2 || prm->ldrain1d;
-  if (evap && prm->rpecons == 0.0) return fail(CLOUDSC2_EINVAL, "parameter derivative with the evaporation branch: rpecons must not be 0");
-  Sweep w;
-  int rc = resolve_in(*traj_in, false, w.s, w.in);
-  if (rc) return rc;
-  memset(&w.out, 0, sizeof(w.out));
-  const cloudsc2_outputs none = {};
-  const cloudsc2_outputs& wt = weight ? *weight : none;
-  const cloudsc2_field* rf[10] = {&resid->tent, &resid->tenq, &resid->tenl, &resid->teni, &resid->clc,
-                                  &resid->fplsl, &resid->fplsn, &resid->fhpsl, &resid->fhpsn, &resid->covptot};
-  const cloudsc2_field* wf[10] = {&wt.tent, &wt.tenq, &wt.tenl, &wt.teni, &wt.clc, &wt.fplsl, &wt.fplsn, &wt.fhpsl, &wt.fhpsn, &wt.covptot};
-  const int group[10] = {0, 0, 0, 0, 1, 2, 2, 2, 2, 1};  // loc, full, half
-  bool weighted[3] = {false, false, false};
-  int nobs = 0;
-  for (int i = 0; i < 10; ++i) {
-    if (rf[i]->ptr) ++nobs;
-    else if (wf[i]->ptr) return fail(CLOUDSC2_EINVAL, "normal equations: a weight is given for an output that is not observed (its residual is NULL)");
-    if (wf[i]->ptr) weighted[group[i]] = true;
-  }
-  if (!nobs) return fail(CLOUDSC2_EINVAL, "normal equations: no output is observed (every residual field is NULL)");
-  ParNormalArgs args;
-  Strides sr = {0, 0, 0, 0, 0}, sw = {0, 0, 0, 0, 0};
-  if ((rc = resolve_out(*resid, false, sr, args.resid)) || (rc = resolve_out(wt, false, sw, args.weight))) return rc;
-  if ((weighted[0] && sw.loc != sr.loc) || (weighted[1] && sw.full != sr.full) || (weighted[2] && sw.half != sr.half))
-    return fail(CLOUDSC2_EINVAL, "normal equations: residuals and weights must have the same block stride per layout group");
-  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
-  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sr.full, sr.half, sr.loc}))) return rc;
-  const unsigned f = w.f & ~C2F_OFF32;  // (64-bit offsets always: a 32-bit form is not built)
-  args.c = w.c; args.g = w.g; args.s = w.s; args.sr = sr; args.in = w.in; args.tab = w.tab; args.work = work;
-  const int np = evap ? (int)PAR_COUNT : (int)PAR_COUNT - 1;
-  for (int b = 0; b < kBatchMax; ++b) {  // (the sets from `np` on are not read: valid contents all the same)
-    double e[PAR_COUNT] = {};
-    e[b < np ? b : 0] = 1.0;
-    args.par[b] = make_parlin(w.c, e);
-  }
-  const KernelFn<ParNormalArgs> fn = parnormal_variant(f);
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
-  schedule(args.g, nullptr, false, nullptr);
-  const hipStream_t st = (hipStream_t)stream;
-  const long long n = w.g.ncols_pad;
-  void* argv[] = {&args};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(n, kBlock)), dim3(kBlock), argv, 0, st));
-  if (evap) {
-    hipLaunchKernelGGL(par_fold_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)w.g.ngptot, normal);
-  } else {  // the rows with rpecons were not written: not read, stored as zeros
-    unsigned unwritten = 1u << normal_row_g(PAR_RPECONS);
-    for (int a = 0; a < PAR_COUNT; ++a) unwritten |= 1u << normal_row_h(a, PAR_RPECONS);
-    hipLaunchKernelGGL(par_fold_rows_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)w.g.ngptot,
-                       unwritten, normal);
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-int vjp_batch_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
-                          const cloudsc2_outputs* traj_out, int nbatch, const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
-                          const cloudsc2_real* scratch, void* stream) {
-  Sweep w;
-  int rc = w.begin(prm, nproma, nlev, ngptot,
-                   (!traj_in || !traj_out || !adj_in || !adj_out) ? "NULL argument block" : nbatch < 1 ? "nbatch >= 1 required" : nullptr);
-  if (rc) return rc;
-  if (!traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "qsat field required");
-  if (nbatch == 1)  // one direction: the single-direction sweep itself
-    return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch), stream,
-                          AdMode{2, true, true});
-  if ((rc = w.trajectory(*traj_in, *traj_out, false))) return rc;
-  if (!w.out.fplsl || !w.out.fplsn) return fail(CLOUDSC2_EINVAL, "reverse sweep: traj_out->fplsl and ->fplsn (PFPLSL5, PFPLSN5) are required");
-  std::vector<InPtrsRW> ain((size_t)nbatch);
-  std::vector<OutPtrs> aout((size_t)nbatch);
-  Strides sa = {0, 0, 0, 0, 0};
-  for (int b = 0; b < nbatch; ++b) {
-    Strides sb = {0, 0, 0, 0, 0};
-    InPtrs checked;
-    if ((rc = resolve_in(adj_in[b], true, sb, checked)) || (rc = resolve_out(adj_out[b], true, sb, aout[b]))) return rc;
-    ain[b] = writable(adj_in[b]);
-    if (b == 0) sa = sb;
-    else if (!same_strides(sa, sb)) return fail(CLOUDSC2_EINVAL, "batched launch: every direction must have the same block stride per layout group");
-  }
-  if ((rc = w.finish(*prm, ptsphy, true, {sa.full, sa.half, sa.cml, sa.clv, sa.loc, (long long)nproma * nlev /* scratch */}))) return rc;
-  if (w.c.evap && !scratch) return fail(CLOUDSC2_EINVAL, "LEVAPLS2/LDRAIN1D: the cover-checkpoint plane `scratch` is required");
-  VjpBatchArgs args;
-  args.nl = w.nl();
-  args.nl.ckpt = const_cast<cloudsc2_real*>(scratch);
-  args.sa = sa;
-  return for_each_chunk(nbatch, [&](int first, int count) {
-    const KernelFn<VjpBatchArgs> fn = vjp_batch_variant(w.f, count);
-    for (int b = 0; b < kBatchMax; ++b) {
-      args.ain[b] = ain[first + (b < count ? b : 0)];
-      args.aout[b] = aout[first + (b < count ? b : 0)];
-    }
-    schedule(args.nl.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
-    return launch_variant(kFamVjpBatch, w.f + 64u * (unsigned)count, fn, args, w.g.ncols_pad, (hipStream_t)stream);
-  });
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // state expansion / validation launchers
 // ---------------------------------------------------------------------------------------------------------
@@ -1006,13 +809,10 @@ int check_expand_args(const cloudsc2_real* table, int klon, int period, long lon
 }
 
 int ten_ptrs(const cloudsc2_outputs* o, int nlev, TenPtrs& t) {
-  // order of the ERROR_NORM calls, cloudsc_driver_tl_mod.F90:233-242
-  const cloudsc2_field* f[10] = {&o->tent, &o->tenq, &o->tenl, &o->teni, &o->clc,
-                                 &o->fplsl, &o->fplsn, &o->fhpsl, &o->fhpsn, &o->covptot};
-  const int half[10] = {0, 0, 0, 0, 0, 1, 1, 1, 1, 0};
-  for (int i = 0; i < 10; ++i) {
-    if (!f[i]->ptr) return fail(CLOUDSC2_EINVAL, "taylor sums: NULL field");
-    t.p[i] = f[i]->ptr; t.stride[i] = f[i]->block_stride; t.nlevx[i] = nlev + half[i];
+  const cloudsc2_field* f = fields_of(*o);  // (the order of the ERROR_NORM calls, cloudsc_driver_tl_mod.F90:233-242)
+  for (int i = 0; i < kNumOut; ++i) {
+    if (!f[i].ptr) return fail(CLOUDSC2_EINVAL, "taylor sums: NULL field");
+    t.p[i] = f[i].ptr; t.stride[i] = f[i].block_stride; t.nlevx[i] = nlev + (kOutGroup[i] == kHalf ? 1 : 0);
   }
   return 0;
 }
@@ -1147,13 +947,15 @@ int cloudsc2_tl_launch(const cloudsc2_params* prm, double ptsphy, int nproma, in
                        const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
                        const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out, void* stream) {
   if (!pert_in) return fail(CLOUDSC2_EINVAL, "NULL argument block");
-  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, pert_in, 0.0, pert_out, nullptr, stream);
+  TlMode m; m.pert_in = pert_in;
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, pert_out, stream, m);
 }
 
 int cloudsc2_tl_launch_self(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
                             const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, double supsat_increment,
                             const cloudsc2_outputs* pert_out, double* yy, void* stream) {
-  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, nullptr, supsat_increment, pert_out, yy, stream);
+  TlMode m; m.supsat_inc = supsat_increment; m.yy = yy;
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, pert_out, stream, m);
 }
 
 int cloudsc2_ad_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
@@ -1197,7 +999,8 @@ int cloudsc2_tl_launch_satur(const cloudsc2_params* prm, double ptsphy, int npro
                              void* stream) {
   if (!pert_in) return fail(CLOUDSC2_EINVAL, "NULL argument block");
   const cloudsc2_outputs none = {};
-  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_in, 0.0, pert_out, nullptr, stream, true);
+  TlMode m; m.pert_in = pert_in; m.satlin = true;
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_out, stream, m);
 }
 
 int cloudsc2_vjp_launch_satur(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
@@ -1210,20 +1013,18 @@ int cloudsc2_vjp_launch_satur(const cloudsc2_params* prm, double ptsphy, int npr
 
 static_assert(CLOUDSC2_NPAR == PAR_COUNT, "the header's parameter count is the level functions'");
 
-int cloudsc2_par_work_doubles(int nproma, int ngptot, long long* n) {
-  if (nproma < 1 || ngptot < 1 || !n) return fail(CLOUDSC2_EINVAL, "nproma >= 1, ngptot >= 1 and a result pointer required");
-  *n = (long long)PAR_COUNT * ((((long long)ngptot + nproma - 1) / nproma) * nproma);
-  return 0;
-}
+int cloudsc2_par_work_doubles(int nproma, int ngptot, long long* n) { return work_doubles(PAR_COUNT, nproma, ngptot, n); }
+int cloudsc2_parnormal_work_doubles(int nproma, int ngptot, long long* n) { return work_doubles(CLOUDSC2_NNORMAL, nproma, ngptot, n); }
 
 int cloudsc2_tl_launch_par(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
                            const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const double* dpar,
                            const cloudsc2_outputs* pert_out, void* stream) {
   if (int rc = check_par(prm, satur)) return rc;
   if (!pert_in || !dpar) return fail(CLOUDSC2_EINVAL, "NULL argument block");
-  if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
+  if (int rc = require_qsat(satur, traj_in)) return rc;
   const cloudsc2_outputs none = {};
-  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_in, 0.0, pert_out, nullptr, stream, satur != 0, dpar);
+  TlMode m; m.pert_in = pert_in; m.satlin = satur != 0; m.dpar = dpar;
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_out, stream, m);
 }
 
 int cloudsc2_vjp_launch_par(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
@@ -1232,39 +1033,17 @@ int cloudsc2_vjp_launch_par(const cloudsc2_params* prm, double ptsphy, int nprom
                             const cloudsc2_real* scratch, double* work, double* par_adj, void* stream) {
   if (int rc = check_par(prm, satur)) return rc;
   if (!work || !par_adj) return fail(CLOUDSC2_EINVAL, "the parameter workspace and result are required");
-  if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
+  if (int rc = require_qsat(satur, traj_in)) return rc;
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
                         stream, AdMode{2, true, true, nullptr, nullptr, satur != 0, work, par_adj});
 }
 
 // ---- perturbed-parameter ensembles: the three launchers above for `members` members, the parameters read on the device ----------------
-namespace {
-int check_ens(const cloudsc2_params* prm, int satur, int members, const double* params_dev, const void* workspace) {
-  if (satur != 0 && satur != 1) return fail(CLOUDSC2_EINVAL, "satur must be 0 (qsat given) or 1 (SATUR differentiated in the sweep)");
-  if (members < 1 || members > 65535) return fail(CLOUDSC2_EINVAL, "ensemble: 1 <= members <= 65535 required");
-  if (!params_dev || !workspace) return fail(CLOUDSC2_EINVAL, "ensemble: the parameter array and the workspace are required");
-  if (prm && !prm->lphylin) return fail(CLOUDSC2_EINVAL, "ensemble: CLOUDSC2TL / CLOUDSC2AD linearise the LPHYLIN form only (prm->lphylin = 0)");
-  return 0;
-}
-// a block the members WRITE (n fields from `first` on): with more than one member no field may be shared (member stride 0), the
-// members would write over each other; then the device check, as in check_par
-static_assert(sizeof(cloudsc2_inputs) == 16 * sizeof(cloudsc2_field) && sizeof(cloudsc2_outputs) == 10 * sizeof(cloudsc2_field), "blocks of fields");
-int check_ens_written(const cloudsc2_field* first, int n, const long long* mstride, int members) {
-  for (int i = 0; first && members > 1 && i < n; ++i)
-    if (first[i].ptr && (!mstride || mstride[i] == 0))
-      return fail(CLOUDSC2_EINVAL, "ensemble: a field the members write has member stride 0 (every member needs its own)");
-  return require_device();
-}
-void ens_copy(long long* dst, const long long* src, int n) {
-  for (int i = 0; i < n; ++i) dst[i] = src ? src[i] : 0;
-}
-}  // namespace
 
 long long cloudsc2_ens_workspace_bytes(int members, int nproma, int nlev, int ngptot) {
   if (members < 1 || members > 65535 || nproma < 1 || nlev < 2 || nlev > CLOUDSC2_MAX_NLEV || ngptot < 1)
     return fail(CLOUDSC2_EINVAL, "1 <= members <= 65535, nproma >= 1, 2 <= nlev <= CLOUDSC2_MAX_NLEV, ngptot >= 1 required");
-  const long long ncols_pad = (((long long)ngptot + nproma - 1) / nproma) * nproma;
-  return (long long)ens_blocks_bytes(members) + (long long)members * PAR_COUNT * ncols_pad * (long long)sizeof(double);
+  return (long long)ens_blocks_bytes(members) + (long long)members * PAR_COUNT * ncols_pad(nproma, ngptot) * (long long)sizeof(double);
 }
 
 int cloudsc2_nl_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int members, const double* params_dev,
@@ -1273,11 +1052,8 @@ int cloudsc2_nl_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma
                            void* stream) {
   if (int rc = check_ens(prm, 0, members, params_dev, workspace)) return rc;
   if (scratch && members > 1 && scratch_mstride == 0) return fail(CLOUDSC2_EINVAL, "ensemble: the cover-checkpoint plane has member stride 0");
-  if (int rc = check_ens_written(traj_out ? &traj_out->tent : nullptr, 10, traj_out_mstride, members)) return rc;
-  EnsSpec e = {members, params_dev, nullptr, {}, workspace, nullptr};
-  ens_copy(e.ms.in, traj_in_mstride, 16); ens_copy(e.ms.out, traj_out_mstride, 10);
-  ens_copy(e.ms.in2, nullptr, 16); ens_copy(e.ms.out2, nullptr, 10);
-  e.ms.ckpt = scratch_mstride;
+  if (int rc = check_ens_written(traj_out, traj_out_mstride, members)) return rc;
+  EnsSpec e = {members, params_dev, nullptr, ens_strides(traj_in_mstride, traj_out_mstride, nullptr, nullptr, scratch_mstride), workspace, nullptr};
   AdMode m{1, false, false};
   m.ens = &e;
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, nullptr, nullptr, scratch, stream, m);
@@ -1288,16 +1064,14 @@ int cloudsc2_tl_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma
                            const long long* traj_in_mstride, const cloudsc2_inputs* pert_in, const long long* pert_in_mstride,
                            const cloudsc2_outputs* pert_out, const long long* pert_out_mstride, void* workspace, void* stream) {
   if (int rc = check_ens(prm, satur, members, params_dev, workspace)) return rc;
-  if (int rc = check_ens_written(pert_out ? &pert_out->tent : nullptr, 10, pert_out_mstride, members)) return rc;
+  if (int rc = check_ens_written(pert_out, pert_out_mstride, members)) return rc;
   if (!pert_in || !dparams_dev) return fail(CLOUDSC2_EINVAL, "NULL argument block");
-  if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
-  EnsSpec e = {members, params_dev, dparams_dev, {}, workspace, nullptr};
-  ens_copy(e.ms.in, traj_in_mstride, 16); ens_copy(e.ms.out, nullptr, 10);
-  ens_copy(e.ms.in2, pert_in_mstride, 16); ens_copy(e.ms.out2, pert_out_mstride, 10);
-  e.ms.ckpt = 0;
+  if (int rc = require_qsat(satur, traj_in)) return rc;
+  EnsSpec e = {members, params_dev, dparams_dev, ens_strides(traj_in_mstride, nullptr, pert_in_mstride, pert_out_mstride, 0), workspace, nullptr};
   const cloudsc2_outputs none = {};
   const double no_tangent[PAR_COUNT] = {};  // (the template's; every member's come from dparams_dev)
-  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_in, 0.0, pert_out, nullptr, stream, satur != 0, no_tangent, &e);
+  TlMode m; m.pert_in = pert_in; m.satlin = satur != 0; m.dpar = no_tangent; m.ens = &e;
+  return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_out, stream, m);
 }
 
 int cloudsc2_vjp_launch_ens(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
@@ -1306,13 +1080,11 @@ int cloudsc2_vjp_launch_ens(const cloudsc2_params* prm, double ptsphy, int nprom
                             const long long* adj_in_mstride, const cloudsc2_outputs* adj_out, const long long* adj_out_mstride,
                             const cloudsc2_real* scratch, long long scratch_mstride, void* workspace, double* par_adj, void* stream) {
   if (int rc = check_ens(prm, satur, members, params_dev, workspace)) return rc;
-  if (int rc = check_ens_written(adj_in ? &adj_in->paph : nullptr, 16, adj_in_mstride, members)) return rc;
+  if (int rc = check_ens_written(adj_in, adj_in_mstride, members)) return rc;
   if (!par_adj) return fail(CLOUDSC2_EINVAL, "the parameter adjoints' array is required");
-  if (!satur && traj_in && !traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required");
-  EnsSpec e = {members, params_dev, nullptr, {}, workspace, par_adj};
-  ens_copy(e.ms.in, traj_in_mstride, 16); ens_copy(e.ms.out, traj_out_mstride, 10);
-  ens_copy(e.ms.in2, adj_in_mstride, 16); ens_copy(e.ms.out2, adj_out_mstride, 10);
-  e.ms.ckpt = scratch_mstride;
+  if (int rc = require_qsat(satur, traj_in)) return rc;
+  EnsSpec e = {members, params_dev, nullptr, ens_strides(traj_in_mstride, traj_out_mstride, adj_in_mstride, adj_out_mstride, scratch_mstride), workspace,
+               par_adj};
   AdMode m{2, true, true, nullptr, nullptr, satur != 0, (double*)((char*)workspace + ens_blocks_bytes(members)), par_adj};
   m.ens = &e;
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch), stream, m);
@@ -1320,34 +1092,169 @@ int cloudsc2_vjp_launch_ens(const cloudsc2_params* prm, double ptsphy, int nprom
 
 int cloudsc2_batch_max(void) { return kBatchMax; }
 
-int cloudsc2_tl_launch_batch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
-                             const cloudsc2_inputs* traj_in, int nbatch, const cloudsc2_inputs* pert_in,
-                             const cloudsc2_outputs* pert_out, void* stream) {
-  return tl_batch_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, nbatch, pert_in, pert_out, stream);
+int cloudsc2_tl_launch_batch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                             int nbatch, const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out, void* stream) {
+  Sweep w;
+  int rc = w.begin(prm, nproma, nlev, ngptot,
+                   (!traj_in || !pert_in || !pert_out) ? "NULL argument block" : nbatch < 1 ? "nbatch >= 1 required" : nullptr);
+  if (rc) return rc;
+  if (nbatch == 1) {  // one direction: the single-direction sweep itself (it requires qsat of pert_in only, so ask here)
+    if (!traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "qsat field required");
+    const cloudsc2_outputs none = {};
+    TlMode m; m.pert_in = pert_in;
+    return tl_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, &none, pert_out, stream, m);
+  }
+  if ((rc = resolve_in(*traj_in, true, w.s, w.in))) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  std::vector<InPtrs> din((size_t)nbatch);
+  std::vector<OutPtrs> dout((size_t)nbatch);
+  Strides sp = {0, 0, 0, 0, 0};
+  for (int b = 0; b < nbatch; ++b) {
+    Strides sb = {0, 0, 0, 0, 0};
+    if ((rc = resolve_in(pert_in[b], true, sb, din[b])) || (rc = resolve_out(pert_out[b], true, sb, dout[b]))) return rc;
+    if (b == 0) sp = sb;
+    else if (!same_strides(sp, sb)) return fail(CLOUDSC2_EINVAL, "batched launch: every direction must have the same block stride per layout group");
+  }
+  if ((rc = w.finish(*prm, ptsphy, true, {sp.full, sp.half, sp.cml, sp.clv, sp.loc}))) return rc;
+  TlBatchArgs args;
+  args.c = w.c; args.g = w.g; args.s = w.s; args.sp = sp; args.in = w.in; args.tab = w.tab;
+  return for_each_chunk(nbatch, [&](int first, int count) {
+    const KernelFn<TlBatchArgs> fn = tl_batch_variant(w.f, count);  // (the direction count is the kernel's compile-time one)
+    for (int b = 0; b < kBatchMax; ++b) {  // (the sets from `count` on are not read: valid pointers all the same)
+      args.din[b] = din[first + (b < count ? b : 0)];
+      args.dout[b] = dout[first + (b < count ? b : 0)];
+    }
+    schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
+    return launch_variant(kFamTlBatch, w.f + 64u * (unsigned)count, fn, args, w.g.ncols_pad, (hipStream_t)stream);
+  });
 }
 
-int cloudsc2_vjp_launch_batch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
-                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, int nbatch,
-                              const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+int cloudsc2_vjp_launch_batch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                              const cloudsc2_outputs* traj_out, int nbatch, const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                               const cloudsc2_real* scratch, void* stream) {
-  return vjp_batch_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, nbatch, adj_in, adj_out, scratch, stream);
+  Sweep w;
+  int rc = w.begin(prm, nproma, nlev, ngptot,
+                   (!traj_in || !traj_out || !adj_in || !adj_out) ? "NULL argument block" : nbatch < 1 ? "nbatch >= 1 required" : nullptr);
+  if (rc) return rc;
+  if (!traj_in->qsat.ptr) return fail(CLOUDSC2_EINVAL, "qsat field required");
+  if (nbatch == 1)  // one direction: the single-direction sweep itself
+    return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch), stream,
+                          AdMode{2, true, true});
+  if ((rc = w.trajectory(*traj_in, *traj_out, false))) return rc;
+  if (!w.out.fplsl || !w.out.fplsn) return fail(CLOUDSC2_EINVAL, "reverse sweep: traj_out->fplsl and ->fplsn (PFPLSL5, PFPLSN5) are required");
+  std::vector<InPtrsRW> ain((size_t)nbatch);
+  std::vector<OutPtrs> aout((size_t)nbatch);
+  Strides sa = {0, 0, 0, 0, 0};
+  for (int b = 0; b < nbatch; ++b) {
+    Strides sb = {0, 0, 0, 0, 0};
+    InPtrs checked;
+    if ((rc = resolve_in(adj_in[b], true, sb, checked)) || (rc = resolve_out(adj_out[b], true, sb, aout[b]))) return rc;
+    ain[b] = writable(adj_in[b]);
+    if (b == 0) sa = sb;
+    else if (!same_strides(sa, sb)) return fail(CLOUDSC2_EINVAL, "batched launch: every direction must have the same block stride per layout group");
+  }
+  if ((rc = w.finish(*prm, ptsphy, true, {sa.full, sa.half, sa.cml, sa.clv, sa.loc, (long long)nproma * nlev /* scratch */}))) return rc;
+  if (w.c.evap && !scratch) return fail(CLOUDSC2_EINVAL, "LEVAPLS2/LDRAIN1D: the cover-checkpoint plane `scratch` is required");
+  VjpBatchArgs args;
+  args.nl = w.nl();
+  args.nl.ckpt = const_cast<cloudsc2_real*>(scratch);
+  args.sa = sa;
+  return for_each_chunk(nbatch, [&](int first, int count) {
+    const KernelFn<VjpBatchArgs> fn = vjp_batch_variant(w.f, count);
+    for (int b = 0; b < kBatchMax; ++b) {
+      args.ain[b] = ain[first + (b < count ? b : 0)];
+      args.aout[b] = aout[first + (b < count ? b : 0)];
+    }
+    schedule(args.nl.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
+    return launch_variant(kFamVjpBatch, w.f + 64u * (unsigned)count, fn, args, w.g.ncols_pad, (hipStream_t)stream);
+  });
 }
 
-int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
-                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* pert_out, void* stream) {
-  return tl_parjac_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, pert_out, stream);
+// The parameter Jacobian: the sensitivities of the ten outputs to the tunable parameters in ONE sweep over the trajectory
+// (tl_parjac_column: no tangent planes; direction k runs with make_parlin of the unit tangent of parameter k).  Without the evaporation
+// branch the kernel runs CLOUDSC2_NPAR - 1 directions and pert_out[PAR_RPECONS] is not looked at.
+int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                              const cloudsc2_outputs* pert_out, void* stream) {
+  // (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
+  if (!prm || !traj_in || !pert_out) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "parameter Jacobian: CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
+  int rc = check_rpecons(prm);
+  if (rc) return rc;
+  const int np = (prm->levapls2 || prm->ldrain1d) ? (int)PAR_COUNT : (int)PAR_COUNT - 1;
+  Sweep w;
+  if ((rc = resolve_in(*traj_in, false, w.s, w.in))) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  TlParJacArgs args;
+  Strides sp = {0, 0, 0, 0, 0};
+  for (int b = 0; b < np; ++b) {
+    Strides sb = {0, 0, 0, 0, 0};
+    if ((rc = resolve_out(pert_out[b], true, sb, args.dout[b]))) return rc;
+    if (b == 0) sp = sb;
+    else if (!same_strides(sp, sb)) return fail(CLOUDSC2_EINVAL, "parameter Jacobian: every block must have the same block stride per layout group");
+  }
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sp.full, sp.half, sp.loc}))) return rc;
+  args.c = w.c; args.g = w.g; args.s = w.s; args.sp = sp; args.in = w.in; args.tab = w.tab;
+  unit_parlins(args.par, w.c, np);
+  for (int b = np; b < kBatchMax; ++b) args.dout[b] = args.dout[0];  // (not read: valid pointers all the same)
+  const KernelFn<TlParJacArgs> fn = tl_parjac_variant(w.f);
+  schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
+  return launch_variant(kFamTlParjac, w.f, fn, args, w.g.ncols_pad, (hipStream_t)stream);
 }
 
-int cloudsc2_parnormal_work_doubles(int nproma, int ngptot, long long* n) {
-  if (nproma < 1 || ngptot < 1 || !n) return fail(CLOUDSC2_EINVAL, "nproma >= 1, ngptot >= 1 and a result pointer required");
-  *n = (long long)CLOUDSC2_NNORMAL * ((((long long)ngptot + nproma - 1) / nproma) * nproma);
+// The Gauss-Newton normal equations of the parameters: J^T W J and J^T W r over every active column, level and observed output, without
+// J ever existing in memory (parnormal_column sums each column in registers; the fold of cloudsc2_vjp_launch_par adds the columns).
+// Two kernel nodes, both launched directly: this is not a sweep family (no family number, no pacing, no launch-log entry).
+static_assert(CLOUDSC2_NNORMAL == normal_sums(PAR_COUNT) && CLOUDSC2_NNORMAL <= 32, "rows of the workspace: one bit each in the fold's mask");
+int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                              const cloudsc2_outputs* resid, const cloudsc2_outputs* weight, double* work, double* normal, void* stream) {
+  // (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
+  if (!prm || !traj_in || !resid || !work || !normal) return fail(CLOUDSC2_EINVAL, "NULL argument block, workspace or result");
+  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "normal equations: CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
+  int rc = check_rpecons(prm);
+  if (rc) return rc;
+  const bool evap = prm->levapls2 || prm->ldrain1d;
+  Sweep w;
+  if ((rc = resolve_in(*traj_in, false, w.s, w.in))) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  const cloudsc2_outputs none = {};
+  const cloudsc2_outputs& wt = weight ? *weight : none;
+  const cloudsc2_field *rf = fields_of(*resid), *wf = fields_of(wt);
+  bool weighted[kGroups] = {};
+  int nobs = 0;
+  for (int i = 0; i < kNumOut; ++i) {
+    if (rf[i].ptr) ++nobs;
+    else if (wf[i].ptr) return fail(CLOUDSC2_EINVAL, "normal equations: a weight is given for an output that is not observed (its residual is NULL)");
+    if (wf[i].ptr) weighted[kOutGroup[i]] = true;
+  }
+  if (!nobs) return fail(CLOUDSC2_EINVAL, "normal equations: no output is observed (every residual field is NULL)");
+  ParNormalArgs args;
+  Strides sr = {0, 0, 0, 0, 0}, sw = {0, 0, 0, 0, 0};
+  if ((rc = resolve_out(*resid, false, sr, args.resid)) || (rc = resolve_out(wt, false, sw, args.weight))) return rc;
+  if ((weighted[kLoc] && sw.loc != sr.loc) || (weighted[kFull] && sw.full != sr.full) || (weighted[kHalf] && sw.half != sr.half))
+    return fail(CLOUDSC2_EINVAL, "normal equations: residuals and weights must have the same block stride per layout group");
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sr.full, sr.half, sr.loc}))) return rc;
+  const unsigned f = w.f & ~C2F_OFF32;  // (64-bit offsets always: a 32-bit form is not built)
+  args.c = w.c; args.g = w.g; args.s = w.s; args.sr = sr; args.in = w.in; args.tab = w.tab; args.work = work;
+  unit_parlins(args.par, w.c, evap ? (int)PAR_COUNT : (int)PAR_COUNT - 1);
+  const KernelFn<ParNormalArgs> fn = parnormal_variant(f);
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  schedule(args.g, nullptr, false, nullptr);
+  const hipStream_t st = (hipStream_t)stream;
+  const long long n = w.g.ncols_pad;
+  void* argv[] = {&args};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(n, kBlock)), dim3(kBlock), argv, 0, st));
+  if (evap) {
+    hipLaunchKernelGGL(par_fold_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)w.g.ngptot, normal);
+  } else {  // the rows with rpecons were not written: not read, stored as zeros
+    unsigned unwritten = 1u << normal_row_g(PAR_RPECONS);
+    for (int a = 0; a < PAR_COUNT; ++a) unwritten |= 1u << normal_row_h(a, PAR_RPECONS);
+    hipLaunchKernelGGL(par_fold_rows_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)w.g.ngptot,
+                       unwritten, normal);
+  }
+  HIP_TRY(hipGetLastError());
   return 0;
-}
-
-int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
-                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* resid, const cloudsc2_outputs* weight,
-                              double* work, double* normal, void* stream) {
-  return parnormal_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, resid, weight, work, normal, stream);
 }
 
 int cloudsc2_ad_launch_reverse_norms(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
@@ -1397,7 +1304,7 @@ int cloudsc2_taylor_sums_launch(int nproma, int nlev, int ngptot, const cloudsc2
 
 int cloudsc2_taylor_sweep_work_doubles(int nproma, int ngptot, long long* n) {
   if (!n || nproma < 1 || ngptot < 1) return fail(CLOUDSC2_EINVAL, "taylor sweep: bad argument");
-  *n = (long long)(10 * kTaylorLambdas + 10) * (((long long)ngptot + nproma - 1) / nproma) * nproma;
+  *n = (long long)(10 * kTaylorLambdas + 10) * ncols_pad(nproma, ngptot);
   return 0;
 }
 
@@ -1443,8 +1350,7 @@ int cloudsc2_adjoint_norms_launch(int nproma, int nlev, int ngptot, const clouds
   if (!norms) return fail(CLOUDSC2_EINVAL, "NULL argument");
   if (!device_ok()) return no_device();
   Geom g;
-  long long nblocks = ((long long)ngptot + nproma - 1) / nproma;
-  g.nproma = nproma; g.nlev = nlev; g.ngptot = ngptot; g.ncols_pad = nblocks * nproma; g.kb0 = g.kb1 = 0; g.fair = 0;
+  g.nproma = nproma; g.nlev = nlev; g.ngptot = ngptot; g.ncols_pad = ncols_pad(nproma, ngptot); g.kb0 = g.kb1 = 0; g.fair = 0;
   dim3 grid(grid_for(g.ncols_pad, kBlock)), block(kBlock);
   int rc;
   if (y) {
