@@ -1,7 +1,7 @@
 """CLOUDSC2 as a differentiable PyTorch operation: the NL sweep forward, the TL sweep as its jvp, the reverse sweep of the adjoint
 (in its vector-Jacobian form, ``cloudsc2_vjp_launch``) as its backward.
 
-    out = cloudsc2(inputs, prm, ptsphy, ngptot=None, satur=False, params=None)
+    out = cloudsc2(inputs, prm, ptsphy, ngptot=None, satur=False, params=None, sparse=False)
 
 ``inputs`` maps every name of ``binding.IN_NAMES`` to a device tensor (with ``satur=True``: every name but ``qsat``); ``out`` is a :class:`Cloudsc2Outputs` namedtuple over
 ``binding.OUT_NAMES``.  ``torch.autograd.grad`` / ``.backward()``, ``torch.autograd.forward_ad`` and ``torch.func.jvp`` / ``vjp`` /
@@ -33,6 +33,16 @@ neither synchronises nor refuses stream capture, and the ensemble is the batch t
 member is the bits of the 0-d ``params`` call with its row.  The 0-d ``params`` path above keeps its host read on purpose: it is
 the one launch whose constants sit in the kernel-argument segment, its bits, launch log and refusals are what callers and tests rely
 on, and a single parameter set has no table to derive on the device.
+
+Sparse losses.  A loss usually touches a few outputs (surface precipitation, the ``t`` / ``q`` tendencies) and wants a few gradients
+(``t``, ``q``), yet the dense backward reads ten cotangent planes -- zeros allocated for the outputs that took no part -- and writes
+all 16 gradients before ``needs_input_grad`` throws most away.  ``cloudsc2(..., sparse=True)`` is the same forward with gradients
+left unmaterialised: backward is one ``cloudsc2_vjp_launch_sparse`` over the cotangents that exist and the gradients that are
+wanted (nothing else is allocated, read or written; the other inputs get ``None``), jvp one ``cloudsc2_tl_launch_sparse`` over the
+tangents that exist (all ten output tangents are stored).  Every plane is the bits of ``sparse=False``.  With every plane present
+the dense sweeps run; with no cotangent nothing is launched; batched directions under ``vmap`` / ``jacfwd`` / ``jacrev`` go through
+the dense batched rules on zero-filled planes; where ``torch.func`` hands over materialised zeros the op moves more planes and returns
+the same bits.  Not with ``params`` (``NotImplementedError``); the default stays ``sparse=False``.
 
 Batches.  Under ``torch.func.vmap`` the op distinguishes two cases.  Several tangents or cotangents over ONE state -- ``jacfwd``,
 ``jacrev``, ``vmap(jvp)``, ``vmap(vjp_fn)`` -- are one ``cloudsc2_tl_launch_batch`` / ``cloudsc2_vjp_launch_batch`` call: the
@@ -288,6 +298,20 @@ def _zero_filled(names, ts, lay: Layout, like: torch.Tensor) -> dict:
     return out
 
 
+def _forward_launch(prm, ptsphy, lay: Layout, x: dict) -> tuple:
+    """the forward of every form of the op: ``cloudsc2_ad_launch_forward`` over the inputs ``x`` (with ``qsat``, or without it: SATUR
+    evaluated in the sweep) -> the 10 outputs and the cover-checkpoint scratch (empty without the evaporation branch)"""
+    like = x["pap"]
+    dev = like.device
+    out = _new(B.OUT_NAMES, lay, like)
+    scratch = torch.empty((lay.nblocks, lay.nlev, lay.nproma) if _evap(prm) else (0,), dtype=like.dtype, device=dev)
+    with torch.cuda.device(dev):
+        B.check(B.lib.cloudsc2_ad_launch_forward(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                 C.byref(_block("in", x, lay)), C.byref(_block("out", out, lay)),
+                                                 _scratch_ptr(scratch), _stream(dev)))
+    return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
+
+
 # ---- what the vmap rules share --------------------------------------------------------------------------------------------------
 # torch.func.vmap hands a rule its operands with the batch level taken off and ``in_dims`` (None: not batched).  The three functions
 # below share one treatment.  ``traj`` operands batched: a batch of states (_fold).  Only direction operands batched: one batched
@@ -461,15 +485,7 @@ class _Cloudsc2(torch.autograd.Function):
     @staticmethod
     def forward(prm, ptsphy, lay, *xs):
         x = dict(zip(B.IN_NAMES, xs))
-        like = x["pap"]
-        dev = like.device
-        out = _new(B.OUT_NAMES, lay, like)
-        scratch = torch.empty((lay.nblocks, lay.nlev, lay.nproma) if _evap(prm) else (0,), dtype=like.dtype, device=dev)
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_ad_launch_forward(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                                     C.byref(_block("in", x, lay)), C.byref(_block("out", out, lay)),
-                                                     _scratch_ptr(scratch), _stream(dev)))
-        return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
+        return _forward_launch(prm, ptsphy, lay, x)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -638,15 +654,7 @@ class _Cloudsc2Satur(torch.autograd.Function):
     @staticmethod
     def forward(prm, ptsphy, lay, *xs):
         x = dict(zip(SAT_NAMES, xs))
-        like = x["pap"]
-        dev = like.device
-        out = _new(B.OUT_NAMES, lay, like)
-        scratch = torch.empty((lay.nblocks, lay.nlev, lay.nproma) if _evap(prm) else (0,), dtype=like.dtype, device=dev)
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_ad_launch_forward(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                                     C.byref(_block("in", x, lay)), C.byref(_block("out", out, lay)),
-                                                     _scratch_ptr(scratch), _stream(dev)))
-        return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
+        return _forward_launch(prm, ptsphy, lay, x)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -855,15 +863,7 @@ class _Cloudsc2Par(torch.autograd.Function):
     def forward(prm, ptsphy, lay, satur, pnames, *ts):
         names, _ = _names(satur)
         x = dict(zip(names, ts[len(pnames):]))
-        like = x["pap"]
-        dev = like.device
-        out = _new(B.OUT_NAMES, lay, like)
-        scratch = torch.empty((lay.nblocks, lay.nlev, lay.nproma) if _evap(prm) else (0,), dtype=like.dtype, device=dev)
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_ad_launch_forward(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                                     C.byref(_block("in", x, lay)), C.byref(_block("out", out, lay)),
-                                                     _scratch_ptr(scratch), _stream(dev)))
-        return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
+        return _forward_launch(prm, ptsphy, lay, x)
 
     @staticmethod
     def setup_context(ctx, inputs, output):
@@ -941,10 +941,180 @@ def _cloudsc2_par(inputs, prm: B.Params, ptsphy: float, ngptot, satur: bool, par
     return Cloudsc2Outputs(*out[:10])
 
 
-def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None) -> Cloudsc2Outputs:
+# ---- sparse=True: the derivative side moves only the planes a loss touches -----------------------------------------------------------
+# The forward is the dense op's launch.  Backward and jvp hand the cotangents / tangents that exist (not None) and the gradients that
+# are wanted (needs_input_grad) to cloudsc2_vjp_launch_sparse / cloudsc2_tl_launch_sparse: no zero plane is allocated or read, no
+# unwanted gradient is allocated or written.  With every plane present they call the dense inner functions (the same bits, and the
+# measured path).  Batched directions under vmap hand over to the dense batched rules with zero-filled planes.
+
+def _present(names, ts) -> dict:
+    return {n: t for n, t in zip(names, ts) if t is not None}
+
+
+def _normalize_present(ts: dict, lay: Layout, groups: dict) -> dict:
+    """:func:`normalize` for a subset of the fields: every layout group's present members"""
+    return normalize(ts, lay, {g: tuple(n for n in names if n in ts) for g, names in groups.items() if any(n in ts for n in names)})
+
+
+def _dense_rules(satur: bool):
+    return (_Cloudsc2SaturTl, _Cloudsc2SaturVjp) if satur else (_Cloudsc2Tl, _Cloudsc2Vjp)
+
+
+class _Cloudsc2SparseTl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, *n trajectory inputs, *n tangents or None) -> 10 output tangents:
+    ``cloudsc2_tl_launch_sparse`` (n = 16, or 15 with satur); a None tangent is a zero tangent that is not read.  Not differentiable."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, *ts):
+        names, groups = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        like = x["pap"]
+        dev = like.device
+        dx = _normalize_present(_present(names, ts[n:]), lay, groups)
+        dy = _new(B.OUT_NAMES, lay, like)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch_sparse(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
+                                                    C.byref(_block("in", x, lay)), C.byref(_block("in", dx, lay)),
+                                                    C.byref(_block("out", dy, lay)), _stream(dev)))
+        return tuple(dy[k] for k in B.OUT_NAMES)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(*output)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, satur, *ts):
+        # the dense rules on zero-filled planes: every direction is the bits of the dense call
+        names, _ = _names(satur)
+        n = len(names)
+        dims = in_dims[4:]
+        dx = _zero_filled(names, ts[n:], lay, ts[0])
+        ddims = tuple(None if t is None else d for t, d in zip(ts[n:], dims[n:]))
+        return _dense_rules(satur)[0].vmap(info, (None,) * 3 + tuple(dims[:n]) + ddims, prm, ptsphy, lay, *ts[:n], *(dx[k] for k in names))
+
+
+class _Cloudsc2SparseVjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, want, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints or None)
+    -> the input adjoints named in ``want``, in that order: ``cloudsc2_vjp_launch_sparse``; a None adjoint is a zero cotangent that is
+    not read, an input not in ``want`` gets no plane.  Not differentiable."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, want, *ts):
+        names, _ = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        fplsl, fplsn, scratch = ts[n:n + 3]
+        like = x["pap"]
+        dev = like.device
+        y = _normalize_present(_present(B.OUT_NAMES, ts[n + 3:]), lay, OUT_GROUPS)
+        xa = _new(want, lay, like)
+        traj_out = B.Outputs()
+        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch_sparse(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
+                                                     C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
+                                                     C.byref(_block("out", y, lay)), _scratch_ptr(scratch), _stream(dev)))
+        return tuple(xa[k] for k in want)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.mark_non_differentiable(*output)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, satur, want, *ts):
+        # the dense rules on zero-filled planes: every direction is the bits of the dense call; the unwanted adjoints are dropped
+        names, _ = _names(satur)
+        n = len(names)
+        dims = in_dims[5:]
+        y = _zero_filled(B.OUT_NAMES, ts[n + 3:], lay, ts[0])
+        ydims = tuple(None if t is None else d for t, d in zip(ts[n + 3:], dims[n + 3:]))
+        xa, od = _dense_rules(satur)[1].vmap(info, (None,) * 3 + tuple(dims[:n + 3]) + ydims, prm, ptsphy, lay, *ts[:n + 3],
+                                             *(y[k] for k in B.OUT_NAMES))
+        sel = [names.index(k) for k in want]
+        return tuple(xa[j] for j in sel), tuple(od[j] for j in sel)
+
+
+class _Cloudsc2Sparse(torch.autograd.Function):
+    # forward(prm, ptsphy, layout, satur, *n inputs) -> 10 outputs + the cover-checkpoint scratch: the launch of _Cloudsc2 /
+    # _Cloudsc2Satur; gradients are not materialised, so backward sees None for an output that took no part in the loss
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, *xs):
+        names, _ = _names(satur)
+        x = dict(zip(names, xs))
+        return _forward_launch(prm, ptsphy, lay, x)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        prm, ptsphy, lay, satur, *xs = inputs
+        out = dict(zip(B.OUT_NAMES, output[:-1]))
+        scratch = output[-1]
+        ctx.mark_non_differentiable(scratch)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*xs, out["fplsl"], out["fplsn"], scratch)
+        ctx.save_for_forward(*xs)
+        ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur = prm, ptsphy, lay, satur
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        names, _ = _names(ctx.satur)
+        need = ctx.needs_input_grad[4:]
+        ys = grads[:10]
+        if not any(need) or all(g is None for g in ys):
+            return (None,) * (4 + len(names))
+        if all(need) and all(g is not None for g in ys):  # everything present: the dense sweep (the same bits)
+            return (None,) * 4 + tuple(_dense_rules(ctx.satur)[1].apply(ctx.prm, ctx.ptsphy, ctx.lay, *saved, *ys))
+        want = tuple(n for n, nd in zip(names, need) if nd)
+        xa = dict(zip(want, _Cloudsc2SparseVjp.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, want, *saved, *ys)))
+        return (None,) * 4 + tuple(xa.get(n) for n in names)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        xs = ctx.saved_tensors
+        dts = tangents[4:]
+        if all(t is not None for t in dts):  # everything present: the dense sweep (the same bits)
+            dy = _dense_rules(ctx.satur)[0].apply(ctx.prm, ctx.ptsphy, ctx.lay, *xs, *dts)
+        else:  # (all ten output tangents are stored: autograd cannot say which will be used)
+            dy = _Cloudsc2SparseTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, *xs, *dts)
+        return tuple(dy) + (None,)
+
+    @staticmethod
+    def vmap(info, in_dims, prm, ptsphy, lay, satur, *xs):
+        _refuse_nested(xs)
+        names, groups = _names(satur)
+        dims = in_dims[4:]
+        if _batch_size(dims, xs) is None:
+            return _Cloudsc2Sparse.apply(prm, ptsphy, lay, satur, *xs), (None,) * 11
+
+        def one(l, flat):
+            x = normalize(dict(zip(names, flat)), l, groups)
+            return _Cloudsc2Sparse.apply(prm, ptsphy, l, satur, *(x[n] for n in names))
+        evap = _evap(prm)
+        outs = _fold(one, lay, names, xs, dims, B.OUT_NAMES + ("scratch" if evap else None,))
+        return outs, (0,) * 10 + (0 if evap else None,)
+
+
+def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None,
+             sparse: bool = False) -> Cloudsc2Outputs:
     """CLOUDSC2 over all blocks as a differentiable op, SATUR-free (``qsat`` is an input) or, with ``satur=True``, with SATUR
     evaluated and differentiated inside (``inputs`` without ``qsat``); ``params``: a mapping of names of ``PARAM_NAMES`` to 0-d
-    float64 tensors that override those constants of (a copy of) ``prm`` and are differentiated too; see the module docstring."""
+    float64 tensors that override those constants of (a copy of) ``prm`` and are differentiated too; ``sparse=True``: backward and
+    jvp move only the cotangent / tangent planes that exist and the gradients that are wanted (not with ``params``); see the module
+    docstring."""
+    if sparse:
+        if params is not None:
+            raise NotImplementedError("cloudsc2: sparse=True with params= is not built (the parameter sweeps have no sparse form); "
+                                      "use sparse=False with params")
+        names, groups = _names(satur)
+        lay = check_layout(inputs, prm, ngptot, satur=bool(satur))
+        dev = check_device(inputs[n] for n in names)
+        _prepare(dev)
+        x = normalize({n: inputs[n] for n in names}, lay, groups)
+        out = _Cloudsc2Sparse.apply(prm, float(ptsphy), lay, bool(satur), *(x[n] for n in names))
+        return Cloudsc2Outputs(*out[:10])
     if params is not None:
         return _cloudsc2_par(inputs, prm, ptsphy, ngptot, satur, params)
     if satur:

@@ -448,7 +448,113 @@ enum : unsigned {
                      // TL: four parameter tangents add their source terms.  Reverse sweep: the lane sums its column's contributions
                      // in four doubles and stores them to the launch's workspace, which a second kernel folds in a fixed order
                      // (cloudsc2_tl_launch_par, cloudsc2_vjp_launch_par; kernels: cloudsc2_kern_{tl,vjp}_par.hip)
+  C2F_SPARSE = 512u, // TL (without TRAJ / SELFINC / PARLIN) and the VJP form of the reverse sweep (without PARLIN), each with QSAT or with
+                     // SATLIN: only the planes of the launch's two bit masks are moved (struct SparseMasks below).  The argument block is
+                     // TlSparseArgs / AdSparseArgs (cloudsc2_tl_launch_sparse, cloudsc2_vjp_launch_sparse; kernels:
+                     // cloudsc2_kern_{tl,vjp}_sparse.hip).  Off in every other instantiation.
 };
+
+// ---------------------------------------------------------------------------------------------------------
+// Sparse sweeps (C2F_SPARSE): presence of a plane is a property of the LAUNCH
+// ---------------------------------------------------------------------------------------------------------
+// A loss that touches two outputs and wants two gradients moves 4 of the 26 derivative planes.  The launcher puts two bit masks into the
+// argument block, one bit per field in the order of cloudsc2_fields.hpp (= the member order of InPtrs / OutPtrs):
+//   TL:             rd over the 16 input tangents (absent: a zero tangent, not read), wr over the 10 output tangents (absent: not stored)
+//   reverse sweep:  rd over the 10 output adjoints (absent: a zero cotangent, not read), wr over the 16 input adjoints (absent: not stored)
+// The masks are kernel arguments, so every test of a bit is wave-uniform: a scalar branch around the access, no lane diverges.  An absent
+// plane's pointer is NULL and is only ever used under its bit.  Contract: every present plane has the bits of the dense sweep given zero
+// planes for the absent ones.  That takes two things (launder_level below says what the compiler does otherwise):
+//   - the zero of an absent plane is opaque (opaque_zero: an empty asm statement per value), so the level is not specialised on it;
+//   - a value that is stored under a bit is pinned before the branch (C2_PIN_V: an empty asm statement that only READS it), so the
+//     arithmetic that feeds it stays in the level's straight line instead of sinking into the conditional block, where it would
+//     contract differently.  The pin must not redefine the value (as C2_LAUNDER_V does): in the fp32 build that keeps the SLP vectoriser
+//     from packing what it packs in the dense sweep, and other products fuse.
+// (The host builds, compiled without contraction, need neither.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define C2_LAUNDER_V(x) asm volatile("" : "+v"(x))
+#define C2_PIN_V(x) asm volatile("" : : "v"(x))  // a use in this block, no new value: what feeds x is not sunk past here
+#else
+#define C2_LAUNDER_V(x) ((void)0)
+#define C2_PIN_V(x) ((void)0)
+#endif
+struct SparseMasks {
+  unsigned rd, wr;
+};
+enum : unsigned {  // bits of a mask over the 16 inputs
+  C2I_PAPH = 1u << 0, C2I_PAP = 1u << 1, C2I_Q = 1u << 2, C2I_QSAT = 1u << 3, C2I_T = 1u << 4, C2I_L = 1u << 5, C2I_I = 1u << 6,
+  C2I_LUDE = 1u << 7, C2I_LU = 1u << 8, C2I_MFU = 1u << 9, C2I_MFD = 1u << 10, C2I_GT = 1u << 11, C2I_GQ = 1u << 12, C2I_GL = 1u << 13,
+  C2I_GI = 1u << 14, C2I_SUPSAT = 1u << 15, C2I_ALL = 0xffffu
+};
+enum : unsigned {  // bits of a mask over the 10 outputs
+  C2O_TENT = 1u << 0, C2O_TENQ = 1u << 1, C2O_TENL = 1u << 2, C2O_TENI = 1u << 3, C2O_CLC = 1u << 4, C2O_FPLSL = 1u << 5,
+  C2O_FPLSN = 1u << 6, C2O_FHPSL = 1u << 7, C2O_FHPSN = 1u << 8, C2O_COVPTOT = 1u << 9, C2O_ALL = 0x3ffu
+};
+struct TlSparseArgs {
+  TlArgs a; SparseMasks m;
+};
+struct AdSparseArgs {
+  AdArgs a; SparseMasks m;
+};
+typedef const C2_CONST_AS TlSparseArgs* TlSparseArgsP;
+typedef const C2_CONST_AS AdSparseArgs* AdSparseArgsP;
+
+C2_HD real_t opaque_zero() {
+  real_t z = RC(0.0);
+  C2_LAUNDER_V(z);
+  return z;
+}
+
+// load_level for the tangents of a sparse TL launch: a plane is read under its bit, else it is an opaque zero
+template <bool HAS_QSAT, class OT>
+C2_HD void load_level_sparse(InPtrsP pp, unsigned m, const LaneOffT<OT>& o, int nproma, int nlev, int jk, RawLevel& r) {
+  const InPtrs p = *pp;
+  const OT d = level_off(OT(), jk, nproma), d1 = d + row_off(OT(), nproma);
+  r.paph_k1 = (m & C2I_PAPH) ? ldg(p.paph, o.half + d1) : opaque_zero();
+  r.lu_k1 = (jk + 1 < nlev) ? ((m & C2I_LU) ? ldg(p.lu, o.full + d1) : opaque_zero()) : RC(0.0);
+  r.pap = (m & C2I_PAP) ? ldg(p.pap, o.full + d) : opaque_zero();
+  r.q = (m & C2I_Q) ? ldg(p.q, o.full + d) : opaque_zero();
+  r.t = (m & C2I_T) ? ldg(p.t, o.full + d) : opaque_zero();
+  r.l = (m & C2I_L) ? ldg(p.l, o.clv + d) : opaque_zero();
+  r.i = (m & C2I_I) ? ldg(p.i, o.clv + d) : opaque_zero();
+  r.lude = (m & C2I_LUDE) ? ldg(p.lude, o.full + d) : opaque_zero();
+  r.mfu = (m & C2I_MFU) ? ldg(p.mfu, o.full + d) : opaque_zero();
+  r.mfd = (m & C2I_MFD) ? ldg(p.mfd, o.full + d) : opaque_zero();
+  r.gt = (m & C2I_GT) ? ldg(p.gt, o.cml + d) : opaque_zero();
+  r.gq = (m & C2I_GQ) ? ldg(p.gq, o.cml + d) : opaque_zero();
+  r.gl = (m & C2I_GL) ? ldg(p.gl, o.cml + d) : opaque_zero();
+  r.gi = (m & C2I_GI) ? ldg(p.gi, o.cml + d) : opaque_zero();
+  r.supsat = (m & C2I_SUPSAT) ? ldg(p.supsat, o.full + d) : opaque_zero();
+  if (HAS_QSAT) r.qsat = (m & C2I_QSAT) ? ldg(p.qsat, o.full + d) : opaque_zero();
+}
+
+// store_out for the output tangents of a sparse TL launch: every value pinned (C2_PIN_V), then stored under its bit
+template <class OT>
+C2_HD void store_out_sparse(OutPtrsP pp, unsigned m, const LaneOffT<OT>& o, int nproma, int jk, LevelOut v) {
+  C2_PIN_V(v.tent); C2_PIN_V(v.tenq); C2_PIN_V(v.tenl); C2_PIN_V(v.teni); C2_PIN_V(v.clc);
+  C2_PIN_V(v.covptot); C2_PIN_V(v.fplsl); C2_PIN_V(v.fplsn); C2_PIN_V(v.fhpsl); C2_PIN_V(v.fhpsn);
+  const OutPtrs p = *pp;
+  const OT d = level_off(OT(), jk, nproma);
+  if (m & C2O_TENT) stg(p.tent, o.loc + d, v.tent);
+  if (m & C2O_TENQ) stg(p.tenq, o.loc + d, v.tenq);
+  if (m & C2O_TENL) stg(p.tenl, o.loc + d, v.tenl);
+  if (m & C2O_TENI) stg(p.teni, o.loc + d, v.teni);
+  if (m & C2O_CLC) stg(p.clc, o.full + d, v.clc);
+  if (m & C2O_COVPTOT) stg(p.covptot, o.full + d, v.covptot);
+  const OT d1 = d + row_off(OT(), nproma);
+  if (m & C2O_FPLSL) stg(p.fplsl, o.half + d1, v.fplsl);
+  if (m & C2O_FPLSN) stg(p.fplsn, o.half + d1, v.fplsn);
+  if (m & C2O_FHPSL) stg(p.fhpsl, o.half + d1, v.fhpsl);
+  if (m & C2O_FHPSN) stg(p.fhpsn, o.half + d1, v.fhpsn);
+}
+
+// store_top for the flux tangents a sparse TL launch stores
+C2_HD void store_top_sparse(OutPtrsP p, unsigned m, const LaneOff& o, ConstsP c) {
+  const real_t z = RC(0.0);
+  if (m & C2O_FPLSL) p->fplsl[o.half] = z;
+  if (m & C2O_FPLSN) p->fplsn[o.half] = z;
+  if (m & C2O_FHPSL) p->fhpsl[o.half] = -z * c->rlvtt;
+  if (m & C2O_FHPSN) p->fhpsn[o.half] = -z * c->rlstt;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // SATUR for one column
@@ -777,7 +883,9 @@ template <unsigned F>
 C2_HD void tl_column(long long gcol, TlArgsP a) {
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, STORE_TRAJ = (F & C2F_TRAJ) != 0, EVAP = (F & C2F_EVAP) != 0;
   constexpr bool SELFINC = (F & C2F_SELFINC) != 0, SATLIN = (F & C2F_SATLIN) != 0, PARLIN = (F & C2F_PARLIN) != 0;
+  constexpr bool SPARSE = (F & C2F_SPARSE) != 0;
   static_assert(!SATLIN || (!HAS_QSAT && !STORE_TRAJ && !SELFINC), "C2F_SATLIN: SATUR fused, no trajectory stores, increments given");
+  static_assert(!SPARSE || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC && !PARLIN), "C2F_SPARSE: QSAT or SATLIN, no trajectory stores, increments given");
   static_assert(!PARLIN || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC), "C2F_PARLIN: QSAT or SATLIN, no trajectory stores, increments given");
   typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
   LaneOff o, op; bool active;
@@ -801,20 +909,25 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   real_t paph_surf = RC(0.0), dpaph_surf = RC(0.0);
   if (EVAP) {
     paph_surf = in->paph[o.half + (long long)nlev * nproma];
-    dpaph_surf = SELFINC ? paph_surf * RC(0.01) : din->paph[op.half + (long long)nlev * nproma];
+    if constexpr (SPARSE) dpaph_surf = (((TlSparseArgsP)a)->m.rd & C2I_PAPH) ? din->paph[op.half + (long long)nlev * nproma] : opaque_zero();
+    else dpaph_surf = SELFINC ? paph_surf * RC(0.01) : din->paph[op.half + (long long)nlev * nproma];
   }
 
   if (STORE_TRAJ) store_top(out, o, c);
-  store_top(dout, op, c);
+  if constexpr (SPARSE) store_top_sparse(dout, ((TlSparseArgsP)a)->m.wr, op, c);  // (a is the head of a TlSparseArgs)
+  else store_top(dout, op, c);
 
   Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
   Carry dcy; dcy.rfl = RC(0.0); dcy.sfl = RC(0.0); dcy.covptot = RC(0.0);
   RawLevel cur, nxt, dcur, dnxt;
   double yy = 0.0;  // SELFINC: <y,y> of the column (cloudsc_driver_ad_mod.F90:184-195; the fluxes' top values are zero)
-  real_t paph_k = in->paph[o.half], dpaph_k = SELFINC ? paph_k * RC(0.01) : din->paph[op.half];
+  real_t paph_k = in->paph[o.half], dpaph_k;
+  if constexpr (SPARSE) dpaph_k = (((TlSparseArgsP)a)->m.rd & C2I_PAPH) ? din->paph[op.half] : opaque_zero();
+  else dpaph_k = SELFINC ? paph_k * RC(0.01) : din->paph[op.half];
   const LaneOffT<OT> ol = lane_off_as<OT>(o), opl = lane_off_as<OT>(op);  // offsets used inside the level loop
   load_level<HAS_QSAT>(in, ol, nproma, nlev, 0, cur);
-  if (!SELFINC) load_level<!SATLIN>(din, opl, nproma, nlev, 0, dcur);
+  if constexpr (SPARSE) load_level_sparse<!SATLIN>(din, ((TlSparseArgsP)a)->m.rd, opl, nproma, nlev, 0, dcur);
+  else if (!SELFINC) load_level<!SATLIN>(din, opl, nproma, nlev, 0, dcur);
   Pace pace;
   pace.begin(&a->g);
 
@@ -832,7 +945,9 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
     if (!SELFINC) dnxt = dcur;
     if (!last) {
       load_level<HAS_QSAT>(in, ol, nproma, nlev, jk + 1, nxt);
-      if (!SELFINC) load_level<!SATLIN>(din, opl, nproma, nlev, jk + 1, dnxt);
+      // (the masks are re-read from the kernel-argument segment where they are used, like the field pointers: transient SGPRs)
+      if constexpr (SPARSE) load_level_sparse<!SATLIN>(din, ((TlSparseArgsP)ap)->m.rd, opl, nproma, nlev, jk + 1, dnxt);
+      else if (!SELFINC) load_level<!SATLIN>(din, opl, nproma, nlev, jk + 1, dnxt);
     }
     pace.nap();  // (with the next level's loads in flight)
     if constexpr (SATLIN) {  // the tangent of qsat from those of pap and t: no qsat plane in either input set
@@ -857,7 +972,8 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
     C2_LAUNDER(ap);
     out = &ap->out; dout = &ap->dout;
     if (STORE_TRAJ) store_out(out, ol, nproma, jk, lo);
-    store_out(dout, opl, nproma, jk, dlo);
+    if constexpr (SPARSE) store_out_sparse(dout, ((TlSparseArgsP)ap)->m.wr, opl, nproma, jk, dlo);
+    else store_out(dout, opl, nproma, jk, dlo);
     if (SELFINC) {
       yy += (double)dlo.tent * dlo.tent + (double)dlo.tenq * dlo.tenq + (double)dlo.tenl * dlo.tenl + (double)dlo.teni * dlo.teni +
             (double)dlo.clc * dlo.clc + (double)dlo.covptot * dlo.covptot + (double)dlo.fplsl * dlo.fplsl + (double)dlo.fplsn * dlo.fplsn +
@@ -895,9 +1011,10 @@ struct AdLevelLoads {
   RawLevel xo;    // old input adjoints (PSUPSAT is assigned, not accumulated: not read)
 };
 
-template <bool HAS_QSAT, bool ASSIGN, bool EVAP, class OT>
+// SPARSE: an output adjoint is read under its bit of `rd`, else it is an opaque zero (assign form: no old input adjoints)
+template <bool HAS_QSAT, bool ASSIGN, bool EVAP, class OT, bool SPARSE = false>
 C2_HD void ad_load_level(AdArgsP ap, const LaneOffT<OT>& o, const LaneOffT<OT>& oa, OT osc, int nproma, int nlev, int jk,
-                         AdLevelLoads& L) {
+                         AdLevelLoads& L, unsigned rd = 0u) {
   const bool last = (jk == nlev - 1);
   const OT d = level_off(OT(), jk, nproma);
   const OT d1 = d + row_off(OT(), nproma);
@@ -926,16 +1043,30 @@ C2_HD void ad_load_level(AdArgsP ap, const LaneOffT<OT>& o, const LaneOffT<OT>& 
     L.cy.covptot = EVAP ? ldg(ap->nl.ckpt, osc + d) : RC(0.0);
   }
   const OutPtrs pa = ap->aout;
-  L.ya.tent = ldg(pa.tent, oa.loc + d);
-  L.ya.tenq = ldg(pa.tenq, oa.loc + d);
-  L.ya.tenl = ldg(pa.tenl, oa.loc + d);
-  L.ya.teni = ldg(pa.teni, oa.loc + d);
-  L.ya.clc = ldg(pa.clc, oa.full + d);
-  L.ya.covptot = ldg(pa.covptot, oa.full + d);
-  L.ya.fplsn = ldg(pa.fplsn, oa.half + d1);
-  L.ya.fplsl = ldg(pa.fplsl, oa.half + d1);
-  L.ya.fhpsn = ldg(pa.fhpsn, oa.half + d1);
-  L.ya.fhpsl = ldg(pa.fhpsl, oa.half + d1);
+  if constexpr (SPARSE) {
+    static_assert(ASSIGN, "the sparse reverse sweep assigns its input adjoints");
+    L.ya.tent = (rd & C2O_TENT) ? ldg(pa.tent, oa.loc + d) : opaque_zero();
+    L.ya.tenq = (rd & C2O_TENQ) ? ldg(pa.tenq, oa.loc + d) : opaque_zero();
+    L.ya.tenl = (rd & C2O_TENL) ? ldg(pa.tenl, oa.loc + d) : opaque_zero();
+    L.ya.teni = (rd & C2O_TENI) ? ldg(pa.teni, oa.loc + d) : opaque_zero();
+    L.ya.clc = (rd & C2O_CLC) ? ldg(pa.clc, oa.full + d) : opaque_zero();
+    L.ya.covptot = (rd & C2O_COVPTOT) ? ldg(pa.covptot, oa.full + d) : opaque_zero();
+    L.ya.fplsn = (rd & C2O_FPLSN) ? ldg(pa.fplsn, oa.half + d1) : opaque_zero();
+    L.ya.fplsl = (rd & C2O_FPLSL) ? ldg(pa.fplsl, oa.half + d1) : opaque_zero();
+    L.ya.fhpsn = (rd & C2O_FHPSN) ? ldg(pa.fhpsn, oa.half + d1) : opaque_zero();
+    L.ya.fhpsl = (rd & C2O_FHPSL) ? ldg(pa.fhpsl, oa.half + d1) : opaque_zero();
+  } else {
+    L.ya.tent = ldg(pa.tent, oa.loc + d);
+    L.ya.tenq = ldg(pa.tenq, oa.loc + d);
+    L.ya.tenl = ldg(pa.tenl, oa.loc + d);
+    L.ya.teni = ldg(pa.teni, oa.loc + d);
+    L.ya.clc = ldg(pa.clc, oa.full + d);
+    L.ya.covptot = ldg(pa.covptot, oa.full + d);
+    L.ya.fplsn = ldg(pa.fplsn, oa.half + d1);
+    L.ya.fplsl = ldg(pa.fplsl, oa.half + d1);
+    L.ya.fhpsn = ldg(pa.fhpsn, oa.half + d1);
+    L.ya.fhpsl = ldg(pa.fhpsl, oa.half + d1);
+  }
   if (ASSIGN) {
     // assign form: the old input adjoints are not read (16 planes of traffic less per level)
     L.xo.pap = L.xo.q = L.xo.qsat = L.xo.t = L.xo.l = L.xo.i = L.xo.lude = L.xo.mfu = L.xo.mfd = RC(0.0);
@@ -972,6 +1103,8 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   static_assert(!PARLIN || (VJP && (HAS_QSAT != SATLIN)), "C2F_PARLIN: the vector-Jacobian form, QSAT or SATLIN");
   static_assert(!ADNORM || ASSIGN, "the fused norms are those of the adjoint test: assign form");
   static_assert(!VJP || (ASSIGN && !ADNORM), "the vector-Jacobian product assigns its input adjoints and forms no norms");
+  constexpr bool SPARSE = (F & C2F_SPARSE) != 0;
+  static_assert(!SPARSE || (VJP && (HAS_QSAT != SATLIN) && !PARLIN), "C2F_SPARSE: the vector-Jacobian form, QSAT or SATLIN, no parameter adjoints");
   typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
   LaneOff o, oa64; bool active;
   if (!lane_setup(&a->nl.g, &a->nl.s, gcol, o, active)) return 0.0;
@@ -1012,7 +1145,10 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     C2_LAUNDER(ap);
     // all 44 loads of the level at its top; requesting the trajectory part (19 values) one level ahead was measured: +1.6 % time
     // at 160 000 columns, -1 % at 1 M (profiles/r02_ab_experiments.txt)
-    ad_load_level<HAS_QSAT, ASSIGN, EVAP>(ap, ol, oa, osc, nproma, nlev, jk, L);
+    // (SPARSE: the masks are re-read from the kernel-argument segment where they are used, like the field pointers; a is the head of
+    // an AdSparseArgs)
+    if constexpr (SPARSE) ad_load_level<HAS_QSAT, ASSIGN, EVAP, OT, true>(ap, ol, oa, osc, nproma, nlev, jk, L, ((AdSparseArgsP)ap)->m.rd);
+    else ad_load_level<HAS_QSAT, ASSIGN, EVAP>(ap, ol, oa, osc, nproma, nlev, jk, L);
     RawLevel& cur = L.cur;
     cur.paph_k1 = paph_k1;
     const RawLevel& xo = L.xo;
@@ -1046,29 +1182,76 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     C2_LAUNDER(ap);
     const InPtrsRW px = ap->ain;
     const OutPtrs pa = ap->aout;
-    // accumulate input adjoints (cloudsc2ad.F90:1723-1738; PSUPSAT assigned, :1733)
-    stg(px.pap, oa.full + d, xo.pap + ax.pap);
-    stg(px.q, oa.full + d, xo.q + ax.q);
-    if constexpr (!SATLIN) stg(px.qsat, oa.full + d, xo.qsat + ax.qs);
-    stg(px.t, oa.full + d, xo.t + ax.t);
-    stg(px.l, oa.clv + d, xo.l + ax.l);
-    stg(px.i, oa.clv + d, xo.i + ax.i);
-    stg(px.lude, oa.full + d, xo.lude + ax.lude);
-    stg(px.mfu, oa.full + d, xo.mfu + ax.mfu);
-    stg(px.mfd, oa.full + d, xo.mfd + ax.mfd);
-    stg(px.gt, oa.cml + d, xo.gt + ax.gt);
-    stg(px.gq, oa.cml + d, xo.gq + ax.gq);
-    stg(px.gl, oa.cml + d, xo.gl + ax.gl);
-    stg(px.gi, oa.cml + d, xo.gi + ax.gi);
-    // VJP: d(zqp1)/d(PSUPSAT) = 1 (cloudsc2tl.F90:345), so the PSUPSAT adjoint is zqp1's own (ax.q); ax.supsat = PTSPHY*zqp1 is the
-    // reference's CLOUDSC2AD, which the other forms reproduce
-    stg(px.supsat, oa.full + d, VJP ? ax.q : ax.supsat);
-    if (!last) stg(px.lu, oa.full + d1, xo.lu_k1 + ax.lu_k1);
-    surf_acc += ax.paph_surf;
-    if (last) {
-      surf_acc += ax.paph_k1;
+    if constexpr (SPARSE) {
+      // the dense form's values (xo + ax with xo = 0: a -0 becomes +0 exactly as there), each pinned in the level's straight line, then
+      // stored under its bit; an absent plane's pointer is never formed into an address.  The pins stand where the dense sweep's stores
+      // stand, in their order and in their blocks (PLU and PAPHP1 under !last): the SLP vectoriser starts its trees from the operands of
+      // instructions without users, stores and these asm statements alike, in program order -- in another order, or with the two
+      // !last values formed up here, the fp32 build packs other pairs and other products fuse (measured: DESIGN.md 3.6)
+      const unsigned wr = ((AdSparseArgsP)ap)->m.wr;
+      const real_t v_pap = xo.pap + ax.pap, v_q = xo.q + ax.q, v_t = xo.t + ax.t, v_l = xo.l + ax.l, v_i = xo.i + ax.i;
+      const real_t v_lude = xo.lude + ax.lude, v_mfu = xo.mfu + ax.mfu, v_mfd = xo.mfd + ax.mfd, v_gt = xo.gt + ax.gt, v_gq = xo.gq + ax.gq;
+      const real_t v_gl = xo.gl + ax.gl, v_gi = xo.gi + ax.gi, v_supsat = ax.q;
+      [[maybe_unused]] real_t v_qsat = RC(0.0);
+      if constexpr (!SATLIN) v_qsat = xo.qsat + ax.qs;
+      C2_PIN_V(v_pap); C2_PIN_V(v_q);
+      if constexpr (!SATLIN) C2_PIN_V(v_qsat);
+      C2_PIN_V(v_t); C2_PIN_V(v_l); C2_PIN_V(v_i); C2_PIN_V(v_lude); C2_PIN_V(v_mfu); C2_PIN_V(v_mfd); C2_PIN_V(v_gt); C2_PIN_V(v_gq);
+      C2_PIN_V(v_gl); C2_PIN_V(v_gi); C2_PIN_V(v_supsat);
+      if (wr & C2I_PAP) stg(px.pap, oa.full + d, v_pap);
+      if (wr & C2I_Q) stg(px.q, oa.full + d, v_q);
+      if constexpr (!SATLIN) {
+        if (wr & C2I_QSAT) stg(px.qsat, oa.full + d, v_qsat);
+      }
+      if (wr & C2I_T) stg(px.t, oa.full + d, v_t);
+      if (wr & C2I_L) stg(px.l, oa.clv + d, v_l);
+      if (wr & C2I_I) stg(px.i, oa.clv + d, v_i);
+      if (wr & C2I_LUDE) stg(px.lude, oa.full + d, v_lude);
+      if (wr & C2I_MFU) stg(px.mfu, oa.full + d, v_mfu);
+      if (wr & C2I_MFD) stg(px.mfd, oa.full + d, v_mfd);
+      if (wr & C2I_GT) stg(px.gt, oa.cml + d, v_gt);
+      if (wr & C2I_GQ) stg(px.gq, oa.cml + d, v_gq);
+      if (wr & C2I_GL) stg(px.gl, oa.cml + d, v_gl);
+      if (wr & C2I_GI) stg(px.gi, oa.cml + d, v_gi);
+      if (wr & C2I_SUPSAT) stg(px.supsat, oa.full + d, v_supsat);
+      if (!last) {
+        const real_t v_lu = xo.lu_k1 + ax.lu_k1;
+        C2_PIN_V(v_lu);
+        if (wr & C2I_LU) stg(px.lu, oa.full + d1, v_lu);
+      }
+      surf_acc += ax.paph_surf;
+      if (last) {
+        surf_acc += ax.paph_k1;
+      } else {
+        const real_t v_paph = xo.paph_k1 + (ax.paph_k1 + paph_pending);
+        C2_PIN_V(v_paph);
+        if (wr & C2I_PAPH) stg(px.paph, oa.half + d1, v_paph);
+      }
     } else {
-      stg(px.paph, oa.half + d1, xo.paph_k1 + (ax.paph_k1 + paph_pending));
+      // accumulate input adjoints (cloudsc2ad.F90:1723-1738; PSUPSAT assigned, :1733)
+      stg(px.pap, oa.full + d, xo.pap + ax.pap);
+      stg(px.q, oa.full + d, xo.q + ax.q);
+      if constexpr (!SATLIN) stg(px.qsat, oa.full + d, xo.qsat + ax.qs);
+      stg(px.t, oa.full + d, xo.t + ax.t);
+      stg(px.l, oa.clv + d, xo.l + ax.l);
+      stg(px.i, oa.clv + d, xo.i + ax.i);
+      stg(px.lude, oa.full + d, xo.lude + ax.lude);
+      stg(px.mfu, oa.full + d, xo.mfu + ax.mfu);
+      stg(px.mfd, oa.full + d, xo.mfd + ax.mfd);
+      stg(px.gt, oa.cml + d, xo.gt + ax.gt);
+      stg(px.gq, oa.cml + d, xo.gq + ax.gq);
+      stg(px.gl, oa.cml + d, xo.gl + ax.gl);
+      stg(px.gi, oa.cml + d, xo.gi + ax.gi);
+      // VJP: d(zqp1)/d(PSUPSAT) = 1 (cloudsc2tl.F90:345), so the PSUPSAT adjoint is zqp1's own (ax.q); ax.supsat = PTSPHY*zqp1 is the
+      // reference's CLOUDSC2AD, which the other forms reproduce
+      stg(px.supsat, oa.full + d, VJP ? ax.q : ax.supsat);
+      if (!last) stg(px.lu, oa.full + d1, xo.lu_k1 + ax.lu_k1);
+      surf_acc += ax.paph_surf;
+      if (last) {
+        surf_acc += ax.paph_k1;
+      } else {
+        stg(px.paph, oa.half + d1, xo.paph_k1 + (ax.paph_k1 + paph_pending));
+      }
     }
     if (ADNORM) {  // (assign form: what has just been stored is ax itself)
       const double e = 0.01;
@@ -1097,7 +1280,14 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     paph_k1 = L.paph_k;
   }
   InPtrsRWP ain = &a->ain;
-  if (ASSIGN) {
+  if constexpr (SPARSE) {  // the stores outside the level loop, each under its plane's bit
+    const unsigned wr = ((AdSparseArgsP)a)->m.wr;
+    if (wr & C2I_PAPH) {
+      ain->paph[oa64.half] = paph_pending;
+      ain->paph[oa64.half + (long long)nlev * nproma] = surf_acc;
+    }
+    if (wr & C2I_LU) ain->lu[oa64.full] = RC(0.0);
+  } else if (ASSIGN) {
     ain->paph[oa64.half] = paph_pending;
     ain->paph[oa64.half + (long long)nlev * nproma] = surf_acc;
     ain->lu[oa64.full] = RC(0.0);  // PLU(1) has no adjoint contribution (only PLU(JK+1) is read, cloudsc2.F90:435)
@@ -1170,12 +1360,7 @@ typedef const C2_CONST_AS VjpBatchArgs* VjpBatchArgsP;
 // statement per value: no instruction) -- under a compile-time direction count.  The compiler can then neither share anything
 // between directions nor tell the copies from loaded values.  The trajectory is still READ once per launch, which is the saving:
 // the sweeps wait for HBM, not for the level's arithmetic (measured: the launch runs at the byte ratio).
-// (The host builds, compiled without contraction, need nothing.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define C2_LAUNDER_V(x) asm volatile("" : "+v"(x))
-#else
-#define C2_LAUNDER_V(x) ((void)0)
-#endif
+// (The host builds, compiled without contraction, need nothing.  C2_LAUNDER_V is defined with the sparse sweeps' helpers above.)
 C2_HD void launder_level(LevelIn& x, LevelCst& k, Carry& cy) {  // (all of x but paph_surf, which is invariant over the levels)
   C2_LAUNDER_V(x.paph_k); C2_LAUNDER_V(x.paph_k1); C2_LAUNDER_V(x.pap); C2_LAUNDER_V(x.q); C2_LAUNDER_V(x.qs); C2_LAUNDER_V(x.t);
   C2_LAUNDER_V(x.l); C2_LAUNDER_V(x.i); C2_LAUNDER_V(x.lude); C2_LAUNDER_V(x.lu_k1); C2_LAUNDER_V(x.mfu); C2_LAUNDER_V(x.mfd);

@@ -80,6 +80,36 @@ inline int resolve_out(const cloudsc2_outputs& out, bool all_required, Strides& 
   return 0;
 }
 
+// The sparse launchers' blocks (cloudsc2_tl_launch_sparse: pert_in, pert_out; cloudsc2_vjp_launch_sparse: adj_in, adj_out): any field
+// may be NULL.  s: the block stride of every layout group with a member present on either side (the full-level and half-level groups
+// span both blocks, as in resolve_out), 0 for a group with none -- it has no stride and needs none; the pointers as given; in_mask /
+// out_mask: one bit per field present, in this table's order.  `written`: which of the two blocks the sweep writes ('i' or 'o'): a plane
+// given twice there is refused.
+inline int resolve_sparse(const cloudsc2_inputs& in, const cloudsc2_outputs& out, char written, Strides& s, InPtrs& pi, OutPtrs& po,
+                          unsigned& in_mask, unsigned& out_mask) {
+  const cloudsc2_field *fi = fields_of(in), *fo = fields_of(out);
+  GroupStrides g;
+  in_mask = out_mask = 0u;
+  for (int k = 0; k < kNumIn; ++k) {
+    g.add(kInGroup[k], fi[k]);
+    reinterpret_cast<const real_t**>(&pi)[k] = fi[k].ptr;
+    if (fi[k].ptr) in_mask |= 1u << k;
+  }
+  for (int k = 0; k < kNumOut; ++k) {
+    g.add(kOutGroup[k], fo[k]);
+    reinterpret_cast<real_t**>(&po)[k] = fo[k].ptr;
+    if (fo[k].ptr) out_mask |= 1u << k;
+  }
+  if (!g.ok) return fail(CLOUDSC2_EINVAL, "sparse sweep: the present fields of one layout group must share one block stride");
+  const cloudsc2_field* fw = written == 'i' ? fi : fo;
+  const int nw = written == 'i' ? kNumIn : kNumOut;
+  for (int a = 0; a < nw; ++a)
+    for (int b = a + 1; b < nw; ++b)
+      if (fw[a].ptr && fw[a].ptr == fw[b].ptr) return fail(CLOUDSC2_EINVAL, "sparse sweep: a written plane is given twice");
+  s.full = g.v[kFull]; s.half = g.v[kHalf]; s.cml = g.v[kCml]; s.clv = g.v[kClv]; s.loc = g.v[kLoc];
+  return 0;
+}
+
 // the pointers of a block the sweep writes (the input adjoints)
 inline InPtrsRW writable(const cloudsc2_inputs& x) {
   InPtrsRW p;

@@ -24,6 +24,8 @@
 #include "cloudsc2_kern_nl_ens.hip"
 #include "cloudsc2_kern_tl_ens.hip"
 #include "cloudsc2_kern_vjp_ens.hip"
+#include "cloudsc2_kern_tl_sparse.hip"
+#include "cloudsc2_kern_vjp_sparse.hip"
 #endif
 
 using namespace cloudsc2;
@@ -1009,6 +1011,78 @@ int cloudsc2_vjp_launch_satur(const cloudsc2_params* prm, double ptsphy, int npr
                               const cloudsc2_real* scratch, void* stream) {
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch),
                         stream, AdMode{2, true, true, nullptr, nullptr, true});
+}
+
+// ---- sparse TL and reverse sweeps: only the planes given are moved (C2F_SPARSE) -------------------------------------------------------
+// Two kernel nodes of their own, launched directly like parnormal_kernel: no family number, no launch-log entry.  Scheduling is the
+// twins' (cloudsc2_tl_launch / _satur without trajectory stores, cloudsc2_vjp_launch / _satur).
+// (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
+static int check_sparse(const cloudsc2_params* prm, int satur, const cloudsc2_inputs* traj_in, const cloudsc2_inputs* other_in) {
+  if (int rc = check_satur(satur)) return rc;
+  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "sparse sweep: CLOUDSC2TL / CLOUDSC2AD linearise the LPHYLIN form only (prm->lphylin = 0)");
+  if (satur && (traj_in->qsat.ptr || other_in->qsat.ptr))
+    return fail(CLOUDSC2_EINVAL, "satur = 1: SATUR is differentiated in the sweep, every qsat field must be NULL");
+  return require_qsat(satur, traj_in);
+}
+
+int cloudsc2_tl_launch_sparse(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out,
+                              void* stream) {
+  if (!prm || !traj_in || !pert_in || !pert_out) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  int rc = check_sparse(prm, satur, traj_in, pert_in);
+  if (rc) return rc;
+  Sweep w;
+  if ((rc = resolve_in(*traj_in, false, w.s, w.in))) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  if (!outputs_given(*pert_out)) return fail(CLOUDSC2_EINVAL, "sparse TL sweep: no output tangent is wanted (every pert_out field is NULL)");
+  TlSparseArgs sargs;
+  TlArgs& args = sargs.a;
+  if ((rc = resolve_sparse(*pert_in, *pert_out, 'o', args.sp, args.din, args.dout, sargs.m.rd, sargs.m.wr))) return rc;
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  const Strides& sp = args.sp;
+  if ((rc = w.finish(*prm, ptsphy, !satur, {sp.full, sp.half, sp.cml, sp.clv, sp.loc}))) return rc;
+  if (satur) w.f |= C2F_SATLIN;
+  args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.out = w.out; args.tab = w.tab;
+  args.supsat_inc = 0; args.yy = nullptr;
+  const KernelFn<TlSparseArgs> fn = tl_sparse_variant(w.f);
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);  // (tl_launch_impl says why)
+  schedule(args.g, abreast ? (const void*)fn : nullptr, false, abreast ? nullptr : (const void*)fn);
+  void* argv[] = {&sargs};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
+  return 0;
+}
+
+int cloudsc2_vjp_launch_sparse(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, const cloudsc2_inputs* adj_in,
+                               const cloudsc2_outputs* adj_out, const cloudsc2_real* scratch, void* stream) {
+  if (!prm || !traj_in || !traj_out || !adj_in || !adj_out) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  int rc = check_sparse(prm, satur, traj_in, adj_in);
+  if (rc) return rc;
+  Sweep w;
+  if ((rc = w.trajectory(*traj_in, *traj_out, false))) return rc;
+  if (!w.out.fplsl || !w.out.fplsn) return fail(CLOUDSC2_EINVAL, "reverse sweep: traj_out->fplsl and ->fplsn (PFPLSL5, PFPLSN5) are required");
+  if ((prm->levapls2 || prm->ldrain1d) && !scratch) return fail(CLOUDSC2_EINVAL, "LEVAPLS2/LDRAIN1D: the cover-checkpoint plane `scratch` is required");
+  AdSparseArgs sargs;
+  memset(&sargs, 0, sizeof(sargs));
+  AdArgs& args = sargs.a;
+  InPtrs ain_c;
+  if ((rc = resolve_sparse(*adj_in, *adj_out, 'i', args.sa, ain_c, args.aout, sargs.m.wr, sargs.m.rd))) return rc;
+  if (!sargs.m.rd) return fail(CLOUDSC2_EINVAL, "sparse reverse sweep: no cotangent is given (every adj_out field is NULL)");
+  if (!sargs.m.wr) return fail(CLOUDSC2_EINVAL, "sparse reverse sweep: no gradient is wanted (every adj_in field is NULL)");
+  args.ain = writable(*adj_in);
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  const Strides& sa = args.sa;
+  if ((rc = w.finish(*prm, ptsphy, !satur, {sa.full, sa.half, sa.cml, sa.clv, sa.loc, (long long)nproma * nlev /* scratch */}))) return rc;
+  if (satur) w.f |= C2F_SATLIN;
+  args.nl = w.nl();
+  args.nl.ckpt = const_cast<cloudsc2_real*>(scratch);
+  const KernelFn<AdSparseArgs> fn = vjp_sparse_variant(w.f);
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  schedule(args.nl.g, nullptr, false, (const void*)fn);
+  void* argv[] = {&sargs};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
+  return 0;
 }
 
 static_assert(CLOUDSC2_NPAR == PAR_COUNT, "the header's parameter count is the level functions'");

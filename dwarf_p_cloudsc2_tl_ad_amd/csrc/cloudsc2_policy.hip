@@ -260,6 +260,10 @@ std::vector<int> paced_kernel_occupancies() {
     }
     add((const void*)tl_parjac_variant(f));  // the parameter Jacobian's sweep
   }
+  for (unsigned f = 0; f < 2u * C2F_SATLIN; ++f) {  // the sparse sweeps (C2F_SPARSE), with QSAT or with SATLIN
+    add((const void*)tl_sparse_variant(f));
+    add((const void*)vjp_sparse_variant(f));
+  }
   return out;
 }
 
@@ -455,7 +459,11 @@ int cloudsc2_device_rules(int workgroups_per_cu, int* nl_nap, int* pacing) {
 int cloudsc2_kernel_occupancy(int kernel, int flags, int* workgroups_per_cu) {
   if (!workgroups_per_cu) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: NULL argument");
   if (int rc = require_device()) return rc;
-  const void* fn = kernel >= kFamNl && kernel <= kFamTlParjac ? variant_entry(kernel, (unsigned)flags) : nullptr;
+  // (the sparse TL and reverse sweeps have no family number: the header's kernel numbers of their own)
+  const void* fn = kernel >= kFamNl && kernel <= kFamTlParjac  ? variant_entry(kernel, (unsigned)flags)
+                   : kernel == CLOUDSC2_KERNEL_TL_SPARSE        ? (const void*)tl_sparse_variant((unsigned)flags)
+                   : kernel == CLOUDSC2_KERNEL_VJP_SPARSE       ? (const void*)vjp_sparse_variant((unsigned)flags)
+                                                                : nullptr;
   if (!fn) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: no such kernel variant in this build");
   Occupancy o;
   HIP_TRY(occupancy(fn, &o));

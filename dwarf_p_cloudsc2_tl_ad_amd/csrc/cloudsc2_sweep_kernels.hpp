@@ -128,6 +128,24 @@ constexpr bool par_variant_valid(unsigned f, unsigned form) {
   return rest == (C2F_PARLIN | form | C2F_QSAT) || rest == (C2F_PARLIN | form | C2F_SATLIN);
 }
 
+// The sparse forms (C2F_SPARSE; units cloudsc2_kern_tl_sparse.hip, cloudsc2_kern_vjp_sparse.hip): the same columns over the argument blocks
+// with the two plane masks, under their twins' launch bounds.  Their variant word is the twin's without the bits every one of them has
+// (SPARSE; the reverse sweep: ASSIGN | VJP too): QSAT or SATLIN, times PRECISE, EVAP, OFF32 -- 16 kernels per family and precision.  Not
+// sweep families: no family number, no launch-log entry; launched directly, like parnormal_kernel.
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, (sizeof(real_t) == 4 && (F & C2F_OFF32) && !(F & C2F_EVAP)) ? 3 : 1)
+tl_sparse_kernel(TlSparseArgs args) {
+  C2_KERNEL_BODY((tl_column<F | C2F_SPARSE>(global_column(), &kernarg<TlSparseArgs>()->a)));
+}
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) vjp_sparse_kernel(AdSparseArgs args) {
+  C2_KERNEL_BODY((ad_reverse_column<F | C2F_ASSIGN | C2F_VJP | C2F_SPARSE>(global_column(), &kernarg<AdSparseArgs>()->a)));
+}
+constexpr bool sparse_variant_valid(unsigned f) {
+  const unsigned rest = f & ~(C2F_PRECISE | C2F_EVAP | C2F_OFF32);
+  return rest == C2F_QSAT || rest == C2F_SATLIN;
+}
+
 // The ensemble forms (units cloudsc2_kern_{nl,tl,vjp}_ens.hip): the same columns again, under their parents' launch bounds, over an
 // argument block that lives in device memory -- one per member, written by ens_args_kernel (cloudsc2_launch.hip) in the launch before.
 // The block's address comes from blockIdx and the kernel arguments alone (ens_locate), so it is workgroup-uniform and the constants
@@ -258,5 +276,7 @@ KernelFn<ParNormalArgs> parnormal_variant(unsigned f);
 KernelFn<NlEnsArgs> nl_ens_variant(unsigned f);
 KernelFn<TlEnsArgs> tl_ens_variant(unsigned f);
 KernelFn<VjpEnsArgs> vjp_ens_variant(unsigned f);
+KernelFn<TlSparseArgs> tl_sparse_variant(unsigned f);
+KernelFn<AdSparseArgs> vjp_sparse_variant(unsigned f);
 
 }  // namespace cloudsc2

@@ -324,6 +324,33 @@ int cloudsc2_vjp_launch_satur(const cloudsc2_params* prm, double ptsphy, int npr
                               const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                               const cloudsc2_real* scratch, void* stream);
 
+/* Sparse TL and reverse sweeps: only the planes a loss touches are moved.  The twins are cloudsc2_tl_launch (without trajectory stores)
+ * / cloudsc2_vjp_launch with satur = 0, cloudsc2_tl_launch_satur / cloudsc2_vjp_launch_satur with satur = 1; here a field of the
+ * derivative blocks may have a NULL ptr:
+ *   pert_in   a zero tangent, not read            pert_out  a tangent not stored
+ *   adj_out   a zero cotangent, not read          adj_in    a gradient not wanted, not written
+ * Every plane that is present has the bits of the twin given zero planes for the absent ones (a stored -0 becomes +0 exactly as
+ * there).  The trajectory stays complete: the 16 inputs (satur = 1: 15, every qsat field NULL; satur = 0: traj_in->qsat required,
+ * pert_in->qsat and adj_in->qsat ordinary optional planes), PFPLSL5 / PFPLSN5 and, with LEVAPLS2 .OR. LDRAIN1D, `scratch`.  The
+ * present members of one layout group share one block stride (full-level and half-level: across both derivative blocks); a group
+ * with no member present needs none.  pert_in may be all NULL: the result is the zero tangent's, bit for bit the twin's.
+ * CLOUDSC2_EINVAL, before the device is looked for: a NULL block, an incomplete trajectory, no plane present in pert_out, in adj_out
+ * or in adj_in, different strides in one group, a written plane given twice, a qsat field with satur = 1, satur outside {0, 1},
+ * prm->lphylin = 0, a missing scratch with the evaporation branch.  Neither launcher allocates or synchronises (apart from the CETA
+ * table of a grid's first use); both are plain kernel nodes under stream capture; padded tail columns are not written.  New entry
+ * points rather than a new meaning of NULL in the existing ones, which refuse a NULL field.  The kernels are not a kernel family of
+ * cloudsc2_variant_built and do not appear in the launch log; cloudsc2_kernel_occupancy knows them as kernel
+ * CLOUDSC2_KERNEL_TL_SPARSE and CLOUDSC2_KERNEL_VJP_SPARSE, flags = C2F_QSAT or C2F_SATLIN, times C2F_PRECISE, C2F_EVAP, C2F_OFF32. */
+#define CLOUDSC2_KERNEL_TL_SPARSE 10
+#define CLOUDSC2_KERNEL_VJP_SPARSE 11
+int cloudsc2_tl_launch_sparse(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out,
+                              void* stream);
+int cloudsc2_vjp_launch_sparse(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                               const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
+                               const cloudsc2_real* scratch, void* stream);
+
 /* The derivative with respect to the scheme's tunable parameters, next to the derivative with respect to its fields.  Four constants
  * of cloudsc2_params enter CLOUDSC2 smoothly, in this order (CLOUDSC2_NPAR):
  *   rkconv   the autoconversion rate, ZCKCODTL = 2 RKCONV PTSPHY, ZCKCODTI = 5 RKCONV PTSPHY (cloudsc2.F90:235-236)
