@@ -88,6 +88,10 @@ Device and stream.  Every launch runs on the inputs' device, on ``torch.cuda.cur
 ``cloudsc2_device_prepare`` (a synchronous probe of the dispatcher).  Capturing the op in ``torch.cuda.graph`` therefore needs one
 eager call first, with the same CETA: it runs that probe and uploads the per-level CETA table, neither of which may happen during
 capture.
+
+Column sums.  ``cloudsc2_column_sums(inputs, prm, ptsphy, ngptot, weights={name: w}, satur=...)`` returns per-column weighted level
+sums ``y_n[c] = sum_k w_n[k] out_n[k, c]`` of the outputs, formed in the sweeps (``cloudsc2_{nl,tl,vjp}_launch_colsum``): neither the
+output planes nor their cotangent or tangent planes exist.  Its docstring has the contract.
 """
 from __future__ import annotations
 
@@ -1567,6 +1571,255 @@ def cloudsc2_ensemble(inputs, prm: B.Params, ptsphy: float, ngptot: int | None =
     x = _normalize_ens({n: inputs[n] for n in names}, lay, groups)
     out = _Cloudsc2Ens.apply(prm, float(ptsphy), lay, bool(satur), K, ptab, *(x[n] for n in names))
     return Cloudsc2Outputs(*out[:10])
+
+
+# ---- cloudsc2_column_sums: per-column weighted level sums of the outputs, formed in the sweeps ------------------------------------------
+
+_NO_VMAP_COLSUM = ("cloudsc2_column_sums: torch.func.vmap, jacfwd, jacrev and is_grads_batched=True are not supported (batched "
+                   "directions of the column-sum sweeps are not built); use .backward() / torch.autograd.grad / torch.func.grad / "
+                   "torch.func.vjp, or torch.autograd.forward_ad / torch.func.jvp, one direction at a time")
+
+_NO_SECOND_COLSUM = ("cloudsc2_column_sums: double backward (and forward-over-reverse, reverse-over-forward) is not supported: the sweeps "
+                     "are first-order derivatives of CLOUDSC2")
+
+
+def check_column_sums(inputs, prm: B.Params, ngptot: int | None = None, satur: bool = False, weights=None) -> tuple:
+    """Every check of :func:`cloudsc2_column_sums` that needs no device; returns ``(layout, the given names in OUT_NAMES order)``.
+    Runs on CPU or meta tensors; raises ``ValueError``."""
+    lay = check_layout(inputs, prm, ngptot, satur=bool(satur))
+    if not hasattr(weights, "keys"):
+        raise ValueError(f"weights must map names of {B.OUT_NAMES} to 1-D tensors of per-level weights; got {type(weights)}")
+    if len(weights.keys()) == 0:
+        raise ValueError(f"weights is empty: give a weight vector for at least one of {B.OUT_NAMES}")
+    unknown = sorted((k for k in weights.keys() if k not in B.OUT_NAMES), key=str)
+    if unknown:
+        raise ValueError(f"weights: unknown name(s) {unknown}; the outputs are {B.OUT_NAMES}")
+    dtype, dev = B.torch_real(), inputs["pap"].device
+    wnames = tuple(n for n in B.OUT_NAMES if n in weights.keys())
+    for n in wnames:
+        w = weights[n]
+        if not isinstance(w, torch.Tensor):
+            raise ValueError(f"weights[{n!r}] is not a tensor")
+        if w.dim() != 1:
+            raise ValueError(f"weights[{n!r}] must be 1-D, one weight per level of the plane; got shape {tuple(w.shape)}")
+        if int(w.shape[0]) != lay.nlevx(n):
+            raise ValueError(f"weights[{n!r}] has length {w.shape[0]}, expected {lay.nlevx(n)} (nlev{' + 1: the half levels, k = 0 the top' if n in HALF_OUT else ''})")
+        if w.dtype != dtype:
+            raise ValueError(f"weights[{n!r}] has dtype {w.dtype}; this library works on {dtype} (CLOUDSC2_PRECISION)")
+        if w.requires_grad:
+            raise ValueError(f"weights[{n!r}] requires grad: the weights are constants (the derivative with respect to a weight is the "
+                             "output plane, which this op exists not to form); detach it")
+        if w.device != dev:
+            raise ValueError(f"weights[{n!r}] is on {w.device}: the weights live on the inputs' device {dev}")
+    return lay, wnames
+
+
+def _refuse_batched_colsum(ts) -> None:
+    if any(_batched_inside(t) for t in ts):
+        raise NotImplementedError(_NO_VMAP_COLSUM)
+
+
+def _new_sums(names, lay: Layout, like: torch.Tensor) -> dict:
+    """fresh contiguous (nblocks, nproma) arrays, padded tail zeroed (that slice only)"""
+    out = {}
+    for n in names:
+        t = torch.empty((lay.nblocks, lay.nproma), dtype=like.dtype, device=like.device)
+        if lay.tail < lay.nproma:
+            t[-1, lay.tail:] = 0
+        out[n] = t
+    return out
+
+
+def _sums_block(ts: dict, lay: Layout):
+    """contiguous (nblocks, nproma) tensors by name -> the launchers' block of sums (block stride nproma)"""
+    blk = B.Outputs()
+    for n, t in ts.items():
+        f = B.Field()
+        f.ptr = _raw(t).data_ptr()
+        f.block_stride = lay.nproma
+        setattr(blk, n, f)
+    return blk
+
+
+class _Cloudsc2ColsumTl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, names, table, *n trajectory inputs, *n tangents or None) -> the sums of the output tangents
+    named: ``cloudsc2_tl_launch_colsum``; a None tangent is a zero tangent that is not read.  Differentiating it again raises
+    ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, wnames, table, *ts):
+        names, groups = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        like = x["pap"]
+        dev = like.device
+        dx = _normalize_present(_present(names, ts[n:]), lay, groups)
+        dy = _new_sums(wnames, lay, like)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
+                                                    C.byref(_block("in", x, lay)), C.byref(_block("in", dx, lay)), _ptr(table),
+                                                    C.byref(_sums_block(dy, lay)), _stream(dev)))
+        return tuple(dy[k] for k in wnames)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError(_NO_SECOND_COLSUM)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        raise NotImplementedError(_NO_SECOND_COLSUM)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP_COLSUM)
+
+
+class _Cloudsc2ColsumVjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, want, names, table, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *the cotangents of
+    the sums named or None) -> the input adjoints named in ``want``, in that order: ``cloudsc2_vjp_launch_colsum``; a None cotangent
+    is a zero one that is not read, an input not in ``want`` gets no plane.  Differentiating it again raises ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, want, wnames, table, *ts):
+        names, _ = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        fplsl, fplsn, scratch = ts[n:n + 3]
+        like = x["pap"]
+        dev = like.device
+        y = {k: t.contiguous() for k, t in _present(wnames, ts[n + 3:]).items()}
+        xa = _new(want, lay, like)
+        traj_out = B.Outputs()
+        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
+                                                     C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
+                                                     _ptr(table), C.byref(_sums_block(y, lay)), _scratch_ptr(scratch), _stream(dev)))
+        return tuple(xa[k] for k in want)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError(_NO_SECOND_COLSUM)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        raise NotImplementedError(_NO_SECOND_COLSUM)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP_COLSUM)
+
+
+class _Cloudsc2Colsum(torch.autograd.Function):
+    # forward(prm, ptsphy, layout, satur, names, keep, table, *n inputs) -> the sums named + PFPLSL5, PFPLSN5 and the cover-checkpoint
+    # scratch (all three empty without `keep`): one cloudsc2_nl_launch_colsum.  keep: the call tracks gradients, so the forward keeps what
+    # the reverse sweep re-reads; else it allocates no plane at all.  backward: one cloudsc2_vjp_launch_colsum; jvp: one
+    # cloudsc2_tl_launch_colsum.  Gradients are not materialised: a sum that took no part in the loss is a None cotangent.
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, wnames, keep, table, *xs):
+        names, _ = _names(satur)
+        x = dict(zip(names, xs))
+        like = x["pap"]
+        dev = like.device
+        sums = _new_sums(wnames, lay, like)
+        none = torch.empty((0,), dtype=like.dtype, device=dev)
+        kept, keep_blk, scratch = {"fplsl": none, "fplsn": none}, None, none
+        if keep:
+            kept = _new(("fplsl", "fplsn"), lay, like)
+            keep_blk = C.byref(_block("out", kept, lay))
+            if _evap(prm):
+                scratch = torch.empty((lay.nblocks, lay.nlev, lay.nproma), dtype=like.dtype, device=dev)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_nl_launch_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                    C.byref(_block("in", x, lay)), _ptr(table), C.byref(_sums_block(sums, lay)), keep_blk,
+                                                    _scratch_ptr(scratch), _stream(dev)))
+        return tuple(sums[k] for k in wnames) + (kept["fplsl"], kept["fplsn"], scratch)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        prm, ptsphy, lay, satur, wnames, keep, table, *xs = inputs
+        fplsl, fplsn, scratch = output[-3:]
+        ctx.mark_non_differentiable(fplsl, fplsn, scratch)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(table, *xs, fplsl, fplsn, scratch)
+        ctx.save_for_forward(table, *xs)
+        ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.wnames, ctx.keep = prm, ptsphy, lay, satur, wnames, keep
+
+    @staticmethod
+    def backward(ctx, *grads):
+        names, _ = _names(ctx.satur)
+        need = ctx.needs_input_grad[7:]
+        ys = grads[:len(ctx.wnames)]
+        nothing = (None,) * (7 + len(names))
+        if not any(need) or all(g is None for g in ys):
+            return nothing
+        _refuse_batched_colsum(ys)
+        if not ctx.keep:
+            raise RuntimeError("cloudsc2_column_sums: backward of a forward that tracked no gradient (nothing was kept for the reverse sweep)")
+        table, *saved = ctx.saved_tensors
+        want = tuple(n for n, nd in zip(names, need) if nd)
+        xa = dict(zip(want, _Cloudsc2ColsumVjp.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, want, ctx.wnames, table, *saved, *ys)))
+        return (None,) * 7 + tuple(xa.get(n) for n in names)
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        _refuse_batched_colsum(tangents)
+        table, *xs = ctx.saved_tensors
+        dy = _Cloudsc2ColsumTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.wnames, table, *xs, *tangents[7:])
+        return tuple(dy) + (None, None, None)
+
+    @staticmethod
+    def vmap(info, in_dims, *args):
+        raise NotImplementedError(_NO_VMAP_COLSUM)
+
+
+def cloudsc2_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, weights=None,
+                         satur: bool = False) -> Cloudsc2Outputs:
+    """Per-column weighted level sums of the outputs of :func:`cloudsc2`, formed inside the sweeps: no output plane, no cotangent plane
+    and no tangent plane exists on this route.
+
+    ``inputs``, ``prm``, ``ptsphy``, ``ngptot`` and ``satur`` are those of :func:`cloudsc2`.  ``weights`` maps a non-empty subset of
+    ``binding.OUT_NAMES`` to 1-D tensors of length ``nlevx(name)`` in the library's dtype on the inputs' device (any stride); index ``k``
+    is the plane's level index, for the four fluxes ``k = 0`` is the top half level.  They are constants (a weight that requires grad
+    is refused) and must be finite, which is not checked: the op packs them into one device table with device ops, reads nothing on
+    the host and does not synchronise, so after one eager call the forward and ``torch.autograd.grad`` of it can be captured in
+    ``torch.cuda.graph``.
+
+    Returns a :class:`Cloudsc2Outputs` holding a ``(nblocks, nproma)`` tensor for every name of ``weights`` and ``None`` for the others.
+    Contract, to the bit, for every active column: ``acc = +0; for k: acc = fl(acc + fl(w[k] * out[k]))`` with ``out`` the bits of
+    ``cloudsc2(inputs, ..., satur=satur)`` -- the product is rounded before the add.  The padded tail is zero.  A hybrid-level mass
+    integral ``sum_k (dA_k + dB_k ps) x_k`` is two sums, ``weights dA`` and ``weights dB``, combined per column afterwards.
+
+    Differentiable with respect to the inputs: ``.backward()``, ``torch.autograd.grad``, ``torch.func.grad`` / ``vjp`` / ``jvp`` and
+    ``forward_ad``.  A call that tracks gradients (grad mode on and an input that requires grad) keeps the two flux planes and the
+    cover checkpoints the reverse sweep re-reads; any other call allocates no plane.  Backward allocates and writes only the gradients
+    that are wanted (``None`` elsewhere) and launches nothing without a cotangent; every gradient is the bits of
+    ``cloudsc2(..., sparse=True)`` differentiated through the same fold written in torch.  ``torch.func.vmap`` / ``jacfwd`` /
+    ``jacrev`` / ``is_grads_batched`` and double backward raise ``NotImplementedError``."""
+    names, groups = _names(satur)
+    lay, wnames = check_column_sums(inputs, prm, ngptot, satur, weights)
+    dev = check_device(inputs[n] for n in names)
+    xs = tuple(inputs[n] for n in names)
+    _refuse_batched_colsum(xs + tuple(weights[n] for n in wnames))
+    _prepare(dev)
+    like = inputs["pap"]
+    with torch.no_grad():  # the table: ten rows of nlev + 1 in the order of OUT_NAMES, device ops only
+        table = torch.zeros((len(B.OUT_NAMES), lay.nlev + 1), dtype=like.dtype, device=dev)
+        for n in wnames:
+            table[B.OUT_NAMES.index(n), :lay.nlevx(n)].copy_(weights[n])
+    keep = torch.is_grad_enabled() and any(t.requires_grad for t in xs)
+    x = normalize({n: inputs[n] for n in names}, lay, groups)
+    out = dict(zip(wnames, _Cloudsc2Colsum.apply(prm, float(ptsphy), lay, bool(satur), wnames, bool(keep), table, *(x[n] for n in names))))
+    return Cloudsc2Outputs(*(out.get(n) for n in B.OUT_NAMES))
 
 
 def satur(pap: torch.Tensor, t: torch.Tensor, prm: B.Params, ngptot: int | None = None, differentiable: bool = False) -> torch.Tensor:

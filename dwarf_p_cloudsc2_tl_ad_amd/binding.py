@@ -15,6 +15,8 @@ CLOUDSC2_MAX_NLEV = 200
 CLOUDSC2_EINVAL, CLOUDSC2_ENODEVICE, CLOUDSC2_ETLWRONG = -1, -2, -3
 # cloudsc2_kernel_occupancy's numbers of the sparse TL / reverse sweeps, which are no kernel families (include/cloudsc2_hip.h)
 CLOUDSC2_KERNEL_TL_SPARSE, CLOUDSC2_KERNEL_VJP_SPARSE = 10, 11
+# ... and of the column-sum NL / TL / reverse sweeps
+CLOUDSC2_KERNEL_NL_COLSUM, CLOUDSC2_KERNEL_TL_COLSUM, CLOUDSC2_KERNEL_VJP_COLSUM = 12, 13, 14
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CLOUDSC2_PRECISION=single: the process works on fp32 arrays through libcloudsc2_hip_sp.so -- the counterpart of
@@ -160,6 +162,16 @@ def _load() -> C.CDLL:
     lib.cloudsc2_vjp_launch_sparse.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs),
                                                C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p, C.c_void_p]
     lib.cloudsc2_vjp_launch_sparse.restype = C.c_int
+    # the column-sum sweeps: the weight table (device, 10 x (nlev + 1) reals) before the block of (nblocks, nproma) sums
+    lib.cloudsc2_nl_launch_colsum.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.c_void_p, C.POINTER(Outputs),
+                                              C.POINTER(Outputs), C.c_void_p, C.c_void_p]
+    lib.cloudsc2_nl_launch_colsum.restype = C.c_int
+    lib.cloudsc2_tl_launch_colsum.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Inputs),
+                                              C.c_void_p, C.POINTER(Outputs), C.c_void_p]
+    lib.cloudsc2_tl_launch_colsum.restype = C.c_int
+    lib.cloudsc2_vjp_launch_colsum.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs),
+                                               C.POINTER(Inputs), C.c_void_p, C.POINTER(Outputs), C.c_void_p, C.c_void_p]
+    lib.cloudsc2_vjp_launch_colsum.restype = C.c_int
     # the derivative with respect to the tunable parameters (order: PARAM_NAMES): dpar is a host array of CLOUDSC2_NPAR doubles,
     # work / par_adj are device pointers
     lib.cloudsc2_par_work_doubles.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_longlong)]
@@ -296,7 +308,7 @@ lib = _load()
 # every symbol include/cloudsc2_hip.h declares
 EXPORTED = ("cloudsc2_params_default", "cloudsc2_last_error", "cloudsc2_device_available", "cloudsc2_current_device", "cloudsc2_set_math_mode",
             "cloudsc2_get_math_mode", "cloudsc2_real_bytes", "cloudsc2_nl_launch",
-            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_tl_launch_sparse", "cloudsc2_vjp_launch_sparse", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch_parjac", "cloudsc2_ens_workspace_bytes", "cloudsc2_nl_launch_ens", "cloudsc2_tl_launch_ens", "cloudsc2_vjp_launch_ens", "cloudsc2_parnormal_work_doubles", "cloudsc2_parnormal_launch", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
+            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_tl_launch_sparse", "cloudsc2_vjp_launch_sparse", "cloudsc2_nl_launch_colsum", "cloudsc2_tl_launch_colsum", "cloudsc2_vjp_launch_colsum", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch_parjac", "cloudsc2_ens_workspace_bytes", "cloudsc2_nl_launch_ens", "cloudsc2_tl_launch_ens", "cloudsc2_vjp_launch_ens", "cloudsc2_parnormal_work_doubles", "cloudsc2_parnormal_launch", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
             "cloudsc2_ad_launch_forward", "cloudsc2_ad_launch_reverse", "cloudsc2_vjp_launch", "cloudsc2_batch_max", "cloudsc2_tl_launch_batch", "cloudsc2_vjp_launch_batch", "cloudsc2_ad_launch_reverse_norms", "cloudsc2_taylor_sums_launch",
             "cloudsc2_taylor_sweep_work_doubles", "cloudsc2_taylor_sweep_launch", "cloudsc2_adjoint_norms_launch", "cloudsc2_nl_run", "cloudsc2_tl_taylor_run", "cloudsc2_ad_symmetry_run",
             "cloudsc2_release_workspace", "cloudsc2_taylor_verdict", "cloudsc2_adjoint_verdict",

@@ -452,6 +452,12 @@ enum : unsigned {
                      // SATLIN: only the planes of the launch's two bit masks are moved (struct SparseMasks below).  The argument block is
                      // TlSparseArgs / AdSparseArgs (cloudsc2_tl_launch_sparse, cloudsc2_vjp_launch_sparse; kernels:
                      // cloudsc2_kern_{tl,vjp}_sparse.hip).  Off in every other instantiation.
+  C2F_COLSUM = 1024u, // NL (LPHYLIN form, never with PERT; with CKPT: the two flux planes and the cover checkpoint are kept), TL and the
+                     // reverse sweep (both with SPARSE): an output is not a plane but its per-column weighted level sum (struct ColsumTab
+                     // below).  NL / TL fold the level's outputs into accumulators and store one row per sum after the last level; the
+                     // reverse sweep forms the cotangent of a level as weight x the column's sum cotangent.  The argument block is
+                     // NlColsumArgs / TlColsumArgs / AdColsumArgs (cloudsc2_{nl,tl,vjp}_launch_colsum; kernels:
+                     // cloudsc2_kern_{nl,tl,vjp}_colsum.hip).  Off in every other instantiation.
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -557,6 +563,115 @@ C2_HD void store_top_sparse(OutPtrsP p, unsigned m, const LaneOff& o, ConstsP c)
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Column sums (C2F_COLSUM): y_n[c] = sum_k w_n[k] out_n[k, c], formed in the sweep
+// ---------------------------------------------------------------------------------------------------------
+// The contract, to the bit, for every active column: acc = +0; for k = 0 .. nlevx-1: acc = fl(acc + fl(w[k] out[k])), the product rounded
+// before the add.  The top half level of a flux is an exact zero, so with finite weights it leaves acc = +0 and is skipped.  w is the
+// launch's device table: ten rows of nlev + 1 entries in the order of OutPtrs, entry k of a row the weight of the plane's level index k
+// (the last entry of a full-level row is unused).  The row entry of level jk is wave-uniform: it is read through the scalar cache, like
+// LevelTab.  The accumulators live in LDS, one slot per lane and sum (ten fp64 accumulators are 20 VGPRs, which the NL sweep's 168 --
+// three waves per SIMD -- do not have beside the look-ahead set; 10 KiB per workgroup keep that occupancy): a lane reads and writes its
+// own slots only, so there is no barrier and no bank conflict (consecutive lanes, consecutive words).  The host builds keep them in
+// an array.  The level's outputs are pinned before the fold and every product is laundered before its add: the device compiler would
+// otherwise sink arithmetic into the conditional blocks and fuse the product into the add.
+struct ColsumTab {
+  const real_t* w;   // (10, nlev + 1)
+  OutPtrs y;         // (nblocks, nproma) arrays: NL / TL the sums written, reverse sweep the cotangents of the sums (read only); NULL: absent
+  long long stride;  // their block stride
+  unsigned mask;     // NL: the sums present, bits C2O_* (TL: SparseMasks::wr; reverse sweep: SparseMasks::rd)
+};
+struct NlColsumArgs {
+  NlArgs a; ColsumTab cs;
+};
+struct TlColsumArgs {
+  TlSparseArgs a; ColsumTab cs;
+};
+struct AdColsumArgs {
+  AdSparseArgs a; ColsumTab cs;
+};
+typedef const C2_CONST_AS ColsumTab* ColsumTabP;
+typedef const C2_CONST_AS real_t* ColsumRowP;
+constexpr int kColsumLanes = 128;  // the sweeps' workgroup size (kBlock, asserted in cloudsc2_sweep_kernels.hpp)
+
+struct ColsumAcc {
+#if defined(__HIP_DEVICE_COMPILE__)
+  real_t* s;  // this lane's slot of sum 0; sum n is kColsumLanes further
+  __device__ __forceinline__ void begin(long long) {
+    __shared__ real_t slots[10 * kColsumLanes];
+    s = slots + threadIdx.x;
+    for (int n = 0; n < 10; ++n) s[n * kColsumLanes] = RC(0.0);
+  }
+  // the lane's column once more after the level loop (the column-sum kernels run global_column()): no register holds it through the loop
+  __device__ __forceinline__ long long column() const { return (long long)blockIdx.x * kColsumLanes + threadIdx.x; }
+  __device__ __forceinline__ real_t get(int n) const { return s[n * kColsumLanes]; }
+  __device__ __forceinline__ void set(int n, real_t v) { s[n * kColsumLanes] = v; }
+#else
+  real_t s[10];
+  long long gcol;
+  void begin(long long column) {
+    gcol = column;
+    for (int n = 0; n < 10; ++n) s[n] = RC(0.0);
+  }
+  long long column() const { return gcol; }
+  real_t get(int n) const { return s[n]; }
+  void set(int n, real_t v) { s[n] = v; }
+#endif
+  C2_HD void add(int n, real_t w, real_t v) {
+    real_t p = w * v;
+    C2_LAUNDER_V(p);
+    set(n, get(n) + p);
+  }
+};
+
+C2_HD long long colsum_off(GeomP g, ColsumTabP cs, long long gcol) {
+  const long long ibl = gcol / g->nproma;
+  return ibl * cs->stride + (gcol - ibl * g->nproma);
+}
+
+// one level's outputs into the sums of mask m: the pins in the order of store_out_sparse, then product and add per sum under its bit.
+// (Reading all ten table entries of the level up front, whatever the mask -- ten scalar loads waited for once instead of one wait per
+// conditional block -- was measured in the TL and reverse sweeps and is no gain: DESIGN.md 3.6.  So the row of an absent sum is not read.)
+C2_HD void colsum_fold(ColsumAcc& acc, ColsumTabP cs, unsigned m, int nlev, int jk, LevelOut v) {
+  C2_PIN_V(v.tent); C2_PIN_V(v.tenq); C2_PIN_V(v.tenl); C2_PIN_V(v.teni); C2_PIN_V(v.clc);
+  C2_PIN_V(v.covptot); C2_PIN_V(v.fplsl); C2_PIN_V(v.fplsn); C2_PIN_V(v.fhpsl); C2_PIN_V(v.fhpsn);
+  const ColsumRowP w = (ColsumRowP)cs->w + jk;
+  const int r = nlev + 1;
+  if (m & C2O_TENT) acc.add(0, w[0 * r], v.tent);
+  if (m & C2O_TENQ) acc.add(1, w[1 * r], v.tenq);
+  if (m & C2O_TENL) acc.add(2, w[2 * r], v.tenl);
+  if (m & C2O_TENI) acc.add(3, w[3 * r], v.teni);
+  if (m & C2O_CLC) acc.add(4, w[4 * r], v.clc);
+  if (m & C2O_FPLSL) acc.add(5, w[5 * r + 1], v.fplsl);
+  if (m & C2O_FPLSN) acc.add(6, w[6 * r + 1], v.fplsn);
+  if (m & C2O_FHPSL) acc.add(7, w[7 * r + 1], v.fhpsl);
+  if (m & C2O_FHPSN) acc.add(8, w[8 * r + 1], v.fhpsn);
+  if (m & C2O_COVPTOT) acc.add(9, w[9 * r], v.covptot);
+}
+
+// after the last level: one row per sum present
+C2_HD void colsum_store(const ColsumAcc& acc, ColsumTabP cs, unsigned m, long long ocs) {
+  const OutPtrs y = cs->y;
+  if (m & C2O_TENT) y.tent[ocs] = acc.get(0);
+  if (m & C2O_TENQ) y.tenq[ocs] = acc.get(1);
+  if (m & C2O_TENL) y.tenl[ocs] = acc.get(2);
+  if (m & C2O_TENI) y.teni[ocs] = acc.get(3);
+  if (m & C2O_CLC) y.clc[ocs] = acc.get(4);
+  if (m & C2O_FPLSL) y.fplsl[ocs] = acc.get(5);
+  if (m & C2O_FPLSN) y.fplsn[ocs] = acc.get(6);
+  if (m & C2O_FHPSL) y.fhpsl[ocs] = acc.get(7);
+  if (m & C2O_FHPSN) y.fhpsn[ocs] = acc.get(8);
+  if (m & C2O_COVPTOT) y.covptot[ocs] = acc.get(9);
+}
+
+// the reverse sweep's cotangent of output n at a level: the rounded product of the table entry and the column's sum cotangent, as
+// opaque as the load it replaces
+C2_HD real_t colsum_cot(real_t w, real_t y) {
+  real_t p = w * y;
+  C2_LAUNDER_V(p);
+  return p;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // SATUR for one column
 // ---------------------------------------------------------------------------------------------------------
 struct SaturArgs {
@@ -644,10 +759,16 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
   typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
   static_assert(!(PERT && CKPT), "the adjoint's trajectory pass is never perturbed");
   static_assert(LIN || !CKPT, "CLOUDSC2AD's trajectory has the LPHYLIN form only");
+  // COLSUM: no output plane is stored, the level's outputs are folded into the column's weighted sums (a is the head of an NlColsumArgs).
+  // With CKPT the sweep keeps what the reverse sweep re-reads, in the bits of the trajectory pass: PFPLSL5 / PFPLSN5 and, with EVAP, the
+  // cover checkpoint.  It is scheduled as the plain NL sweep is unless it is the one-wave-per-SIMD EVAP form.
+  constexpr bool COLSUM = (F & C2F_COLSUM) != 0;
+  static_assert(!COLSUM || (LIN && !PERT), "C2F_COLSUM: the LPHYLIN form, never perturbed");
+  constexpr bool ONEWAVE = CKPT && (!COLSUM || EVAP);
   LaneOff o; bool active;
   if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
   const int nlev = a->g.nlev, nproma = a->g.nproma;
-  const int fair = CKPT ? 0 : a->g.fair;  // (the adjoint's trajectory pass runs one wave per SIMD: compiled without the priority code)
+  const int fair = ONEWAVE ? 0 : a->g.fair;  // (the adjoint's trajectory pass runs one wave per SIMD: compiled without the priority code)
   const real_t lam = PERT ? a->lam : RC(0.0);
   real_t* zero_plane = a->zero_plane;
   long long ozero = 0;
@@ -656,6 +777,7 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
     ozero = ibl * a->zero_stride + (gcol - ibl * nproma);
   }
   if (!active) {
+    if constexpr (COLSUM) return;  // (no covptot plane: the padded tail of the sums is not written)
     // padded tail of the last block: the driver zeroes the whole block's PCOVPTOT and CLD(:,:,NCLV)
     // (cloudsc_driver_mod.F90:87-88); nothing else is touched.
     real_t* cov = a->out.covptot;
@@ -686,7 +808,16 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
     if (PERT) paph_surf = pert(paph_surf, lam);
   }
 
-  store_top(out, o, c);
+  [[maybe_unused]] ColsumAcc acc;
+  if constexpr (COLSUM) {
+    acc.begin(gcol);
+    if (CKPT) {  // the kept flux planes' top half level (store_top's zeros)
+      out->fplsl[o.half] = RC(0.0);
+      out->fplsn[o.half] = RC(0.0);
+    }
+  } else {
+    store_top(out, o, c);
+  }
 
   Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
   real_t paph_k = in->paph[o.half];
@@ -696,18 +827,18 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
   const OT ozl = (OT)(ozero * (OFF32 ? (long long)sizeof(real_t) : 1)), oscl = (OT)(osc * (OFF32 ? (long long)sizeof(real_t) : 1));
 
   Pace pace;
-  if (!CKPT && (fair & 4)) pace.begin_light(&a->g);
+  if (!ONEWAVE && (fair & 4)) pace.begin_light(&a->g);
 
   // one level: `cur` holds the raw inputs of level jk (requested one level ago), `nxt` receives those of level jk+1
   auto step = [&](int jk, RawLevel& cur, RawLevel& nxt) {
     const bool last = (jk == nlev - 1);
-    if (!CKPT) progress_priority(jk, fair & 1);
+    if (!ONEWAVE) progress_priority(jk, fair & 1);
     NlArgsP ap = a;  // field pointers are re-read from the kernel-argument segment every level (transient SGPRs);
     C2_LAUNDER(ap);  // the physical constants stay resident
     // request everything level jk+1 needs now; nothing below touches `nxt` before the end of this level, so the
     // HBM latency is covered by the whole level's arithmetic
     if (!last) load_level<HAS_QSAT>(&ap->in, ol, nproma, nlev, jk + 1, nxt);
-    if (!CKPT) pace.nap();
+    if (!ONEWAVE) pace.nap();
 
     if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);  // SATUR on the unperturbed PAP, PT
     if (PERT) perturb_raw(cur, lam);
@@ -721,8 +852,19 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
     LevelOut lo;
     level_forward<P, EVAP, LIN>(c, k, rh, x, cy, tr, lo);
     C2_LAUNDER(ap);
-    store_out(&ap->out, ol, nproma, jk, lo);
-    if (zero_plane) stg(zero_plane, ozl + level_off(OT(), jk, nproma), RC(0.0));
+    if constexpr (COLSUM) {
+      const ColsumTabP cs = &((const C2_CONST_AS NlColsumArgs*)ap)->cs;
+      colsum_fold(acc, cs, cs->mask, nlev, jk, lo);
+      if (CKPT) {
+        const OutPtrs p = ap->out;
+        const OT d1 = level_off(OT(), jk, nproma) + row_off(OT(), nproma);
+        stg(p.fplsl, ol.half + d1, lo.fplsl);
+        stg(p.fplsn, ol.half + d1, lo.fplsn);
+      }
+    } else {
+      store_out(&ap->out, ol, nproma, jk, lo);
+      if (zero_plane) stg(zero_plane, ozl + level_off(OT(), jk, nproma), RC(0.0));
+    }
     paph_k = cur.paph_k1;
   };
 
@@ -743,6 +885,10 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
   for (int jk = 0; jk < nlev; ++jk) {
     step(jk, ra, rb);
     ra = rb;
+  }
+  if constexpr (COLSUM) {
+    const ColsumTabP cs = &((const C2_CONST_AS NlColsumArgs*)a)->cs;
+    colsum_store(acc, cs, cs->mask, colsum_off(&a->g, cs, acc.column()));
   }
 }
 
@@ -883,7 +1029,8 @@ template <unsigned F>
 C2_HD void tl_column(long long gcol, TlArgsP a) {
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, STORE_TRAJ = (F & C2F_TRAJ) != 0, EVAP = (F & C2F_EVAP) != 0;
   constexpr bool SELFINC = (F & C2F_SELFINC) != 0, SATLIN = (F & C2F_SATLIN) != 0, PARLIN = (F & C2F_PARLIN) != 0;
-  constexpr bool SPARSE = (F & C2F_SPARSE) != 0;
+  constexpr bool SPARSE = (F & C2F_SPARSE) != 0, COLSUM = (F & C2F_COLSUM) != 0;
+  static_assert(!COLSUM || SPARSE, "C2F_COLSUM: the sparse form's tangent loads (a is the head of a TlColsumArgs)");
   static_assert(!SATLIN || (!HAS_QSAT && !STORE_TRAJ && !SELFINC), "C2F_SATLIN: SATUR fused, no trajectory stores, increments given");
   static_assert(!SPARSE || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC && !PARLIN), "C2F_SPARSE: QSAT or SATLIN, no trajectory stores, increments given");
   static_assert(!PARLIN || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC), "C2F_PARLIN: QSAT or SATLIN, no trajectory stores, increments given");
@@ -914,7 +1061,9 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   }
 
   if (STORE_TRAJ) store_top(out, o, c);
-  if constexpr (SPARSE) store_top_sparse(dout, ((TlSparseArgsP)a)->m.wr, op, c);  // (a is the head of a TlSparseArgs)
+  [[maybe_unused]] ColsumAcc acc;
+  if constexpr (COLSUM) acc.begin(gcol);  // (no tangent plane is stored: the flux tangents' top zeros contribute nothing to a sum)
+  else if constexpr (SPARSE) store_top_sparse(dout, ((TlSparseArgsP)a)->m.wr, op, c);  // (a is the head of a TlSparseArgs)
   else store_top(dout, op, c);
 
   Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
@@ -972,7 +1121,8 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
     C2_LAUNDER(ap);
     out = &ap->out; dout = &ap->dout;
     if (STORE_TRAJ) store_out(out, ol, nproma, jk, lo);
-    if constexpr (SPARSE) store_out_sparse(dout, ((TlSparseArgsP)ap)->m.wr, opl, nproma, jk, dlo);
+    if constexpr (COLSUM) colsum_fold(acc, &((const C2_CONST_AS TlColsumArgs*)ap)->cs, ((TlSparseArgsP)ap)->m.wr, nlev, jk, dlo);
+    else if constexpr (SPARSE) store_out_sparse(dout, ((TlSparseArgsP)ap)->m.wr, opl, nproma, jk, dlo);
     else store_out(dout, opl, nproma, jk, dlo);
     if (SELFINC) {
       yy += (double)dlo.tent * dlo.tent + (double)dlo.tenq * dlo.tenq + (double)dlo.tenl * dlo.tenl + (double)dlo.teni * dlo.teni +
@@ -986,6 +1136,10 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   if (SELFINC) {
     double* p = a->yy;
     if (p) p[gcol] = yy;
+  }
+  if constexpr (COLSUM) {
+    const ColsumTabP cs = &((const C2_CONST_AS TlColsumArgs*)a)->cs;
+    colsum_store(acc, cs, ((TlSparseArgsP)a)->m.wr, colsum_off(&a->g, cs, acc.column()));
   }
 }
 
@@ -1012,9 +1166,11 @@ struct AdLevelLoads {
 };
 
 // SPARSE: an output adjoint is read under its bit of `rd`, else it is an opaque zero (assign form: no old input adjoints)
-template <bool HAS_QSAT, bool ASSIGN, bool EVAP, class OT, bool SPARSE = false>
+// COLSUM (with SPARSE): the adjoint of output n is not a plane but weight x the column's sum cotangent (colsum_cot), under the same bit;
+// the sum cotangents are re-read every level from their (nblocks, nproma) rows, which stay in cache (ap is the head of an AdColsumArgs)
+template <bool HAS_QSAT, bool ASSIGN, bool EVAP, class OT, bool SPARSE = false, bool COLSUM = false>
 C2_HD void ad_load_level(AdArgsP ap, const LaneOffT<OT>& o, const LaneOffT<OT>& oa, OT osc, int nproma, int nlev, int jk,
-                         AdLevelLoads& L, unsigned rd = 0u) {
+                         AdLevelLoads& L, unsigned rd = 0u, [[maybe_unused]] long long ocs = 0) {
   const bool last = (jk == nlev - 1);
   const OT d = level_off(OT(), jk, nproma);
   const OT d1 = d + row_off(OT(), nproma);
@@ -1043,7 +1199,23 @@ C2_HD void ad_load_level(AdArgsP ap, const LaneOffT<OT>& o, const LaneOffT<OT>& 
     L.cy.covptot = EVAP ? ldg(ap->nl.ckpt, osc + d) : RC(0.0);
   }
   const OutPtrs pa = ap->aout;
-  if constexpr (SPARSE) {
+  if constexpr (COLSUM) {
+    static_assert(SPARSE && ASSIGN, "the column-sum reverse sweep is a sparse one");
+    const ColsumTabP cs = &((const C2_CONST_AS AdColsumArgs*)ap)->cs;
+    const ColsumRowP w = (ColsumRowP)cs->w + jk;
+    const int r = nlev + 1;
+    const OutPtrs y = cs->y;
+    L.ya.tent = (rd & C2O_TENT) ? colsum_cot(w[0 * r], y.tent[ocs]) : opaque_zero();
+    L.ya.tenq = (rd & C2O_TENQ) ? colsum_cot(w[1 * r], y.tenq[ocs]) : opaque_zero();
+    L.ya.tenl = (rd & C2O_TENL) ? colsum_cot(w[2 * r], y.tenl[ocs]) : opaque_zero();
+    L.ya.teni = (rd & C2O_TENI) ? colsum_cot(w[3 * r], y.teni[ocs]) : opaque_zero();
+    L.ya.clc = (rd & C2O_CLC) ? colsum_cot(w[4 * r], y.clc[ocs]) : opaque_zero();
+    L.ya.covptot = (rd & C2O_COVPTOT) ? colsum_cot(w[9 * r], y.covptot[ocs]) : opaque_zero();
+    L.ya.fplsn = (rd & C2O_FPLSN) ? colsum_cot(w[6 * r + 1], y.fplsn[ocs]) : opaque_zero();
+    L.ya.fplsl = (rd & C2O_FPLSL) ? colsum_cot(w[5 * r + 1], y.fplsl[ocs]) : opaque_zero();
+    L.ya.fhpsn = (rd & C2O_FHPSN) ? colsum_cot(w[8 * r + 1], y.fhpsn[ocs]) : opaque_zero();
+    L.ya.fhpsl = (rd & C2O_FHPSL) ? colsum_cot(w[7 * r + 1], y.fhpsl[ocs]) : opaque_zero();
+  } else if constexpr (SPARSE) {
     static_assert(ASSIGN, "the sparse reverse sweep assigns its input adjoints");
     L.ya.tent = (rd & C2O_TENT) ? ldg(pa.tent, oa.loc + d) : opaque_zero();
     L.ya.tenq = (rd & C2O_TENQ) ? ldg(pa.tenq, oa.loc + d) : opaque_zero();
@@ -1103,8 +1275,9 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   static_assert(!PARLIN || (VJP && (HAS_QSAT != SATLIN)), "C2F_PARLIN: the vector-Jacobian form, QSAT or SATLIN");
   static_assert(!ADNORM || ASSIGN, "the fused norms are those of the adjoint test: assign form");
   static_assert(!VJP || (ASSIGN && !ADNORM), "the vector-Jacobian product assigns its input adjoints and forms no norms");
-  constexpr bool SPARSE = (F & C2F_SPARSE) != 0;
+  constexpr bool SPARSE = (F & C2F_SPARSE) != 0, COLSUM = (F & C2F_COLSUM) != 0;
   static_assert(!SPARSE || (VJP && (HAS_QSAT != SATLIN) && !PARLIN), "C2F_SPARSE: the vector-Jacobian form, QSAT or SATLIN, no parameter adjoints");
+  static_assert(!COLSUM || SPARSE, "C2F_COLSUM: the sparse form's gradient stores (a is the head of an AdColsumArgs)");
   typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
   LaneOff o, oa64; bool active;
   if (!lane_setup(&a->nl.g, &a->nl.s, gcol, o, active)) return 0.0;
@@ -1133,6 +1306,8 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   real_t paph_k1 = paph_bottom;
   double n2 = 0.0;  // ADNORM: <x0, x_adj>, x0 = 0.01 * trajectory inputs, ZSUPSAT0 = 0 (cloudsc_driver_ad_mod.F90:139,240-256)
   AdLevelLoads L;
+  [[maybe_unused]] long long ocs = 0;  // COLSUM: the column's place in the sum cotangents
+  if constexpr (COLSUM) ocs = colsum_off(&a->nl.g, &((const C2_CONST_AS AdColsumArgs*)a)->cs, gcol);
   [[maybe_unused]] ParAcc pacc = {{0.0, 0.0, 0.0, 0.0}};  // PARLIN
   Pace pace;
   pace.begin(&a->nl.g);
@@ -1147,7 +1322,8 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     // at 160 000 columns, -1 % at 1 M (profiles/r02_ab_experiments.txt)
     // (SPARSE: the masks are re-read from the kernel-argument segment where they are used, like the field pointers; a is the head of
     // an AdSparseArgs)
-    if constexpr (SPARSE) ad_load_level<HAS_QSAT, ASSIGN, EVAP, OT, true>(ap, ol, oa, osc, nproma, nlev, jk, L, ((AdSparseArgsP)ap)->m.rd);
+    if constexpr (COLSUM) ad_load_level<HAS_QSAT, ASSIGN, EVAP, OT, true, true>(ap, ol, oa, osc, nproma, nlev, jk, L, ((AdSparseArgsP)ap)->m.rd, ocs);
+    else if constexpr (SPARSE) ad_load_level<HAS_QSAT, ASSIGN, EVAP, OT, true>(ap, ol, oa, osc, nproma, nlev, jk, L, ((AdSparseArgsP)ap)->m.rd);
     else ad_load_level<HAS_QSAT, ASSIGN, EVAP>(ap, ol, oa, osc, nproma, nlev, jk, L);
     RawLevel& cur = L.cur;
     cur.paph_k1 = paph_k1;

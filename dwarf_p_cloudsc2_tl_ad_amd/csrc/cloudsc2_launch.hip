@@ -26,6 +26,9 @@
 #include "cloudsc2_kern_vjp_ens.hip"
 #include "cloudsc2_kern_tl_sparse.hip"
 #include "cloudsc2_kern_vjp_sparse.hip"
+#include "cloudsc2_kern_nl_colsum.hip"
+#include "cloudsc2_kern_tl_colsum.hip"
+#include "cloudsc2_kern_vjp_colsum.hip"
 #endif
 
 using namespace cloudsc2;
@@ -1083,6 +1086,169 @@ int cloudsc2_vjp_launch_sparse(const cloudsc2_params* prm, double ptsphy, int np
   void* argv[] = {&sargs};
   HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
   return 0;
+}
+
+// ---- column sums formed in the sweeps (C2F_COLSUM) -------------------------------------------------------------------------------------
+// Three kernel nodes of their own, launched directly like the sparse ones: no family number, no launch-log entry.  Scheduling is the
+// twins': cloudsc2_nl_launch's (the keep form with the evaporation branch: the trajectory pass's), the sparse launchers'.
+// (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
+// (every refusal of the three names its launcher: the entry points run their implementation through `named`)
+static int named(const char* who, int rc) {
+  if (rc != CLOUDSC2_EINVAL) return rc;
+  const std::string msg = std::string(who) + ": " + g_err;
+  return fail(rc, msg.c_str());
+}
+static int check_colsum_geom(const cloudsc2_params* prm, int nproma, int nlev, int ngptot) {
+  if (nproma < 1 || nlev < 2 || ngptot < 1 || nlev > CLOUDSC2_MAX_NLEV || prm->nlev != nlev || prm->math_mode < 0 || prm->math_mode > 2)
+    return fail(CLOUDSC2_EINVAL, "nproma >= 1, 2 <= nlev = params.nlev <= CLOUDSC2_MAX_NLEV, ngptot >= 1, params.math_mode in 0..2 required");
+  return 0;
+}
+// the table and the block of sums: cs.w, cs.y, cs.stride; mask: the sums present
+static int resolve_colsum(const cloudsc2_real* weights, const cloudsc2_outputs* sums, int nproma, const char* none, ColsumTab& cs,
+                          unsigned& mask) {
+  auto refuse = [&](const char* what) { return fail(CLOUDSC2_EINVAL, what); };
+  if (!weights) return refuse("the weight table is NULL");
+  const cloudsc2_field* f = fields_of(*sums);
+  mask = 0u;
+  long long stride = 0;
+  for (int k = 0; k < kNumOut; ++k) {
+    reinterpret_cast<real_t**>(&cs.y)[k] = f[k].ptr;
+    if (!f[k].ptr) continue;
+    if (mask && f[k].block_stride != stride) return refuse("the sums given must share one block stride");
+    stride = f[k].block_stride;
+    mask |= 1u << k;
+  }
+  if (!mask) return refuse(none);
+  if (stride < nproma) return refuse("the block stride of the sums is below nproma");
+  cs.w = weights; cs.stride = stride; cs.mask = mask;
+  return 0;
+}
+
+static int nl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* in,
+                          const cloudsc2_real* weights, const cloudsc2_outputs* sums, const cloudsc2_outputs* keep,
+                          cloudsc2_real* scratch, void* stream) {
+  if (!prm || !in || !sums) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  int rc = check_colsum_geom(prm, nproma, nlev, ngptot);
+  if (rc) return rc;
+  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "the LPHYLIN form only (prm->lphylin = 0)");
+  NlColsumArgs cargs;
+  memset(&cargs, 0, sizeof(cargs));
+  unsigned mask;
+  if ((rc = resolve_colsum(weights, sums, nproma, "no sum is given (every sums field is NULL)", cargs.cs, mask))) return rc;
+  Sweep w;
+  if ((rc = resolve_in(*in, false, w.s, w.in))) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  if (keep) {
+    if (!keep->fplsl.ptr != !keep->fplsn.ptr) return fail(CLOUDSC2_EINVAL, "keep needs both planes, fplsl and fplsn");
+    if (!keep->fplsl.ptr) return fail(CLOUDSC2_EINVAL, "keep needs both planes, fplsl and fplsn (neither is given)");
+    if (keep->fplsl.block_stride != w.s.half || keep->fplsn.block_stride != w.s.half)
+      return fail(CLOUDSC2_EINVAL, "the kept flux planes must have the block stride of in->paph");
+    if (keep->fplsl.ptr == keep->fplsn.ptr) return fail(CLOUDSC2_EINVAL, "keep->fplsl and keep->fplsn are one plane");
+    if ((prm->levapls2 || prm->ldrain1d) && !scratch)
+      return fail(CLOUDSC2_EINVAL, "keep with LEVAPLS2/LDRAIN1D: the cover-checkpoint plane `scratch` is required");
+    w.out.fplsl = keep->fplsl.ptr; w.out.fplsn = keep->fplsn.ptr;
+  }
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  if ((rc = w.finish(*prm, ptsphy, in->qsat.ptr, {cargs.cs.stride, keep ? (long long)nproma * nlev : 0LL}))) return rc;
+  if (keep) w.f |= C2F_CKPT;
+  cargs.a = w.nl();
+  cargs.a.ckpt = (keep && w.c.evap) ? scratch : nullptr;
+  const KernelFn<NlColsumArgs> fn = nl_colsum_variant(w.f);
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  schedule(cargs.a.g, (const void*)fn, !keep, nullptr);
+  void* argv[] = {&cargs};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
+  return 0;
+}
+
+static int tl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                          const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const cloudsc2_real* weights,
+                          const cloudsc2_outputs* pert_sums, void* stream) {
+  if (!prm || !traj_in || !pert_in || !pert_sums) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  int rc = check_colsum_geom(prm, nproma, nlev, ngptot);
+  if (rc) return rc;
+  if ((rc = check_sparse(prm, satur, traj_in, pert_in))) return rc;
+  TlColsumArgs cargs;
+  memset(&cargs, 0, sizeof(cargs));
+  TlSparseArgs& sargs = cargs.a;
+  TlArgs& args = sargs.a;
+  if ((rc = resolve_colsum(weights, pert_sums, nproma, "no sum is wanted (every pert_sums field is NULL)", cargs.cs, sargs.m.wr))) return rc;
+  Sweep w;
+  if ((rc = resolve_in(*traj_in, false, w.s, w.in))) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  const cloudsc2_outputs none = {};
+  unsigned none_mask;
+  if ((rc = resolve_sparse(*pert_in, none, 'o', args.sp, args.din, args.dout, sargs.m.rd, none_mask))) return rc;
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  const Strides& sp = args.sp;
+  if ((rc = w.finish(*prm, ptsphy, !satur, {sp.full, sp.half, sp.cml, sp.clv, sp.loc, cargs.cs.stride}))) return rc;
+  if (satur) w.f |= C2F_SATLIN;
+  args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.out = w.out; args.tab = w.tab;
+  args.supsat_inc = 0; args.yy = nullptr;
+  const KernelFn<TlColsumArgs> fn = tl_colsum_variant(w.f);
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);  // (tl_launch_impl says why)
+  schedule(args.g, abreast ? (const void*)fn : nullptr, false, abreast ? nullptr : (const void*)fn);
+  void* argv[] = {&cargs};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
+  return 0;
+}
+
+static int vjp_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                           const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, const cloudsc2_inputs* adj_in,
+                           const cloudsc2_real* weights, const cloudsc2_outputs* adj_sums, const cloudsc2_real* scratch,
+                           void* stream) {
+  if (!prm || !traj_in || !traj_out || !adj_in || !adj_sums) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  int rc = check_colsum_geom(prm, nproma, nlev, ngptot);
+  if (rc) return rc;
+  if ((rc = check_sparse(prm, satur, traj_in, adj_in))) return rc;
+  AdColsumArgs cargs;
+  memset(&cargs, 0, sizeof(cargs));
+  AdSparseArgs& sargs = cargs.a;
+  AdArgs& args = sargs.a;
+  if ((rc = resolve_colsum(weights, adj_sums, nproma, "no cotangent is given (every adj_sums field is NULL)", cargs.cs, sargs.m.rd))) return rc;
+  Sweep w;
+  if ((rc = w.trajectory(*traj_in, *traj_out, false))) return rc;
+  if (!w.out.fplsl || !w.out.fplsn)
+    return fail(CLOUDSC2_EINVAL, "traj_out->fplsl and ->fplsn (PFPLSL5, PFPLSN5) are required");
+  if ((prm->levapls2 || prm->ldrain1d) && !scratch)
+    return fail(CLOUDSC2_EINVAL, "LEVAPLS2/LDRAIN1D: the cover-checkpoint plane `scratch` is required");
+  const cloudsc2_outputs none = {};
+  InPtrs ain_c;
+  unsigned none_mask;
+  if ((rc = resolve_sparse(*adj_in, none, 'i', args.sa, ain_c, args.aout, sargs.m.wr, none_mask))) return rc;
+  if (!sargs.m.wr) return fail(CLOUDSC2_EINVAL, "no gradient is wanted (every adj_in field is NULL)");
+  args.ain = writable(*adj_in);
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  const Strides& sa = args.sa;
+  if ((rc = w.finish(*prm, ptsphy, !satur, {sa.full, sa.half, sa.cml, sa.clv, sa.loc, (long long)nproma * nlev /* scratch */, cargs.cs.stride})))
+    return rc;
+  if (satur) w.f |= C2F_SATLIN;
+  args.nl = w.nl();
+  args.nl.ckpt = const_cast<cloudsc2_real*>(scratch);
+  const KernelFn<AdColsumArgs> fn = vjp_colsum_variant(w.f);
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  schedule(args.nl.g, nullptr, false, (const void*)fn);
+  void* argv[] = {&cargs};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
+  return 0;
+}
+
+int cloudsc2_nl_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* in,
+                              const cloudsc2_real* weights, const cloudsc2_outputs* sums, const cloudsc2_outputs* keep,
+                              cloudsc2_real* scratch, void* stream) {
+  return named("cloudsc2_nl_launch_colsum", nl_colsum_impl(prm, ptsphy, nproma, nlev, ngptot, in, weights, sums, keep, scratch, stream));
+}
+int cloudsc2_tl_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const cloudsc2_real* weights,
+                              const cloudsc2_outputs* pert_sums, void* stream) {
+  return named("cloudsc2_tl_launch_colsum", tl_colsum_impl(prm, ptsphy, nproma, nlev, ngptot, satur, traj_in, pert_in, weights, pert_sums, stream));
+}
+int cloudsc2_vjp_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, const cloudsc2_inputs* adj_in,
+                               const cloudsc2_real* weights, const cloudsc2_outputs* adj_sums, const cloudsc2_real* scratch,
+                               void* stream) {
+  return named("cloudsc2_vjp_launch_colsum", vjp_colsum_impl(prm, ptsphy, nproma, nlev, ngptot, satur, traj_in, traj_out, adj_in, weights, adj_sums, scratch, stream));
 }
 
 static_assert(CLOUDSC2_NPAR == PAR_COUNT, "the header's parameter count is the level functions'");

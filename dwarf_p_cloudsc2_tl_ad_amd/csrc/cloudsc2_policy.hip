@@ -263,6 +263,8 @@ std::vector<int> paced_kernel_occupancies() {
   for (unsigned f = 0; f < 2u * C2F_SATLIN; ++f) {  // the sparse sweeps (C2F_SPARSE), with QSAT or with SATLIN
     add((const void*)tl_sparse_variant(f));
     add((const void*)vjp_sparse_variant(f));
+    add((const void*)tl_colsum_variant(f));  // the column-sum sweeps (C2F_COLSUM), scheduled like the sparse ones
+    add((const void*)vjp_colsum_variant(f));
   }
   return out;
 }
@@ -463,6 +465,9 @@ int cloudsc2_kernel_occupancy(int kernel, int flags, int* workgroups_per_cu) {
   const void* fn = kernel >= kFamNl && kernel <= kFamTlParjac  ? variant_entry(kernel, (unsigned)flags)
                    : kernel == CLOUDSC2_KERNEL_TL_SPARSE        ? (const void*)tl_sparse_variant((unsigned)flags)
                    : kernel == CLOUDSC2_KERNEL_VJP_SPARSE       ? (const void*)vjp_sparse_variant((unsigned)flags)
+                   : kernel == CLOUDSC2_KERNEL_NL_COLSUM        ? (const void*)nl_colsum_variant((unsigned)flags)
+                   : kernel == CLOUDSC2_KERNEL_TL_COLSUM        ? (const void*)tl_colsum_variant((unsigned)flags)
+                   : kernel == CLOUDSC2_KERNEL_VJP_COLSUM       ? (const void*)vjp_colsum_variant((unsigned)flags)
                                                                 : nullptr;
   if (!fn) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: no such kernel variant in this build");
   Occupancy o;

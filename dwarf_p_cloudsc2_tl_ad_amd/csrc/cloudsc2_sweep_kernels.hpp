@@ -146,6 +146,27 @@ constexpr bool sparse_variant_valid(unsigned f) {
   return rest == C2F_QSAT || rest == C2F_SATLIN;
 }
 
+// The column-sum forms (C2F_COLSUM; units cloudsc2_kern_{nl,tl,vjp}_colsum.hip): the same columns over the argument blocks that carry the
+// weight table and the sums, under their twins' launch bounds (NL: nl_kernel's, TL / reverse sweep: the sparse kernels').  Variant words:
+// NL: QSAT (or SATUR in the sweep), PRECISE, EVAP, OFF32, and CKPT for the form that keeps PFPLSL5 / PFPLSN5 and the cover checkpoint --
+// 32 kernels per precision; TL / reverse sweep: the sparse forms' words, 16 each.  Not sweep families: no family number, no launch-log
+// entry; launched directly, like the sparse kernels.
+static_assert(kColsumLanes == kBlock, "one LDS slot per lane of the workgroup and sum");
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, (F & C2F_EVAP) ? 1 : 3) nl_colsum_kernel(NlColsumArgs args) {
+  C2_KERNEL_BODY((nl_column<F | C2F_COLSUM>(global_column(), &kernarg<NlColsumArgs>()->a)));
+}
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, (sizeof(real_t) == 4 && (F & C2F_OFF32) && !(F & C2F_EVAP)) ? 3 : 1)
+tl_colsum_kernel(TlColsumArgs args) {
+  C2_KERNEL_BODY((tl_column<F | C2F_SPARSE | C2F_COLSUM>(global_column(), &kernarg<TlColsumArgs>()->a.a)));
+}
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) vjp_colsum_kernel(AdColsumArgs args) {
+  C2_KERNEL_BODY((ad_reverse_column<F | C2F_ASSIGN | C2F_VJP | C2F_SPARSE | C2F_COLSUM>(global_column(), &kernarg<AdColsumArgs>()->a.a)));
+}
+constexpr bool nl_colsum_variant_valid(unsigned f) { return (f & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_CKPT | C2F_OFF32)) == 0; }
+
 // The ensemble forms (units cloudsc2_kern_{nl,tl,vjp}_ens.hip): the same columns again, under their parents' launch bounds, over an
 // argument block that lives in device memory -- one per member, written by ens_args_kernel (cloudsc2_launch.hip) in the launch before.
 // The block's address comes from blockIdx and the kernel arguments alone (ens_locate), so it is workgroup-uniform and the constants
@@ -278,5 +299,8 @@ KernelFn<TlEnsArgs> tl_ens_variant(unsigned f);
 KernelFn<VjpEnsArgs> vjp_ens_variant(unsigned f);
 KernelFn<TlSparseArgs> tl_sparse_variant(unsigned f);
 KernelFn<AdSparseArgs> vjp_sparse_variant(unsigned f);
+KernelFn<NlColsumArgs> nl_colsum_variant(unsigned f);
+KernelFn<TlColsumArgs> tl_colsum_variant(unsigned f);
+KernelFn<AdColsumArgs> vjp_colsum_variant(unsigned f);
 
 }  // namespace cloudsc2

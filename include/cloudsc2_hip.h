@@ -351,6 +351,47 @@ int cloudsc2_vjp_launch_sparse(const cloudsc2_params* prm, double ptsphy, int np
                                const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out,
                                const cloudsc2_real* scratch, void* stream);
 
+/* Column sums of the outputs, formed in the sweeps: y_n[c] = sum_k w_n[k] out_n[k, c] for the outputs n that are given, one number per
+ * column instead of a plane.  `weights` is a device table of 10 x (nlev + 1) cloudsc2_real, row n (the order of cloudsc2_outputs) at
+ * weights + n (nlev + 1), entry k of a row the weight of the plane's level index k: k = 0 .. nlev - 1 for the full-level outputs (the
+ * last entry is unused), k = 0 .. nlev for the four fluxes, k = 0 the top half level.  The rows of absent sums are not read.  Weights
+ * must be finite (not checked).  The blocks `sums`, `pert_sums`, `adj_sums` are cloudsc2_outputs whose fields point at
+ * (nblocks, nproma) arrays; the present ones share one block_stride >= nproma; a NULL ptr means absent.  The definition, to the bit,
+ * for every active column in the library's real type: acc = +0; for k = 0 .. nlevx - 1: acc = fl(acc + fl(w[k] out[k])), out the bits
+ * of the dense launch's output, the product rounded before the add (no fused multiply-add).  The top half level of a flux is an exact
+ * zero and contributes nothing.  Padded tail columns are not written.
+ *   cloudsc2_nl_launch_colsum   the NL sweep (LPHYLIN form; in->qsat.ptr NULL: SATUR in the sweep, as in cloudsc2_nl_launch).  keep NULL:
+ *                               the sums are stored and nothing else.  keep given: its fplsl and fplsn fields (both, with the stride of
+ *                               in->paph; its other fields are ignored) receive PFPLSL5 / PFPLSN5 in the bits of
+ *                               cloudsc2_ad_launch_forward, and with LEVAPLS2 .OR. LDRAIN1D `scratch` the cover checkpoints: what the
+ *                               reverse sweep re-reads.  Without the evaporation branch scratch is not touched.
+ *   cloudsc2_tl_launch_colsum   the sparse TL sweep (a NULL field of pert_in is a zero tangent, not read: the rule of
+ *                               cloudsc2_tl_launch_sparse); no tangent plane is stored, pert_sums receives the sums of the output tangents.
+ *   cloudsc2_vjp_launch_colsum  the sparse reverse sweep (the gradients wanted are the non-NULL fields of adj_in) in which the cotangent
+ *                               of output n at level k is not loaded from a plane but formed as fl(w_n[k] ybar_n[c]) from the table and
+ *                               the per-column adj_sums (read only; NULL: a zero cotangent).  Every gradient has the bits of
+ *                               cloudsc2_vjp_launch_sparse given those products as planes.
+ * CLOUDSC2_EINVAL, before the device is looked for: a NULL block, bad geometry, prm->lphylin = 0, a NULL table, no sum given or wanted
+ * (TL: every pert_sums field NULL; reverse: every adj_sums or every adj_in field NULL), sums of different strides or a stride below
+ * nproma, keep with only one of the two planes, keep with the evaporation branch and no scratch, satur outside {0, 1}, satur = 1
+ * together with a qsat plane, an incomplete trajectory.  No launcher allocates or synchronises (apart from the CETA table of a grid's
+ * first use); all are plain kernel nodes under stream capture.  The kernels are no kernel family of cloudsc2_variant_built and do not
+ * appear in the launch log; cloudsc2_kernel_occupancy knows them as CLOUDSC2_KERNEL_{NL,TL,VJP}_COLSUM (flags: NL C2F_QSAT, C2F_PRECISE,
+ * C2F_EVAP, C2F_OFF32 and C2F_CKPT = 16 for the keep form; TL / reverse: the sparse kernels' flags). */
+#define CLOUDSC2_KERNEL_NL_COLSUM 12
+#define CLOUDSC2_KERNEL_TL_COLSUM 13
+#define CLOUDSC2_KERNEL_VJP_COLSUM 14
+int cloudsc2_nl_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                              const cloudsc2_inputs* in, const cloudsc2_real* weights, const cloudsc2_outputs* sums,
+                              const cloudsc2_outputs* keep, cloudsc2_real* scratch, void* stream);
+int cloudsc2_tl_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const cloudsc2_real* weights,
+                              const cloudsc2_outputs* pert_sums, void* stream);
+int cloudsc2_vjp_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, const cloudsc2_inputs* adj_in,
+                               const cloudsc2_real* weights, const cloudsc2_outputs* adj_sums, const cloudsc2_real* scratch,
+                               void* stream);
+
 /* The derivative with respect to the scheme's tunable parameters, next to the derivative with respect to its fields.  Four constants
  * of cloudsc2_params enter CLOUDSC2 smoothly, in this order (CLOUDSC2_NPAR):
  *   rkconv   the autoconversion rate, ZCKCODTL = 2 RKCONV PTSPHY, ZCKCODTI = 5 RKCONV PTSPHY (cloudsc2.F90:235-236)

@@ -1,0 +1,232 @@
+"""The column-sum sweeps (nl_column / tl_column / ad_reverse_column with C2F_COLSUM: what cloudsc2_nl_launch_colsum,
+cloudsc2_tl_launch_colsum and cloudsc2_vjp_launch_colsum run) compiled for the HOST against the dense and sparse host sweeps of the same
+library.  A sum is the bits of the fold ``acc = 0; acc = fl(acc + fl(w[k] * out[k]))`` over the dense planes, done in numpy in the
+library's real type; a gradient is the bits of the sparse reverse sweep fed the planes ``w[k] * ybar[c]``.  Absent sums, gradients and
+tangents are NULL pointers, and the lean forward is given no output plane at all: a missing guard is a segmentation fault here, on
+the CPU."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests.sparse_patterns import NARROW, in_names
+from tests.test_hostcheck_vjp import host_qsat
+from tests.util import B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, hfld, host_traj_blocks, increments_of, make_params
+
+COLSUM_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_colsum_sp.so" if B.SINGLE else "libhostcheck_colsum.so")
+BITS = np.int32 if B.SINGLE else np.int64
+HALF = ("fplsl", "fplsn", "fhpsl", "fhpsn")
+
+
+def build_hostcheck_colsum() -> str:
+    src = os.path.join(HOSTCHECK_DIR, "hostcheck_colsum.hip")
+    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck_sparse.hip"), os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
+        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp", "cloudsc2_fields.hpp")]
+    if (not os.path.exists(COLSUM_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(COLSUM_LIB) for d in deps):
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
+                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", COLSUM_LIB, src])
+    return COLSUM_LIB
+
+
+_lib = None
+
+
+def colsum_lib():
+    global _lib
+    if _lib is None:
+        lib = C.CDLL(build_hostcheck_colsum())
+        pp, pi, po = C.POINTER(B.Params), C.POINTER(B.Inputs), C.POINTER(B.Outputs)
+        geom = [pp, C.c_double, C.c_int, C.c_int, C.c_int]
+        lib.hostcheck_sparse_forward.argtypes = geom + [pi, po, C.c_void_p]
+        lib.hostcheck_nl.argtypes = geom + [pi, po, B.Field, C.c_double]
+        lib.hostcheck_sparse_tl.argtypes = geom + [C.c_int, C.c_int, pi, pi, po]
+        lib.hostcheck_sparse_vjp.argtypes = geom + [C.c_int, C.c_int, pi, po, pi, po, C.c_void_p]
+        lib.hostcheck_colsum_nl.argtypes = geom + [pi, C.c_void_p, po, po, C.c_void_p]
+        lib.hostcheck_colsum_tl.argtypes = geom + [C.c_int, pi, pi, C.c_void_p, po]
+        lib.hostcheck_colsum_vjp.argtypes = geom + [C.c_int, pi, po, pi, C.c_void_p, po, C.c_void_p]
+        for f in (lib.hostcheck_sparse_forward, lib.hostcheck_nl, lib.hostcheck_sparse_tl, lib.hostcheck_sparse_vjp, lib.hostcheck_colsum_nl,
+                  lib.hostcheck_colsum_tl, lib.hostcheck_colsum_vjp):
+            f.restype = C.c_int
+        _lib = lib
+    return _lib
+
+
+@pytest.fixture(params=["fast", "precise"])
+def precise(request):
+    p = int(request.param == "precise")
+    colsum_lib().hostcheck_set_precise(p)
+    yield p
+    colsum_lib().hostcheck_set_precise(0)
+
+
+def same_bits(a: np.ndarray, b: np.ndarray) -> bool:
+    return np.array_equal(np.ascontiguousarray(a).view(BITS), np.ascontiguousarray(b).view(BITS))
+
+
+def weight_patterns(nlev: int) -> list:
+    """(name, {output: weights of length nlevx}); (a) has negative entries, exact zeros and non-zero entries at both ends"""
+    rng = np.random.default_rng(20261020)
+    nlevx = lambda n: nlev + (1 if n in HALF else 0)  # noqa: E731
+    a = {}
+    for n in B.OUT_NAMES:
+        w = rng.uniform(-1.0, 1.0, nlevx(n))
+        w[rng.random(nlevx(n)) < 0.2] = 0.0
+        w[0], w[-1] = -0.75, 0.625
+        a[n] = w.astype(B.REAL)
+    assert all((w < 0).any() and (w == 0).any() for w in a.values())
+    surface = np.zeros(nlev + 1, dtype=B.REAL)
+    surface[-1] = 1.0
+    pick = lambda *names: {n: a[n] for n in names}  # noqa: E731
+    return [("all", a), ("surface", {"fplsl": surface, "fplsn": surface.copy()}), ("tent,tenq", pick("tent", "tenq")), ("covptot", pick("covptot"))]
+
+
+def table_of(weights: dict, nlev: int) -> np.ndarray:
+    """the launchers' table: ten rows of nlev + 1, NaN where a row is not given or an entry is unused"""
+    t = np.full((len(B.OUT_NAMES), nlev + 1), np.nan, dtype=B.REAL)
+    for n, w in weights.items():
+        t[B.OUT_NAMES.index(n), :len(w)] = w
+    return t
+
+
+def fold(w: np.ndarray, plane: np.ndarray) -> np.ndarray:
+    """the contract: acc = +0; acc = fl(acc + fl(w[k] * plane[:, k, :])) in the library's real type"""
+    assert w.dtype == B.REAL and plane.dtype == B.REAL and len(w) == plane.shape[1]
+    acc = np.zeros((plane.shape[0], plane.shape[2]), dtype=B.REAL)
+    for k in range(len(w)):
+        p = w[k] * plane[:, k, :]
+        acc = acc + p
+    return acc
+
+
+def sums_block(names, nb: int, nproma: int, fill=np.nan):
+    arrays = {n: np.full((nb, nproma), fill, dtype=B.REAL) for n in names}
+    return arrays, flat_block("out", arrays)
+
+
+def check_sums(got: dict, want: dict, nproma: int, ngptot: int, what) -> None:
+    nb = next(iter(got.values())).shape[0]
+    for n, g in got.items():
+        for ibl in range(nb):
+            icend = min(nproma, ngptot - ibl * nproma)
+            assert not np.any(np.isnan(g[ibl, :icend])), (what, n, "an active sum was not written")
+            assert same_bits(g[ibl, :icend], want[n][ibl, :icend]), (what, n, "differs from the fold over the planes")
+            assert np.all(np.isnan(g[ibl, icend:])), (what, n, "the padded tail was touched")
+
+
+def tangent_masks(satur: bool) -> list:
+    ins = in_names(satur)
+    rng = np.random.default_rng(20261021 + int(satur))
+    return [ins, NARROW[0], (), ("paph", "lu"), tuple(n for n in ins if rng.random() < 0.4) or ("t",)]
+
+
+@pytest.mark.parametrize("satur", [False, True], ids=["qsat", "satur"])
+@pytest.mark.parametrize("flags", [dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(lregcl=True)])
+def test_column_sums_are_the_fold_over_the_planes(precise, flags, satur):
+    nlev, nproma, ngptot = 137, 16, 30
+    tab = c2.random_table(nlev, 30, seed=11)
+    prm = make_params(tab, **flags)
+    evap = bool(flags.get("levapls2") or flags.get("ldrain1d"))
+    st = c2.state_from_table(tab, nproma, ngptot)
+    nb = st.nblocks
+    qsat = None if satur else host_qsat(st)
+    ins = in_names(satur)
+    lib = colsum_lib()
+    geom = (C.byref(prm), st.ptsphy, nproma, nlev, ngptot)
+    active = (np.arange(nb * nproma) < ngptot).reshape(nb, nproma)
+
+    # the dense forward: the ten planes, and what the reverse sweep re-reads
+    traj = st.copy()
+    i, o = host_traj_blocks(traj, qsat)
+    scratch = np.zeros((nb, nlev, nproma), dtype=B.REAL)
+    assert lib.hostcheck_sparse_forward(*geom, C.byref(i), C.byref(o), scratch.ctypes.data) == 0
+    S = nproma * nlev
+    planes = {"tent": traj.B_LOC[:, 0], "tenq": traj.B_LOC[:, 2], "tenl": traj.B_LOC[:, 3], "teni": traj.B_LOC[:, 4], "clc": traj.PA,
+              "covptot": traj.PCOVPTOT, "fplsl": traj.PFPLSL, "fplsn": traj.PFPLSN, "fhpsl": traj.PFHPSL, "fhpsn": traj.PFHPSN}
+    planes = {n: np.ascontiguousarray(a, dtype=B.REAL) for n, a in planes.items()}
+    assert planes["tent"].shape == (nb, nlev, nproma) and planes["fplsl"].shape == (nb, nlev + 1, nproma) and S
+
+    inc = increments_of(st, host_qsat(st))  # v = 0.01 x
+    rng = np.random.default_rng(20261022)
+    ybar_all = {n: rng.uniform(-1.0, 1.0, (nb, nproma)).astype(B.REAL) for n in B.OUT_NAMES}
+
+    for wname, weights in weight_patterns(nlev):
+        table = table_of(weights, nlev)
+        names = tuple(weights)
+        want = {n: fold(weights[n], planes[n]) for n in names}
+
+        # ---- forward, lean: no plane anywhere, a NaN-filled output block that is passed nowhere stays NaN
+        bystander = flat_fields("out", nb, nlev, nproma, fill=np.nan)
+        got, blk = sums_block(names, nb, nproma)
+        assert lib.hostcheck_colsum_nl(*geom, C.byref(i), table.ctypes.data, C.byref(blk), None, None) == 0
+        check_sums(got, want, nproma, ngptot, ("NL lean", wname))
+        assert all(np.all(np.isnan(a)) for a in bystander.values())
+
+        # ---- forward with keep: the two flux planes and the checkpoints are the trajectory pass's bits
+        keep = {n: np.full((nb, nlev + 1, nproma), np.nan, dtype=B.REAL) for n in ("fplsl", "fplsn")}
+        ck = np.full((nb, nlev, nproma), np.nan, dtype=B.REAL)
+        got, blk = sums_block(names, nb, nproma)
+        assert lib.hostcheck_colsum_nl(*geom, C.byref(i), table.ctypes.data, C.byref(blk), C.byref(flat_block("out", keep)), ck.ctypes.data) == 0
+        check_sums(got, want, nproma, ngptot, ("NL keep", wname))
+        for n in keep:
+            assert same_bits(keep[n][active[:, None, :].repeat(nlev + 1, 1)], planes[n][active[:, None, :].repeat(nlev + 1, 1)]), (wname, n)
+            assert np.all(np.isnan(keep[n][~active[:, None, :].repeat(nlev + 1, 1)])), (wname, n, "tail")
+        act3 = active[:, None, :].repeat(nlev, 1)
+        if evap:
+            assert same_bits(ck[act3], scratch[act3]) and np.all(np.isnan(ck[~act3])), (wname, "checkpoints")
+        else:
+            assert np.all(np.isnan(ck)), (wname, "scratch was touched without the evaporation branch")
+
+        # ---- TL: the sums of the sparse host TL's tangent planes
+        tl_sum = {}
+        for pin in tangent_masks(satur):
+            din = {n: inc[n].copy() for n in pin}
+            dy = flat_fields("out", nb, nlev, nproma, fill=np.nan)
+            assert lib.hostcheck_sparse_tl(*geom, int(satur), 1, C.byref(i), C.byref(flat_block("in", din)), C.byref(flat_block("out", dy))) == 0
+            dwant = {n: fold(weights[n], np.where(np.isnan(dy[n]), B.REAL(0), dy[n])) for n in names}
+            got, blk = sums_block(names, nb, nproma)
+            assert lib.hostcheck_colsum_tl(*geom, int(satur), C.byref(i), C.byref(flat_block("in", din)), table.ctypes.data, C.byref(blk)) == 0
+            check_sums(got, dwant, nproma, ngptot, ("TL", wname, pin))
+            for n in din:
+                assert same_bits(din[n], inc[n]), ("TL changed a tangent", n)
+            if pin == ins:
+                tl_sum = got
+
+        # ---- reverse: the sparse host reverse sweep fed the planes w[k] * ybar[c], zero planes for the absent sums
+        ybar = {n: ybar_all[n].copy() for n in names}
+        yplanes = {}
+        for n in B.OUT_NAMES:
+            nlevx = nlev + (1 if n in HALF else 0)
+            if n in names:
+                yplanes[n] = np.ascontiguousarray((weights[n][None, :, None] * ybar[n][:, None, :]).astype(B.REAL))
+            else:
+                yplanes[n] = np.zeros((nb, nlevx, nproma), dtype=B.REAL)
+        vjp_all = {}
+        for pin in [m for m in tangent_masks(satur) if m]:
+            xw = {n: a for n, a in flat_fields("in", nb, nlev, nproma, fill=np.nan).items() if n in pin}
+            assert lib.hostcheck_sparse_vjp(*geom, int(satur), 1, C.byref(i), C.byref(o), C.byref(flat_block("in", xw)),
+                                            C.byref(flat_block("out", yplanes)), scratch.ctypes.data) == 0
+            xa = {n: a for n, a in flat_fields("in", nb, nlev, nproma, fill=np.nan).items() if n in pin}
+            assert lib.hostcheck_colsum_vjp(*geom, int(satur), C.byref(i), C.byref(o), C.byref(flat_block("in", xa)), table.ctypes.data,
+                                            C.byref(flat_block("out", ybar)), scratch.ctypes.data) == 0
+            for n in pin:
+                nlevx = xa[n].shape[1]
+                a3 = active[:, None, :].repeat(nlevx, 1)
+                assert not np.any(np.isnan(xa[n][a3])), ("VJP", wname, n, "an active element was not written")
+                assert same_bits(xa[n][a3], xw[n][a3]), ("VJP", wname, n, "differs from the sparse sweep fed the product planes")
+                assert np.all(np.isnan(xa[n][~a3])), ("VJP", wname, n, "the padded tail was touched")
+            for n in names:
+                assert same_bits(ybar[n], ybar_all[n]), ("the reverse sweep changed a sum cotangent", n)
+            if pin == ins:
+                vjp_all = xa
+
+        # ---- <ybar, TLsum(v)> = <VJPsum(ybar), v>: the bound of tests/test_hostcheck_satur_lin.py (fp64 only)
+        if not B.SINGLE:
+            lhs = [ybar[n][active] * tl_sum[n][active] for n in names]
+            rhs = [vjp_all[n][active[:, None, :].repeat(vjp_all[n].shape[1], 1)] * inc[n][active[:, None, :].repeat(inc[n].shape[1], 1)] for n in ins]
+            l, r = sum(float(x.sum()) for x in lhs), sum(float(x.sum()) for x in rhs)
+            scale = sum(float(np.abs(x).sum()) for x in lhs) + sum(float(np.abs(x).sum()) for x in rhs)
+            assert abs(l - r) <= 1e-12 * scale, (wname, l, r, scale)
