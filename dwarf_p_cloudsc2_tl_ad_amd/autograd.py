@@ -119,6 +119,11 @@ OUT_GROUPS = {"loc": ("tent", "tenq", "tenl", "teni"), "full": ("clc", "covptot"
 SAT_NAMES = tuple(n for n in B.IN_NAMES if n != "qsat")
 SAT_GROUPS = {g: tuple(n for n in names if n != "qsat") for g, names in IN_GROUPS.items()}
 PARAM_NAMES = B.PARAM_NAMES  # the constants of prm that cloudsc2(..., params=...) differentiates
+FPLSL, FPLSN = B.OUT_NAMES.index("fplsl"), B.OUT_NAMES.index("fplsn")  # the two outputs the reverse sweep re-reads
+
+
+def _names(satur: bool):
+    return (SAT_NAMES, SAT_GROUPS) if satur else (B.IN_NAMES, IN_GROUPS)
 
 
 class Layout(namedtuple("Layout", "nblocks nlev nproma ngptot")):
@@ -146,15 +151,21 @@ def _fits(t: torch.Tensor, lay: Layout, name: str) -> bool:
     return (lay.nproma == 1 or t.stride(2) == 1) and t.stride(1) == lay.nproma
 
 
-def check_layout(inputs, prm: B.Params, ngptot: int | None = None, satur: bool = False) -> Layout:
-    """Every check of :func:`cloudsc2` that needs no device: names, dtype, shapes, strides, ``ngptot``, ``nlev`` and the parameters.
-    Runs on CPU or meta tensors; raises ``ValueError``.  ``satur``: the names are those of ``SAT_NAMES`` (no ``qsat``)."""
+def _check_names(inputs, satur: bool) -> tuple:
+    """``inputs`` maps exactly the names of this form of the op, which are returned; raises ``ValueError``"""
     IN_NAMES = SAT_NAMES if satur else B.IN_NAMES
     names = set(inputs.keys()) if hasattr(inputs, "keys") else None
     if satur and names is not None and "qsat" in names:
         raise ValueError("satur=True: SATUR is evaluated and differentiated inside the op, inputs must not have a 'qsat'")
     if names is None or names != set(IN_NAMES):
         raise ValueError(f"inputs must map exactly the names {IN_NAMES}; got {sorted(names) if names is not None else type(inputs)}")
+    return IN_NAMES
+
+
+def check_layout(inputs, prm: B.Params, ngptot: int | None = None, satur: bool = False) -> Layout:
+    """Every check of :func:`cloudsc2` that needs no device: names, dtype, shapes, strides, ``ngptot``, ``nlev`` and the parameters.
+    Runs on CPU or meta tensors; raises ``ValueError``.  ``satur``: the names are those of ``SAT_NAMES`` (no ``qsat``)."""
+    IN_NAMES = _check_names(inputs, satur)
     dtype = B.torch_real()
     for n in IN_NAMES:
         t = inputs[n]
@@ -200,7 +211,13 @@ def check_device(tensors) -> torch.device:
     return dev
 
 
+def _member0(t: torch.Tensor) -> torch.Tensor:
+    """the first member of a 4-D ensemble tensor ``(K, nblocks, nlevx, nproma)``; a 3-D tensor as it is"""
+    return t[0] if t.dim() == 4 else t
+
+
 def _group_fits(ts: dict, lay: Layout, names, want: int | None) -> bool:
+    ts = {n: _member0(ts[n]) for n in names}
     strides = {_block_stride(ts[n], lay, n) for n in names}
     if len(strides) != 1 or not all(_fits(ts[n], lay, n) for n in names):
         return False
@@ -210,7 +227,8 @@ def _group_fits(ts: dict, lay: Layout, names, want: int | None) -> bool:
 def normalize(ts: dict, lay: Layout, groups: dict) -> dict:
     """Copy contiguous every group of ``ts`` the launchers cannot take as it is: members of a group with different block strides, or
     a full-level / half-level group whose stride is not that of the contiguous arrays the op allocates (or a member without the
-    in-block layout: expanded, zero-strided)."""
+    in-block layout: expanded, zero-strided).  The tensors of an ensemble are 3-D (shared) or 4-D (one per member): its launchers
+    take one block stride per layout group and any member stride per field."""
     out = dict(ts)
     for g, names in groups.items():
         want = lay.nlev * lay.nproma if g == "full" else (lay.nlev + 1) * lay.nproma if g == "half" else None
@@ -379,160 +397,98 @@ def _block_array(kind: str, per_direction: list, lay: Layout):
     return (typ * len(per_direction))(*[_block(kind, d, lay) for d in per_direction])
 
 
-class _Cloudsc2Tl(torch.autograd.Function):
-    """forward(prm, ptsphy, layout, *16 trajectory inputs, *16 tangents) -> 10 output tangents: the TL sweep without trajectory
-    stores.  Not differentiable (no double backward)."""
+def _vmap_states(cls, in_dims, prm, ptsphy, lay: Layout, satur: bool, xs):
+    """The vmap rule of an op-level Function ``cls`` with the operands ``(prm, ptsphy, layout, satur, *inputs)``: nothing batched is
+    the plain call, a batch of states is folded into the blocks (:func:`_fold`); the cover scratch is batched only where it exists."""
+    _refuse_nested(xs)
+    names, groups = _names(satur)
+    dims = in_dims[4:]
+    if _batch_size(dims, xs) is None:
+        return cls.apply(prm, ptsphy, lay, satur, *xs), (None,) * 11
 
-    @staticmethod
-    def forward(prm, ptsphy, lay, *ts):
-        x = dict(zip(B.IN_NAMES, ts[:16]))
-        like = x["pap"]
-        dev = like.device
-        dx = normalize(dict(zip(B.IN_NAMES, ts[16:])), lay, IN_GROUPS)
-        dy = _new(B.OUT_NAMES, lay, like)
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_tl_launch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                             C.byref(_block("in", x, lay)), C.byref(B.Outputs()),  # no trajectory stores
-                                             C.byref(_block("in", dx, lay)), C.byref(_block("out", dy, lay)), _stream(dev)))
-        return tuple(dy[n] for n in B.OUT_NAMES)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        ctx.mark_non_differentiable(*output)
-
-    @staticmethod
-    def vmap(info, in_dims, prm, ptsphy, lay, *ts):
-        _refuse_nested(ts)
-        dims = in_dims[3:]
-        K = _batch_size(dims, ts)
-        if K is None:
-            return _Cloudsc2Tl.apply(prm, ptsphy, lay, *ts), (None,) * 10
-        if any(d is not None for d in dims[:16]):  # a batch of states
-            def one(l, flat):
-                x = normalize(dict(zip(B.IN_NAMES, flat[:16])), l, IN_GROUPS)
-                return _Cloudsc2Tl.apply(prm, ptsphy, l, *(x[n] for n in B.IN_NAMES), *flat[16:])
-            return _fold(one, lay, B.IN_NAMES * 2, ts, dims, B.OUT_NAMES), (0,) * 10
-        x = dict(zip(B.IN_NAMES, ts[:16]))
-        like = x["pap"]
-        dev = like.device
-        dxs = _directions(B.IN_NAMES, ts[16:], dims[16:], K, lay, IN_GROUPS)
-        dy = _new(B.OUT_NAMES, lay, like, batch=K)
-        dys = [{n: dy[n][k] for n in B.OUT_NAMES} for k in range(K)]
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_tl_launch_batch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                                   C.byref(_block("in", x, lay)), K, _block_array("in", dxs, lay),
-                                                   _block_array("out", dys, lay), _stream(dev)))
-        return tuple(dy[n] for n in B.OUT_NAMES), (0,) * 10
+    def one(l, flat):
+        x = normalize(dict(zip(names, flat)), l, groups)
+        return cls.apply(prm, ptsphy, l, satur, *(x[n] for n in names))
+    evap = _evap(prm)
+    outs = _fold(one, lay, names, xs, dims, B.OUT_NAMES + ("scratch" if evap else None,))
+    return outs, (0,) * 10 + (0 if evap else None,)
 
 
-_VJP_TRAJ = B.IN_NAMES + ("fplsl", "fplsn", "scratch")  # the trajectory operands of _Cloudsc2Vjp
+# ---- what the Function classes share ---------------------------------------------------------------------------------------------
+# An op-level Function (_Cloudsc2, _Cloudsc2Par, _Cloudsc2Sparse, _Cloudsc2Ens, _Cloudsc2Colsum) is the forward launch; its jvp and
+# backward each apply an inner Function (...Tl, ...Vjp), which is one launcher of the C ABI.
+
+def _inner(raises: str | None):
+    """Class decorator of an inner Function: what differentiating it again does.  ``raises=None`` (dense, par, sparse): its outputs
+    are marked non-differentiable, and it is reached under ``once_differentiable``.  ``raises=message`` (ens, colsum): its
+    ``backward`` and ``jvp`` raise ``NotImplementedError(message)``."""
+    def decorate(cls):
+        if raises is None:
+            def setup_context(ctx, inputs, output):
+                ctx.mark_non_differentiable(*output)
+        else:
+            def setup_context(ctx, inputs, output):
+                pass
+
+            def refuse(ctx, *args):
+                raise NotImplementedError(raises)
+            cls.backward = cls.jvp = staticmethod(refuse)
+        cls.setup_context = staticmethod(setup_context)
+        return cls
+    return decorate
 
 
-class _Cloudsc2Vjp(torch.autograd.Function):
-    """forward(prm, ptsphy, layout, *16 trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints) -> 16 input
-    adjoints: the reverse sweep in its vector-Jacobian form.  Not differentiable (no double backward)."""
-
-    @staticmethod
-    def forward(prm, ptsphy, lay, *ts):
-        x = dict(zip(B.IN_NAMES, ts[:16]))
-        fplsl, fplsn, scratch = ts[16:19]
-        like = x["pap"]
-        dev = like.device
-        y = normalize(dict(zip(B.OUT_NAMES, ts[19:])), lay, OUT_GROUPS)
-        xa = _new(B.IN_NAMES, lay, like)
-        traj_out = B.Outputs()
-        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_vjp_launch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                              C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
-                                              C.byref(_block("out", y, lay)), _scratch_ptr(scratch), _stream(dev)))
-        return tuple(xa[n] for n in B.IN_NAMES)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        ctx.mark_non_differentiable(*output)
-
-    @staticmethod
-    def vmap(info, in_dims, prm, ptsphy, lay, *ts):
-        _refuse_nested(ts)
-        dims = in_dims[3:]
-        K = _batch_size(dims, ts)
-        if K is None:
-            return _Cloudsc2Vjp.apply(prm, ptsphy, lay, *ts), (None,) * 16
-        if any(d is not None for d in dims[:19]):  # a batch of states
-            def one(l, flat):
-                x = normalize(dict(zip(B.IN_NAMES, flat[:16])), l, IN_GROUPS)
-                fl = [t if _fits(t, l, "fplsl") and _block_stride(t, l, "fplsl") == (l.nlev + 1) * l.nproma else t.contiguous() for t in flat[16:18]]
-                sc = flat[18].contiguous()
-                return _Cloudsc2Vjp.apply(prm, ptsphy, l, *(x[n] for n in B.IN_NAMES), *fl, sc, *flat[19:])
-            return _fold(one, lay, _VJP_TRAJ + B.OUT_NAMES, ts, dims, B.IN_NAMES), (0,) * 16
-        x = dict(zip(B.IN_NAMES, ts[:16]))
-        fplsl, fplsn, scratch = ts[16:19]
-        like = x["pap"]
-        dev = like.device
-        ys = _directions(B.OUT_NAMES, ts[19:], dims[19:], K, lay, OUT_GROUPS)
-        xa = _new(B.IN_NAMES, lay, like, batch=K)
-        xas = [{n: xa[n][k] for n in B.IN_NAMES} for k in range(K)]
-        traj_out = B.Outputs()
-        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
-        with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_vjp_launch_batch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                                    C.byref(_block("in", x, lay)), C.byref(traj_out), K, _block_array("in", xas, lay),
-                                                    _block_array("out", ys, lay), _scratch_ptr(scratch), _stream(dev)))
-        return tuple(xa[n] for n in B.IN_NAMES), (0,) * 16
+def _no_vmap(message: str):
+    """Class decorator of a Function of a family without vmap rules: ``vmap`` raises ``NotImplementedError(message)``"""
+    def decorate(cls):
+        def vmap(info, in_dims, *args):
+            raise NotImplementedError(message)
+        cls.vmap = staticmethod(vmap)
+        return cls
+    return decorate
 
 
-class _Cloudsc2(torch.autograd.Function):
-    # forward(prm, ptsphy, layout, *16 inputs in IN_NAMES order) -> 10 outputs + the cover-checkpoint scratch (non-differentiable);
-    # its jvp and backward are the two functions above, whose vmap rules carry batched tangents and cotangents
+def _split(names, ts) -> tuple:
+    """the tensor operands of a ...Vjp Function: the trajectory inputs by name, PFPLSL5, PFPLSN5, the cover scratch, the cotangents"""
+    n = len(names)
+    return (dict(zip(names, ts[:n])), *ts[n:n + 3], ts[n + 3:])
 
-    @staticmethod
-    def forward(prm, ptsphy, lay, *xs):
-        x = dict(zip(B.IN_NAMES, xs))
-        return _forward_launch(prm, ptsphy, lay, x)
 
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        prm, ptsphy, lay, *xs = inputs
-        out = dict(zip(B.OUT_NAMES, output[:-1]))
-        scratch = output[-1]
-        ctx.mark_non_differentiable(scratch)
-        ctx.save_for_backward(*xs, out["fplsl"], out["fplsn"], scratch)
-        ctx.save_for_forward(*xs)
-        ctx.prm, ctx.ptsphy, ctx.lay = prm, ptsphy, lay
+def _traj_out(fplsl, fplsn, lay: Layout) -> B.Outputs:
+    """the trajectory outputs the reverse sweeps re-read: the two precipitation fluxes, every other field NULL"""
+    out = B.Outputs()
+    out.fplsl, out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
+    return out
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *grads):
-        saved = ctx.saved_tensors
-        lay, like = ctx.lay, saved[0]
-        need = ctx.needs_input_grad[3:]
-        if not any(need):
-            return (None, None, None) + (None,) * 16
-        y = _zero_filled(B.OUT_NAMES, grads[:10], lay, like)
-        xa = _Cloudsc2Vjp.apply(ctx.prm, ctx.ptsphy, lay, *saved, *(y[n] for n in B.OUT_NAMES))
-        return (None, None, None) + tuple(a if nd else None for a, nd in zip(xa, need))
 
-    @staticmethod
-    def jvp(ctx, *tangents):
-        xs = ctx.saved_tensors
-        dx = _zero_filled(B.IN_NAMES, tangents[3:], ctx.lay, xs[0])
-        dy = _Cloudsc2Tl.apply(ctx.prm, ctx.ptsphy, ctx.lay, *xs, *(dx[n] for n in B.IN_NAMES))
-        return tuple(dy) + (None,)
+def _save_trajectory(ctx, xs, fplsl, fplsn, scratch, table=None, fluxes_are_outputs: bool = True, materialize: bool = True, **attrs) -> None:
+    """The ``setup_context`` of the op-level Functions: the inputs, PFPLSL5, PFPLSN5 and the cover scratch saved for backward, the
+    inputs for jvp, behind the family's device table where it has one; the scratch (and the fluxes, where they are kept planes and
+    not outputs) non-differentiable; ``materialize=False``: backward sees None for an output that took no part in the loss;
+    ``attrs`` are set on ``ctx``."""
+    lead = () if table is None else (table,)
+    ctx.mark_non_differentiable(*(() if fluxes_are_outputs else (fplsl, fplsn)), scratch)
+    if not materialize:
+        ctx.set_materialize_grads(False)
+    ctx.save_for_backward(*lead, *xs, fplsl, fplsn, scratch)
+    ctx.save_for_forward(*lead, *xs)
+    for k, v in attrs.items():
+        setattr(ctx, k, v)
 
-    @staticmethod
-    def vmap(info, in_dims, prm, ptsphy, lay, *xs):
-        _refuse_nested(xs)
-        dims = in_dims[3:]
-        if _batch_size(dims, xs) is None:
-            return _Cloudsc2.apply(prm, ptsphy, lay, *xs), (None,) * 11
 
-        def one(l, flat):
-            x = normalize(dict(zip(B.IN_NAMES, flat)), l, IN_GROUPS)
-            return _Cloudsc2.apply(prm, ptsphy, l, *(x[n] for n in B.IN_NAMES))
-        evap = _evap(prm)
-        outs = _fold(one, lay, B.IN_NAMES, xs, dims, B.OUT_NAMES + ("scratch" if evap else None,))
-        return outs, (0,) * 10 + (0 if evap else None,)
+def _enter(inputs, prm: B.Params, ngptot, satur: bool, check=None, *more) -> tuple:
+    """What the public entry points begin with: the names and layout groups of this form, the device-free checks (``check``:
+    :func:`check_layout`, or the entry point's own, which ends in it) and the device check -> (names, groups, what ``check``
+    returned, device)"""
+    names, groups = _names(satur)
+    checked = (check or check_layout)(inputs, prm, ngptot, bool(satur), *more)
+    return names, groups, checked, check_device(inputs[n] for n in names)
+
+
+def _apply(cls, lead: tuple, inputs, names, groups: dict, lay: Layout) -> tuple:
+    """What the public entry points end with: the groups the launchers cannot take copied contiguous, then the Function"""
+    x = normalize({n: inputs[n] for n in names}, lay, groups)
+    return cls.apply(*lead, *(x[n] for n in names))
 
 
 # ---- satur=True: pap, t -> SATUR -> CLOUDSC2, differentiated through SATUR inside the sweeps -------------------------------------
@@ -553,155 +509,178 @@ def _with_qsat(x15: dict, qsat) -> list:
     return [qsat if n == "qsat" else x15[n] for n in B.IN_NAMES]
 
 
-class _Cloudsc2SaturTl(torch.autograd.Function):
-    """forward(prm, ptsphy, layout, *15 trajectory inputs, *15 tangents) -> 10 output tangents: ``cloudsc2_tl_launch_satur``.  Not
-    differentiable (no double backward)."""
+# ---- the dense op: every plane of every cotangent and tangent, with qsat as an input or (satur) SATUR in the sweeps -----------------
+# Batched directions over ONE state are one batched launch over the 16 inputs.  With satur they run by composition: SATUR's partials
+# once (cloudsc2_satur_lin_launch), the chain rule in torch, the batched sweep with qsat as a plane.
+
+def _tl_batch(prm, ptsphy, lay: Layout, x: dict, dts, ddims, K: int) -> tuple:
+    """K tangents (``dts`` in IN_NAMES order, batched where ``ddims`` says) over one state ``x``: one ``cloudsc2_tl_launch_batch``
+    -> the 10 output tangents ``(K, ...)``"""
+    like = x["pap"]
+    dev = like.device
+    dxs = _directions(B.IN_NAMES, dts, ddims, K, lay, IN_GROUPS)
+    dy = _new(B.OUT_NAMES, lay, like, batch=K)
+    dys = [{n: dy[n][k] for n in B.OUT_NAMES} for k in range(K)]
+    with torch.cuda.device(dev):
+        B.check(B.lib.cloudsc2_tl_launch_batch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                               C.byref(_block("in", x, lay)), K, _block_array("in", dxs, lay),
+                                               _block_array("out", dys, lay), _stream(dev)))
+    return tuple(dy[n] for n in B.OUT_NAMES)
+
+
+def _vjp_batch(prm, ptsphy, lay: Layout, x: dict, fplsl, fplsn, scratch, ys, ydims, K: int) -> tuple:
+    """K cotangents (``ys`` in OUT_NAMES order, batched where ``ydims`` says) over one state ``x``: one
+    ``cloudsc2_vjp_launch_batch`` -> the 16 input adjoints ``(K, ...)``"""
+    like = x["pap"]
+    dev = like.device
+    ys = _directions(B.OUT_NAMES, ys, ydims, K, lay, OUT_GROUPS)
+    xa = _new(B.IN_NAMES, lay, like, batch=K)
+    xas = [{n: xa[n][k] for n in B.IN_NAMES} for k in range(K)]
+    with torch.cuda.device(dev):
+        B.check(B.lib.cloudsc2_vjp_launch_batch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                C.byref(_block("in", x, lay)), C.byref(_traj_out(fplsl, fplsn, lay)), K,
+                                                _block_array("in", xas, lay), _block_array("out", ys, lay), _scratch_ptr(scratch),
+                                                _stream(dev)))
+    return tuple(xa[n] for n in B.IN_NAMES)
+
+
+@_inner(raises=None)
+class _Cloudsc2Tl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, *n trajectory inputs, *n tangents) -> 10 output tangents: the TL sweep without trajectory
+    stores, ``cloudsc2_tl_launch`` (n = 16) or ``cloudsc2_tl_launch_satur`` (n = 15).  Not differentiable (no double backward)."""
 
     @staticmethod
-    def forward(prm, ptsphy, lay, *ts):
-        x = dict(zip(SAT_NAMES, ts[:15]))
+    def forward(prm, ptsphy, lay, satur, *ts):
+        names, groups = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
         like = x["pap"]
         dev = like.device
-        dx = normalize(dict(zip(SAT_NAMES, ts[15:])), lay, SAT_GROUPS)
+        dx = normalize(dict(zip(names, ts[n:])), lay, groups)
         dy = _new(B.OUT_NAMES, lay, like)
         with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_tl_launch_satur(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                                   C.byref(_block("in", x, lay)), C.byref(_block("in", dx, lay)),
-                                                   C.byref(_block("out", dy, lay)), _stream(dev)))
-        return tuple(dy[n] for n in B.OUT_NAMES)
+            if satur:
+                B.check(B.lib.cloudsc2_tl_launch_satur(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                       C.byref(_block("in", x, lay)), C.byref(_block("in", dx, lay)),
+                                                       C.byref(_block("out", dy, lay)), _stream(dev)))
+            else:
+                B.check(B.lib.cloudsc2_tl_launch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                 C.byref(_block("in", x, lay)), C.byref(B.Outputs()),  # no trajectory stores
+                                                 C.byref(_block("in", dx, lay)), C.byref(_block("out", dy, lay)), _stream(dev)))
+        return tuple(dy[k] for k in B.OUT_NAMES)
 
     @staticmethod
-    def setup_context(ctx, inputs, output):
-        ctx.mark_non_differentiable(*output)
-
-    @staticmethod
-    def vmap(info, in_dims, prm, ptsphy, lay, *ts):
+    def vmap(info, in_dims, prm, ptsphy, lay, satur, *ts):
         _refuse_nested(ts)
-        dims = in_dims[3:]
+        names, groups = _names(satur)
+        n = len(names)
+        dims = in_dims[4:]
         K = _batch_size(dims, ts)
         if K is None:
-            return _Cloudsc2SaturTl.apply(prm, ptsphy, lay, *ts), (None,) * 10
-        if any(d is not None for d in dims[:15]):  # a batch of states
+            return _Cloudsc2Tl.apply(prm, ptsphy, lay, satur, *ts), (None,) * 10
+        if any(d is not None for d in dims[:n]):  # a batch of states
             def one(l, flat):
-                x = normalize(dict(zip(SAT_NAMES, flat[:15])), l, SAT_GROUPS)
-                return _Cloudsc2SaturTl.apply(prm, ptsphy, l, *(x[n] for n in SAT_NAMES), *flat[15:])
-            return _fold(one, lay, SAT_NAMES * 2, ts, dims, B.OUT_NAMES), (0,) * 10
-        # K directions over one state, by composition: SATUR's partials once, the tangent of qsat of every direction in torch, the
-        # batched TL sweep with qsat as a plane
-        x = dict(zip(SAT_NAMES, ts[:15]))
-        dx = {n: _front(t, d) for n, t, d in zip(SAT_NAMES, ts[15:], dims[15:])}
-        ddim = dict(zip(SAT_NAMES, (None if d is None else 0 for d in dims[15:])))
-        qsat, dqp, dqt = _satur_planes(prm, lay, x["pap"], x["t"])
-        dx["qsat"] = dqp * dx["pap"] + dqt * dx["t"]
-        ddim["qsat"] = None if ddim["pap"] is None and ddim["t"] is None else 0
-        x16 = normalize(dict(zip(B.IN_NAMES, _with_qsat(x, qsat))), lay, IN_GROUPS)
-        return _Cloudsc2Tl.vmap(info, (None,) * 19 + tuple(ddim[n] for n in B.IN_NAMES), prm, ptsphy, lay,
-                                *(x16[n] for n in B.IN_NAMES), *(dx[n] for n in B.IN_NAMES))
+                x = normalize(dict(zip(names, flat[:n])), l, groups)
+                return _Cloudsc2Tl.apply(prm, ptsphy, l, satur, *(x[k] for k in names), *flat[n:])
+            return _fold(one, lay, names * 2, ts, dims, B.OUT_NAMES), (0,) * 10
+        x, dts, ddims = dict(zip(names, ts[:n])), ts[n:], dims[n:]
+        if satur:  # SATUR's partials once, the tangent of qsat of every direction in torch, the batched TL sweep with qsat as a plane
+            dx = {k: _front(t, d) for k, t, d in zip(names, dts, ddims)}
+            ddim = dict(zip(names, (None if d is None else 0 for d in ddims)))
+            qsat, dqp, dqt = _satur_planes(prm, lay, x["pap"], x["t"])
+            dx["qsat"] = dqp * dx["pap"] + dqt * dx["t"]
+            ddim["qsat"] = None if ddim["pap"] is None and ddim["t"] is None else 0
+            x = normalize(dict(zip(B.IN_NAMES, _with_qsat(x, qsat))), lay, IN_GROUPS)
+            dts, ddims = [dx[k] for k in B.IN_NAMES], [ddim[k] for k in B.IN_NAMES]
+        return _tl_batch(prm, ptsphy, lay, x, dts, ddims, K), (0,) * 10
 
 
-_SAT_VJP_TRAJ = SAT_NAMES + ("fplsl", "fplsn", "scratch")  # the trajectory operands of _Cloudsc2SaturVjp
-
-
-class _Cloudsc2SaturVjp(torch.autograd.Function):
-    """forward(prm, ptsphy, layout, *15 trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints) -> 15 input
-    adjoints: ``cloudsc2_vjp_launch_satur``.  Not differentiable (no double backward)."""
+@_inner(raises=None)
+class _Cloudsc2Vjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints) -> n input
+    adjoints: the reverse sweep in its vector-Jacobian form, ``cloudsc2_vjp_launch`` (n = 16) or ``cloudsc2_vjp_launch_satur``
+    (n = 15).  Not differentiable (no double backward)."""
 
     @staticmethod
-    def forward(prm, ptsphy, lay, *ts):
-        x = dict(zip(SAT_NAMES, ts[:15]))
-        fplsl, fplsn, scratch = ts[15:18]
+    def forward(prm, ptsphy, lay, satur, *ts):
+        names, _ = _names(satur)
+        x, fplsl, fplsn, scratch, ys = _split(names, ts)
         like = x["pap"]
         dev = like.device
-        y = normalize(dict(zip(B.OUT_NAMES, ts[18:])), lay, OUT_GROUPS)
-        xa = _new(SAT_NAMES, lay, like)
-        traj_out = B.Outputs()
-        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
+        y = normalize(dict(zip(B.OUT_NAMES, ys)), lay, OUT_GROUPS)
+        xa = _new(names, lay, like)
+        launch = B.lib.cloudsc2_vjp_launch_satur if satur else B.lib.cloudsc2_vjp_launch
         with torch.cuda.device(dev):
-            B.check(B.lib.cloudsc2_vjp_launch_satur(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
-                                                    C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
-                                                    C.byref(_block("out", y, lay)), _scratch_ptr(scratch), _stream(dev)))
-        return tuple(xa[n] for n in SAT_NAMES)
+            B.check(launch(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                           C.byref(_block("in", x, lay)), C.byref(_traj_out(fplsl, fplsn, lay)), C.byref(_block("in", xa, lay)),
+                           C.byref(_block("out", y, lay)), _scratch_ptr(scratch), _stream(dev)))
+        return tuple(xa[k] for k in names)
 
     @staticmethod
-    def setup_context(ctx, inputs, output):
-        ctx.mark_non_differentiable(*output)
-
-    @staticmethod
-    def vmap(info, in_dims, prm, ptsphy, lay, *ts):
+    def vmap(info, in_dims, prm, ptsphy, lay, satur, *ts):
         _refuse_nested(ts)
-        dims = in_dims[3:]
+        names, groups = _names(satur)
+        n = len(names)
+        dims = in_dims[4:]
         K = _batch_size(dims, ts)
         if K is None:
-            return _Cloudsc2SaturVjp.apply(prm, ptsphy, lay, *ts), (None,) * 15
-        if any(d is not None for d in dims[:18]):  # a batch of states
+            return _Cloudsc2Vjp.apply(prm, ptsphy, lay, satur, *ts), (None,) * n
+        if any(d is not None for d in dims[:n + 3]):  # a batch of states
             def one(l, flat):
-                x = normalize(dict(zip(SAT_NAMES, flat[:15])), l, SAT_GROUPS)
-                fl = [t if _fits(t, l, "fplsl") and _block_stride(t, l, "fplsl") == (l.nlev + 1) * l.nproma else t.contiguous() for t in flat[15:17]]
-                sc = flat[17].contiguous()
-                return _Cloudsc2SaturVjp.apply(prm, ptsphy, l, *(x[n] for n in SAT_NAMES), *fl, sc, *flat[18:])
-            return _fold(one, lay, _SAT_VJP_TRAJ + B.OUT_NAMES, ts, dims, SAT_NAMES), (0,) * 15
-        # K cotangents over one state, by composition: the batched reverse sweep with qsat as a plane, then SATUR's transpose in torch
-        x = dict(zip(SAT_NAMES, ts[:15]))
+                x = normalize(dict(zip(names, flat[:n])), l, groups)
+                fl = [t if _fits(t, l, "fplsl") and _block_stride(t, l, "fplsl") == (l.nlev + 1) * l.nproma else t.contiguous() for t in flat[n:n + 2]]
+                sc = flat[n + 2].contiguous()
+                return _Cloudsc2Vjp.apply(prm, ptsphy, l, satur, *(x[k] for k in names), *fl, sc, *flat[n + 3:])
+            return _fold(one, lay, names + ("fplsl", "fplsn", "scratch") + B.OUT_NAMES, ts, dims, names), (0,) * n
+        x, fplsl, fplsn, scratch, ys = _split(names, ts)
+        if not satur:
+            return _vjp_batch(prm, ptsphy, lay, x, fplsl, fplsn, scratch, ys, dims[n + 3:], K), (0,) * n
+        # the batched reverse sweep with qsat as a plane, then SATUR's transpose in torch
         qsat, dqp, dqt = _satur_planes(prm, lay, x["pap"], x["t"])
         x16 = normalize(dict(zip(B.IN_NAMES, _with_qsat(x, qsat))), lay, IN_GROUPS)
-        xa, _ = _Cloudsc2Vjp.vmap(info, (None,) * 22 + tuple(dims[18:]), prm, ptsphy, lay, *(x16[n] for n in B.IN_NAMES), *ts[15:])
-        xa = dict(zip(B.IN_NAMES, xa))
+        xa = dict(zip(B.IN_NAMES, _vjp_batch(prm, ptsphy, lay, x16, fplsl, fplsn, scratch, ys, dims[n + 3:], K)))
         xa["pap"] = xa["pap"] + dqp * xa["qsat"]
         xa["t"] = xa["t"] + dqt * xa["qsat"]
-        return tuple(xa[n] for n in SAT_NAMES), (0,) * 15
+        return tuple(xa[k] for k in names), (0,) * n
 
 
-class _Cloudsc2Satur(torch.autograd.Function):
-    # forward(prm, ptsphy, layout, *15 inputs in SAT_NAMES order) -> 10 outputs + the cover-checkpoint scratch (non-differentiable):
-    # the NL sweep with SATUR fused; its jvp and backward are the two functions above.  One plane less than _Cloudsc2 is saved.
+class _Cloudsc2(torch.autograd.Function):
+    # forward(prm, ptsphy, layout, satur, *n inputs in the order of the names) -> 10 outputs + the cover-checkpoint scratch
+    # (non-differentiable): the NL sweep, with SATUR fused when satur (n = 15: one plane less is saved).  Its jvp and backward are the
+    # two functions above, whose vmap rules carry batched tangents and cotangents.
 
     @staticmethod
-    def forward(prm, ptsphy, lay, *xs):
-        x = dict(zip(SAT_NAMES, xs))
-        return _forward_launch(prm, ptsphy, lay, x)
+    def forward(prm, ptsphy, lay, satur, *xs):
+        return _forward_launch(prm, ptsphy, lay, dict(zip(_names(satur)[0], xs)))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
-        prm, ptsphy, lay, *xs = inputs
-        out = dict(zip(B.OUT_NAMES, output[:-1]))
-        scratch = output[-1]
-        ctx.mark_non_differentiable(scratch)
-        ctx.save_for_backward(*xs, out["fplsl"], out["fplsn"], scratch)
-        ctx.save_for_forward(*xs)
-        ctx.prm, ctx.ptsphy, ctx.lay = prm, ptsphy, lay
+        prm, ptsphy, lay, satur, *xs = inputs
+        _save_trajectory(ctx, xs, output[FPLSL], output[FPLSN], output[-1], prm=prm, ptsphy=ptsphy, lay=lay, satur=satur)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grads):
         saved = ctx.saved_tensors
         lay, like = ctx.lay, saved[0]
-        need = ctx.needs_input_grad[3:]
+        need = ctx.needs_input_grad[4:]
         if not any(need):
-            return (None, None, None) + (None,) * 15
+            return (None,) * (4 + len(need))
         y = _zero_filled(B.OUT_NAMES, grads[:10], lay, like)
-        xa = _Cloudsc2SaturVjp.apply(ctx.prm, ctx.ptsphy, lay, *saved, *(y[n] for n in B.OUT_NAMES))
-        return (None, None, None) + tuple(a if nd else None for a, nd in zip(xa, need))
+        xa = _Cloudsc2Vjp.apply(ctx.prm, ctx.ptsphy, lay, ctx.satur, *saved, *(y[n] for n in B.OUT_NAMES))
+        return (None,) * 4 + tuple(a if nd else None for a, nd in zip(xa, need))
 
     @staticmethod
     def jvp(ctx, *tangents):
+        names, _ = _names(ctx.satur)
         xs = ctx.saved_tensors
-        dx = _zero_filled(SAT_NAMES, tangents[3:], ctx.lay, xs[0])
-        dy = _Cloudsc2SaturTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, *xs, *(dx[n] for n in SAT_NAMES))
+        dx = _zero_filled(names, tangents[4:], ctx.lay, xs[0])
+        dy = _Cloudsc2Tl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, *xs, *(dx[n] for n in names))
         return tuple(dy) + (None,)
 
     @staticmethod
-    def vmap(info, in_dims, prm, ptsphy, lay, *xs):
-        _refuse_nested(xs)
-        dims = in_dims[3:]
-        if _batch_size(dims, xs) is None:
-            return _Cloudsc2Satur.apply(prm, ptsphy, lay, *xs), (None,) * 11
-
-        def one(l, flat):
-            x = normalize(dict(zip(SAT_NAMES, flat)), l, SAT_GROUPS)
-            return _Cloudsc2Satur.apply(prm, ptsphy, l, *(x[n] for n in SAT_NAMES))
-        evap = _evap(prm)
-        outs = _fold(one, lay, SAT_NAMES, xs, dims, B.OUT_NAMES + ("scratch" if evap else None,))
-        return outs, (0,) * 10 + (0 if evap else None,)
+    def vmap(info, in_dims, prm, ptsphy, lay, satur, *xs):
+        return _vmap_states(_Cloudsc2, in_dims, prm, ptsphy, lay, satur, xs)
 
 
 class _Satur(torch.autograd.Function):
@@ -780,19 +759,33 @@ def _batched_inside(t) -> bool:
     return False
 
 
-def _refuse_batched(ts) -> None:
+def _refuse_batched(ts, message: str = _NO_VMAP) -> None:
     if any(_batched_inside(t) for t in ts):
-        raise NotImplementedError(_NO_VMAP)
+        raise NotImplementedError(message)
 
 
 def _host_value(t: torch.Tensor | None) -> float:
     return 0.0 if t is None else float(_raw(t).detach())
 
 
-def _names(satur: bool):
-    return (SAT_NAMES, SAT_GROUPS) if satur else (B.IN_NAMES, IN_GROUPS)
+def _check_param_devices(pnames, ps, dev: torch.device) -> None:
+    for n, p in zip(pnames, ps):
+        if p.device.type != "cpu" and p.device != dev:
+            raise ValueError(f"params[{n!r}] is on {p.device}: parameters live on the CPU or on the inputs' device {dev}")
 
 
+def _with_host_values(prm: B.Params, pnames, ps, who: str) -> B.Params:
+    """a copy of ``prm`` that holds the parameters' values, read on the HOST; with the evaporation branch ``rpecons`` must not be 0"""
+    prm = copy.copy(prm)  # (a ctypes structure: a copy of its bytes)
+    for n, p in zip(pnames, ps):
+        setattr(prm, n, _host_value(p))  # synchronises when the parameter lives on the device
+    if _evap(prm) and prm.rpecons == 0.0:
+        raise ValueError(f"{who} with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
+    return prm
+
+
+@_no_vmap(_NO_VMAP)
+@_inner(raises=None)
 class _Cloudsc2ParTl(torch.autograd.Function):
     """forward(prm, ptsphy, layout, satur, (4 parameter tangents), *n trajectory inputs, *n tangents) -> 10 output tangents:
     ``cloudsc2_tl_launch_par`` (n = 16, or 15 with satur).  Not differentiable."""
@@ -812,15 +805,9 @@ class _Cloudsc2ParTl(torch.autograd.Function):
                                                  (C.c_double * len(PARAM_NAMES))(*dpar), C.byref(_block("out", dy, lay)), _stream(dev)))
         return tuple(dy[k] for k in B.OUT_NAMES)
 
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        ctx.mark_non_differentiable(*output)
 
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP)
-
-
+@_no_vmap(_NO_VMAP)
+@_inner(raises=None)
 class _Cloudsc2ParVjp(torch.autograd.Function):
     """forward(prm, ptsphy, layout, satur, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints) -> n input
     adjoints and the 4 parameter adjoints (device float64): ``cloudsc2_vjp_launch_par``.  Not differentiable."""
@@ -828,58 +815,39 @@ class _Cloudsc2ParVjp(torch.autograd.Function):
     @staticmethod
     def forward(prm, ptsphy, lay, satur, *ts):
         names, _ = _names(satur)
-        n = len(names)
-        x = dict(zip(names, ts[:n]))
-        fplsl, fplsn, scratch = ts[n:n + 3]
+        x, fplsl, fplsn, scratch, ys = _split(names, ts)
         like = x["pap"]
         dev = like.device
-        y = normalize(dict(zip(B.OUT_NAMES, ts[n + 3:])), lay, OUT_GROUPS)
+        y = normalize(dict(zip(B.OUT_NAMES, ys)), lay, OUT_GROUPS)
         xa = _new(names, lay, like)
-        traj_out = B.Outputs()
-        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
         nwork = C.c_longlong()
         B.check(B.lib.cloudsc2_par_work_doubles(lay.nproma, lay.ngptot, C.byref(nwork)))
         work = torch.empty(nwork.value, dtype=torch.float64, device=dev)
         par_adj = torch.empty(len(PARAM_NAMES), dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
             B.check(B.lib.cloudsc2_vjp_launch_par(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
-                                                  C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
-                                                  C.byref(_block("out", y, lay)), _scratch_ptr(scratch), C.c_void_p(work.data_ptr()),
-                                                  C.c_void_p(par_adj.data_ptr()), _stream(dev)))
+                                                  C.byref(_block("in", x, lay)), C.byref(_traj_out(fplsl, fplsn, lay)),
+                                                  C.byref(_block("in", xa, lay)), C.byref(_block("out", y, lay)), _scratch_ptr(scratch),
+                                                  C.c_void_p(work.data_ptr()), C.c_void_p(par_adj.data_ptr()), _stream(dev)))
         return tuple(xa[k] for k in names) + (par_adj,)
 
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        ctx.mark_non_differentiable(*output)
 
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP)
-
-
+@_no_vmap(_NO_VMAP)
 class _Cloudsc2Par(torch.autograd.Function):
     # forward(prm, ptsphy, layout, satur, parameter names, *their 0-d tensors, *n inputs) -> 10 outputs + the cover-checkpoint scratch:
-    # prm already holds the parameters' values, so the forward is the NL sweep of _Cloudsc2 / _Cloudsc2Satur; the tensors are operands
-    # for autograd's sake.  backward: one cloudsc2_vjp_launch_par (today's launch when no parameter needs a gradient); jvp: one
+    # prm already holds the parameters' values, so the forward is the NL sweep of _Cloudsc2; the tensors are operands for autograd's
+    # sake.  backward: one cloudsc2_vjp_launch_par (today's launch when no parameter needs a gradient); jvp: one
     # cloudsc2_tl_launch_par.
 
     @staticmethod
     def forward(prm, ptsphy, lay, satur, pnames, *ts):
-        names, _ = _names(satur)
-        x = dict(zip(names, ts[len(pnames):]))
-        return _forward_launch(prm, ptsphy, lay, x)
+        return _forward_launch(prm, ptsphy, lay, dict(zip(_names(satur)[0], ts[len(pnames):])))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
         prm, ptsphy, lay, satur, pnames, *ts = inputs
-        xs = ts[len(pnames):]
-        out = dict(zip(B.OUT_NAMES, output[:-1]))
-        scratch = output[-1]
-        ctx.mark_non_differentiable(scratch)
-        ctx.save_for_backward(*xs, out["fplsl"], out["fplsn"], scratch)
-        ctx.save_for_forward(*xs)
-        ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.pnames = prm, ptsphy, lay, satur, pnames
-        ctx.pdevs = tuple(p.device for p in ts[:len(pnames)])
+        _save_trajectory(ctx, ts[len(pnames):], output[FPLSL], output[FPLSN], output[-1], prm=prm, ptsphy=ptsphy, lay=lay, satur=satur,
+                         pnames=pnames, pdevs=tuple(p.device for p in ts[:len(pnames)]))
 
     @staticmethod
     @once_differentiable
@@ -892,8 +860,7 @@ class _Cloudsc2Par(torch.autograd.Function):
             return (None,) * (5 + P + len(need_x))
         y = _zero_filled(B.OUT_NAMES, grads[:10], lay, like)
         if not any(need_p):  # the field gradients alone: today's launch
-            vjp = _Cloudsc2SaturVjp if ctx.satur else _Cloudsc2Vjp
-            xa = vjp.apply(ctx.prm, ctx.ptsphy, lay, *saved, *(y[n] for n in B.OUT_NAMES))
+            xa = _Cloudsc2Vjp.apply(ctx.prm, ctx.ptsphy, lay, ctx.satur, *saved, *(y[n] for n in B.OUT_NAMES))
             return (None,) * (5 + P) + tuple(a if nd else None for a, nd in zip(xa, need_x))
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("cloudsc2 with params: the backward cannot run while the stream is capturing")
@@ -916,10 +883,6 @@ class _Cloudsc2Par(torch.autograd.Function):
         dy = _Cloudsc2ParTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, tuple(dpar), *xs, *(dx[n] for n in names))
         return tuple(dy) + (None,)
 
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP)
-
 
 def _cloudsc2_par(inputs, prm: B.Params, ptsphy: float, ngptot, satur: bool, params) -> Cloudsc2Outputs:
     names, groups = _names(satur)
@@ -928,21 +891,13 @@ def _cloudsc2_par(inputs, prm: B.Params, ptsphy: float, ngptot, satur: bool, par
     dev = check_device(inputs[n] for n in names)
     ps = tuple(params[n] for n in pnames)
     _refuse_batched(ps + tuple(inputs[n] for n in names))
-    for n, p in zip(pnames, ps):
-        if p.device.type != "cpu" and p.device != dev:
-            raise ValueError(f"params[{n!r}] is on {p.device}: parameters live on the CPU or on the inputs' device {dev}")
+    _check_param_devices(pnames, ps, dev)
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError("cloudsc2 with params: the parameters' values are read on the host (they travel in the kernel-argument "
                            "segment), which cannot happen while the stream is capturing")
     _prepare(dev)
-    prm = copy.copy(prm)  # (a ctypes structure: a copy of its bytes)
-    for n, p in zip(pnames, ps):
-        setattr(prm, n, _host_value(p))  # synchronises when the parameter lives on the device
-    if _evap(prm) and prm.rpecons == 0.0:
-        raise ValueError("params with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
-    x = normalize({n: inputs[n] for n in names}, lay, groups)
-    out = _Cloudsc2Par.apply(prm, float(ptsphy), lay, bool(satur), pnames, *ps, *(x[n] for n in names))
-    return Cloudsc2Outputs(*out[:10])
+    prm = _with_host_values(prm, pnames, ps, "params")
+    return Cloudsc2Outputs(*_apply(_Cloudsc2Par, (prm, float(ptsphy), lay, bool(satur), pnames, *ps), inputs, names, groups, lay)[:10])
 
 
 # ---- sparse=True: the derivative side moves only the planes a loss touches -----------------------------------------------------------
@@ -960,10 +915,7 @@ def _normalize_present(ts: dict, lay: Layout, groups: dict) -> dict:
     return normalize(ts, lay, {g: tuple(n for n in names if n in ts) for g, names in groups.items() if any(n in ts for n in names)})
 
 
-def _dense_rules(satur: bool):
-    return (_Cloudsc2SaturTl, _Cloudsc2SaturVjp) if satur else (_Cloudsc2Tl, _Cloudsc2Vjp)
-
-
+@_inner(raises=None)
 class _Cloudsc2SparseTl(torch.autograd.Function):
     """forward(prm, ptsphy, layout, satur, *n trajectory inputs, *n tangents or None) -> 10 output tangents:
     ``cloudsc2_tl_launch_sparse`` (n = 16, or 15 with satur); a None tangent is a zero tangent that is not read.  Not differentiable."""
@@ -984,10 +936,6 @@ class _Cloudsc2SparseTl(torch.autograd.Function):
         return tuple(dy[k] for k in B.OUT_NAMES)
 
     @staticmethod
-    def setup_context(ctx, inputs, output):
-        ctx.mark_non_differentiable(*output)
-
-    @staticmethod
     def vmap(info, in_dims, prm, ptsphy, lay, satur, *ts):
         # the dense rules on zero-filled planes: every direction is the bits of the dense call
         names, _ = _names(satur)
@@ -995,9 +943,10 @@ class _Cloudsc2SparseTl(torch.autograd.Function):
         dims = in_dims[4:]
         dx = _zero_filled(names, ts[n:], lay, ts[0])
         ddims = tuple(None if t is None else d for t, d in zip(ts[n:], dims[n:]))
-        return _dense_rules(satur)[0].vmap(info, (None,) * 3 + tuple(dims[:n]) + ddims, prm, ptsphy, lay, *ts[:n], *(dx[k] for k in names))
+        return _Cloudsc2Tl.vmap(info, (None,) * 4 + tuple(dims[:n]) + ddims, prm, ptsphy, lay, satur, *ts[:n], *(dx[k] for k in names))
 
 
+@_inner(raises=None)
 class _Cloudsc2SparseVjp(torch.autograd.Function):
     """forward(prm, ptsphy, layout, satur, want, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output adjoints or None)
     -> the input adjoints named in ``want``, in that order: ``cloudsc2_vjp_launch_sparse``; a None adjoint is a zero cotangent that is
@@ -1006,24 +955,17 @@ class _Cloudsc2SparseVjp(torch.autograd.Function):
     @staticmethod
     def forward(prm, ptsphy, lay, satur, want, *ts):
         names, _ = _names(satur)
-        n = len(names)
-        x = dict(zip(names, ts[:n]))
-        fplsl, fplsn, scratch = ts[n:n + 3]
+        x, fplsl, fplsn, scratch, ys = _split(names, ts)
         like = x["pap"]
         dev = like.device
-        y = _normalize_present(_present(B.OUT_NAMES, ts[n + 3:]), lay, OUT_GROUPS)
+        y = _normalize_present(_present(B.OUT_NAMES, ys), lay, OUT_GROUPS)
         xa = _new(want, lay, like)
-        traj_out = B.Outputs()
-        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
         with torch.cuda.device(dev):
             B.check(B.lib.cloudsc2_vjp_launch_sparse(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
-                                                     C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
-                                                     C.byref(_block("out", y, lay)), _scratch_ptr(scratch), _stream(dev)))
+                                                     C.byref(_block("in", x, lay)), C.byref(_traj_out(fplsl, fplsn, lay)),
+                                                     C.byref(_block("in", xa, lay)), C.byref(_block("out", y, lay)),
+                                                     _scratch_ptr(scratch), _stream(dev)))
         return tuple(xa[k] for k in want)
-
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        ctx.mark_non_differentiable(*output)
 
     @staticmethod
     def vmap(info, in_dims, prm, ptsphy, lay, satur, want, *ts):
@@ -1033,32 +975,24 @@ class _Cloudsc2SparseVjp(torch.autograd.Function):
         dims = in_dims[5:]
         y = _zero_filled(B.OUT_NAMES, ts[n + 3:], lay, ts[0])
         ydims = tuple(None if t is None else d for t, d in zip(ts[n + 3:], dims[n + 3:]))
-        xa, od = _dense_rules(satur)[1].vmap(info, (None,) * 3 + tuple(dims[:n + 3]) + ydims, prm, ptsphy, lay, *ts[:n + 3],
-                                             *(y[k] for k in B.OUT_NAMES))
+        xa, od = _Cloudsc2Vjp.vmap(info, (None,) * 4 + tuple(dims[:n + 3]) + ydims, prm, ptsphy, lay, satur, *ts[:n + 3],
+                                   *(y[k] for k in B.OUT_NAMES))
         sel = [names.index(k) for k in want]
         return tuple(xa[j] for j in sel), tuple(od[j] for j in sel)
 
 
 class _Cloudsc2Sparse(torch.autograd.Function):
-    # forward(prm, ptsphy, layout, satur, *n inputs) -> 10 outputs + the cover-checkpoint scratch: the launch of _Cloudsc2 /
-    # _Cloudsc2Satur; gradients are not materialised, so backward sees None for an output that took no part in the loss
+    # forward(prm, ptsphy, layout, satur, *n inputs) -> 10 outputs + the cover-checkpoint scratch: the launch of _Cloudsc2;
+    # gradients are not materialised, so backward sees None for an output that took no part in the loss
 
     @staticmethod
     def forward(prm, ptsphy, lay, satur, *xs):
-        names, _ = _names(satur)
-        x = dict(zip(names, xs))
-        return _forward_launch(prm, ptsphy, lay, x)
+        return _forward_launch(prm, ptsphy, lay, dict(zip(_names(satur)[0], xs)))
 
     @staticmethod
     def setup_context(ctx, inputs, output):
         prm, ptsphy, lay, satur, *xs = inputs
-        out = dict(zip(B.OUT_NAMES, output[:-1]))
-        scratch = output[-1]
-        ctx.mark_non_differentiable(scratch)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(*xs, out["fplsl"], out["fplsn"], scratch)
-        ctx.save_for_forward(*xs)
-        ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur = prm, ptsphy, lay, satur
+        _save_trajectory(ctx, xs, output[FPLSL], output[FPLSN], output[-1], materialize=False, prm=prm, ptsphy=ptsphy, lay=lay, satur=satur)
 
     @staticmethod
     @once_differentiable
@@ -1070,7 +1004,7 @@ class _Cloudsc2Sparse(torch.autograd.Function):
         if not any(need) or all(g is None for g in ys):
             return (None,) * (4 + len(names))
         if all(need) and all(g is not None for g in ys):  # everything present: the dense sweep (the same bits)
-            return (None,) * 4 + tuple(_dense_rules(ctx.satur)[1].apply(ctx.prm, ctx.ptsphy, ctx.lay, *saved, *ys))
+            return (None,) * 4 + tuple(_Cloudsc2Vjp.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, *saved, *ys))
         want = tuple(n for n, nd in zip(names, need) if nd)
         xa = dict(zip(want, _Cloudsc2SparseVjp.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, want, *saved, *ys)))
         return (None,) * 4 + tuple(xa.get(n) for n in names)
@@ -1080,25 +1014,14 @@ class _Cloudsc2Sparse(torch.autograd.Function):
         xs = ctx.saved_tensors
         dts = tangents[4:]
         if all(t is not None for t in dts):  # everything present: the dense sweep (the same bits)
-            dy = _dense_rules(ctx.satur)[0].apply(ctx.prm, ctx.ptsphy, ctx.lay, *xs, *dts)
+            dy = _Cloudsc2Tl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, *xs, *dts)
         else:  # (all ten output tangents are stored: autograd cannot say which will be used)
             dy = _Cloudsc2SparseTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, *xs, *dts)
         return tuple(dy) + (None,)
 
     @staticmethod
     def vmap(info, in_dims, prm, ptsphy, lay, satur, *xs):
-        _refuse_nested(xs)
-        names, groups = _names(satur)
-        dims = in_dims[4:]
-        if _batch_size(dims, xs) is None:
-            return _Cloudsc2Sparse.apply(prm, ptsphy, lay, satur, *xs), (None,) * 11
-
-        def one(l, flat):
-            x = normalize(dict(zip(names, flat)), l, groups)
-            return _Cloudsc2Sparse.apply(prm, ptsphy, l, satur, *(x[n] for n in names))
-        evap = _evap(prm)
-        outs = _fold(one, lay, names, xs, dims, B.OUT_NAMES + ("scratch" if evap else None,))
-        return outs, (0,) * 10 + (0 if evap else None,)
+        return _vmap_states(_Cloudsc2Sparse, in_dims, prm, ptsphy, lay, satur, xs)
 
 
 def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None,
@@ -1108,32 +1031,15 @@ def cloudsc2(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, sa
     float64 tensors that override those constants of (a copy of) ``prm`` and are differentiated too; ``sparse=True``: backward and
     jvp move only the cotangent / tangent planes that exist and the gradients that are wanted (not with ``params``); see the module
     docstring."""
-    if sparse:
-        if params is not None:
-            raise NotImplementedError("cloudsc2: sparse=True with params= is not built (the parameter sweeps have no sparse form); "
-                                      "use sparse=False with params")
-        names, groups = _names(satur)
-        lay = check_layout(inputs, prm, ngptot, satur=bool(satur))
-        dev = check_device(inputs[n] for n in names)
-        _prepare(dev)
-        x = normalize({n: inputs[n] for n in names}, lay, groups)
-        out = _Cloudsc2Sparse.apply(prm, float(ptsphy), lay, bool(satur), *(x[n] for n in names))
-        return Cloudsc2Outputs(*out[:10])
+    if sparse and params is not None:
+        raise NotImplementedError("cloudsc2: sparse=True with params= is not built (the parameter sweeps have no sparse form); "
+                                  "use sparse=False with params")
     if params is not None:
         return _cloudsc2_par(inputs, prm, ptsphy, ngptot, satur, params)
-    if satur:
-        lay = check_layout(inputs, prm, ngptot, satur=True)
-        dev = check_device(inputs[n] for n in SAT_NAMES)
-        _prepare(dev)
-        x = normalize({n: inputs[n] for n in SAT_NAMES}, lay, SAT_GROUPS)
-        out = _Cloudsc2Satur.apply(prm, float(ptsphy), lay, *(x[n] for n in SAT_NAMES))
-        return Cloudsc2Outputs(*out[:10])
-    lay = check_layout(inputs, prm, ngptot)
-    dev = check_device(inputs[n] for n in B.IN_NAMES)
+    names, groups, lay, dev = _enter(inputs, prm, ngptot, satur)
     _prepare(dev)
-    x = normalize({n: inputs[n] for n in B.IN_NAMES}, lay, IN_GROUPS)
-    out = _Cloudsc2.apply(prm, float(ptsphy), lay, *(x[n] for n in B.IN_NAMES))
-    return Cloudsc2Outputs(*out[:10])
+    cls = _Cloudsc2Sparse if sparse else _Cloudsc2
+    return Cloudsc2Outputs(*_apply(cls, (prm, float(ptsphy), lay, bool(satur)), inputs, names, groups, lay)[:10])
 
 
 def param_jacobian(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None) -> dict:
@@ -1151,19 +1057,13 @@ def param_jacobian(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = No
     ps = () if params is None else tuple(params[n] for n in pnames)
     if any(_batched_inside(t) for t in ps + tuple(inputs[n] for n in names)):
         raise NotImplementedError("param_jacobian: batched (vmap-wrapped) operands are not supported; call it once per state")
-    for n, p in zip(pnames, ps):
-        if p.device.type != "cpu" and p.device != dev:
-            raise ValueError(f"params[{n!r}] is on {p.device}: parameters live on the CPU or on the inputs' device {dev}")
+    _check_param_devices(pnames, ps, dev)
     if any(p.device.type != "cpu" for p in ps) and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("param_jacobian: the parameters' values are read on the host (they travel in the kernel-argument segment), "
                            "which cannot happen for device tensors while the stream is capturing")
     _prepare(dev)
-    prm = copy.copy(prm)  # (a ctypes structure: a copy of its bytes)
-    for n, p in zip(pnames, ps):
-        setattr(prm, n, _host_value(p))  # synchronises when the parameter lives on the device
+    prm = _with_host_values(prm, pnames, ps, "param_jacobian")
     evap = _evap(prm)
-    if evap and prm.rpecons == 0.0:
-        raise ValueError("param_jacobian with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
     with torch.no_grad():
         x = normalize({n: _raw(inputs[n]).detach() for n in names}, lay, groups)
         like = x["pap"]
@@ -1250,18 +1150,12 @@ def param_normal_equations(inputs, prm: B.Params, ptsphy: float, ngptot: int | N
     ps = () if params is None else tuple(params[n] for n in pnames)
     if any(_batched_inside(t) for t in ps + tuple(inputs[n] for n in names) + tuple(r.values()) + tuple(w.values())):
         raise NotImplementedError("param_normal_equations: batched (vmap-wrapped) operands are not supported; call it once per state")
-    for n, p in zip(pnames, ps):
-        if p.device.type != "cpu" and p.device != dev:
-            raise ValueError(f"params[{n!r}] is on {p.device}: parameters live on the CPU or on the inputs' device {dev}")
+    _check_param_devices(pnames, ps, dev)
     if any(p.device.type != "cpu" for p in ps) and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("param_normal_equations: the parameters' values are read on the host (they travel in the kernel-argument "
                            "segment), which cannot happen for device tensors while the stream is capturing")
     _prepare(dev)
-    prm = copy.copy(prm)  # (a ctypes structure: a copy of its bytes)
-    for n, p in zip(pnames, ps):
-        setattr(prm, n, _host_value(p))  # synchronises when the parameter lives on the device
-    if _evap(prm) and prm.rpecons == 0.0:
-        raise ValueError("param_normal_equations with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
+    prm = _with_host_values(prm, pnames, ps, "param_normal_equations")
     with torch.no_grad():
         if not pnames:
             return NormalEquations((), torch.zeros((0, 0), dtype=torch.float64, device=dev), torch.zeros((0,), dtype=torch.float64, device=dev))
@@ -1316,12 +1210,7 @@ def check_ensemble(inputs, prm: B.Params, ngptot: int | None = None, satur: bool
             K = int(p.shape[0])
         elif int(p.shape[0]) != K:
             raise ValueError(f"params[{n!r}] has {p.shape[0]} members, params[{pnames[0]!r}] has {K}: one common length K is required")
-    IN_NAMES = SAT_NAMES if satur else B.IN_NAMES
-    names = set(inputs.keys()) if hasattr(inputs, "keys") else None
-    if satur and names is not None and "qsat" in names:
-        raise ValueError("satur=True: SATUR is evaluated and differentiated inside the op, inputs must not have a 'qsat'")
-    if names is None or names != set(IN_NAMES):
-        raise ValueError(f"inputs must map exactly the names {IN_NAMES}; got {sorted(names) if names is not None else type(inputs)}")
+    IN_NAMES = _check_names(inputs, satur)
     member0 = {}
     for n in IN_NAMES:
         t = inputs[n]
@@ -1334,22 +1223,6 @@ def check_ensemble(inputs, prm: B.Params, ngptot: int | None = None, satur: bool
                              f"got shape {tuple(t.shape)}")
         member0[n] = t
     return check_layout(member0, prm, ngptot, satur=satur), K, pnames
-
-
-def _member0(t: torch.Tensor) -> torch.Tensor:
-    return t[0] if t.dim() == 4 else t
-
-
-def _normalize_ens(ts: dict, lay: Layout, groups: dict) -> dict:
-    """:func:`normalize` for tensors that are 3-D (shared) or 4-D (one per member): the launchers take one block stride per layout
-    group and any member stride per field"""
-    out = dict(ts)
-    for g, names in groups.items():
-        want = lay.nlev * lay.nproma if g == "full" else (lay.nlev + 1) * lay.nproma if g == "half" else None
-        if not _group_fits({n: _member0(out[n]) for n in names}, lay, names, want):
-            for n in names:
-                out[n] = out[n].contiguous()
-    return out
 
 
 def _ens_block(kind: str, ts: dict, lay: Layout, K: int):
@@ -1379,11 +1252,8 @@ def _table(t: torch.Tensor) -> torch.Tensor:
     return _raw(t).detach().contiguous()
 
 
-def _refuse_batched_ens(ts) -> None:
-    if any(_batched_inside(t) for t in ts):
-        raise NotImplementedError(_NO_VMAP_ENS)
-
-
+@_no_vmap(_NO_VMAP_ENS)
+@_inner(raises=_NO_SECOND_ENS)
 class _Cloudsc2EnsTl(torch.autograd.Function):
     """forward(prm, ptsphy, layout, satur, K, (K, 4) parameters, (K, 4) parameter tangents, *n trajectory inputs, *n tangents) -> 10
     output tangents ``(K, ...)``: ``cloudsc2_tl_launch_ens``.  Inputs and tangents are 3-D (shared) or 4-D.  Differentiating it again
@@ -1396,7 +1266,7 @@ class _Cloudsc2EnsTl(torch.autograd.Function):
         x = dict(zip(names, ts[:n]))
         like = x["pap"]
         dev = like.device
-        dx = _normalize_ens(dict(zip(names, ts[n:])), lay, groups)
+        dx = normalize(dict(zip(names, ts[n:])), lay, groups)
         dy = _new(B.OUT_NAMES, lay, like, batch=K)
         ptab, dptab = _table(ptab), _table(dptab)
         work = _ens_workspace(K, lay, dev)
@@ -1406,23 +1276,9 @@ class _Cloudsc2EnsTl(torch.autograd.Function):
                                                  _ptr(dptab), C.byref(xb), xm, C.byref(db), dm, C.byref(yb), ym, _ptr(work), _stream(dev)))
         return tuple(dy[k] for k in B.OUT_NAMES)
 
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        pass
 
-    @staticmethod
-    def backward(ctx, *grads):
-        raise NotImplementedError(_NO_SECOND_ENS)
-
-    @staticmethod
-    def jvp(ctx, *tangents):
-        raise NotImplementedError(_NO_SECOND_ENS)
-
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP_ENS)
-
-
+@_no_vmap(_NO_VMAP_ENS)
+@_inner(raises=_NO_SECOND_ENS)
 class _Cloudsc2EnsVjp(torch.autograd.Function):
     """forward(prm, ptsphy, layout, satur, K, (K, 4) parameters, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output
     adjoints) -> n input adjoints ``(K, ...)`` and the ``(K, 4)`` parameter adjoints: ``cloudsc2_vjp_launch_ens``.  Differentiating it
@@ -1431,12 +1287,10 @@ class _Cloudsc2EnsVjp(torch.autograd.Function):
     @staticmethod
     def forward(prm, ptsphy, lay, satur, K, ptab, *ts):
         names, _ = _names(satur)
-        n = len(names)
-        x = dict(zip(names, ts[:n]))
-        fplsl, fplsn, scratch = ts[n:n + 3]
+        x, fplsl, fplsn, scratch, ys = _split(names, ts)
         like = x["pap"]
         dev = like.device
-        y = _normalize_ens(dict(zip(B.OUT_NAMES, ts[n + 3:])), lay, OUT_GROUPS)
+        y = normalize(dict(zip(B.OUT_NAMES, ys)), lay, OUT_GROUPS)
         xa = _new(names, lay, like, batch=K)
         ptab = _table(ptab)
         work = _ens_workspace(K, lay, dev)
@@ -1450,23 +1304,8 @@ class _Cloudsc2EnsVjp(torch.autograd.Function):
                                                   sc.stride(0) if sc.dim() == 4 and K > 1 else 0, _ptr(work), _ptr(par_adj), _stream(dev)))
         return tuple(xa[k] for k in names) + (par_adj,)
 
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        pass
 
-    @staticmethod
-    def backward(ctx, *grads):
-        raise NotImplementedError(_NO_SECOND_ENS)
-
-    @staticmethod
-    def jvp(ctx, *tangents):
-        raise NotImplementedError(_NO_SECOND_ENS)
-
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP_ENS)
-
-
+@_no_vmap(_NO_VMAP_ENS)
 class _Cloudsc2Ens(torch.autograd.Function):
     # forward(prm, ptsphy, layout, satur, K, the (K, 4) parameter table, *n inputs, 3-D or 4-D) -> 10 outputs (K, ...) + the members'
     # cover-checkpoint scratch: cloudsc2_nl_launch_ens.  prm holds the values of the parameters that are not given; the table is a device
@@ -1493,16 +1332,11 @@ class _Cloudsc2Ens(torch.autograd.Function):
     @staticmethod
     def setup_context(ctx, inputs, output):
         prm, ptsphy, lay, satur, K, ptab, *xs = inputs
-        out = dict(zip(B.OUT_NAMES, output[:-1]))
-        scratch = output[-1]
-        ctx.mark_non_differentiable(scratch)
-        ctx.save_for_backward(ptab, *xs, out["fplsl"], out["fplsn"], scratch)
-        ctx.save_for_forward(ptab, *xs)
-        ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.K = prm, ptsphy, lay, satur, K
+        _save_trajectory(ctx, xs, output[FPLSL], output[FPLSN], output[-1], table=ptab, prm=prm, ptsphy=ptsphy, lay=lay, satur=satur, K=K)
 
     @staticmethod
     def backward(ctx, *grads):
-        _refuse_batched_ens(grads)
+        _refuse_batched(grads, _NO_VMAP_ENS)
         ptab, *saved = ctx.saved_tensors
         lay, like = ctx.lay, saved[0]
         need_p, need_x = ctx.needs_input_grad[5], ctx.needs_input_grad[6:]
@@ -1516,17 +1350,13 @@ class _Cloudsc2Ens(torch.autograd.Function):
 
     @staticmethod
     def jvp(ctx, *tangents):
-        _refuse_batched_ens(tangents)
+        _refuse_batched(tangents, _NO_VMAP_ENS)
         names, _ = _names(ctx.satur)
         ptab, *xs = ctx.saved_tensors
         dptab = tangents[5] if tangents[5] is not None else torch.zeros_like(ptab)
         dx = _zero_filled(names, tangents[6:], ctx.lay, xs[0])  # (no tangent: one shared zero plane)
         dy = _Cloudsc2EnsTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.K, ptab, dptab, *xs, *(dx[n] for n in names))
         return tuple(dy) + (None,)
-
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP_ENS)
 
 
 def cloudsc2_ensemble(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None) -> Cloudsc2Outputs:
@@ -1554,11 +1384,9 @@ def cloudsc2_ensemble(inputs, prm: B.Params, ptsphy: float, ngptot: int | None =
     bit what ``cloudsc2(inputs_k, prm, ptsphy, ngptot, satur=..., params={the four 0-d values of row k})`` gives forward, in
     ``backward`` and in ``jvp``.  The gradient of a shared input is the members' sum (``xa.sum(0)``): equal to the sum of those
     calls' gradients up to the order of summation, not to the bit."""
-    names, groups = _names(satur)
-    lay, K, pnames = check_ensemble(inputs, prm, ngptot, satur, params)
-    dev = check_device(inputs[n] for n in names)
+    names, groups, (lay, K, pnames), dev = _enter(inputs, prm, ngptot, satur, check_ensemble, params)
     ps = tuple(params[n] for n in pnames)
-    _refuse_batched_ens(ps + tuple(inputs[n] for n in names))
+    _refuse_batched(ps + tuple(inputs[n] for n in names), _NO_VMAP_ENS)
     for n, p in zip(pnames, ps):
         if p.device != dev:
             raise ValueError(f"params[{n!r}] is on {p.device}: the parameters of an ensemble live on the inputs' device {dev} (they are read there)")
@@ -1568,9 +1396,7 @@ def cloudsc2_ensemble(inputs, prm: B.Params, ptsphy: float, ngptot: int | None =
     given = dict(zip(pnames, ps))
     ptab = torch.stack([given[n] if n in given else torch.full((K,), float(getattr(prm, n)), dtype=torch.float64, device=dev)
                         for n in PARAM_NAMES], dim=1)
-    x = _normalize_ens({n: inputs[n] for n in names}, lay, groups)
-    out = _Cloudsc2Ens.apply(prm, float(ptsphy), lay, bool(satur), K, ptab, *(x[n] for n in names))
-    return Cloudsc2Outputs(*out[:10])
+    return Cloudsc2Outputs(*_apply(_Cloudsc2Ens, (prm, float(ptsphy), lay, bool(satur), K, ptab), inputs, names, groups, lay)[:10])
 
 
 # ---- cloudsc2_column_sums: per-column weighted level sums of the outputs, formed in the sweeps ------------------------------------------
@@ -1614,11 +1440,6 @@ def check_column_sums(inputs, prm: B.Params, ngptot: int | None = None, satur: b
     return lay, wnames
 
 
-def _refuse_batched_colsum(ts) -> None:
-    if any(_batched_inside(t) for t in ts):
-        raise NotImplementedError(_NO_VMAP_COLSUM)
-
-
 def _new_sums(names, lay: Layout, like: torch.Tensor) -> dict:
     """fresh contiguous (nblocks, nproma) arrays, padded tail zeroed (that slice only)"""
     out = {}
@@ -1641,6 +1462,8 @@ def _sums_block(ts: dict, lay: Layout):
     return blk
 
 
+@_no_vmap(_NO_VMAP_COLSUM)
+@_inner(raises=_NO_SECOND_COLSUM)
 class _Cloudsc2ColsumTl(torch.autograd.Function):
     """forward(prm, ptsphy, layout, satur, names, table, *n trajectory inputs, *n tangents or None) -> the sums of the output tangents
     named: ``cloudsc2_tl_launch_colsum``; a None tangent is a zero tangent that is not read.  Differentiating it again raises
@@ -1661,23 +1484,9 @@ class _Cloudsc2ColsumTl(torch.autograd.Function):
                                                     C.byref(_sums_block(dy, lay)), _stream(dev)))
         return tuple(dy[k] for k in wnames)
 
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        pass
 
-    @staticmethod
-    def backward(ctx, *grads):
-        raise NotImplementedError(_NO_SECOND_COLSUM)
-
-    @staticmethod
-    def jvp(ctx, *tangents):
-        raise NotImplementedError(_NO_SECOND_COLSUM)
-
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP_COLSUM)
-
-
+@_no_vmap(_NO_VMAP_COLSUM)
+@_inner(raises=_NO_SECOND_COLSUM)
 class _Cloudsc2ColsumVjp(torch.autograd.Function):
     """forward(prm, ptsphy, layout, satur, want, names, table, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *the cotangents of
     the sums named or None) -> the input adjoints named in ``want``, in that order: ``cloudsc2_vjp_launch_colsum``; a None cotangent
@@ -1686,38 +1495,20 @@ class _Cloudsc2ColsumVjp(torch.autograd.Function):
     @staticmethod
     def forward(prm, ptsphy, lay, satur, want, wnames, table, *ts):
         names, _ = _names(satur)
-        n = len(names)
-        x = dict(zip(names, ts[:n]))
-        fplsl, fplsn, scratch = ts[n:n + 3]
+        x, fplsl, fplsn, scratch, ys = _split(names, ts)
         like = x["pap"]
         dev = like.device
-        y = {k: t.contiguous() for k, t in _present(wnames, ts[n + 3:]).items()}
+        y = {k: t.contiguous() for k, t in _present(wnames, ys).items()}
         xa = _new(want, lay, like)
-        traj_out = B.Outputs()
-        traj_out.fplsl, traj_out.fplsn = _field(fplsl, lay, "fplsl"), _field(fplsn, lay, "fplsn")
         with torch.cuda.device(dev):
             B.check(B.lib.cloudsc2_vjp_launch_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur),
-                                                     C.byref(_block("in", x, lay)), C.byref(traj_out), C.byref(_block("in", xa, lay)),
-                                                     _ptr(table), C.byref(_sums_block(y, lay)), _scratch_ptr(scratch), _stream(dev)))
+                                                     C.byref(_block("in", x, lay)), C.byref(_traj_out(fplsl, fplsn, lay)),
+                                                     C.byref(_block("in", xa, lay)), _ptr(table), C.byref(_sums_block(y, lay)),
+                                                     _scratch_ptr(scratch), _stream(dev)))
         return tuple(xa[k] for k in want)
 
-    @staticmethod
-    def setup_context(ctx, inputs, output):
-        pass
 
-    @staticmethod
-    def backward(ctx, *grads):
-        raise NotImplementedError(_NO_SECOND_COLSUM)
-
-    @staticmethod
-    def jvp(ctx, *tangents):
-        raise NotImplementedError(_NO_SECOND_COLSUM)
-
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP_COLSUM)
-
-
+@_no_vmap(_NO_VMAP_COLSUM)
 class _Cloudsc2Colsum(torch.autograd.Function):
     # forward(prm, ptsphy, layout, satur, names, keep, table, *n inputs) -> the sums named + PFPLSL5, PFPLSN5 and the cover-checkpoint
     # scratch (all three empty without `keep`): one cloudsc2_nl_launch_colsum.  keep: the call tracks gradients, so the forward keeps what
@@ -1747,12 +1538,8 @@ class _Cloudsc2Colsum(torch.autograd.Function):
     @staticmethod
     def setup_context(ctx, inputs, output):
         prm, ptsphy, lay, satur, wnames, keep, table, *xs = inputs
-        fplsl, fplsn, scratch = output[-3:]
-        ctx.mark_non_differentiable(fplsl, fplsn, scratch)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(table, *xs, fplsl, fplsn, scratch)
-        ctx.save_for_forward(table, *xs)
-        ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.wnames, ctx.keep = prm, ptsphy, lay, satur, wnames, keep
+        _save_trajectory(ctx, xs, *output[-3:], table=table, fluxes_are_outputs=False, materialize=False, prm=prm, ptsphy=ptsphy, lay=lay,
+                         satur=satur, wnames=wnames, keep=keep)
 
     @staticmethod
     def backward(ctx, *grads):
@@ -1762,7 +1549,7 @@ class _Cloudsc2Colsum(torch.autograd.Function):
         nothing = (None,) * (7 + len(names))
         if not any(need) or all(g is None for g in ys):
             return nothing
-        _refuse_batched_colsum(ys)
+        _refuse_batched(ys, _NO_VMAP_COLSUM)
         if not ctx.keep:
             raise RuntimeError("cloudsc2_column_sums: backward of a forward that tracked no gradient (nothing was kept for the reverse sweep)")
         table, *saved = ctx.saved_tensors
@@ -1772,14 +1559,10 @@ class _Cloudsc2Colsum(torch.autograd.Function):
 
     @staticmethod
     def jvp(ctx, *tangents):
-        _refuse_batched_colsum(tangents)
+        _refuse_batched(tangents, _NO_VMAP_COLSUM)
         table, *xs = ctx.saved_tensors
         dy = _Cloudsc2ColsumTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.wnames, table, *xs, *tangents[7:])
         return tuple(dy) + (None, None, None)
-
-    @staticmethod
-    def vmap(info, in_dims, *args):
-        raise NotImplementedError(_NO_VMAP_COLSUM)
 
 
 def cloudsc2_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, weights=None,
@@ -1805,11 +1588,9 @@ def cloudsc2_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | Non
     that are wanted (``None`` elsewhere) and launches nothing without a cotangent; every gradient is the bits of
     ``cloudsc2(..., sparse=True)`` differentiated through the same fold written in torch.  ``torch.func.vmap`` / ``jacfwd`` /
     ``jacrev`` / ``is_grads_batched`` and double backward raise ``NotImplementedError``."""
-    names, groups = _names(satur)
-    lay, wnames = check_column_sums(inputs, prm, ngptot, satur, weights)
-    dev = check_device(inputs[n] for n in names)
+    names, groups, (lay, wnames), dev = _enter(inputs, prm, ngptot, satur, check_column_sums, weights)
     xs = tuple(inputs[n] for n in names)
-    _refuse_batched_colsum(xs + tuple(weights[n] for n in wnames))
+    _refuse_batched(xs + tuple(weights[n] for n in wnames), _NO_VMAP_COLSUM)
     _prepare(dev)
     like = inputs["pap"]
     with torch.no_grad():  # the table: ten rows of nlev + 1 in the order of OUT_NAMES, device ops only
@@ -1817,8 +1598,7 @@ def cloudsc2_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | Non
         for n in wnames:
             table[B.OUT_NAMES.index(n), :lay.nlevx(n)].copy_(weights[n])
     keep = torch.is_grad_enabled() and any(t.requires_grad for t in xs)
-    x = normalize({n: inputs[n] for n in names}, lay, groups)
-    out = dict(zip(wnames, _Cloudsc2Colsum.apply(prm, float(ptsphy), lay, bool(satur), wnames, bool(keep), table, *(x[n] for n in names))))
+    out = dict(zip(wnames, _apply(_Cloudsc2Colsum, (prm, float(ptsphy), lay, bool(satur), wnames, bool(keep), table), inputs, names, groups, lay)))
     return Cloudsc2Outputs(*(out.get(n) for n in B.OUT_NAMES))
 
 

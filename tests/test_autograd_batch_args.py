@@ -46,13 +46,13 @@ def test_nested_vmap_is_refused_before_any_launch():
     lay = ag.Layout(NB, NLEV, NPROMA, NB * NPROMA)
     x = state(lay, 1)
     prm = params()
-    f = lambda t: ag._Cloudsc2.apply(prm, 3600.0, lay, t, *x[1:])  # noqa: E731
+    f = lambda t: ag._Cloudsc2.apply(prm, 3600.0, lay, False, t, *x[1:])  # noqa: E731
     with pytest.raises(NotImplementedError, match="nested vmap"):
         torch.func.vmap(torch.func.vmap(f))(torch.zeros((2, 3) + lay.shape(B.IN_NAMES[0]), dtype=B.torch_real()))
     for fn, n_in, n_extra in ((ag._Cloudsc2Tl, 32, 0), (ag._Cloudsc2Vjp, 16, 3)):
         ops = list(x) + [torch.zeros(lay.shape("fplsl"), dtype=B.torch_real())] * 2 * (n_extra > 0) + [torch.zeros(0)] * (n_extra > 0)
         ops += [torch.zeros(lay.shape(n), dtype=B.torch_real()) for n in (B.IN_NAMES if n_extra == 0 else B.OUT_NAMES)]
-        g = lambda t: fn.apply(prm, 3600.0, lay, *ops[:-1], t)  # noqa: E731,B023
+        g = lambda t: fn.apply(prm, 3600.0, lay, False, *ops[:-1], t)  # noqa: E731,B023
         with pytest.raises(NotImplementedError, match="nested vmap"):
             torch.func.vmap(torch.func.vmap(g))(torch.zeros((2, 3) + tuple(ops[-1].shape), dtype=B.torch_real()))
 

@@ -47,21 +47,20 @@ def test_which_function_class_the_op_builds(monkeypatch, satur):
             calls.append((cls, args))
             return tuple(range(11))
         return apply
-    for cls in (ag._Cloudsc2, ag._Cloudsc2Satur, ag._Cloudsc2Sparse):
+    for cls in (ag._Cloudsc2, ag._Cloudsc2Sparse):
         monkeypatch.setattr(cls, "apply", recorder(cls))
     monkeypatch.setattr(ag, "check_device", lambda ts: torch.device("cpu"))
     monkeypatch.setattr(ag, "_prepare", lambda dev: None)
     x = inputs15() if satur else inputs()
     names = ag.SAT_NAMES if satur else B.IN_NAMES
     prm = params()
-    dense = ag._Cloudsc2Satur if satur else ag._Cloudsc2
     for kw in (dict(), dict(sparse=False)):
         calls.clear()
         out = ag.cloudsc2(x, prm, 3600.0, satur=satur, **kw)
         assert isinstance(out, ag.Cloudsc2Outputs) and tuple(out) == tuple(range(10))
         (cls, args), = calls
-        assert cls is dense and args[0] is prm and args[1] == 3600.0 and len(args) == 3 + len(names)
-        assert all(a is x[n] for a, n in zip(args[3:], names))
+        assert cls is ag._Cloudsc2 and args[0] is prm and args[1] == 3600.0 and args[3] is satur and len(args) == 4 + len(names)
+        assert all(a is x[n] for a, n in zip(args[4:], names))
     calls.clear()
     out = ag.cloudsc2(x, prm, 3600.0, satur=satur, sparse=True)
     assert tuple(out) == tuple(range(10))
