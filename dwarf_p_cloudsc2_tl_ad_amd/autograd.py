@@ -1385,8 +1385,15 @@ def cloudsc2_ensemble(inputs, prm: B.Params, ptsphy: float, ngptot: int | None =
     ``backward`` and in ``jvp``.  The gradient of a shared input is the members' sum (``xa.sum(0)``): equal to the sum of those
     calls' gradients up to the order of summation, not to the bit."""
     names, groups, (lay, K, pnames), dev = _enter(inputs, prm, ngptot, satur, check_ensemble, params)
+    ptab = _ens_table(inputs, names, prm, params, pnames, K, dev, _NO_VMAP_ENS)
+    return Cloudsc2Outputs(*_apply(_Cloudsc2Ens, (prm, float(ptsphy), lay, bool(satur), K, ptab), inputs, names, groups, lay)[:10])
+
+
+def _ens_table(inputs, names, prm: B.Params, params, pnames, K: int, dev: torch.device, no_vmap: str, more=()) -> torch.Tensor:
+    """What the ensemble entry points do between their checks and their Function: the refusals that need the device's name, the device
+    prepared, and the ``(K, 4)`` parameter table assembled with torch ops (a name not given: ``prm``'s value in every member)"""
     ps = tuple(params[n] for n in pnames)
-    _refuse_batched(ps + tuple(inputs[n] for n in names), _NO_VMAP_ENS)
+    _refuse_batched(ps + tuple(inputs[n] for n in names) + tuple(more), no_vmap)
     for n, p in zip(pnames, ps):
         if p.device != dev:
             raise ValueError(f"params[{n!r}] is on {p.device}: the parameters of an ensemble live on the inputs' device {dev} (they are read there)")
@@ -1394,9 +1401,8 @@ def cloudsc2_ensemble(inputs, prm: B.Params, ptsphy: float, ngptot: int | None =
         raise ValueError("cloudsc2_ensemble with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
     _prepare(dev)
     given = dict(zip(pnames, ps))
-    ptab = torch.stack([given[n] if n in given else torch.full((K,), float(getattr(prm, n)), dtype=torch.float64, device=dev)
+    return torch.stack([given[n] if n in given else torch.full((K,), float(getattr(prm, n)), dtype=torch.float64, device=dev)
                         for n in PARAM_NAMES], dim=1)
-    return Cloudsc2Outputs(*_apply(_Cloudsc2Ens, (prm, float(ptsphy), lay, bool(satur), K, ptab), inputs, names, groups, lay)[:10])
 
 
 # ---- cloudsc2_column_sums: per-column weighted level sums of the outputs, formed in the sweeps ------------------------------------------
@@ -1413,6 +1419,12 @@ def check_column_sums(inputs, prm: B.Params, ngptot: int | None = None, satur: b
     """Every check of :func:`cloudsc2_column_sums` that needs no device; returns ``(layout, the given names in OUT_NAMES order)``.
     Runs on CPU or meta tensors; raises ``ValueError``."""
     lay = check_layout(inputs, prm, ngptot, satur=bool(satur))
+    return lay, check_weights(weights, lay, inputs["pap"].device)
+
+
+def check_weights(weights, lay: Layout, dev: torch.device) -> tuple:
+    """The checks of the ``weights`` of the column-sum ops for a layout and the inputs' device; returns the given names in OUT_NAMES
+    order.  Raises ``ValueError``."""
     if not hasattr(weights, "keys"):
         raise ValueError(f"weights must map names of {B.OUT_NAMES} to 1-D tensors of per-level weights; got {type(weights)}")
     if len(weights.keys()) == 0:
@@ -1420,7 +1432,7 @@ def check_column_sums(inputs, prm: B.Params, ngptot: int | None = None, satur: b
     unknown = sorted((k for k in weights.keys() if k not in B.OUT_NAMES), key=str)
     if unknown:
         raise ValueError(f"weights: unknown name(s) {unknown}; the outputs are {B.OUT_NAMES}")
-    dtype, dev = B.torch_real(), inputs["pap"].device
+    dtype = B.torch_real()
     wnames = tuple(n for n in B.OUT_NAMES if n in weights.keys())
     for n in wnames:
         w = weights[n]
@@ -1437,18 +1449,27 @@ def check_column_sums(inputs, prm: B.Params, ngptot: int | None = None, satur: b
                              "output plane, which this op exists not to form); detach it")
         if w.device != dev:
             raise ValueError(f"weights[{n!r}] is on {w.device}: the weights live on the inputs' device {dev}")
-    return lay, wnames
+    return wnames
 
 
-def _new_sums(names, lay: Layout, like: torch.Tensor) -> dict:
-    """fresh contiguous (nblocks, nproma) arrays, padded tail zeroed (that slice only)"""
+def _new_sums(names, lay: Layout, like: torch.Tensor, batch: int | None = None) -> dict:
+    """fresh contiguous (nblocks, nproma) arrays, padded tail zeroed (that slice only); batch: ``(batch, nblocks, nproma)``"""
     out = {}
     for n in names:
-        t = torch.empty((lay.nblocks, lay.nproma), dtype=like.dtype, device=like.device)
+        t = torch.empty(((batch,) if batch is not None else ()) + (lay.nblocks, lay.nproma), dtype=like.dtype, device=like.device)
         if lay.tail < lay.nproma:
-            t[-1, lay.tail:] = 0
+            t[..., -1, lay.tail:] = 0
         out[n] = t
     return out
+
+
+def _weight_table(weights, wnames, lay: Layout, like: torch.Tensor) -> torch.Tensor:
+    """the launchers' table: ten rows of nlev + 1 in the order of OUT_NAMES, device ops only"""
+    with torch.no_grad():
+        table = torch.zeros((len(B.OUT_NAMES), lay.nlev + 1), dtype=like.dtype, device=like.device)
+        for n in wnames:
+            table[B.OUT_NAMES.index(n), :lay.nlevx(n)].copy_(weights[n])
+    return table
 
 
 def _sums_block(ts: dict, lay: Layout):
@@ -1592,13 +1613,191 @@ def cloudsc2_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | Non
     xs = tuple(inputs[n] for n in names)
     _refuse_batched(xs + tuple(weights[n] for n in wnames), _NO_VMAP_COLSUM)
     _prepare(dev)
-    like = inputs["pap"]
-    with torch.no_grad():  # the table: ten rows of nlev + 1 in the order of OUT_NAMES, device ops only
-        table = torch.zeros((len(B.OUT_NAMES), lay.nlev + 1), dtype=like.dtype, device=dev)
-        for n in wnames:
-            table[B.OUT_NAMES.index(n), :lay.nlevx(n)].copy_(weights[n])
+    table = _weight_table(weights, wnames, lay, inputs["pap"])
     keep = torch.is_grad_enabled() and any(t.requires_grad for t in xs)
     out = dict(zip(wnames, _apply(_Cloudsc2Colsum, (prm, float(ptsphy), lay, bool(satur), wnames, bool(keep), table), inputs, names, groups, lay)))
+    return Cloudsc2Outputs(*(out.get(n) for n in B.OUT_NAMES))
+
+
+# ---- cloudsc2_ensemble_column_sums: the column sums of K members in one launch, no output plane -------------------------------------
+
+_NO_VMAP_ENSCOLSUM = ("cloudsc2_ensemble_column_sums: torch.func.vmap, jacfwd, jacrev and is_grads_batched=True are not supported (the "
+                      "ensemble is the batch: give the members' parameters as (K,) tensors and per-member states as 4-D inputs); use "
+                      ".backward() / torch.autograd.grad / torch.func.grad / torch.func.vjp, or torch.autograd.forward_ad / torch.func.jvp")
+
+_NO_SECOND_ENSCOLSUM = ("cloudsc2_ensemble_column_sums: double backward (and forward-over-reverse, reverse-over-forward) is not supported: "
+                        "the sweeps are first-order derivatives of CLOUDSC2")
+
+
+def check_ensemble_column_sums(inputs, prm: B.Params, ngptot: int | None = None, satur: bool = False, params=None, weights=None) -> tuple:
+    """Every check of :func:`cloudsc2_ensemble_column_sums` that needs no device: :func:`check_ensemble`, then the weight checks of
+    :func:`check_column_sums`; returns ``(layout, K, the given parameter names, the given weight names)``.  Raises ``ValueError``."""
+    lay, K, pnames = check_ensemble(inputs, prm, ngptot, satur, params)
+    return lay, K, pnames, check_weights(weights, lay, inputs["pap"].device)
+
+
+def _ens_sums_block(ts: dict, lay: Layout, K: int):
+    """contiguous (K, nblocks, nproma) tensors by name -> member 0's block of sums and the member strides"""
+    ms = (C.c_longlong * len(B.OUT_NAMES))()
+    for n, t in ts.items():
+        ms[B.OUT_NAMES.index(n)] = _raw(t).stride(0) if K > 1 else 0
+    return _sums_block({n: _raw(t)[0] for n, t in ts.items()}, lay), ms
+
+
+def _mstride(t: torch.Tensor, K: int) -> int:
+    t = _raw(t)
+    return t.stride(0) if t.dim() == 4 and K > 1 else 0
+
+
+@_no_vmap(_NO_VMAP_ENSCOLSUM)
+@_inner(raises=_NO_SECOND_ENSCOLSUM)
+class _Cloudsc2EnsColsumTl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, K, names, table, (K, 4) parameters, (K, 4) parameter tangents, *n trajectory inputs, *n
+    tangents or None) -> the ``(K, nblocks, nproma)`` sums of the output tangents named: ``cloudsc2_tl_launch_ens_colsum``; a None
+    tangent is a zero tangent that is not read.  Differentiating it again raises ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, K, wnames, table, ptab, dptab, *ts):
+        names, groups = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        like = x["pap"]
+        dev = like.device
+        dx = _normalize_present(_present(names, ts[n:]), lay, groups)
+        dy = _new_sums(wnames, lay, like, batch=K)
+        ptab, dptab = _table(ptab), _table(dptab)
+        work = _ens_workspace(K, lay, dev)
+        (xb, xm), (db, dm), (yb, ym) = _ens_block("in", x, lay, K), _ens_block("in", dx, lay, K), _ens_sums_block(dy, lay, K)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch_ens_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur), K,
+                                                        _ptr(ptab), _ptr(dptab), C.byref(xb), xm, C.byref(db), dm, _ptr(table),
+                                                        C.byref(yb), ym, _ptr(work), _stream(dev)))
+        return tuple(dy[k] for k in wnames)
+
+
+@_no_vmap(_NO_VMAP_ENSCOLSUM)
+@_inner(raises=_NO_SECOND_ENSCOLSUM)
+class _Cloudsc2EnsColsumVjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, K, want, names, table, (K, 4) parameters, *n trajectory inputs, PFPLSL5, PFPLSN5, cover
+    scratch, *the cotangents of the sums named or None) -> the ``(K, ...)`` input adjoints named in ``want`` (possibly none: no plane is
+    allocated or written) and the ``(K, 4)`` parameter adjoints: ``cloudsc2_vjp_launch_ens_colsum``.  Differentiating it again raises
+    ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, K, want, wnames, table, ptab, *ts):
+        names, _ = _names(satur)
+        x, fplsl, fplsn, scratch, ys = _split(names, ts)
+        like = x["pap"]
+        dev = like.device
+        y = {k: t.contiguous() for k, t in _present(wnames, ys).items()}
+        xa = _new(want, lay, like, batch=K)
+        ptab = _table(ptab)
+        work = _ens_workspace(K, lay, dev)
+        par_adj = torch.empty((K, len(PARAM_NAMES)), dtype=torch.float64, device=dev)
+        (xb, xm), (ab, am), (yb, ym) = _ens_block("in", x, lay, K), _ens_block("in", xa, lay, K), _ens_sums_block(y, lay, K)
+        tb, tm = _ens_block("out", {"fplsl": fplsl, "fplsn": fplsn}, lay, K)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch_ens_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur), K,
+                                                         _ptr(ptab), C.byref(xb), xm, C.byref(tb), tm, C.byref(ab), am, _ptr(table),
+                                                         C.byref(yb), ym, _scratch_ptr(scratch), _mstride(scratch, K), _ptr(work),
+                                                         _ptr(par_adj), _stream(dev)))
+        return tuple(xa[k] for k in want) + (par_adj,)
+
+
+@_no_vmap(_NO_VMAP_ENSCOLSUM)
+class _Cloudsc2EnsColsum(torch.autograd.Function):
+    # forward(prm, ptsphy, layout, satur, K, names, keep, table, the (K, 4) parameter table, *n inputs, 3-D or 4-D) -> the (K, nblocks,
+    # nproma) sums named + the members' PFPLSL5, PFPLSN5 and cover-checkpoint scratch (all three empty without `keep`): one
+    # cloudsc2_nl_launch_ens_colsum.  backward: one cloudsc2_vjp_launch_ens_colsum, which allocates the field gradients wanted and nothing
+    # else; jvp: one cloudsc2_tl_launch_ens_colsum.  Gradients are not materialised: a sum that took no part in the loss is a None cotangent.
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, K, wnames, keep, table, ptab, *xs):
+        names, _ = _names(satur)
+        x = dict(zip(names, xs))
+        like = x["pap"]
+        dev = like.device
+        sums = _new_sums(wnames, lay, like, batch=K)
+        none = torch.empty((0,), dtype=like.dtype, device=dev)
+        kept, keep_blk, keep_ms, scratch = {"fplsl": none, "fplsn": none}, None, None, none
+        if keep:
+            kept = _new(("fplsl", "fplsn"), lay, like, batch=K)
+            kb, keep_ms = _ens_block("out", kept, lay, K)
+            keep_blk = C.byref(kb)
+            if _evap(prm):
+                scratch = torch.empty((K, lay.nblocks, lay.nlev, lay.nproma), dtype=like.dtype, device=dev)
+        ptab = _table(ptab)
+        work = _ens_workspace(K, lay, dev)
+        (xb, xm), (sb, sm) = _ens_block("in", x, lay, K), _ens_sums_block(sums, lay, K)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_nl_launch_ens_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, K, _ptr(ptab),
+                                                        C.byref(xb), xm, _ptr(table), C.byref(sb), sm, keep_blk, keep_ms,
+                                                        _scratch_ptr(scratch), _mstride(scratch, K), _ptr(work), _stream(dev)))
+        return tuple(sums[k] for k in wnames) + (kept["fplsl"], kept["fplsn"], scratch)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        prm, ptsphy, lay, satur, K, wnames, keep, table, ptab, *xs = inputs
+        _save_trajectory(ctx, (ptab, *xs), *output[-3:], table=table, fluxes_are_outputs=False, materialize=False, prm=prm, ptsphy=ptsphy,
+                         lay=lay, satur=satur, K=K, wnames=wnames, keep=keep)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        names, _ = _names(ctx.satur)
+        need_p, need = ctx.needs_input_grad[8], ctx.needs_input_grad[9:]
+        ys = grads[:len(ctx.wnames)]
+        nothing = (None,) * (9 + len(names))
+        if (not need_p and not any(need)) or all(g is None for g in ys):
+            return nothing
+        _refuse_batched(ys, _NO_VMAP_ENSCOLSUM)
+        if not ctx.keep:
+            raise RuntimeError("cloudsc2_ensemble_column_sums: backward of a forward that tracked no gradient (nothing was kept for the "
+                               "reverse sweep)")
+        table, ptab, *saved = ctx.saved_tensors
+        want = tuple(n for n, nd in zip(names, need) if nd)
+        *xa, par_adj = _Cloudsc2EnsColsumVjp.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.K, want, ctx.wnames, table, ptab, *saved, *ys)
+        xa = dict(zip(want, xa))
+        # a per-member input gets its members' gradients, a shared one their sum
+        gx = tuple((xa[n] if x.dim() == 4 else xa[n].sum(0)) if n in xa else None for n, x in zip(names, saved))
+        return (None,) * 8 + (par_adj if need_p else None,) + gx
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        _refuse_batched(tangents, _NO_VMAP_ENSCOLSUM)
+        table, ptab, *xs = ctx.saved_tensors
+        dptab = tangents[8] if tangents[8] is not None else torch.zeros_like(ptab)
+        dy = _Cloudsc2EnsColsumTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ctx.K, ctx.wnames, table, ptab, dptab, *xs, *tangents[9:])
+        return tuple(dy) + (None, None, None)
+
+
+def cloudsc2_ensemble_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, weights=None, params=None,
+                                  satur: bool = False) -> Cloudsc2Outputs:
+    """The column sums of a perturbed-parameter ensemble in one launch: :func:`cloudsc2_ensemble` and :func:`cloudsc2_column_sums` at
+    once, which is what a calibration needs -- K members' surface precipitation or column-integrated tendencies and their gradient with
+    respect to the parameters -- without an output, cotangent or tangent plane for any member.
+
+    ``inputs``, ``params``, ``satur``, ``prm`` and ``ngptot`` are those of :func:`cloudsc2_ensemble` (3-D shared or 4-D per-member
+    inputs with any member stride; ``(K,)`` float64 parameters on the inputs' device, a name not given keeps ``prm``'s value; the same
+    refusals).  ``weights`` is that of :func:`cloudsc2_column_sums`, shared by all members.  Nothing is read on the host and nothing
+    synchronises: after one eager call the forward and ``torch.autograd.grad`` of it can be captured in ``torch.cuda.graph``, and a
+    replay after ``params[name].copy_(new)`` computes with the new values.
+
+    Returns a :class:`Cloudsc2Outputs` holding a ``(K, nblocks, nproma)`` tensor for every name of ``weights`` and ``None`` for the
+    others, the padded tail zero.  Member k of every sum is the bits of ``cloudsc2_column_sums`` for a ``prm`` holding row k.
+
+    ``.backward()``, ``torch.autograd.grad``, ``torch.func.grad`` / ``vjp`` / ``jvp`` and ``forward_ad`` differentiate with respect to
+    the ``(K,)`` parameters (gradient ``(K,)``, float64, on the device: the bits of ``cloudsc2(..., params=row k)`` differentiated
+    through the same fold written in torch) and the fields (a 4-D input gets per-member gradients, the bits of
+    ``cloudsc2_column_sums``'s; a 3-D shared input their sum over the members).  A call that tracks no gradient allocates no plane; one
+    that does keeps, per member, the two flux planes and (evaporation branch) the cover checkpoint.  Backward allocates the field
+    gradients that are wanted and nothing else: with only parameter gradients wanted it allocates no plane at all.
+    ``torch.func.vmap`` / ``jacfwd`` / ``jacrev`` / ``is_grads_batched`` and double backward raise ``NotImplementedError``."""
+    names, groups, (lay, K, pnames, wnames), dev = _enter(inputs, prm, ngptot, satur, check_ensemble_column_sums, params, weights)
+    ptab = _ens_table(inputs, names, prm, params, pnames, K, dev, _NO_VMAP_ENSCOLSUM, more=tuple(weights[n] for n in wnames))
+    table = _weight_table(weights, wnames, lay, inputs["pap"])
+    keep = torch.is_grad_enabled() and (ptab.requires_grad or any(inputs[n].requires_grad for n in names))
+    lead = (prm, float(ptsphy), lay, bool(satur), K, wnames, bool(keep), table, ptab)
+    out = dict(zip(wnames, _apply(_Cloudsc2EnsColsum, lead, inputs, names, groups, lay)))
     return Cloudsc2Outputs(*(out.get(n) for n in B.OUT_NAMES))
 
 

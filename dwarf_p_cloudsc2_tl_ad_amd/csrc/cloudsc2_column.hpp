@@ -145,6 +145,14 @@ C2_HD void ens_locate(unsigned wg, unsigned wgs_per_member, unsigned thread, uns
   member = wg / wgs_per_member;
   column = (long long)(wg - member * wgs_per_member) * block + thread;
 }
+// The NL column-sum sweep of an ensemble locates its workgroups itself (`wgs`: the grid).  Member-major like ens_locate.  The
+// member-interleaved order -- member = wg mod members, column = (wg / members) x block + thread, so that the members' re-reads of a shared
+// state meet in the Infinity Cache -- was measured: equal within the spread at 8 members, 7 % faster at 32, identical bits; it had to
+// win at both to be kept (profiles/EXPERIMENTS.md, "Ensemble column sums: workgroup order").
+C2_HD void ens_colsum_locate(unsigned wg, unsigned wgs_per_member, [[maybe_unused]] unsigned wgs, unsigned thread, unsigned block,
+                             unsigned& member, long long& column) {
+  ens_locate(wg, wgs_per_member, thread, block, member, column);
+}
 
 // Per-lane offsets of the column inside each layout group.  LaneOff: element offsets (64 bit).  LaneOff32: BYTE offsets
 // in 32 bits, usable when every buffer is smaller than 4 GiB (C2F_OFF32): the accesses then take the
@@ -448,7 +456,7 @@ enum : unsigned {
                      // TL: four parameter tangents add their source terms.  Reverse sweep: the lane sums its column's contributions
                      // in four doubles and stores them to the launch's workspace, which a second kernel folds in a fixed order
                      // (cloudsc2_tl_launch_par, cloudsc2_vjp_launch_par; kernels: cloudsc2_kern_{tl,vjp}_par.hip)
-  C2F_SPARSE = 512u, // TL (without TRAJ / SELFINC / PARLIN) and the VJP form of the reverse sweep (without PARLIN), each with QSAT or with
+  C2F_SPARSE = 512u, // TL (without TRAJ / SELFINC; with PARLIN only as C2F_MEMBER says) and the VJP form of the reverse sweep, each with QSAT or with
                      // SATLIN: only the planes of the launch's two bit masks are moved (struct SparseMasks below).  The argument block is
                      // TlSparseArgs / AdSparseArgs (cloudsc2_tl_launch_sparse, cloudsc2_vjp_launch_sparse; kernels:
                      // cloudsc2_kern_{tl,vjp}_sparse.hip).  Off in every other instantiation.
@@ -458,6 +466,12 @@ enum : unsigned {
                      // reverse sweep forms the cotangent of a level as weight x the column's sum cotangent.  The argument block is
                      // NlColsumArgs / TlColsumArgs / AdColsumArgs (cloudsc2_{nl,tl,vjp}_launch_colsum; kernels:
                      // cloudsc2_kern_{nl,tl,vjp}_colsum.hip).  Off in every other instantiation.
+  C2F_MEMBER = 2048u, // NL and TL with COLSUM: the column belongs to a member of an ensemble, so it is not the grid's global column; the lane
+                     // keeps it in an LDS slot for the store of the sums after the level loop (ColsumAcc).  The TL and the reverse sweep of
+                     // an ensemble's column sums are SPARSE | COLSUM | PARLIN: the parameter tangents add their source terms while absent
+                     // field tangents are opaque zeros; the parameter adjoints are summed while the gradient planes are stored under the
+                     // write mask, which may be empty.  The argument block is NlColsumArgs / TlEnsColsumArgs / AdEnsColsumArgs
+                     // (cloudsc2_{nl,tl,vjp}_launch_ens_colsum; kernels: cloudsc2_kern_{nl,tl,vjp}_ens_colsum.hip).
 };
 
 // ---------------------------------------------------------------------------------------------------------
@@ -589,6 +603,41 @@ struct TlColsumArgs {
 struct AdColsumArgs {
   AdSparseArgs a; ColsumTab cs;
 };
+// Column sums of an ensemble's members (C2F_MEMBER; cloudsc2_{nl,tl,vjp}_launch_ens_colsum): the column-sum blocks, the TL and the reverse
+// sweep's with the parameter derivative behind them (C2F_PARLIN with C2F_SPARSE | C2F_COLSUM: tl_column / ad_reverse_column step on to `par`
+// from the head of the block).  NL: NlColsumArgs itself.
+struct TlEnsColsumArgs {
+  TlColsumArgs a; ParLin par;
+};
+struct AdEnsColsumArgs {
+  AdColsumArgs a; ParLin par;
+  double* work;  // (PAR_COUNT, ncols_pad) doubles, as AdParArgs::work
+};
+typedef const C2_CONST_AS TlEnsColsumArgs* TlEnsColsumArgsP;
+typedef const C2_CONST_AS AdEnsColsumArgs* AdEnsColsumArgsP;
+// the sums (NL / TL: written, reverse sweep: the cotangents) advance by a member stride of their own, EnsStrides::out2 (no output tangent
+// or output adjoint plane exists to claim it); the kept flux planes and the cover checkpoint by ::out and ::ckpt as in the dense ensemble
+C2_HD void ens_advance(NlColsumArgs& a, const EnsStrides& m, long long member) {
+  ens_advance(a.a, m, member);
+  ens_advance_ptrs(a.cs.y, m.out2, member);
+}
+C2_HD void ens_advance(TlEnsColsumArgs& a, const EnsStrides& m, long long member) {
+  ens_advance_ptrs(a.a.a.a.in, m.in, member);
+  ens_advance_ptrs(a.a.a.a.din, m.in2, member);
+  ens_advance_ptrs(a.a.cs.y, m.out2, member);
+}
+C2_HD void ens_advance(AdEnsColsumArgs& a, const EnsStrides& m, long long member) {
+  ens_advance(a.a.a.a.nl, m, member);
+  ens_advance_ptrs(a.a.a.a.ain, m.in2, member);
+  ens_advance_ptrs(a.a.cs.y, m.out2, member);
+  a.work += member * (long long)PAR_COUNT * a.a.a.a.nl.g.ncols_pad;
+}
+C2_HD Consts& ens_consts_of(NlColsumArgs& a) { return a.a.c; }
+C2_HD Consts& ens_consts_of(TlEnsColsumArgs& a) { return a.a.a.a.c; }
+C2_HD Consts& ens_consts_of(AdEnsColsumArgs& a) { return a.a.a.a.nl.c; }
+C2_HD ParLin* ens_parlin_of(NlColsumArgs&) { return nullptr; }
+C2_HD ParLin* ens_parlin_of(TlEnsColsumArgs& a) { return &a.par; }
+C2_HD ParLin* ens_parlin_of(AdEnsColsumArgs& a) { return &a.par; }
 typedef const C2_CONST_AS ColsumTab* ColsumTabP;
 typedef const C2_CONST_AS real_t* ColsumRowP;
 constexpr int kColsumLanes = 128;  // the sweeps' workgroup size (kBlock, asserted in cloudsc2_sweep_kernels.hpp)
@@ -605,6 +654,16 @@ struct ColsumAcc {
   __device__ __forceinline__ long long column() const { return (long long)blockIdx.x * kColsumLanes + threadIdx.x; }
   __device__ __forceinline__ real_t get(int n) const { return s[n * kColsumLanes]; }
   __device__ __forceinline__ void set(int n, real_t v) { s[n * kColsumLanes] = v; }
+  // C2F_MEMBER: the column is a member's own, which blockIdx alone does not give: one more LDS slot per lane holds it through the loop
+  __device__ __forceinline__ long long& member_slot() const {
+    __shared__ long long cols[kColsumLanes];
+    return cols[threadIdx.x];
+  }
+  __device__ __forceinline__ void begin_member(long long column) {
+    begin(column);
+    member_slot() = column;
+  }
+  __device__ __forceinline__ long long member_column() const { return member_slot(); }
 #else
   real_t s[10];
   long long gcol;
@@ -613,6 +672,8 @@ struct ColsumAcc {
     for (int n = 0; n < 10; ++n) s[n] = RC(0.0);
   }
   long long column() const { return gcol; }
+  void begin_member(long long column) { begin(column); }
+  long long member_column() const { return gcol; }
   real_t get(int n) const { return s[n]; }
   void set(int n, real_t v) { s[n] = v; }
 #endif
@@ -764,6 +825,8 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
   // cover checkpoint.  It is scheduled as the plain NL sweep is unless it is the one-wave-per-SIMD EVAP form.
   constexpr bool COLSUM = (F & C2F_COLSUM) != 0;
   static_assert(!COLSUM || (LIN && !PERT), "C2F_COLSUM: the LPHYLIN form, never perturbed");
+  constexpr bool MEMBER = (F & C2F_MEMBER) != 0;  // (gcol is the column of an ensemble's member)
+  static_assert(!MEMBER || COLSUM, "C2F_MEMBER: the column sums of an ensemble's member");
   constexpr bool ONEWAVE = CKPT && (!COLSUM || EVAP);
   LaneOff o; bool active;
   if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
@@ -810,7 +873,8 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
 
   [[maybe_unused]] ColsumAcc acc;
   if constexpr (COLSUM) {
-    acc.begin(gcol);
+    if constexpr (MEMBER) acc.begin_member(gcol);
+    else acc.begin(gcol);
     if (CKPT) {  // the kept flux planes' top half level (store_top's zeros)
       out->fplsl[o.half] = RC(0.0);
       out->fplsn[o.half] = RC(0.0);
@@ -888,7 +952,7 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
   }
   if constexpr (COLSUM) {
     const ColsumTabP cs = &((const C2_CONST_AS NlColsumArgs*)a)->cs;
-    colsum_store(acc, cs, cs->mask, colsum_off(&a->g, cs, acc.column()));
+    colsum_store(acc, cs, cs->mask, colsum_off(&a->g, cs, MEMBER ? acc.member_column() : acc.column()));
   }
 }
 
@@ -1031,8 +1095,11 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   constexpr bool SELFINC = (F & C2F_SELFINC) != 0, SATLIN = (F & C2F_SATLIN) != 0, PARLIN = (F & C2F_PARLIN) != 0;
   constexpr bool SPARSE = (F & C2F_SPARSE) != 0, COLSUM = (F & C2F_COLSUM) != 0;
   static_assert(!COLSUM || SPARSE, "C2F_COLSUM: the sparse form's tangent loads (a is the head of a TlColsumArgs)");
+  // PARLIN with SPARSE: the column sums of an ensemble's member (a is the head of a TlEnsColsumArgs; gcol is the member's column)
+  constexpr bool MEMBER = (F & C2F_MEMBER) != 0;
+  static_assert(MEMBER == (SPARSE && PARLIN) && (!MEMBER || COLSUM), "C2F_MEMBER: SPARSE | COLSUM | PARLIN, and only there");
   static_assert(!SATLIN || (!HAS_QSAT && !STORE_TRAJ && !SELFINC), "C2F_SATLIN: SATUR fused, no trajectory stores, increments given");
-  static_assert(!SPARSE || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC && !PARLIN), "C2F_SPARSE: QSAT or SATLIN, no trajectory stores, increments given");
+  static_assert(!SPARSE || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC), "C2F_SPARSE: QSAT or SATLIN, no trajectory stores, increments given");
   static_assert(!PARLIN || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC), "C2F_PARLIN: QSAT or SATLIN, no trajectory stores, increments given");
   typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
   LaneOff o, op; bool active;
@@ -1062,7 +1129,8 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
 
   if (STORE_TRAJ) store_top(out, o, c);
   [[maybe_unused]] ColsumAcc acc;
-  if constexpr (COLSUM) acc.begin(gcol);  // (no tangent plane is stored: the flux tangents' top zeros contribute nothing to a sum)
+  if constexpr (MEMBER) acc.begin_member(gcol);
+  else if constexpr (COLSUM) acc.begin(gcol);  // (no tangent plane is stored: the flux tangents' top zeros contribute nothing to a sum)
   else if constexpr (SPARSE) store_top_sparse(dout, ((TlSparseArgsP)a)->m.wr, op, c);  // (a is the head of a TlSparseArgs)
   else store_top(dout, op, c);
 
@@ -1116,7 +1184,8 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
     LevelTraj tr;
     LevelOut lo, dlo;
     level_forward<P, EVAP>(c, k, rh, x, cy, tr, lo);
-    if constexpr (PARLIN) level_tl<true>(c, k, x, tr, dx, dcy, dlo, &((TlParArgsP)ap)->par);  // (a is the head of a TlParArgs)
+    if constexpr (MEMBER) level_tl<true>(c, k, x, tr, dx, dcy, dlo, &((TlEnsColsumArgsP)ap)->par);
+    else if constexpr (PARLIN) level_tl<true>(c, k, x, tr, dx, dcy, dlo, &((TlParArgsP)ap)->par);  // (a is the head of a TlParArgs)
     else level_tl(c, k, x, tr, dx, dcy, dlo);
     C2_LAUNDER(ap);
     out = &ap->out; dout = &ap->dout;
@@ -1139,7 +1208,7 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   }
   if constexpr (COLSUM) {
     const ColsumTabP cs = &((const C2_CONST_AS TlColsumArgs*)a)->cs;
-    colsum_store(acc, cs, ((TlSparseArgsP)a)->m.wr, colsum_off(&a->g, cs, acc.column()));
+    colsum_store(acc, cs, ((TlSparseArgsP)a)->m.wr, colsum_off(&a->g, cs, MEMBER ? acc.member_column() : acc.column()));
   }
 }
 
@@ -1276,8 +1345,11 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   static_assert(!ADNORM || ASSIGN, "the fused norms are those of the adjoint test: assign form");
   static_assert(!VJP || (ASSIGN && !ADNORM), "the vector-Jacobian product assigns its input adjoints and forms no norms");
   constexpr bool SPARSE = (F & C2F_SPARSE) != 0, COLSUM = (F & C2F_COLSUM) != 0;
-  static_assert(!SPARSE || (VJP && (HAS_QSAT != SATLIN) && !PARLIN), "C2F_SPARSE: the vector-Jacobian form, QSAT or SATLIN, no parameter adjoints");
+  static_assert(!SPARSE || (VJP && (HAS_QSAT != SATLIN)), "C2F_SPARSE: the vector-Jacobian form, QSAT or SATLIN");
   static_assert(!COLSUM || SPARSE, "C2F_COLSUM: the sparse form's gradient stores (a is the head of an AdColsumArgs)");
+  // PARLIN with SPARSE: the column sums of an ensemble's member (a is the head of an AdEnsColsumArgs); the write mask may be empty
+  constexpr bool MEMBER = SPARSE && PARLIN;
+  static_assert(!MEMBER || COLSUM, "parameter adjoints of a sparse reverse sweep: the column-sum form of an ensemble");
   typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
   LaneOff o, oa64; bool active;
   if (!lane_setup(&a->nl.g, &a->nl.s, gcol, o, active)) return 0.0;
@@ -1348,7 +1420,8 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     ya.fplsn = ya.fplsn - ya.fhpsn * c->rlstt;
     ya.fplsl = ya.fplsl - ya.fhpsl * c->rlvtt;
     LevelIn ax;
-    if constexpr (PARLIN) level_ad<true>(c, k, x, tr, ya, acy, ax, &((AdParArgsP)ap)->par, &pacc);  // (a is the head of an AdParArgs)
+    if constexpr (MEMBER) level_ad<true>(c, k, x, tr, ya, acy, ax, &((AdEnsColsumArgsP)ap)->par, &pacc);
+    else if constexpr (PARLIN) level_ad<true>(c, k, x, tr, ya, acy, ax, &((AdParArgsP)ap)->par, &pacc);  // (a is the head of an AdParArgs)
     else level_ad(c, k, x, tr, ya, acy, ax);
     if constexpr (SATLIN) {  // the adjoint of qsat goes to pap and t through SATUR's transpose; it has no plane of its own
       ax.pap += dqs_dpap * ax.qs;
@@ -1472,7 +1545,9 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     ain->paph[oa64.half + (long long)nlev * nproma] += surf_acc;
   }
   if constexpr (PARLIN) {  // the lane's four sums: consecutive lanes, consecutive doubles of each row (gcol < ncols_pad: lane_setup)
-    double* work = ((AdParArgsP)a)->work;
+    double* work;
+    if constexpr (MEMBER) work = ((AdEnsColsumArgsP)a)->work;
+    else work = ((AdParArgsP)a)->work;
     const long long np = a->nl.g.ncols_pad;
 #pragma unroll
     for (int i = 0; i < PAR_COUNT; ++i) work[i * np + gcol] = pacc.v[i];

@@ -29,6 +29,9 @@
 #include "cloudsc2_kern_nl_colsum.hip"
 #include "cloudsc2_kern_tl_colsum.hip"
 #include "cloudsc2_kern_vjp_colsum.hip"
+#include "cloudsc2_kern_nl_ens_colsum.hip"
+#include "cloudsc2_kern_tl_ens_colsum.hip"
+#include "cloudsc2_kern_vjp_ens_colsum.hip"
 #endif
 
 using namespace cloudsc2;
@@ -96,7 +99,8 @@ ens_args_kernel(Args tmpl, EnsStrides ms, double ptsphy, int members, const doub
   if (k >= members) return;
   ens_member_args(blocks[k], tmpl, ms, ptsphy, k, params + k * PAR_COUNT, dparams ? dparams + k * PAR_COUNT : nullptr);
 }
-static_assert(sizeof(AdParArgs) + sizeof(EnsStrides) + 64 <= 4096 && sizeof(TlParArgs) + sizeof(EnsStrides) + 64 <= 4096,
+static_assert(sizeof(AdParArgs) + sizeof(EnsStrides) + 64 <= 4096 && sizeof(TlParArgs) + sizeof(EnsStrides) + 64 <= 4096 &&
+                  sizeof(AdEnsColsumArgs) + sizeof(EnsStrides) + 64 <= 4096 && sizeof(TlEnsColsumArgs) + sizeof(EnsStrides) + 64 <= 4096,
               "ens_args_kernel's arguments fit the kernel-argument segment");
 
 // ---------------------------------------------------------------------------------------------------------
@@ -535,7 +539,11 @@ struct EnsSpec {
 const Geom& geom_of(const NlArgs& a) { return a.g; }
 const Geom& geom_of(const TlParArgs& a) { return a.a.g; }
 const Geom& geom_of(const AdParArgs& a) { return a.a.nl.g; }
-constexpr size_t kEnsBlockBytes = std::max({sizeof(NlArgs), sizeof(TlParArgs), sizeof(AdParArgs)});
+const Geom& geom_of(const NlColsumArgs& a) { return a.a.g; }
+const Geom& geom_of(const TlEnsColsumArgs& a) { return a.a.a.a.g; }
+const Geom& geom_of(const AdEnsColsumArgs& a) { return a.a.a.a.nl.g; }
+constexpr size_t kEnsBlockBytes = std::max({sizeof(NlArgs), sizeof(TlParArgs), sizeof(AdParArgs), sizeof(NlColsumArgs), sizeof(TlEnsColsumArgs),
+                                            sizeof(AdEnsColsumArgs)});
 size_t ens_blocks_bytes(int members) { return ((size_t)members * kEnsBlockBytes + 255) / 256 * 256; }
 
 // Two launches, neither paced nor logged: the members' argument blocks, then the sweep over members x ceil(ncols_pad / kBlock) workgroups.
@@ -759,10 +767,15 @@ int check_ens(const cloudsc2_params* prm, int satur, int members, const double* 
 // a block the members WRITE: with more than one member no field may be shared (member stride 0), the
 // members would write over each other; then the device check, as in check_par
 template <class Block>
-int check_ens_written(const Block* b, const long long* mstride, int members) {
+int check_ens_unshared(const Block* b, const long long* mstride, int members) {
   for (int i = 0; b && members > 1 && i < (int)(sizeof(Block) / sizeof(cloudsc2_field)); ++i)
     if (fields_of(*b)[i].ptr && (!mstride || mstride[i] == 0))
       return fail(CLOUDSC2_EINVAL, "ensemble: a field the members write has member stride 0 (every member needs its own)");
+  return 0;
+}
+template <class Block>
+int check_ens_written(const Block* b, const long long* mstride, int members) {
+  if (int rc = check_ens_unshared(b, mstride, members)) return rc;
   return require_device();
 }
 // the member strides of a launch's four blocks and its checkpoint plane (NULL: all members share the block's fields)
@@ -1126,7 +1139,7 @@ static int resolve_colsum(const cloudsc2_real* weights, const cloudsc2_outputs* 
 
 static int nl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* in,
                           const cloudsc2_real* weights, const cloudsc2_outputs* sums, const cloudsc2_outputs* keep,
-                          cloudsc2_real* scratch, void* stream) {
+                          cloudsc2_real* scratch, void* stream, const EnsSpec* ens = nullptr) {
   if (!prm || !in || !sums) return fail(CLOUDSC2_EINVAL, "NULL argument block");
   int rc = check_colsum_geom(prm, nproma, nlev, ngptot);
   if (rc) return rc;
@@ -1153,6 +1166,7 @@ static int nl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
   if (keep) w.f |= C2F_CKPT;
   cargs.a = w.nl();
   cargs.a.ckpt = (keep && w.c.evap) ? scratch : nullptr;
+  if (ens) return ens_launch(nl_ens_colsum_variant(w.f), cargs, ptsphy, *ens, (hipStream_t)stream);  // (neither paced nor kept abreast)
   const KernelFn<NlColsumArgs> fn = nl_colsum_variant(w.f);
   if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(cargs.a.g, (const void*)fn, !keep, nullptr);
@@ -1163,7 +1177,7 @@ static int nl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
 
 static int tl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
                           const cloudsc2_inputs* traj_in, const cloudsc2_inputs* pert_in, const cloudsc2_real* weights,
-                          const cloudsc2_outputs* pert_sums, void* stream) {
+                          const cloudsc2_outputs* pert_sums, void* stream, const EnsSpec* ens = nullptr) {
   if (!prm || !traj_in || !pert_in || !pert_sums) return fail(CLOUDSC2_EINVAL, "NULL argument block");
   int rc = check_colsum_geom(prm, nproma, nlev, ngptot);
   if (rc) return rc;
@@ -1185,6 +1199,12 @@ static int tl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
   if (satur) w.f |= C2F_SATLIN;
   args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.out = w.out; args.tab = w.tab;
   args.supsat_inc = 0; args.yy = nullptr;
+  if (ens) {  // the members' blocks: the parameter derivative behind the column-sum block (the template's tangents: every member's row replaces them)
+    TlEnsColsumArgs eargs;
+    eargs.a = cargs;
+    eargs.par = make_parlin(w.c, nullptr);
+    return ens_launch(tl_ens_colsum_variant(w.f), eargs, ptsphy, *ens, (hipStream_t)stream);
+  }
   const KernelFn<TlColsumArgs> fn = tl_colsum_variant(w.f);
   if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);  // (tl_launch_impl says why)
@@ -1197,7 +1217,7 @@ static int tl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
 static int vjp_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
                            const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, const cloudsc2_inputs* adj_in,
                            const cloudsc2_real* weights, const cloudsc2_outputs* adj_sums, const cloudsc2_real* scratch,
-                           void* stream) {
+                           void* stream, const EnsSpec* ens = nullptr) {
   if (!prm || !traj_in || !traj_out || !adj_in || !adj_sums) return fail(CLOUDSC2_EINVAL, "NULL argument block");
   int rc = check_colsum_geom(prm, nproma, nlev, ngptot);
   if (rc) return rc;
@@ -1217,7 +1237,8 @@ static int vjp_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma
   InPtrs ain_c;
   unsigned none_mask;
   if ((rc = resolve_sparse(*adj_in, none, 'i', args.sa, ain_c, args.aout, sargs.m.wr, none_mask))) return rc;
-  if (!sargs.m.wr) return fail(CLOUDSC2_EINVAL, "no gradient is wanted (every adj_in field is NULL)");
+  // (an ensemble's launch always has the parameter adjoints to form: its write mask may be empty)
+  if (!sargs.m.wr && !ens) return fail(CLOUDSC2_EINVAL, "no gradient is wanted (every adj_in field is NULL)");
   args.ain = writable(*adj_in);
   if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
   const Strides& sa = args.sa;
@@ -1226,6 +1247,25 @@ static int vjp_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma
   if (satur) w.f |= C2F_SATLIN;
   args.nl = w.nl();
   args.nl.ckpt = const_cast<cloudsc2_real*>(scratch);
+  if (ens) {  // the members' blocks, one (PAR_COUNT, ncols_pad) slab of sums each behind them in the workspace, then the fold per member
+    AdEnsColsumArgs eargs;
+    eargs.a = cargs;
+    eargs.par = make_parlin(w.c, nullptr);
+    eargs.work = (double*)((char*)ens->workspace + ens_blocks_bytes(ens->members));
+    if ((rc = ens_launch(vjp_ens_colsum_variant(w.f), eargs, ptsphy, *ens, (hipStream_t)stream))) return rc;
+    if (kEnsColsumFieldsPass && sargs.m.wr) {  // fp32: the field gradients once more, in the column-sum twin's bits, over the same blocks
+      const KernelFn<VjpEnsColsumKArgs> fields = vjp_ens_colsum_fields_variant(w.f);
+      if (!fields) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+      VjpEnsColsumKArgs ka;
+      ka.blocks = (const AdEnsColsumArgs*)ens->workspace; ka.wgs_per_member = grid_for(w.g.ncols_pad, kBlock);
+      void* argv[] = {&ka};
+      HIP_TRY(hipLaunchKernel((const void*)fields, dim3(ka.wgs_per_member * (unsigned)ens->members), dim3(kBlock), argv, 0, (hipStream_t)stream));
+    }
+    hipLaunchKernelGGL(par_fold_ens_kernel, dim3(PAR_COUNT, (unsigned)ens->members), dim3(kParFoldBlock), 0, (hipStream_t)stream,
+                       (const double*)eargs.work, w.g.ncols_pad, (long long)w.g.ngptot, ens->par_adj);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
   const KernelFn<AdColsumArgs> fn = vjp_colsum_variant(w.f);
   if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(args.nl.g, nullptr, false, (const void*)fn);
@@ -1328,6 +1368,58 @@ int cloudsc2_vjp_launch_ens(const cloudsc2_params* prm, double ptsphy, int nprom
   AdMode m{2, true, true, nullptr, nullptr, satur != 0, (double*)((char*)workspace + ens_blocks_bytes(members)), par_adj};
   m.ens = &e;
   return ad_launch_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, traj_out, adj_in, adj_out, const_cast<cloudsc2_real*>(scratch), stream, m);
+}
+
+// ---- column sums of an ensemble's members: the column-sum launchers for `members` members (C2F_MEMBER) ------------------------------------
+// check_ens and the written-field rule first, then the column-sum parent checks the call and builds the template block; ens_launch runs it.
+// The sums advance by EnsStrides::out2, the NL sweep's kept planes by ::out.
+static int check_ens_colsum(const cloudsc2_params* prm, int satur, int members, const double* params_dev, const void* workspace) {
+  if (!prm) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  return check_ens(prm, satur, members, params_dev, workspace);
+}
+
+int cloudsc2_nl_launch_ens_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int members,
+                                  const double* params_dev, const cloudsc2_inputs* in, const long long* in_mstride,
+                                  const cloudsc2_real* weights, const cloudsc2_outputs* sums, const long long* sums_mstride,
+                                  const cloudsc2_outputs* keep, const long long* keep_mstride, cloudsc2_real* scratch,
+                                  long long scratch_mstride, void* workspace, void* stream) {
+  const char* who = "cloudsc2_nl_launch_ens_colsum";
+  if (int rc = named(who, check_ens_colsum(prm, 0, members, params_dev, workspace))) return rc;
+  if (keep && scratch && members > 1 && scratch_mstride == 0)
+    return named(who, fail(CLOUDSC2_EINVAL, "ensemble: the cover-checkpoint plane has member stride 0"));
+  if (int rc = named(who, check_ens_unshared(sums, sums_mstride, members))) return rc;
+  if (int rc = named(who, check_ens_unshared(keep, keep_mstride, members))) return rc;
+  EnsSpec e = {members, params_dev, nullptr, ens_strides(in_mstride, keep ? keep_mstride : nullptr, nullptr, sums_mstride, scratch_mstride),
+               workspace, nullptr};
+  return named(who, nl_colsum_impl(prm, ptsphy, nproma, nlev, ngptot, in, weights, sums, keep, scratch, stream, &e));
+}
+
+int cloudsc2_tl_launch_ens_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
+                                  const double* params_dev, const double* dparams_dev, const cloudsc2_inputs* traj_in,
+                                  const long long* traj_in_mstride, const cloudsc2_inputs* pert_in, const long long* pert_in_mstride,
+                                  const cloudsc2_real* weights, const cloudsc2_outputs* pert_sums, const long long* sums_mstride,
+                                  void* workspace, void* stream) {
+  const char* who = "cloudsc2_tl_launch_ens_colsum";
+  if (int rc = named(who, check_ens_colsum(prm, satur, members, params_dev, workspace))) return rc;
+  if (int rc = named(who, check_ens_unshared(pert_sums, sums_mstride, members))) return rc;
+  if (!dparams_dev) return named(who, fail(CLOUDSC2_EINVAL, "NULL argument block"));
+  EnsSpec e = {members, params_dev, dparams_dev, ens_strides(traj_in_mstride, nullptr, pert_in_mstride, sums_mstride, 0), workspace, nullptr};
+  return named(who, tl_colsum_impl(prm, ptsphy, nproma, nlev, ngptot, satur, traj_in, pert_in, weights, pert_sums, stream, &e));
+}
+
+int cloudsc2_vjp_launch_ens_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
+                                   const double* params_dev, const cloudsc2_inputs* traj_in, const long long* traj_in_mstride,
+                                   const cloudsc2_outputs* traj_out, const long long* traj_out_mstride, const cloudsc2_inputs* adj_in,
+                                   const long long* adj_in_mstride, const cloudsc2_real* weights, const cloudsc2_outputs* adj_sums,
+                                   const long long* sums_mstride, const cloudsc2_real* scratch, long long scratch_mstride,
+                                   void* workspace, double* par_adj, void* stream) {
+  const char* who = "cloudsc2_vjp_launch_ens_colsum";
+  if (int rc = named(who, check_ens_colsum(prm, satur, members, params_dev, workspace))) return rc;
+  if (int rc = named(who, check_ens_unshared(adj_in, adj_in_mstride, members))) return rc;
+  if (!par_adj) return named(who, fail(CLOUDSC2_EINVAL, "the parameter adjoints' array is required"));
+  EnsSpec e = {members, params_dev, nullptr, ens_strides(traj_in_mstride, traj_out_mstride, adj_in_mstride, sums_mstride, scratch_mstride),
+               workspace, par_adj};
+  return named(who, vjp_colsum_impl(prm, ptsphy, nproma, nlev, ngptot, satur, traj_in, traj_out, adj_in, weights, adj_sums, scratch, stream, &e));
 }
 
 int cloudsc2_batch_max(void) { return kBatchMax; }

@@ -218,6 +218,56 @@ constexpr bool nl_ens_variant_valid(unsigned f) {
   return (f & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_CKPT | C2F_OFF32)) == 0 && ((f & C2F_CKPT) != 0) == ((f & C2F_EVAP) != 0);
 }
 
+// The column sums of an ensemble's members (C2F_MEMBER; units cloudsc2_kern_{nl,tl,vjp}_ens_colsum.hip): the column-sum sweeps over member
+// blocks in device memory, under their twins' launch bounds and with their twins' variant words (NL: nl_colsum_kernel's, TL / reverse
+// sweep: the sparse forms').  The TL and the reverse sweep carry the parameter derivative (C2F_PARLIN).  Not sweep families: no family
+// number, no pacing, no launch-log entry.  The NL family has a locate function of its own (ens_colsum_locate).
+typedef EnsArgs<NlColsumArgs> NlEnsColsumArgs;
+typedef EnsArgs<TlEnsColsumArgs> TlEnsColsumKArgs;
+typedef EnsArgs<AdEnsColsumArgs> VjpEnsColsumKArgs;
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, (F & C2F_EVAP) ? 1 : 3) nl_ens_colsum_kernel(NlEnsColsumArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const C2_CONST_AS NlEnsColsumArgs* e = kernarg<NlEnsColsumArgs>();
+  unsigned member;
+  long long column;
+  ens_colsum_locate(blockIdx.x, e->wgs_per_member, gridDim.x, threadIdx.x, blockDim.x, member, column);
+  nl_column<F | C2F_COLSUM | C2F_MEMBER>(column, &((const C2_CONST_AS NlColsumArgs*)(e->blocks + member))->a);
+#endif
+}
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, (sizeof(real_t) == 4 && (F & C2F_OFF32) && !(F & C2F_EVAP)) ? 3 : 1)
+tl_ens_colsum_kernel(TlEnsColsumKArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  long long column;
+  const C2_CONST_AS TlEnsColsumArgs* a = ens_block(kernarg<TlEnsColsumKArgs>(), column);
+  tl_column<F | C2F_PARLIN | C2F_SPARSE | C2F_COLSUM | C2F_MEMBER>(column, &a->a.a.a);
+#endif
+}
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) vjp_ens_colsum_kernel(VjpEnsColsumKArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  long long column;
+  const C2_CONST_AS AdEnsColsumArgs* a = ens_block(kernarg<VjpEnsColsumKArgs>(), column);
+  ad_reverse_column<F | C2F_ASSIGN | C2F_VJP | C2F_PARLIN | C2F_SPARSE | C2F_COLSUM>(column, &a->a.a.a);
+#endif
+}
+// fp32 only.  With level_ad carrying the parameter sums, the fp32 device build packs and contracts the level of the sparse reverse sweep
+// differently, and the field gradients of vjp_ens_colsum_kernel miss the column-sum twin's bits by up to two units in the last place
+// (measured on the MI355X; its parameter adjoints are the parameter form's bits, and the fp64 build holds both).  So the fp32 launcher
+// runs this kernel after it when a field gradient is wanted: the twin's own column function, ad_reverse_column without PARLIN, over the
+// same member blocks (an AdEnsColsumArgs begins with the twin's AdColsumArgs), which stores the twin's bits over the planes.  The fp32
+// reverse sweep of an ensemble's column sums therefore runs twice unless only the parameter adjoints are wanted.
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) vjp_ens_colsum_fields_kernel(VjpEnsColsumKArgs args) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  long long column;
+  const C2_CONST_AS AdEnsColsumArgs* a = ens_block(kernarg<VjpEnsColsumKArgs>(), column);
+  ad_reverse_column<F | C2F_ASSIGN | C2F_VJP | C2F_SPARSE | C2F_COLSUM>(column, &a->a.a.a);
+#endif
+}
+constexpr bool kEnsColsumFieldsPass = sizeof(real_t) == 4;
+
 // The batched TL and reverse sweeps (tl_batch_column, vjp_batch_column: up to kBatchMax directions over one trajectory).  One wave
 // per SIMD in fp64 like their single-direction twins, whose registers they extend by the carries of the further directions and one
 // more set of direction inputs; the fp32 builds take what they need (nothing is measured for them yet).
@@ -302,5 +352,9 @@ KernelFn<AdSparseArgs> vjp_sparse_variant(unsigned f);
 KernelFn<NlColsumArgs> nl_colsum_variant(unsigned f);
 KernelFn<TlColsumArgs> tl_colsum_variant(unsigned f);
 KernelFn<AdColsumArgs> vjp_colsum_variant(unsigned f);
+KernelFn<NlEnsColsumArgs> nl_ens_colsum_variant(unsigned f);
+KernelFn<TlEnsColsumKArgs> tl_ens_colsum_variant(unsigned f);
+KernelFn<VjpEnsColsumKArgs> vjp_ens_colsum_variant(unsigned f);
+KernelFn<VjpEnsColsumKArgs> vjp_ens_colsum_fields_variant(unsigned f);  // (built in the fp32 library only: kEnsColsumFieldsPass)
 
 }  // namespace cloudsc2

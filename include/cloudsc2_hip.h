@@ -508,6 +508,45 @@ int cloudsc2_vjp_launch_ens(const cloudsc2_params* prm, double ptsphy, int nprom
                             const long long* adj_out_mstride, const cloudsc2_real* scratch, long long scratch_mstride, void* workspace,
                             double* par_adj, void* stream);
 
+/* Column sums of an ensemble's members: the column-sum launchers for `members` parameter sets in ONE call, the parameters read on the
+ * device, no output, cotangent or tangent plane.  What a calibration needs of a member is K x (a few) x one value per column; the
+ * dense ensemble writes ten planes per member.  Argument blocks, member strides, params_dev / dparams_dev / par_adj and the workspace
+ * (the same query) are those of the ensemble launchers above; weights (shared by the members), sums, keep and the definition of a sum
+ * are those of the column-sum launchers.  Member k's results are the bits of the parent for a prm holding row k's values:
+ *   cloudsc2_nl_launch_ens_colsum   cloudsc2_nl_launch_colsum.  keep given: every member keeps its PFPLSL5 / PFPLSN5 (keep_mstride, the
+ *                                   two entries of fplsl / fplsn; never shared) and, with the evaporation branch, its cover checkpoint.
+ *   cloudsc2_tl_launch_ens_colsum   cloudsc2_tl_launch_colsum plus the source terms of the parameter tangents, row k of dparams_dev: each
+ *                                   sum is the column-sum fold of cloudsc2_tl_launch_par's output tangent.  pert_in may have every
+ *                                   field NULL (parameter tangents alone).
+ *   cloudsc2_vjp_launch_ens_colsum  cloudsc2_vjp_launch_colsum for the field gradients given in adj_in, and row k of par_adj the bits of
+ *                                   cloudsc2_vjp_launch_par given the planes fl(w_n[k] ybar_n[c]).  adj_in may have every field NULL:
+ *                                   the parameter adjoints alone, no plane is written (the calibration case).
+ *   (The fp32 library runs the reverse sweep twice when a field gradient is wanted: once for the parameter adjoints, once more without
+ *   them for the field gradients, which only then have the parent's bits on the MI355X -- one more kernel node.)
+ *   sums_mstride   the member strides of the sums / cotangent sums, in elements, per field of cloudsc2_outputs.  Sums the members write
+ *                  must not be shared; cotangent sums may be (stride 0).
+ * The refusals are the parents': CLOUDSC2_EINVAL for a NULL block, a sum with no weight table, no sum given, members < 1, members x
+ * ceil(ncols_pad / 128) >= 2^31, a written field shared by the members, and the column-sum launchers' own list.  No launcher allocates,
+ * copies or synchronises; two plain kernel nodes in a chain under stream capture, the reverse sweep three.  Not paced, no kernel family,
+ * no launch-log entry. */
+int cloudsc2_nl_launch_ens_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int members,
+                                  const double* params_dev, const cloudsc2_inputs* in, const long long* in_mstride,
+                                  const cloudsc2_real* weights, const cloudsc2_outputs* sums, const long long* sums_mstride,
+                                  const cloudsc2_outputs* keep, const long long* keep_mstride, cloudsc2_real* scratch,
+                                  long long scratch_mstride, void* workspace, void* stream);
+int cloudsc2_tl_launch_ens_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
+                                  const double* params_dev, const double* dparams_dev, const cloudsc2_inputs* traj_in,
+                                  const long long* traj_in_mstride, const cloudsc2_inputs* pert_in, const long long* pert_in_mstride,
+                                  const cloudsc2_real* weights, const cloudsc2_outputs* pert_sums, const long long* sums_mstride,
+                                  void* workspace, void* stream);
+int cloudsc2_vjp_launch_ens_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur, int members,
+                                   const double* params_dev, const cloudsc2_inputs* traj_in, const long long* traj_in_mstride,
+                                   const cloudsc2_outputs* traj_out, const long long* traj_out_mstride, const cloudsc2_inputs* adj_in,
+                                   const long long* adj_in_mstride, const cloudsc2_real* weights,
+                                   const cloudsc2_outputs* adj_sums /* read only */, const long long* sums_mstride,
+                                   const cloudsc2_real* scratch, long long scratch_mstride, void* workspace, double* par_adj,
+                                   void* stream);
+
 /* Several tangents or cotangents over ONE trajectory -- a Jacobian block, a singular-vector iteration, an ensemble of perturbations.
  * cloudsc2_tl_launch_batch replaces nbatch calls of cloudsc2_tl_launch without trajectory stores (traj_out all NULL),
  * cloudsc2_vjp_launch_batch nbatch calls of cloudsc2_vjp_launch, over the same traj_in: every direction's results are the bits those
