@@ -1619,6 +1619,142 @@ def cloudsc2_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | Non
     return Cloudsc2Outputs(*(out.get(n) for n in B.OUT_NAMES))
 
 
+# ---- the parameter Jacobian and the normal equations of the column sums, one sweep, no sensitivity plane -----------------------------
+
+_PAR_SUMS = tuple(n for n in B.OUT_NAMES if n not in ("clc", "covptot"))  # the outputs that depend on a parameter
+
+
+def check_sum_residual(residual, weights, wnames, lay: Layout) -> tuple:
+    """The checks of :func:`param_normal_equations_column_sums` on its residuals and weights that need no device; raises
+    ``ValueError``.  ``residual``: a non-empty mapping of names among ``wnames`` (the names of ``level_weights``) to ``(nblocks, nproma)``
+    tensors in the library's dtype; ``weights``: ``None`` or a mapping over a subset of ``residual``'s names with the same shape (a
+    missing name is weight 1).  Returns ``(residual, weights)`` as dicts in ``OUT_NAMES`` order."""
+    if not hasattr(residual, "keys") or (weights is not None and not hasattr(weights, "keys")):
+        raise ValueError(f"residual (and weights, if given) must map names of {B.OUT_NAMES} to tensors; got {type(residual)}, {type(weights)}")
+    if len(residual.keys()) == 0:
+        raise ValueError("residual is empty: at least one column sum must be observed")
+    weights = {} if weights is None else weights
+    for what, d in (("residual", residual), ("weights", weights)):
+        unknown = sorted(set(d.keys()) - set(B.OUT_NAMES), key=str)
+        if unknown:
+            raise ValueError(f"{what}: unknown name(s) {unknown}; the outputs are {B.OUT_NAMES}")
+    unsummed = sorted(set(residual.keys()) - set(wnames))
+    if unsummed:
+        raise ValueError(f"residual given for sum(s) {unsummed} that have no level weights (level_weights names {tuple(wnames)})")
+    unobserved = sorted(set(weights.keys()) - set(residual.keys()))
+    if unobserved:
+        raise ValueError(f"weights given for sum(s) {unobserved} that are not observed (no residual)")
+    dtype = B.torch_real()
+    shape = (lay.nblocks, lay.nproma)
+    for what, d in (("residual", residual), ("weights", weights)):
+        for n, t in d.items():
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{what}[{n!r}] is not a tensor")
+            if t.dtype != dtype:
+                raise ValueError(f"{what}[{n!r}] has dtype {t.dtype}; this library works on {dtype} (CLOUDSC2_PRECISION)")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{what}[{n!r}] has shape {tuple(t.shape)}, expected {shape} (one value per column)")
+    return ({n: residual[n] for n in B.OUT_NAMES if n in residual.keys()}, {n: weights[n] for n in B.OUT_NAMES if n in weights.keys()})
+
+
+def _enter_parcolsum(inputs, prm: B.Params, ngptot, satur: bool, params, level_weights) -> tuple:
+    """what the two functions below check first, as :func:`param_jacobian` does: the layout, the weights' and the parameters' names"""
+    names, groups = _names(satur)
+    lay = check_layout(inputs, prm, ngptot, satur=satur)
+    wnames = check_weights(level_weights, lay, inputs["pap"].device)
+    pnames = PARAM_NAMES if params is None else check_params(params, prm)
+    ps = () if params is None else tuple(params[n] for n in pnames)
+    return names, groups, lay, wnames, pnames, ps
+
+
+def _finish_parcolsum(who: str, prm: B.Params, pnames, ps, operands) -> tuple:
+    """... and then: the operands' device, the refusals of batched operands and of device parameters under capture, ``prm`` with the values"""
+    dev = check_device(operands)
+    if any(_batched_inside(t) for t in tuple(ps) + tuple(operands)):
+        raise NotImplementedError(f"{who}: batched (vmap-wrapped) operands are not supported; call it once per state")
+    _check_param_devices(pnames, ps, dev)
+    if any(p.device.type != "cpu" for p in ps) and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{who}: the parameters' values are read on the host (they travel in the kernel-argument segment), "
+                           "which cannot happen for device tensors while the stream is capturing")
+    _prepare(dev)
+    return dev, _with_host_values(prm, pnames, ps, who)
+
+
+def param_jacobian_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, level_weights=None, satur: bool = False,
+                               params=None) -> dict:
+    """The parameter Jacobian of the column sums of :func:`cloudsc2_column_sums` at one state: a dict ``name -> Cloudsc2Outputs`` holding,
+    for every name of ``level_weights``, the ``(nblocks, nproma)`` tensor ``s[c] = sum_k w[k] * (d out / d name)[k, c]`` (``None`` for the
+    other outputs), for every name of ``PARAM_NAMES`` or of ``params``.  One ``cloudsc2_parjac_launch_colsum``: the sweep of
+    :func:`param_jacobian` with its sensitivities folded into per-lane accumulators, no sensitivity plane exists.  Every sum is the
+    bits of the fold ``acc = +0; acc = fl(acc + fl(w[k] * J[k]))`` over :func:`param_jacobian`'s planes.
+
+    ``level_weights`` is the ``weights`` of :func:`cloudsc2_column_sums` (packed into a device table with device ops: no host read);
+    ``params``, ``satur``, batched operands and stream capture follow :func:`param_jacobian`.  The result is plain tensors without a
+    graph, padded tails zero; without the evaporation branch the ``rpecons`` entry is zero tensors; ``clc`` and ``covptot`` depend on
+    no parameter: their entries are zero tensors and their weights are accepted and not used."""
+    who = "param_jacobian_column_sums"
+    names, groups, lay, wnames, pnames, ps = _enter_parcolsum(inputs, prm, ngptot, satur, params, level_weights)
+    dev, prm = _finish_parcolsum(who, prm, pnames, ps, [inputs[n] for n in names] + [level_weights[n] for n in wnames])
+    evap = _evap(prm)
+    with torch.no_grad():
+        x = normalize({n: _raw(inputs[n]).detach() for n in names}, lay, groups)
+        like = x["pap"]
+        ran = PARAM_NAMES if evap else PARAM_NAMES[:-1]  # (nothing depends on rpecons without the evaporation branch: not run)
+        swept = tuple(n for n in wnames if n in _PAR_SUMS)
+        launch = bool(swept) and any(n in ran for n in pnames)
+        dy = {n: _new_sums(swept, lay, like) for n in ran} if launch else {}
+        if launch:
+            table = _weight_table(level_weights, swept, lay, like)
+            blocks = (B.Outputs * len(PARAM_NAMES))(*(_sums_block(dy[n], lay) for n in ran))
+            with torch.cuda.device(dev):
+                B.check(B.lib.cloudsc2_parjac_launch_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                            C.byref(_block("in", x, lay)), _ptr(table), blocks, _stream(dev)))
+
+        def entry(p, k):
+            if k not in wnames:
+                return None
+            if p in dy and k in dy[p]:
+                return dy[p][k]
+            return torch.zeros((lay.nblocks, lay.nproma), dtype=like.dtype, device=dev)
+
+        return {p: Cloudsc2Outputs(*(entry(p, k) for k in B.OUT_NAMES)) for p in pnames}
+
+
+def param_normal_equations_column_sums(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, level_weights=None, residual=None,
+                                       weights=None, satur: bool = False, params=None) -> NormalEquations:
+    """The Gauss-Newton normal equations of the parameters against observed COLUMN SUMS: ``NormalEquations(names, jtj, jtr)`` as
+    :func:`param_normal_equations` returns them, with ``J`` the Jacobian of :func:`param_jacobian_column_sums` (one row per active
+    column and observed sum), ``r`` the ``residual`` (model sum - observed sum, from :func:`cloudsc2_column_sums`; a mapping of names
+    of ``level_weights`` to ``(nblocks, nproma)`` tensors) and ``W`` the diagonal ``weights`` (``None``, or a mapping over a subset of
+    ``residual``'s names, same shape; a missing name is weight 1).  One ``cloudsc2_parnormal_launch_colsum``: neither a sensitivity
+    plane nor a sensitivity sum exists in memory; the products are summed in double in a fixed order, the same bits from run to run.
+    ``jtj`` is the upper triangle mirrored bit for bit.  The values of ``residual`` and ``weights`` in a padded tail are not read.
+    The rules for ``params``, ``satur``, batched operands, ``rpecons`` and stream capture are :func:`param_normal_equations`'s."""
+    who = "param_normal_equations_column_sums"
+    names, groups, lay, wnames, pnames, ps = _enter_parcolsum(inputs, prm, ngptot, satur, params, level_weights)
+    r, w = check_sum_residual(residual, weights, wnames, lay)
+    dev, prm = _finish_parcolsum(who, prm, pnames, ps,
+                                 [inputs[n] for n in names] + [level_weights[n] for n in wnames] + list(r.values()) + list(w.values()))
+    with torch.no_grad():
+        if not pnames:
+            return NormalEquations((), torch.zeros((0, 0), dtype=torch.float64, device=dev), torch.zeros((0,), dtype=torch.float64, device=dev))
+        x = normalize({n: _raw(inputs[n]).detach() for n in names}, lay, groups)
+        r = {n: _raw(t).detach().contiguous() for n, t in r.items()}
+        w = {n: _raw(t).detach().contiguous() for n, t in w.items()}
+        table = _weight_table(level_weights, tuple(n for n in r if n in _PAR_SUMS), lay, x["pap"])
+        work = torch.empty(B.NNORMAL * lay.nblocks * lay.nproma, dtype=torch.float64, device=dev)
+        normal = torch.empty(B.NNORMAL, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_parnormal_launch_colsum(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot,
+                                                           C.byref(_block("in", x, lay)), _ptr(table), C.byref(_sums_block(r, lay)),
+                                                           C.byref(_sums_block(w, lay)) if w else None, C.c_void_p(work.data_ptr()),
+                                                           C.c_void_p(normal.data_ptr()), _stream(dev)))
+        idx = [PARAM_NAMES.index(n) for n in pnames]
+        jtj = torch.stack([normal[normal_row(a, b)] for a in idx for b in idx]).reshape(len(idx), len(idx))
+        jtr = torch.stack([normal[B.NNORMAL - len(PARAM_NAMES) + a] for a in idx])
+        return NormalEquations(tuple(pnames), jtj, jtr)
+
+
 # ---- cloudsc2_ensemble_column_sums: the column sums of K members in one launch, no output plane -------------------------------------
 
 _NO_VMAP_ENSCOLSUM = ("cloudsc2_ensemble_column_sums: torch.func.vmap, jacfwd, jacrev and is_grads_batched=True are not supported (the "

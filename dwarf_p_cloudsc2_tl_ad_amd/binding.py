@@ -220,6 +220,13 @@ def _load() -> C.CDLL:
     lib.cloudsc2_parnormal_launch.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs),
                                               C.POINTER(Outputs), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cloudsc2_parnormal_launch.restype = C.c_int
+    # the same two for column sums: the column-sum launchers' weight table, blocks of (nblocks, nproma) fields
+    lib.cloudsc2_parjac_launch_colsum.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.c_void_p, C.POINTER(Outputs),
+                                                  C.c_void_p]
+    lib.cloudsc2_parjac_launch_colsum.restype = C.c_int
+    lib.cloudsc2_parnormal_launch_colsum.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.c_void_p,
+                                                     C.POINTER(Outputs), C.POINTER(Outputs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cloudsc2_parnormal_launch_colsum.restype = C.c_int
     # several directions over one trajectory: arrays of argument blocks, (Inputs * K)(...) / (Outputs * K)(...)
     lib.cloudsc2_batch_max.argtypes = []
     lib.cloudsc2_batch_max.restype = C.c_int
@@ -321,7 +328,7 @@ lib = _load()
 # every symbol include/cloudsc2_hip.h declares
 EXPORTED = ("cloudsc2_params_default", "cloudsc2_last_error", "cloudsc2_device_available", "cloudsc2_current_device", "cloudsc2_set_math_mode",
             "cloudsc2_get_math_mode", "cloudsc2_real_bytes", "cloudsc2_nl_launch",
-            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_tl_launch_sparse", "cloudsc2_vjp_launch_sparse", "cloudsc2_nl_launch_colsum", "cloudsc2_tl_launch_colsum", "cloudsc2_vjp_launch_colsum", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch_parjac", "cloudsc2_ens_workspace_bytes", "cloudsc2_nl_launch_ens", "cloudsc2_tl_launch_ens", "cloudsc2_vjp_launch_ens", "cloudsc2_nl_launch_ens_colsum", "cloudsc2_tl_launch_ens_colsum", "cloudsc2_vjp_launch_ens_colsum", "cloudsc2_parnormal_work_doubles", "cloudsc2_parnormal_launch", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
+            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_tl_launch_sparse", "cloudsc2_vjp_launch_sparse", "cloudsc2_nl_launch_colsum", "cloudsc2_tl_launch_colsum", "cloudsc2_vjp_launch_colsum", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch_parjac", "cloudsc2_ens_workspace_bytes", "cloudsc2_nl_launch_ens", "cloudsc2_tl_launch_ens", "cloudsc2_vjp_launch_ens", "cloudsc2_nl_launch_ens_colsum", "cloudsc2_tl_launch_ens_colsum", "cloudsc2_vjp_launch_ens_colsum", "cloudsc2_parnormal_work_doubles", "cloudsc2_parnormal_launch", "cloudsc2_parjac_launch_colsum", "cloudsc2_parnormal_launch_colsum", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
             "cloudsc2_ad_launch_forward", "cloudsc2_ad_launch_reverse", "cloudsc2_vjp_launch", "cloudsc2_batch_max", "cloudsc2_tl_launch_batch", "cloudsc2_vjp_launch_batch", "cloudsc2_ad_launch_reverse_norms", "cloudsc2_taylor_sums_launch",
             "cloudsc2_taylor_sweep_work_doubles", "cloudsc2_taylor_sweep_launch", "cloudsc2_adjoint_norms_launch", "cloudsc2_nl_run", "cloudsc2_tl_taylor_run", "cloudsc2_ad_symmetry_run",
             "cloudsc2_release_workspace", "cloudsc2_taylor_verdict", "cloudsc2_adjoint_verdict",

@@ -2019,6 +2019,211 @@ C2_HD void parnormal_column(long long gcol, ParNormalArgsP a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The parameter Jacobian and the normal equations of the COLUMN SUMS in one sweep (cloudsc2_parjac_launch_colsum,
+// cloudsc2_parnormal_launch_colsum)
+// ---------------------------------------------------------------------------------------------------------
+// A cloud scheme is confronted with column sums y_n[c] = sum_k w_n[k] out_n[k, c] (surface rain and snow, column-integrated heating).
+// Their sensitivities s[a][n][c] = sum_k w_n[k] (d out_n / d p_a)[k, c] need nothing but tl_parjac_column's level loop: this sweep is
+// that loop with store_out replaced by a fold of direction a's sensitivities into the lane's accumulators acc[a][n], the fold of
+// ColsumAcc::add to the bit: acc = fl(acc + fl(w_n[k] J)), the level's sensitivities pinned before the fold and the product laundered
+// before its add, half level 0 of a flux skipped.  No sensitivity plane exists.  clc and covptot depend on no parameter: they have no
+// accumulator and their rows of the table are not read.  The accumulators live in LDS, one slot per lane, direction and sum (up to
+// 4 x 8 fp64 values: kept in registers the kernels take 45-55 registers more, in LDS fewer than tl_parjac_kernel; neither form uses
+// scratch -- DESIGN.md 3.6): a lane touches its own slots only, so there is no barrier.  The host builds keep them in an array.
+// The end of the column has two forms (C2F_NORMAL):
+//   sums form    s[a][n] stored for every run parameter a and every sum n of the mask into (nblocks, nproma) arrays addressed as in
+//                colsum_off (y[a]); the padded tail is not written; a clc or covptot array present receives its exact zero.
+//   normal form  the column's residual r_n[c] and diagonal weight of every observed sum are read from (nblocks, nproma) arrays (y[0],
+//                y[1]; a NULL weight is weight 1) and normal_add<NP> is called with j[a] = s[a][n] for the observed n in the order of
+//                OutPtrs; the 14 (or 9) doubles go to `work` as in parnormal_column, for the same fold over the columns.
+constexpr unsigned C2F_NORMAL = 8u;  // this sweep only: the normal-equations end of the column
+// (par and y from the launch's direction count on are not read)
+struct ParColsumArgs {
+  Consts c; Geom g; Strides s; InPtrs in; ParLin par[kBatchMax]; const LevelTab* tab;
+  ColsumTab cs;          // w: the table; y: not used; stride: the block stride of every (nblocks, nproma) array; mask: the sums present / observed
+  OutPtrs y[kBatchMax];  // sums form: the sums of direction b, written; normal form: y[0] the residuals, y[1] the weights, read only
+  double* work;          // normal form: (normal_sums(PAR_COUNT), ncols_pad) doubles, as ParNormalArgs::work
+};
+typedef const C2_CONST_AS ParColsumArgs* ParColsumArgsP;
+
+template <int NP>
+struct ParColsumAcc {
+#if defined(__HIP_DEVICE_COMPILE__)
+  real_t* s;  // this lane's slot of (direction 0, sum 0); (b, n) is (b * kNormalObs + n) * kColsumLanes further
+  __device__ __forceinline__ void begin() {
+    __shared__ real_t slots[NP * kNormalObs * kColsumLanes];
+    s = slots + threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < NP * kNormalObs; ++i) s[i * kColsumLanes] = RC(0.0);
+  }
+  // the lane's column once more after the level loop, as ColsumAcc::column(): no register holds it through the loop
+  __device__ __forceinline__ long long column(long long) const { return (long long)blockIdx.x * kColsumLanes + threadIdx.x; }
+  __device__ __forceinline__ real_t get(int b, int n) const { return s[(b * kNormalObs + n) * kColsumLanes]; }
+  __device__ __forceinline__ void set(int b, int n, real_t v) { s[(b * kNormalObs + n) * kColsumLanes] = v; }
+#else
+  real_t s[NP * kNormalObs];
+  void begin() {
+    for (int i = 0; i < NP * kNormalObs; ++i) s[i] = RC(0.0);
+  }
+  long long column(long long gcol) const { return gcol; }
+  real_t get(int b, int n) const { return s[b * kNormalObs + n]; }
+  void set(int b, int n, real_t v) { s[b * kNormalObs + n] = v; }
+#endif
+  C2_HD void add(int b, int n, real_t w, real_t v) {  // (ColsumAcc::add)
+    real_t p = w * v;
+    C2_LAUNDER_V(p);
+    set(b, n, get(b, n) + p);
+  }
+};
+
+// one level's sensitivities of direction b into its sums of mask m: colsum_fold without the two outputs that depend on no parameter
+template <int NP>
+C2_HD void parcolsum_fold(ParColsumAcc<NP>& acc, int b, ColsumTabP cs, unsigned m, int nlev, int jk, LevelOut v) {
+  C2_PIN_V(v.tent); C2_PIN_V(v.tenq); C2_PIN_V(v.tenl); C2_PIN_V(v.teni); C2_PIN_V(v.clc);
+  C2_PIN_V(v.covptot); C2_PIN_V(v.fplsl); C2_PIN_V(v.fplsn); C2_PIN_V(v.fhpsl); C2_PIN_V(v.fhpsn);
+  const ColsumRowP w = (ColsumRowP)cs->w + jk;
+  const int r = nlev + 1;
+  if (m & C2O_TENT) acc.add(b, 0, w[0 * r], v.tent);
+  if (m & C2O_TENQ) acc.add(b, 1, w[1 * r], v.tenq);
+  if (m & C2O_TENL) acc.add(b, 2, w[2 * r], v.tenl);
+  if (m & C2O_TENI) acc.add(b, 3, w[3 * r], v.teni);
+  if (m & C2O_FPLSL) acc.add(b, 4, w[5 * r + 1], v.fplsl);
+  if (m & C2O_FPLSN) acc.add(b, 5, w[6 * r + 1], v.fplsn);
+  if (m & C2O_FHPSL) acc.add(b, 6, w[7 * r + 1], v.fhpsl);
+  if (m & C2O_FHPSN) acc.add(b, 7, w[8 * r + 1], v.fhpsn);
+}
+
+// F: C2F_QSAT (otherwise the trajectory's SATUR is evaluated in the sweep) | C2F_PRECISE | C2F_EVAP | C2F_OFF32 | C2F_NORMAL
+template <unsigned F>
+C2_HD void parcolsum_column(long long gcol, ParColsumArgsP a) {
+  constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0, NORMAL = (F & C2F_NORMAL) != 0;
+  constexpr int NP = parjac_directions(F);
+  static_assert(!(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32 | C2F_NORMAL)),
+                "flags of the parameter column-sum sweep: QSAT, PRECISE, EVAP, OFF32, NORMAL");
+  typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
+  LaneOff o; bool active;
+  if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
+  if (!active) return;
+  const int nlev = a->g.nlev, nproma = a->g.nproma;
+  LevelTabP tab = (LevelTabP)a->tab;
+  ConstsP c = C2_CONSTS(a);
+  InPtrsP in = &a->in;
+
+  // once per column, not once per direction: the tropopause pre-scan, the critical-humidity setup, the lane offsets, the loads
+  real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->g, RC(0.0));
+  RhCrit rh;
+  rhcrit_setup(ztrpaus, rh);
+  real_t paph_surf = RC(0.0);
+  if (EVAP) paph_surf = in->paph[o.half + (long long)nlev * nproma];
+
+  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
+  Carry dcy[NP];
+#pragma unroll
+  for (int b = 0; b < NP; ++b) { dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0); }
+  ParColsumAcc<NP> acc;
+  acc.begin();
+  RawLevel cur, nxt;
+  real_t paph_k = in->paph[o.half];
+  const LaneOffT<OT> ol = lane_off_as<OT>(o);  // offsets used inside the level loop
+  load_level<HAS_QSAT>(in, ol, nproma, nlev, 0, cur);
+
+  // The trajectory inputs of level jk+1 are requested at the top of level jk, as in tl_parjac_column; nothing else is read.
+  for (int jk = 0; jk < nlev; ++jk) {
+    const bool last = (jk == nlev - 1);
+    ParColsumArgsP ap = a;
+    C2_LAUNDER(ap);
+    nxt = cur;
+    if (!last) load_level<HAS_QSAT>(&ap->in, ol, nproma, nlev, jk + 1, nxt);
+    if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);  // (once per level: every direction gets its own opaque copy)
+
+    LevelCst k;
+    level_cst(tab, jk, last, k);
+    LevelIn x;
+    make_level_in(cur, paph_k, paph_surf, x);
+    Carry cy_out = cy;
+#pragma unroll
+    for (int b = 0; b < NP; ++b) {
+      // this direction's own straight line (launder_level says why): every direction leaves the same trajectory carry
+      LevelIn xb = x;
+      LevelCst kb = k;
+      RhCrit rhb = rh;
+      cy_out = cy;
+      launder_level(xb, kb, cy_out);
+      C2_LAUNDER_V(xb.paph_surf); C2_LAUNDER_V(rhb.zeta3); C2_LAUNDER_V(rhb.zrh2); C2_LAUNDER_V(rhb.zdeta1);
+      ConstsP cb = c;  // (and its own view of the constants: a product of two of them is shared otherwise)
+      C2_LAUNDER(cb);
+      LevelTraj tr;
+      LevelOut lo;
+      level_forward<P, EVAP>(cb, kb, rhb, xb, cy_out, tr, lo);
+      LevelIn dx;
+      zero_level_in<EVAP>(dx);
+      LevelOut dlo;
+      C2_LAUNDER(ap);
+      level_tl<true>(cb, kb, xb, tr, dx, dcy[b], dlo, &ap->par[b]);
+      C2_LAUNDER(ap);
+      parcolsum_fold<NP>(acc, b, &ap->cs, ap->cs.mask, nlev, jk, dlo);
+    }
+    cy = cy_out;
+    paph_k = cur.paph_k1;
+    cur = nxt;
+  }
+
+  const unsigned m = a->cs.mask;
+  const long long col = acc.column(gcol);
+  const long long ocs = colsum_off(&a->g, &a->cs, col);
+  if constexpr (!NORMAL) {
+    // one row per run parameter and sum present (clc, covptot: the exact zero)
+#pragma unroll
+    for (int b = 0; b < NP; ++b) {
+      const OutPtrs y = a->y[b];
+      if (m & C2O_TENT) y.tent[ocs] = acc.get(b, 0);
+      if (m & C2O_TENQ) y.tenq[ocs] = acc.get(b, 1);
+      if (m & C2O_TENL) y.tenl[ocs] = acc.get(b, 2);
+      if (m & C2O_TENI) y.teni[ocs] = acc.get(b, 3);
+      if (m & C2O_CLC) y.clc[ocs] = RC(0.0);
+      if (m & C2O_FPLSL) y.fplsl[ocs] = acc.get(b, 4);
+      if (m & C2O_FPLSN) y.fplsn[ocs] = acc.get(b, 5);
+      if (m & C2O_FHPSL) y.fhpsl[ocs] = acc.get(b, 6);
+      if (m & C2O_FHPSN) y.fhpsn[ocs] = acc.get(b, 7);
+      if (m & C2O_COVPTOT) y.covptot[ocs] = RC(0.0);
+    }
+  } else {
+    NormalAcc<NP> na;
+#pragma unroll
+    for (int b = 0; b < NP; ++b) na.g[b] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NP * (NP + 1) / 2; ++i) na.h[i] = 0.0;
+    const OutPtrs r = a->y[0], w = a->y[1];
+    // the observed sums in the order of struct cloudsc2_outputs (clc and covptot: exact zeros, their residuals are not read)
+#define C2_PARCOLSUM_ADD(bit, n, field)                                   \
+  if (m & (bit)) {                                                        \
+    real_t j[NP], rv, wv;                                                 \
+    _Pragma("unroll") for (int b = 0; b < NP; ++b) j[b] = acc.get(b, n);  \
+    load_obs_one(r.field, w.field, ocs, rv, wv);                          \
+    normal_add<NP>(na, j, rv, wv);                                        \
+  }
+    C2_PARCOLSUM_ADD(C2O_TENT, 0, tent)
+    C2_PARCOLSUM_ADD(C2O_TENQ, 1, tenq)
+    C2_PARCOLSUM_ADD(C2O_TENL, 2, tenl)
+    C2_PARCOLSUM_ADD(C2O_TENI, 3, teni)
+    C2_PARCOLSUM_ADD(C2O_FPLSL, 4, fplsl)
+    C2_PARCOLSUM_ADD(C2O_FPLSN, 5, fplsn)
+    C2_PARCOLSUM_ADD(C2O_FHPSL, 6, fhpsl)
+    C2_PARCOLSUM_ADD(C2O_FHPSN, 7, fhpsn)
+#undef C2_PARCOLSUM_ADD
+    // the lane's sums: consecutive lanes, consecutive doubles of each row (col < ngptot <= ncols_pad)
+    double* work = a->work;
+    const long long np = a->g.ncols_pad;
+#pragma unroll
+    for (int ia = 0; ia < NP; ++ia) {
+#pragma unroll
+      for (int ib = ia; ib < NP; ++ib) work[normal_row_h(ia, ib) * np + col] = na.h[ia * NP - ia * (ia - 1) / 2 + (ib - ia)];
+      work[normal_row_g(ia) * np + col] = na.g[ia];
+    }
+  }
+}
+
 template <class OT>
 C2_HD void load_out_adjoint(OutPtrsP pp, const LaneOffT<OT>& oa, OT d, OT d1, LevelOut& ya) {
   const OutPtrs pa = *pp;

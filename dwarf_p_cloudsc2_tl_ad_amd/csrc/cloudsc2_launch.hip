@@ -21,6 +21,7 @@
 #include "cloudsc2_kern_vjp_par.hip"
 #include "cloudsc2_kern_tl_parjac.hip"
 #include "cloudsc2_kern_parnormal.hip"
+#include "cloudsc2_kern_parcolsum.hip"
 #include "cloudsc2_kern_nl_ens.hip"
 #include "cloudsc2_kern_tl_ens.hip"
 #include "cloudsc2_kern_vjp_ens.hip"
@@ -1587,6 +1588,116 @@ int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int npr
   }
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+// ---- the parameter Jacobian and the normal equations of the column sums (parcolsum_column) ------------------------------------------------
+// The sensitivities of the column sums to the tunable parameters, stored (cloudsc2_parjac_launch_colsum) or contracted per column into the
+// normal equations (cloudsc2_parnormal_launch_colsum: then the fold of cloudsc2_parnormal_launch).  Launched directly like parnormal_kernel:
+// no family number, no pacing, no launch-log entry.  What is wrong with the call itself is reported before the device is looked for.
+// the common part: `blocks` holds `nblk` blocks of (nblocks, nproma) fields, block 0 the one whose present fields are the mask; `form`:
+// 0 or C2F_NORMAL
+static int parcolsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                   const cloudsc2_real* wtable, ParColsumArgs& args, unsigned form, void* stream) {
+  Sweep w;
+  int rc;
+  if ((rc = resolve_in(*traj_in, false, w.s, w.in))) return rc;
+  memset(&w.out, 0, sizeof(w.out));
+  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
+  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {args.cs.stride}))) return rc;
+  args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.tab = w.tab;
+  args.cs.w = wtable;
+  unit_parlins(args.par, w.c, w.c.evap ? (int)PAR_COUNT : (int)PAR_COUNT - 1);
+  const KernelFn<ParColsumArgs> fn = parcolsum_variant(w.f | form);
+  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
+  schedule(args.g, nullptr, false, nullptr);
+  void* argv[] = {&args};
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
+  return 0;
+}
+// what both launchers refuse first
+static int check_parcolsum(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, const cloudsc2_real* wtable) {
+  int rc = check_colsum_geom(prm, nproma, nlev, ngptot);
+  if (rc) return rc;
+  if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
+  if ((rc = check_rpecons(prm))) return rc;
+  if (!wtable) return fail(CLOUDSC2_EINVAL, "the weight table is NULL");
+  return 0;
+}
+
+static int parjac_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                       const cloudsc2_real* wtable, const cloudsc2_outputs* sens_sums, void* stream) {
+  if (!prm || !traj_in || !sens_sums) return fail(CLOUDSC2_EINVAL, "NULL argument block");
+  int rc = check_parcolsum(prm, nproma, nlev, ngptot, wtable);
+  if (rc) return rc;
+  const int np = (prm->levapls2 || prm->ldrain1d) ? (int)PAR_COUNT : (int)PAR_COUNT - 1;
+  ParColsumArgs args;
+  memset(&args, 0, sizeof(args));
+  unsigned mask = 0u;
+  if ((rc = resolve_colsum(wtable, &sens_sums[0], nproma, "no sum is wanted (every field of sens_sums[0] is NULL)", args.cs, mask))) return rc;
+  args.y[0] = args.cs.y;
+  for (int b = 1; b < np; ++b) {
+    ColsumTab cb;
+    unsigned mb = 0u;
+    if ((rc = resolve_colsum(wtable, &sens_sums[b], nproma, "every parameter's block of sens_sums must hold the same sums (one holds none)", cb, mb)))
+      return rc;
+    if (mb != mask) return fail(CLOUDSC2_EINVAL, "every parameter's block of sens_sums must hold the same sums");
+    if (cb.stride != args.cs.stride) return fail(CLOUDSC2_EINVAL, "the sums given must share one block stride");
+    args.y[b] = cb.y;
+  }
+  for (int b = np; b < kBatchMax; ++b) args.y[b] = args.y[0];  // (not read: valid pointers all the same)
+  memset(&args.cs.y, 0, sizeof(args.cs.y));
+  return parcolsum_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, wtable, args, 0u, stream);
+}
+
+static int parnormal_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                          const cloudsc2_real* wtable, const cloudsc2_outputs* resid, const cloudsc2_outputs* weight, double* work,
+                          double* normal, void* stream) {
+  if (!prm || !traj_in || !resid || !work || !normal) return fail(CLOUDSC2_EINVAL, "NULL argument block, workspace or result");
+  int rc = check_parcolsum(prm, nproma, nlev, ngptot, wtable);
+  if (rc) return rc;
+  const bool evap = prm->levapls2 || prm->ldrain1d;
+  const cloudsc2_outputs none = {};
+  const cloudsc2_outputs& wt = weight ? *weight : none;
+  const cloudsc2_field *rf = fields_of(*resid), *wf = fields_of(wt);
+  for (int i = 0; i < kNumOut; ++i)
+    if (!rf[i].ptr && wf[i].ptr) return fail(CLOUDSC2_EINVAL, "a weight is given for a sum that is not observed (its residual is NULL)");
+  ParColsumArgs args;
+  memset(&args, 0, sizeof(args));
+  unsigned mask = 0u, wmask = 0u;
+  if ((rc = resolve_colsum(wtable, resid, nproma, "no sum is observed (every residual field is NULL)", args.cs, mask))) return rc;
+  args.y[0] = args.cs.y;
+  if (outputs_given(wt)) {
+    ColsumTab cw;
+    if ((rc = resolve_colsum(wtable, &wt, nproma, "", cw, wmask))) return rc;
+    if (cw.stride != args.cs.stride) return fail(CLOUDSC2_EINVAL, "residuals and weights must share one block stride");
+    args.y[1] = cw.y;
+  }
+  memset(&args.cs.y, 0, sizeof(args.cs.y));
+  args.work = work;
+  if ((rc = parcolsum_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, wtable, args, C2F_NORMAL, stream))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const long long n = args.g.ncols_pad;
+  if (evap) {
+    hipLaunchKernelGGL(par_fold_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)args.g.ngptot, normal);
+  } else {  // the rows with rpecons were not written: not read, stored as zeros
+    unsigned unwritten = 1u << normal_row_g(PAR_RPECONS);
+    for (int a = 0; a < PAR_COUNT; ++a) unwritten |= 1u << normal_row_h(a, PAR_RPECONS);
+    hipLaunchKernelGGL(par_fold_rows_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)args.g.ngptot,
+                       unwritten, normal);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int cloudsc2_parjac_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                                  const cloudsc2_real* wtable, const cloudsc2_outputs* sens_sums, void* stream) {
+  return named("cloudsc2_parjac_launch_colsum", parjac_colsum_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, wtable, sens_sums, stream));
+}
+int cloudsc2_parnormal_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                                     const cloudsc2_real* wtable, const cloudsc2_outputs* resid, const cloudsc2_outputs* weight, double* work,
+                                     double* normal, void* stream) {
+  return named("cloudsc2_parnormal_launch_colsum",
+               parnormal_colsum_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, wtable, resid, weight, work, normal, stream));
 }
 
 int cloudsc2_ad_launch_reverse_norms(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,

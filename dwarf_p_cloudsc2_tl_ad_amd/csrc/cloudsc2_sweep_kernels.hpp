@@ -306,6 +306,17 @@ __global__ void __launch_bounds__(kBlock, 1) parnormal_kernel(ParNormalArgs args
   C2_KERNEL_BODY((parnormal_column<F>(global_column(), kernarg<ParNormalArgs>())));
 }
 
+// The parameter Jacobian and the normal equations of the column sums in one sweep (parcolsum_column; unit cloudsc2_kern_parcolsum.hip):
+// tl_parjac_kernel's launch bounds; the 32 KiB of LDS a 128-lane workgroup takes for its accumulators let two workgroups share a CU,
+// which is what one wave per SIMD asks for.  Flag words: QSAT, PRECISE, EVAP, OFF32 times the two ends of the column (C2F_NORMAL) --
+// 32 kernels per precision.  Not a sweep family: no family number, no pacing, no launch-log entry; launched directly, like
+// parnormal_kernel.
+template <unsigned F>
+__global__ void __launch_bounds__(kBlock, 1) parcolsum_kernel(ParColsumArgs args) {
+  C2_KERNEL_BODY((parcolsum_column<F>(global_column(), kernarg<ParColsumArgs>())));
+}
+constexpr bool parcolsum_variant_valid(unsigned f) { return (f & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32 | C2F_NORMAL)) == 0; }
+
 // The ten perturbed NL runs of the Taylor test in one sweep, the lambdas on the lanes (taylor_column): the grid is over THREADS,
 // 64 per kTaylorCols columns.  A wave reads 6 columns = 48 bytes of every 128-byte line it touches, so two or three consecutive
 // waves share each line -- the one sweep whose workgroups share data.  Blocks are dealt round-robin over the 8 XCDs (b and b + 8
@@ -344,6 +355,7 @@ KernelFn<TlBatchArgs> tl_batch_variant(unsigned f, int directions);
 KernelFn<VjpBatchArgs> vjp_batch_variant(unsigned f, int directions);
 KernelFn<TlParJacArgs> tl_parjac_variant(unsigned f);
 KernelFn<ParNormalArgs> parnormal_variant(unsigned f);
+KernelFn<ParColsumArgs> parcolsum_variant(unsigned f);
 KernelFn<NlEnsArgs> nl_ens_variant(unsigned f);
 KernelFn<TlEnsArgs> tl_ens_variant(unsigned f);
 KernelFn<VjpEnsArgs> vjp_ens_variant(unsigned f);

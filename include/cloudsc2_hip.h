@@ -469,6 +469,39 @@ int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int npr
                               const cloudsc2_inputs* traj_in, const cloudsc2_outputs* resid, const cloudsc2_outputs* weight,
                               double* work, double* normal /* device, [CLOUDSC2_NNORMAL] */, void* stream);
 
+/* The parameter Jacobian and the normal equations of COLUMN SUMS in one sweep.  Observations of a cloud scheme are sums over the column,
+ * y_n[c] = sum_k w_n[k] out_n[k, c] (cloudsc2_nl_launch_colsum): surface rain and snow, column-integrated heating.  Their sensitivities
+ * s[a][n][c] = sum_k w_n[k] (d out_n / d p_a)[k, c] need only the level loop of cloudsc2_tl_launch_parjac: its sensitivities are folded
+ * into per-lane accumulators, the fold of the column-sum sweeps to the bit (acc = +0; acc = fl(acc + fl(w_n[k] J[k])), half level 0 of a
+ * flux skipped), and no sensitivity plane exists.  Bytes per column (NLEV 137, fp64): 17 544 read plus 8 per stored sum, against
+ * 17 544 + NP x 10 992 of cloudsc2_tl_launch_parjac plus the reads of a fold over its planes.
+ *   wtable     device, the table of the column-sum launchers: ten rows of nlev + 1 in the order of cloudsc2_outputs.  The rows of clc
+ *              and covptot, which depend on no parameter, are not read.
+ *   cloudsc2_parjac_launch_colsum     sens_sums[a] (a in CLOUDSC2_NPAR order): 2-D (nblocks, nproma) fields, a NULL field is an absent sum;
+ *              the same fields must be present in every block that is looked at and all must share one block stride >= nproma.  Every
+ *              active column of a present sum is assigned; a clc or covptot sum receives exact zeros; the padded tail is not written.
+ *              Without LEVAPLS2 .OR. LDRAIN1D three directions run and sens_sums[CLOUDSC2_NPAR - 1] (rpecons) is not looked at.
+ *   cloudsc2_parnormal_launch_colsum  resid / weight: 2-D (nblocks, nproma) fields, read only: the column's residual (model sum -
+ *              observed sum) and diagonal weight per observed sum; a NULL residual is an unobserved sum, weight NULL or a NULL weight
+ *              field is weight 1.  Per active column the observed sums are taken in the order of cloudsc2_outputs and
+ *              H[a][b] += (w s_a) s_b, g[a] += (w s_a) r are formed in double; work and normal are those of cloudsc2_parnormal_launch
+ *              (cloudsc2_parnormal_work_doubles), the same fold over the columns, the rpecons entries exactly 0.0 without the
+ *              evaporation branch.
+ * CLOUDSC2_EINVAL (reported before the device is looked for, the message names the launcher): a NULL prm, traj_in, wtable, sens_sums /
+ * resid, work or normal; prm->lphylin = 0; the evaporation branch with rpecons = 0; no sum present / observed; a weight without its
+ * residual; block strides that differ inside one call or lie below nproma; blocks of sens_sums with different fields present; a kernel
+ * variant that is not built; bad shapes.  Without a device: CLOUDSC2_ENODEVICE.
+ * Both take the caller's stream, neither allocate nor synchronise (apart from the CETA table of a grid's first use) and are plain kernel
+ * nodes under stream capture (one, and two in a chain).  Not paced; no kernel family of cloudsc2_variant_built /
+ * cloudsc2_kernel_occupancy / the launch log. */
+int cloudsc2_parjac_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                                  const cloudsc2_inputs* traj_in, const cloudsc2_real* wtable,
+                                  const cloudsc2_outputs* sens_sums /* [CLOUDSC2_NPAR] */, void* stream);
+int cloudsc2_parnormal_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                                     const cloudsc2_inputs* traj_in, const cloudsc2_real* wtable, const cloudsc2_outputs* resid,
+                                     const cloudsc2_outputs* weight, double* work, double* normal /* device, [CLOUDSC2_NNORMAL] */,
+                                     void* stream);
+
 /* Perturbed-parameter ensembles: `members` parameter sets over one state (or one state each) in ONE call, the four parameters read on the
  * DEVICE.  The launchers above carry the parameters inside the constants of the kernel-argument segment, so the host must know their
  * values; these three put one argument block per member into device memory instead: a first kernel derives member k's block from the

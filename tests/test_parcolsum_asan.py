@@ -1,0 +1,59 @@
+"""The host build of the parameter column-sum sweep under the host sanitizers, as a stand-alone program (its own ``main``, no Python in
+the process): tests/hostcheck/parcolsum_asan_main.cpp compiled with ``-fsanitize=address,undefined`` and run directly.  Every present
+array -- plane, (nblocks, nproma) sum, residual or weight, weight table, workspace -- is a ``malloc`` of exactly its extent and every
+absent one a NULL pointer, for the patterns of sums x the four flag sets x qsat given / SATUR in the sweep x fast / precise at NPROMA 8,
+NLEV 137, NGPTOT 12.  Passes on exit 0 with no sanitizer report."""
+from __future__ import annotations
+
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests.test_hostcheck_vjp import host_qsat
+from tests.test_sparse_asan import sanitizer_runtimes
+from tests.util import B, HOSTCHECK_DIR, ROOT, c2, increments_of, make_params
+
+HIPCC = "/opt/rocm/bin/hipcc"
+EXE = os.path.join(HOSTCHECK_DIR, "parcolsum_asan_main_sp" if B.SINGLE else "parcolsum_asan_main")
+FLAGSETS = (dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(lregcl=True))
+
+
+def build() -> str:
+    src = os.path.join(HOSTCHECK_DIR, "parcolsum_asan_main.cpp")
+    deps = [src] + [os.path.join(HOSTCHECK_DIR, f) for f in ("hostcheck_parcolsum.hip", "hostcheck.hip")] + [
+        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
+    if (not os.path.exists(EXE)) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
+        # host code only; -O0: the instrumented sweeps take minutes to optimise and a second to run as they are
+        subprocess.check_call([HIPCC, "--cuda-host-only", "-x", "hip", "-O0", "-g", "-fno-omit-frame-pointer", "-Xarch_host",
+                               "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
+                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", EXE, src])
+    return EXE
+
+
+def test_parameter_column_sums_under_the_host_sanitizers(tmp_path):
+    if not sanitizer_runtimes():
+        pytest.skip("no AddressSanitizer / UndefinedBehaviorSanitizer runtime in this toolchain")
+    exe = build()
+    nproma, nlev, ngptot = 8, 137, 12
+    tab = c2.random_table(nlev, 30, seed=11)
+    st = c2.state_from_table(tab, nproma, ngptot)
+    planes = {n: a * B.REAL(100.0) for n, a in increments_of(st, host_qsat(st)).items()}  # (the 16 inputs as flat planes)
+    case_file = tmp_path / "cases.bin"
+    with open(case_file, "wb") as f:
+        f.write(struct.pack("4i", nproma, nlev, ngptot, len(FLAGSETS)))
+        for flags in FLAGSETS:
+            f.write(bytes(make_params(tab, **flags)))
+            f.write(struct.pack("d", float(st.ptsphy)))
+        for n in B.IN_NAMES:
+            a = np.ascontiguousarray(planes[n], dtype=B.REAL)
+            assert a.shape == (st.nblocks, nlev + (1 if n == "paph" else 0), nproma)
+            f.write(a.tobytes())
+    # (the sanitizer runtimes are linked into the executable: it runs in the environment as it is)
+    r = subprocess.run([exe, str(case_file)], capture_output=True, text=True, timeout=600)
+    print(r.stdout[-2000:], r.stderr[-4000:])
+    assert r.returncode == 0, (r.returncode, r.stderr[-4000:])
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert "every sum the fold's bits and every normal form the contraction's" in r.stdout
