@@ -1746,16 +1746,32 @@ C2_HD void zero_level_in(LevelIn& dx) {
   if (EVAP) C2_LAUNDER_V(dx.paph_surf);
 }
 
-// F: C2F_QSAT (otherwise the trajectory's SATUR is evaluated in the sweep) | C2F_PRECISE | C2F_EVAP | C2F_OFF32
-template <unsigned F>
-C2_HD void tl_parjac_column(long long gcol, TlParJacArgsP a) {
+// The level loop of the three parameter sweeps (tl_parjac_column here, parnormal_column and parcolsum_column below), written once:
+// the trajectory side, the NP laundered straight lines and the carry hand-over are the skeleton's; what a family does with a
+// direction's sensitivities is its End, a plain struct of per-lane state whose hooks are called at fixed points:
+//   setup(a, gcol, active)                 after the first lane_setup, before the inactive lanes leave
+//   begin(a, c)                            before the level loop
+//   level_top(ap, nproma, jk)              at the top of a level, with the look-ahead loads of level jk+1 issued
+//   direction(ap, b, nproma, nlev, jk, v)  after level_tl of direction b: v = its sensitivities of level jk (ap: the loop's laundered
+//                                          argument block, by reference, so that an End launders THAT pointer again before it stores)
+//   level_end()                            after the level's last direction
+//   column_end(a, gcol)                    after the last level
+// and whose PaceT says at compile time whether the sweep is paced (Pace) or not (NoPace).
+struct NoPace {
+  C2_HD void begin(GeomP) {}
+  C2_HD void nap() {}
+};
+
+// F: C2F_QSAT (otherwise the trajectory's SATUR is evaluated in the sweep) | C2F_PRECISE | C2F_EVAP | C2F_OFF32 (| bits of the End's own)
+// ArgsP: pointer to an argument block with c g s in par tab
+template <unsigned F, class ArgsP, class End>
+C2_HD void par_sweep(long long gcol, ArgsP a, End& e) {
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0;
   constexpr int NP = parjac_directions(F);
-  static_assert(!(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32)), "flags of the parameter-Jacobian sweep: QSAT, PRECISE, EVAP, OFF32");
   typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
-  LaneOff o, op; bool active;
+  LaneOff o; bool active;
   if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
-  lane_setup(&a->g, &a->sp, gcol, op, active);
+  e.setup(a, gcol, active);
   if (!active) return;
   const int nlev = a->g.nlev, nproma = a->g.nproma;
   LevelTabP tab = (LevelTabP)a->tab;
@@ -1772,24 +1788,23 @@ C2_HD void tl_parjac_column(long long gcol, TlParJacArgsP a) {
   Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
   Carry dcy[NP];
 #pragma unroll
-  for (int b = 0; b < NP; ++b) {
-    dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0);
-    store_top(&a->dout[b], op, c);
-  }
+  for (int b = 0; b < NP; ++b) { dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0); }
+  e.begin(a, c);
   RawLevel cur, nxt;
   real_t paph_k = in->paph[o.half];
-  const LaneOffT<OT> ol = lane_off_as<OT>(o), opl = lane_off_as<OT>(op);  // offsets used inside the level loop
+  const LaneOffT<OT> ol = lane_off_as<OT>(o);  // offsets used inside the level loop
   load_level<HAS_QSAT>(in, ol, nproma, nlev, 0, cur);
-  Pace pace;
+  typename End::PaceT pace;
   pace.begin(&a->g);
 
-  // The trajectory inputs of level jk+1 are requested at the top of level jk, as in tl_column; nothing else is read.
+  // The trajectory inputs of level jk+1 are requested at the top of level jk, as in tl_column; what else a level reads is its End's.
   for (int jk = 0; jk < nlev; ++jk) {
     const bool last = (jk == nlev - 1);
-    TlParJacArgsP ap = a;
+    ArgsP ap = a;
     C2_LAUNDER(ap);
     nxt = cur;
     if (!last) load_level<HAS_QSAT>(&ap->in, ol, nproma, nlev, jk + 1, nxt);
+    e.level_top(ap, nproma, jk);
     pace.nap();  // (with the loads in flight)
     if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);  // (once per level: every direction gets its own opaque copy)
 
@@ -1817,20 +1832,50 @@ C2_HD void tl_parjac_column(long long gcol, TlParJacArgsP a) {
       LevelOut dlo;
       C2_LAUNDER(ap);
       level_tl<true>(cb, kb, xb, tr, dx, dcy[b], dlo, &ap->par[b]);
-      C2_LAUNDER(ap);
-      store_out(&ap->dout[b], opl, nproma, jk, dlo);
+      e.direction(ap, b, nproma, nlev, jk, dlo);
     }
+    e.level_end();
     cy = cy_out;
     paph_k = cur.paph_k1;
     cur = nxt;
   }
+  e.column_end(a, gcol);
+}
+
+// the Jacobian's End: direction b's sensitivities of a level go to its planes dout[b], addressed with the block strides sp
+template <unsigned F>
+struct ParJacEnd {
+  typedef Pace PaceT;
+  typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
+  LaneOff op;
+  LaneOffT<OT> opl;  // (op as used inside the level loop)
+  C2_HD void setup(TlParJacArgsP a, long long gcol, bool& active) { lane_setup(&a->g, &a->sp, gcol, op, active); }
+  C2_HD void begin(TlParJacArgsP a, ConstsP c) {
+#pragma unroll
+    for (int b = 0; b < parjac_directions(F); ++b) store_top(&a->dout[b], op, c);
+    opl = lane_off_as<OT>(op);
+  }
+  C2_HD void level_top(TlParJacArgsP, int, int) {}
+  C2_HD void direction(TlParJacArgsP& ap, int b, int nproma, int, int jk, const LevelOut& dlo) {
+    C2_LAUNDER(ap);
+    store_out(&ap->dout[b], opl, nproma, jk, dlo);
+  }
+  C2_HD void level_end() {}
+  C2_HD void column_end(TlParJacArgsP, long long) {}
+};
+
+template <unsigned F>
+C2_HD void tl_parjac_column(long long gcol, TlParJacArgsP a) {
+  static_assert(!(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32)), "flags of the parameter-Jacobian sweep: QSAT, PRECISE, EVAP, OFF32");
+  ParJacEnd<F> e;
+  par_sweep<F>(gcol, a, e);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // The Gauss-Newton normal equations of the parameters in one sweep: H = J^T W J and g = J^T W r (cloudsc2_parnormal_launch)
 // ---------------------------------------------------------------------------------------------------------
 // A Gauss-Newton or Levenberg-Marquardt step needs the 4 x 4 matrix H and the 4-vector g, never J = d out / d p itself.  This sweep
-// is tl_parjac_column with the stores replaced by sums: the NP sensitivities of a level stay in registers, the level's residual r
+// is tl_parjac_column's (par_sweep) with the stores replaced by sums: the NP sensitivities of a level stay in registers, the level's residual r
 // (model - observation) and diagonal weight w of every observed output are read, and the lane accumulates, in double in both
 // builds, H[a][b] += (w J_a) J_b for a <= b and g[a] += (w J_a) r.  The order of every sum is fixed -- levels outermost, outputs in
 // the order of struct cloudsc2_outputs -- and a lane's sums go to row `normal_row` of `work`, which a second kernel folds over the
@@ -1845,6 +1890,11 @@ constexpr int normal_sums(int np) { return np * (np + 1) / 2 + np; }
 constexpr int normal_row_h(int a, int b) { return a * PAR_COUNT - a * (a - 1) / 2 + (b - a); }
 constexpr int normal_row_g(int a) { return PAR_COUNT * (PAR_COUNT + 1) / 2 + a; }
 constexpr int kNormalObs = 8;  // the outputs that depend on a parameter: tent tenq tenl teni fplsl fplsn fhpsl fhpsn
+// THE list of them, in the order of struct cloudsc2_outputs: X(index, C2O_* bit, OutPtrs member, 1 on half levels (half level 0 is
+// store_top's zero) / 0 on full levels, row of the column-sum table).  Every list of these outputs below expands from it.
+#define C2_PAR_OUTPUTS(X)                                                                                 \
+  X(0, C2O_TENT, tent, 0, 0) X(1, C2O_TENQ, tenq, 0, 1) X(2, C2O_TENL, tenl, 0, 2) X(3, C2O_TENI, teni, 0, 3) \
+  X(4, C2O_FPLSL, fplsl, 1, 5) X(5, C2O_FPLSN, fplsn, 1, 6) X(6, C2O_FHPSL, fhpsl, 1, 7) X(7, C2O_FHPSN, fhpsn, 1, 8)
 
 // (par from the launch's direction count on is not read; resid / weight: read only, NULL members as above; sr: their block strides)
 struct ParNormalArgs {
@@ -1868,20 +1918,30 @@ C2_HD void load_obs_one(const real_t* r, const real_t* w, long long i, real_t& r
 C2_HD void load_obs(ParNormalArgsP ap, const LaneOff& o, int nproma, int jk, ObsLevel& v) {
   const OutPtrs r = ap->resid, w = ap->weight;
   const long long d = level_off(0LL, jk, nproma), d1 = d + row_off(0LL, nproma);
-  load_obs_one(r.tent, w.tent, o.loc + d, v.r[0], v.w[0]);
-  load_obs_one(r.tenq, w.tenq, o.loc + d, v.r[1], v.w[1]);
-  load_obs_one(r.tenl, w.tenl, o.loc + d, v.r[2], v.w[2]);
-  load_obs_one(r.teni, w.teni, o.loc + d, v.r[3], v.w[3]);
-  load_obs_one(r.fplsl, w.fplsl, o.half + d1, v.r[4], v.w[4]);
-  load_obs_one(r.fplsn, w.fplsn, o.half + d1, v.r[5], v.w[5]);
-  load_obs_one(r.fhpsl, w.fhpsl, o.half + d1, v.r[6], v.w[6]);
-  load_obs_one(r.fhpsn, w.fhpsn, o.half + d1, v.r[7], v.w[7]);
+#define C2_X(n, bit, field, half_level, row) load_obs_one(r.field, w.field, half_level ? o.half + d1 : o.loc + d, v.r[n], v.w[n]);
+  C2_PAR_OUTPUTS(C2_X)
+#undef C2_X
 }
 
 // one lane's sums: the upper triangle of its NP x NP block row by row, and g
 template <int NP>
 struct NormalAcc {
   double h[NP * (NP + 1) / 2], g[NP];
+  C2_HD void zero() {
+#pragma unroll
+    for (int b = 0; b < NP; ++b) g[b] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NP * (NP + 1) / 2; ++i) h[i] = 0.0;
+  }
+  // the lane's sums to `work`: consecutive lanes, consecutive doubles of each row (col < ngptot <= ncols_pad = np)
+  C2_HD void store(double* work, long long np, long long col) const {
+#pragma unroll
+    for (int ia = 0; ia < NP; ++ia) {
+#pragma unroll
+      for (int ib = ia; ib < NP; ++ib) work[normal_row_h(ia, ib) * np + col] = h[ia * NP - ia * (ia - 1) / 2 + (ib - ia)];
+      work[normal_row_g(ia) * np + col] = g[ia];
+    }
+  }
 };
 // one output of one level: j[a] = its sensitivity to parameter a.  The operands are converted before the products (fp32 build).
 template <int NP>
@@ -1907,116 +1967,50 @@ C2_HD void launder_sens(LevelOut& v) {
   C2_LAUNDER_V(v.fplsl); C2_LAUNDER_V(v.fplsn); C2_LAUNDER_V(v.fhpsl); C2_LAUNDER_V(v.fhpsn);
 }
 
+// the normal equations' End (par_sweep).  The residuals and weights of level jk are requested at its top, with the trajectory inputs of
+// level jk+1: they are used after the level's NP directions and are in flight under that arithmetic.
+template <unsigned F>
+struct ParNormalEnd {
+  static constexpr int NP = parjac_directions(F);
+  typedef NoPace PaceT;
+  LaneOff orw;
+  unsigned obs;  // which outputs are observed, bit n of C2_PAR_OUTPUTS (wave-uniform: the pointers are the argument block's)
+  ObsLevel ob;
+  LevelOut dlo[NP];
+  NormalAcc<NP> acc;
+  C2_HD void setup(ParNormalArgsP a, long long gcol, bool& active) { lane_setup(&a->g, &a->sr, gcol, orw, active); }
+  C2_HD void begin(ParNormalArgsP a, ConstsP) {
+    const OutPtrs r = a->resid;
+#define C2_X(n, bit, field, half_level, row) | (r.field ? 1u << n : 0u)
+    obs = 0u C2_PAR_OUTPUTS(C2_X);
+#undef C2_X
+    acc.zero();
+  }
+  C2_HD void level_top(ParNormalArgsP ap, int nproma, int jk) { load_obs(ap, orw, nproma, jk, ob); }
+  C2_HD void direction(ParNormalArgsP&, int b, int, int, int, const LevelOut& v) {
+    dlo[b] = v;
+    launder_sens(dlo[b]);
+  }
+  // the level's contributions, output by output in the order of struct cloudsc2_outputs (clc and covptot: exact zeros, skipped)
+  C2_HD void level_end() {
+#define C2_X(n, bit, field, half_level, row)                            \
+  if (obs & (1u << n)) {                                                \
+    real_t j[NP];                                                       \
+    _Pragma("unroll") for (int b = 0; b < NP; ++b) j[b] = dlo[b].field; \
+    normal_add<NP>(acc, j, ob.r[n], ob.w[n]);                           \
+  }
+    C2_PAR_OUTPUTS(C2_X)
+#undef C2_X
+  }
+  C2_HD void column_end(ParNormalArgsP a, long long gcol) { acc.store(a->work, a->g.ncols_pad, gcol); }
+};
+
 // F: C2F_QSAT (otherwise the trajectory's SATUR is evaluated in the sweep) | C2F_PRECISE | C2F_EVAP; 64-bit offsets always
 template <unsigned F>
 C2_HD void parnormal_column(long long gcol, ParNormalArgsP a) {
-  constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0;
-  constexpr int NP = parjac_directions(F);
   static_assert(!(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP)), "flags of the normal-equations sweep: QSAT, PRECISE, EVAP");
-  LaneOff o, orw; bool active;
-  if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
-  lane_setup(&a->g, &a->sr, gcol, orw, active);
-  if (!active) return;
-  const int nlev = a->g.nlev, nproma = a->g.nproma;
-  LevelTabP tab = (LevelTabP)a->tab;
-  ConstsP c = C2_CONSTS(a);
-  InPtrsP in = &a->in;
-
-  // once per column, not once per direction: the tropopause pre-scan, the critical-humidity setup, the lane offsets, the loads
-  real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->g, RC(0.0));
-  RhCrit rh;
-  rhcrit_setup(ztrpaus, rh);
-  real_t paph_surf = RC(0.0);
-  if (EVAP) paph_surf = in->paph[o.half + (long long)nlev * nproma];
-  // which outputs are observed (wave-uniform: the pointers are the argument block's)
-  unsigned obs;
-  {
-    const OutPtrs r = a->resid;
-    obs = (r.tent ? 1u : 0u) | (r.tenq ? 2u : 0u) | (r.tenl ? 4u : 0u) | (r.teni ? 8u : 0u) | (r.fplsl ? 16u : 0u) |
-          (r.fplsn ? 32u : 0u) | (r.fhpsl ? 64u : 0u) | (r.fhpsn ? 128u : 0u);
-  }
-
-  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
-  Carry dcy[NP];
-  NormalAcc<NP> acc;
-#pragma unroll
-  for (int b = 0; b < NP; ++b) {
-    dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0);
-    acc.g[b] = 0.0;
-  }
-#pragma unroll
-  for (int i = 0; i < NP * (NP + 1) / 2; ++i) acc.h[i] = 0.0;
-  RawLevel cur, nxt;
-  real_t paph_k = in->paph[o.half];
-  load_level<HAS_QSAT>(in, o, nproma, nlev, 0, cur);
-
-  // The trajectory inputs of level jk+1 are requested at the top of level jk, as in tl_parjac_column, and with them the residuals and
-  // weights of level jk itself: they are used after the level's NP directions and are in flight under that arithmetic.
-  for (int jk = 0; jk < nlev; ++jk) {
-    const bool last = (jk == nlev - 1);
-    ParNormalArgsP ap = a;
-    C2_LAUNDER(ap);
-    nxt = cur;
-    if (!last) load_level<HAS_QSAT>(&ap->in, o, nproma, nlev, jk + 1, nxt);
-    ObsLevel ob;
-    load_obs(ap, orw, nproma, jk, ob);
-    if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);  // (once per level: every direction gets its own opaque copy)
-
-    LevelCst k;
-    level_cst(tab, jk, last, k);
-    LevelIn x;
-    make_level_in(cur, paph_k, paph_surf, x);
-    Carry cy_out = cy;
-    LevelOut dlo[NP];
-#pragma unroll
-    for (int b = 0; b < NP; ++b) {
-      // this direction's own straight line (launder_level says why): every direction leaves the same trajectory carry
-      LevelIn xb = x;
-      LevelCst kb = k;
-      RhCrit rhb = rh;
-      cy_out = cy;
-      launder_level(xb, kb, cy_out);
-      C2_LAUNDER_V(xb.paph_surf); C2_LAUNDER_V(rhb.zeta3); C2_LAUNDER_V(rhb.zrh2); C2_LAUNDER_V(rhb.zdeta1);
-      ConstsP cb = c;  // (and its own view of the constants: a product of two of them is shared otherwise)
-      C2_LAUNDER(cb);
-      LevelTraj tr;
-      LevelOut lo;
-      level_forward<P, EVAP>(cb, kb, rhb, xb, cy_out, tr, lo);
-      LevelIn dx;
-      zero_level_in<EVAP>(dx);
-      C2_LAUNDER(ap);
-      level_tl<true>(cb, kb, xb, tr, dx, dcy[b], dlo[b], &ap->par[b]);
-      launder_sens(dlo[b]);
-    }
-    // the level's contributions, output by output in the order of struct cloudsc2_outputs (clc and covptot: exact zeros, skipped)
-#define C2_NORMAL_ADD(bit, field)                          \
-  if (obs & (1u << (bit))) {                               \
-    real_t j[NP];                                          \
-    _Pragma("unroll") for (int b = 0; b < NP; ++b) j[b] = dlo[b].field; \
-    normal_add<NP>(acc, j, ob.r[bit], ob.w[bit]);          \
-  }
-    C2_NORMAL_ADD(0, tent)
-    C2_NORMAL_ADD(1, tenq)
-    C2_NORMAL_ADD(2, tenl)
-    C2_NORMAL_ADD(3, teni)
-    C2_NORMAL_ADD(4, fplsl)
-    C2_NORMAL_ADD(5, fplsn)
-    C2_NORMAL_ADD(6, fhpsl)
-    C2_NORMAL_ADD(7, fhpsn)
-#undef C2_NORMAL_ADD
-    cy = cy_out;
-    paph_k = cur.paph_k1;
-    cur = nxt;
-  }
-  // the lane's sums: consecutive lanes, consecutive doubles of each row (gcol < ngptot <= ncols_pad)
-  double* work = a->work;
-  const long long np = a->g.ncols_pad;
-#pragma unroll
-  for (int ia = 0; ia < NP; ++ia) {
-#pragma unroll
-    for (int ib = ia; ib < NP; ++ib) work[normal_row_h(ia, ib) * np + gcol] = acc.h[ia * NP - ia * (ia - 1) / 2 + (ib - ia)];
-    work[normal_row_g(ia) * np + gcol] = acc.g[ia];
-  }
+  ParNormalEnd<F> e;
+  par_sweep<F>(gcol, a, e);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2025,7 +2019,7 @@ C2_HD void parnormal_column(long long gcol, ParNormalArgsP a) {
 // ---------------------------------------------------------------------------------------------------------
 // A cloud scheme is confronted with column sums y_n[c] = sum_k w_n[k] out_n[k, c] (surface rain and snow, column-integrated heating).
 // Their sensitivities s[a][n][c] = sum_k w_n[k] (d out_n / d p_a)[k, c] need nothing but tl_parjac_column's level loop: this sweep is
-// that loop with store_out replaced by a fold of direction a's sensitivities into the lane's accumulators acc[a][n], the fold of
+// that loop (par_sweep) with store_out replaced by a fold of direction a's sensitivities into the lane's accumulators acc[a][n], the fold of
 // ColsumAcc::add to the bit: acc = fl(acc + fl(w_n[k] J)), the level's sensitivities pinned before the fold and the product laundered
 // before its add, half level 0 of a flux skipped.  No sensitivity plane exists.  clc and covptot depend on no parameter: they have no
 // accumulator and their rows of the table are not read.  The accumulators live in LDS, one slot per lane, direction and sum (up to
@@ -2084,144 +2078,66 @@ C2_HD void parcolsum_fold(ParColsumAcc<NP>& acc, int b, ColsumTabP cs, unsigned 
   C2_PIN_V(v.covptot); C2_PIN_V(v.fplsl); C2_PIN_V(v.fplsn); C2_PIN_V(v.fhpsl); C2_PIN_V(v.fhpsn);
   const ColsumRowP w = (ColsumRowP)cs->w + jk;
   const int r = nlev + 1;
-  if (m & C2O_TENT) acc.add(b, 0, w[0 * r], v.tent);
-  if (m & C2O_TENQ) acc.add(b, 1, w[1 * r], v.tenq);
-  if (m & C2O_TENL) acc.add(b, 2, w[2 * r], v.tenl);
-  if (m & C2O_TENI) acc.add(b, 3, w[3 * r], v.teni);
-  if (m & C2O_FPLSL) acc.add(b, 4, w[5 * r + 1], v.fplsl);
-  if (m & C2O_FPLSN) acc.add(b, 5, w[6 * r + 1], v.fplsn);
-  if (m & C2O_FHPSL) acc.add(b, 6, w[7 * r + 1], v.fhpsl);
-  if (m & C2O_FHPSN) acc.add(b, 7, w[8 * r + 1], v.fhpsn);
+#define C2_X(n, bit, field, half_level, row) if (m & bit) acc.add(b, n, w[row * r + half_level], v.field);
+  C2_PAR_OUTPUTS(C2_X)
+#undef C2_X
 }
 
-// F: C2F_QSAT (otherwise the trajectory's SATUR is evaluated in the sweep) | C2F_PRECISE | C2F_EVAP | C2F_OFF32 | C2F_NORMAL
+// the column sums' End (par_sweep): nothing but the trajectory is read in the level loop
 template <unsigned F>
-C2_HD void parcolsum_column(long long gcol, ParColsumArgsP a) {
-  constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0, NORMAL = (F & C2F_NORMAL) != 0;
-  constexpr int NP = parjac_directions(F);
-  static_assert(!(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32 | C2F_NORMAL)),
-                "flags of the parameter column-sum sweep: QSAT, PRECISE, EVAP, OFF32, NORMAL");
-  typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
-  LaneOff o; bool active;
-  if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
-  if (!active) return;
-  const int nlev = a->g.nlev, nproma = a->g.nproma;
-  LevelTabP tab = (LevelTabP)a->tab;
-  ConstsP c = C2_CONSTS(a);
-  InPtrsP in = &a->in;
-
-  // once per column, not once per direction: the tropopause pre-scan, the critical-humidity setup, the lane offsets, the loads
-  real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->g, RC(0.0));
-  RhCrit rh;
-  rhcrit_setup(ztrpaus, rh);
-  real_t paph_surf = RC(0.0);
-  if (EVAP) paph_surf = in->paph[o.half + (long long)nlev * nproma];
-
-  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
-  Carry dcy[NP];
-#pragma unroll
-  for (int b = 0; b < NP; ++b) { dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0); }
+struct ParColsumEnd {
+  static constexpr int NP = parjac_directions(F);
+  typedef NoPace PaceT;
   ParColsumAcc<NP> acc;
-  acc.begin();
-  RawLevel cur, nxt;
-  real_t paph_k = in->paph[o.half];
-  const LaneOffT<OT> ol = lane_off_as<OT>(o);  // offsets used inside the level loop
-  load_level<HAS_QSAT>(in, ol, nproma, nlev, 0, cur);
-
-  // The trajectory inputs of level jk+1 are requested at the top of level jk, as in tl_parjac_column; nothing else is read.
-  for (int jk = 0; jk < nlev; ++jk) {
-    const bool last = (jk == nlev - 1);
-    ParColsumArgsP ap = a;
+  C2_HD void setup(ParColsumArgsP, long long, bool&) {}
+  C2_HD void begin(ParColsumArgsP, ConstsP) { acc.begin(); }
+  C2_HD void level_top(ParColsumArgsP, int, int) {}
+  C2_HD void direction(ParColsumArgsP& ap, int b, int, int nlev, int jk, const LevelOut& dlo) {
     C2_LAUNDER(ap);
-    nxt = cur;
-    if (!last) load_level<HAS_QSAT>(&ap->in, ol, nproma, nlev, jk + 1, nxt);
-    if (!HAS_QSAT) cur.qsat = satur_point<P>(c, cur.pap, cur.t);  // (once per level: every direction gets its own opaque copy)
-
-    LevelCst k;
-    level_cst(tab, jk, last, k);
-    LevelIn x;
-    make_level_in(cur, paph_k, paph_surf, x);
-    Carry cy_out = cy;
-#pragma unroll
-    for (int b = 0; b < NP; ++b) {
-      // this direction's own straight line (launder_level says why): every direction leaves the same trajectory carry
-      LevelIn xb = x;
-      LevelCst kb = k;
-      RhCrit rhb = rh;
-      cy_out = cy;
-      launder_level(xb, kb, cy_out);
-      C2_LAUNDER_V(xb.paph_surf); C2_LAUNDER_V(rhb.zeta3); C2_LAUNDER_V(rhb.zrh2); C2_LAUNDER_V(rhb.zdeta1);
-      ConstsP cb = c;  // (and its own view of the constants: a product of two of them is shared otherwise)
-      C2_LAUNDER(cb);
-      LevelTraj tr;
-      LevelOut lo;
-      level_forward<P, EVAP>(cb, kb, rhb, xb, cy_out, tr, lo);
-      LevelIn dx;
-      zero_level_in<EVAP>(dx);
-      LevelOut dlo;
-      C2_LAUNDER(ap);
-      level_tl<true>(cb, kb, xb, tr, dx, dcy[b], dlo, &ap->par[b]);
-      C2_LAUNDER(ap);
-      parcolsum_fold<NP>(acc, b, &ap->cs, ap->cs.mask, nlev, jk, dlo);
-    }
-    cy = cy_out;
-    paph_k = cur.paph_k1;
-    cur = nxt;
+    parcolsum_fold<NP>(acc, b, &ap->cs, ap->cs.mask, nlev, jk, dlo);
   }
-
-  const unsigned m = a->cs.mask;
-  const long long col = acc.column(gcol);
-  const long long ocs = colsum_off(&a->g, &a->cs, col);
-  if constexpr (!NORMAL) {
-    // one row per run parameter and sum present (clc, covptot: the exact zero)
+  C2_HD void level_end() {}
+  C2_HD void column_end(ParColsumArgsP a, long long gcol) {
+    const unsigned m = a->cs.mask;
+    const long long col = acc.column(gcol);
+    const long long ocs = colsum_off(&a->g, &a->cs, col);
+    if constexpr (!(F & C2F_NORMAL)) {
+      // one row per run parameter and sum present (clc, covptot: the exact zero)
 #pragma unroll
-    for (int b = 0; b < NP; ++b) {
-      const OutPtrs y = a->y[b];
-      if (m & C2O_TENT) y.tent[ocs] = acc.get(b, 0);
-      if (m & C2O_TENQ) y.tenq[ocs] = acc.get(b, 1);
-      if (m & C2O_TENL) y.tenl[ocs] = acc.get(b, 2);
-      if (m & C2O_TENI) y.teni[ocs] = acc.get(b, 3);
-      if (m & C2O_CLC) y.clc[ocs] = RC(0.0);
-      if (m & C2O_FPLSL) y.fplsl[ocs] = acc.get(b, 4);
-      if (m & C2O_FPLSN) y.fplsn[ocs] = acc.get(b, 5);
-      if (m & C2O_FHPSL) y.fhpsl[ocs] = acc.get(b, 6);
-      if (m & C2O_FHPSN) y.fhpsn[ocs] = acc.get(b, 7);
-      if (m & C2O_COVPTOT) y.covptot[ocs] = RC(0.0);
-    }
-  } else {
-    NormalAcc<NP> na;
-#pragma unroll
-    for (int b = 0; b < NP; ++b) na.g[b] = 0.0;
-#pragma unroll
-    for (int i = 0; i < NP * (NP + 1) / 2; ++i) na.h[i] = 0.0;
-    const OutPtrs r = a->y[0], w = a->y[1];
-    // the observed sums in the order of struct cloudsc2_outputs (clc and covptot: exact zeros, their residuals are not read)
-#define C2_PARCOLSUM_ADD(bit, n, field)                                   \
-  if (m & (bit)) {                                                        \
+      for (int b = 0; b < NP; ++b) {
+        const OutPtrs y = a->y[b];
+#define C2_X(n, bit, field, half_level, row) if (m & bit) y.field[ocs] = acc.get(b, n);
+        C2_PAR_OUTPUTS(C2_X)
+#undef C2_X
+        if (m & C2O_CLC) y.clc[ocs] = RC(0.0);
+        if (m & C2O_COVPTOT) y.covptot[ocs] = RC(0.0);
+      }
+    } else {
+      NormalAcc<NP> na;
+      na.zero();
+      const OutPtrs r = a->y[0], w = a->y[1];
+      // the observed sums in the order of struct cloudsc2_outputs (clc and covptot: exact zeros, their residuals are not read)
+#define C2_X(n, bit, field, half_level, row)                              \
+  if (m & bit) {                                                          \
     real_t j[NP], rv, wv;                                                 \
     _Pragma("unroll") for (int b = 0; b < NP; ++b) j[b] = acc.get(b, n);  \
     load_obs_one(r.field, w.field, ocs, rv, wv);                          \
     normal_add<NP>(na, j, rv, wv);                                        \
   }
-    C2_PARCOLSUM_ADD(C2O_TENT, 0, tent)
-    C2_PARCOLSUM_ADD(C2O_TENQ, 1, tenq)
-    C2_PARCOLSUM_ADD(C2O_TENL, 2, tenl)
-    C2_PARCOLSUM_ADD(C2O_TENI, 3, teni)
-    C2_PARCOLSUM_ADD(C2O_FPLSL, 4, fplsl)
-    C2_PARCOLSUM_ADD(C2O_FPLSN, 5, fplsn)
-    C2_PARCOLSUM_ADD(C2O_FHPSL, 6, fhpsl)
-    C2_PARCOLSUM_ADD(C2O_FHPSN, 7, fhpsn)
-#undef C2_PARCOLSUM_ADD
-    // the lane's sums: consecutive lanes, consecutive doubles of each row (col < ngptot <= ncols_pad)
-    double* work = a->work;
-    const long long np = a->g.ncols_pad;
-#pragma unroll
-    for (int ia = 0; ia < NP; ++ia) {
-#pragma unroll
-      for (int ib = ia; ib < NP; ++ib) work[normal_row_h(ia, ib) * np + col] = na.h[ia * NP - ia * (ia - 1) / 2 + (ib - ia)];
-      work[normal_row_g(ia) * np + col] = na.g[ia];
+      C2_PAR_OUTPUTS(C2_X)
+#undef C2_X
+      na.store(a->work, a->g.ncols_pad, col);
     }
   }
+};
+
+// F: C2F_QSAT (otherwise the trajectory's SATUR is evaluated in the sweep) | C2F_PRECISE | C2F_EVAP | C2F_OFF32 | C2F_NORMAL
+template <unsigned F>
+C2_HD void parcolsum_column(long long gcol, ParColsumArgsP a) {
+  static_assert(!(F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP | C2F_OFF32 | C2F_NORMAL)),
+                "flags of the parameter column-sum sweep: QSAT, PRECISE, EVAP, OFF32, NORMAL");
+  ParColsumEnd<F> e;
+  par_sweep<F>(gcol, a, e);
 }
 
 template <class OT>

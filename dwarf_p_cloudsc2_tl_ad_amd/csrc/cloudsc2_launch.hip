@@ -750,6 +750,21 @@ void unit_parlins(ParLin* par, const Consts& c, int np) {
     par[b] = make_parlin(c, e);
   }
 }
+// the directions a parameter sweep runs: without the evaporation branch nothing depends on rpecons (parjac_directions of the kernel's flags)
+int par_directions(const cloudsc2_params* prm) { return (prm->levapls2 || prm->ldrain1d) ? (int)PAR_COUNT : (int)PAR_COUNT - 1; }
+// What the launchers of the three parameter sweeps share once their own blocks are resolved (tl_parjac, parnormal, parcolsum: argument
+// blocks with c g s in par tab): geometry, tables, constants and flags, then the block's common members and the unit ParLin of
+// every run direction.  `more`: Sweep::finish's.
+template <class Args>
+int par_sweep_args(Sweep& w, const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
+                   std::initializer_list<long long> more, Args& a) {
+  int rc = w.begin(prm, nproma, nlev, ngptot, nullptr);
+  if (!rc) rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, more);
+  if (rc) return rc;
+  a.c = w.c; a.g = w.g; a.s = w.s; a.in = w.in; a.tab = w.tab;
+  unit_parlins(a.par, w.c, par_directions(prm));
+  return 0;
+}
 
 int work_doubles(int rows, int nproma, int ngptot, long long* n) {  // rows x the padded column count
   if (nproma < 1 || ngptot < 1 || !n) return fail(CLOUDSC2_EINVAL, "nproma >= 1, ngptot >= 1 and a result pointer required");
@@ -1513,7 +1528,7 @@ int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int npr
   if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "parameter Jacobian: CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
   int rc = check_rpecons(prm);
   if (rc) return rc;
-  const int np = (prm->levapls2 || prm->ldrain1d) ? (int)PAR_COUNT : (int)PAR_COUNT - 1;
+  const int np = par_directions(prm);
   Sweep w;
   if ((rc = resolve_in(*traj_in, false, w.s, w.in))) return rc;
   memset(&w.out, 0, sizeof(w.out));
@@ -1525,10 +1540,8 @@ int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int npr
     if (b == 0) sp = sb;
     else if (!same_strides(sp, sb)) return fail(CLOUDSC2_EINVAL, "parameter Jacobian: every block must have the same block stride per layout group");
   }
-  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
-  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sp.full, sp.half, sp.loc}))) return rc;
-  args.c = w.c; args.g = w.g; args.s = w.s; args.sp = sp; args.in = w.in; args.tab = w.tab;
-  unit_parlins(args.par, w.c, np);
+  if ((rc = par_sweep_args(w, prm, ptsphy, nproma, nlev, ngptot, traj_in, {sp.full, sp.half, sp.loc}, args))) return rc;
+  args.sp = sp;
   for (int b = np; b < kBatchMax; ++b) args.dout[b] = args.dout[0];  // (not read: valid pointers all the same)
   const KernelFn<TlParJacArgs> fn = tl_parjac_variant(w.f);
   schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
@@ -1539,6 +1552,19 @@ int cloudsc2_tl_launch_parjac(const cloudsc2_params* prm, double ptsphy, int npr
 // J ever existing in memory (parnormal_column sums each column in registers; the fold of cloudsc2_vjp_launch_par adds the columns).
 // Two kernel nodes, both launched directly: this is not a sweep family (no family number, no pacing, no launch-log entry).
 static_assert(CLOUDSC2_NNORMAL == normal_sums(PAR_COUNT) && CLOUDSC2_NNORMAL <= 32, "rows of the workspace: one bit each in the fold's mask");
+// the CLOUDSC2_NNORMAL rows of `work` folded over the columns into `normal` (both normal-equation launchers)
+static int fold_normal(const Geom& g, bool evap, const double* work, double* normal, hipStream_t st) {
+  const long long n = g.ncols_pad;
+  if (evap) {
+    hipLaunchKernelGGL(par_fold_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, work, n, (long long)g.ngptot, normal);
+  } else {  // the rows with rpecons were not written: not read, stored as zeros
+    unsigned unwritten = 1u << normal_row_g(PAR_RPECONS);
+    for (int a = 0; a < PAR_COUNT; ++a) unwritten |= 1u << normal_row_h(a, PAR_RPECONS);
+    hipLaunchKernelGGL(par_fold_rows_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, work, n, (long long)g.ngptot, unwritten, normal);
+  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
 int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,
                               const cloudsc2_outputs* resid, const cloudsc2_outputs* weight, double* work, double* normal, void* stream) {
   // (what is wrong with the call itself is reported before the device is looked for: CLOUDSC2_EINVAL with or without one)
@@ -1546,7 +1572,6 @@ int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int npr
   if (!prm->lphylin) return fail(CLOUDSC2_EINVAL, "normal equations: CLOUDSC2TL linearises the LPHYLIN form only (prm->lphylin = 0)");
   int rc = check_rpecons(prm);
   if (rc) return rc;
-  const bool evap = prm->levapls2 || prm->ldrain1d;
   Sweep w;
   if ((rc = resolve_in(*traj_in, false, w.s, w.in))) return rc;
   memset(&w.out, 0, sizeof(w.out));
@@ -1566,28 +1591,15 @@ int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int npr
   if ((rc = resolve_out(*resid, false, sr, args.resid)) || (rc = resolve_out(wt, false, sw, args.weight))) return rc;
   if ((weighted[kLoc] && sw.loc != sr.loc) || (weighted[kFull] && sw.full != sr.full) || (weighted[kHalf] && sw.half != sr.half))
     return fail(CLOUDSC2_EINVAL, "normal equations: residuals and weights must have the same block stride per layout group");
-  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
-  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {sr.full, sr.half, sr.loc}))) return rc;
+  if ((rc = par_sweep_args(w, prm, ptsphy, nproma, nlev, ngptot, traj_in, {sr.full, sr.half, sr.loc}, args))) return rc;
   const unsigned f = w.f & ~C2F_OFF32;  // (64-bit offsets always: a 32-bit form is not built)
-  args.c = w.c; args.g = w.g; args.s = w.s; args.sr = sr; args.in = w.in; args.tab = w.tab; args.work = work;
-  unit_parlins(args.par, w.c, evap ? (int)PAR_COUNT : (int)PAR_COUNT - 1);
+  args.sr = sr; args.work = work;
   const KernelFn<ParNormalArgs> fn = parnormal_variant(f);
   if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(args.g, nullptr, false, nullptr);
-  const hipStream_t st = (hipStream_t)stream;
-  const long long n = w.g.ncols_pad;
   void* argv[] = {&args};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(n, kBlock)), dim3(kBlock), argv, 0, st));
-  if (evap) {
-    hipLaunchKernelGGL(par_fold_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)w.g.ngptot, normal);
-  } else {  // the rows with rpecons were not written: not read, stored as zeros
-    unsigned unwritten = 1u << normal_row_g(PAR_RPECONS);
-    for (int a = 0; a < PAR_COUNT; ++a) unwritten |= 1u << normal_row_h(a, PAR_RPECONS);
-    hipLaunchKernelGGL(par_fold_rows_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)w.g.ngptot,
-                       unwritten, normal);
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
+  return fold_normal(w.g, w.c.evap, work, normal, (hipStream_t)stream);
 }
 
 // ---- the parameter Jacobian and the normal equations of the column sums (parcolsum_column) ------------------------------------------------
@@ -1602,11 +1614,8 @@ static int parcolsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
   int rc;
   if ((rc = resolve_in(*traj_in, false, w.s, w.in))) return rc;
   memset(&w.out, 0, sizeof(w.out));
-  if ((rc = w.begin(prm, nproma, nlev, ngptot, nullptr))) return rc;
-  if ((rc = w.finish(*prm, ptsphy, traj_in->qsat.ptr, {args.cs.stride}))) return rc;
-  args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.tab = w.tab;
+  if ((rc = par_sweep_args(w, prm, ptsphy, nproma, nlev, ngptot, traj_in, {args.cs.stride}, args))) return rc;
   args.cs.w = wtable;
-  unit_parlins(args.par, w.c, w.c.evap ? (int)PAR_COUNT : (int)PAR_COUNT - 1);
   const KernelFn<ParColsumArgs> fn = parcolsum_variant(w.f | form);
   if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(args.g, nullptr, false, nullptr);
@@ -1629,7 +1638,7 @@ static int parjac_colsum_impl(const cloudsc2_params* prm, double ptsphy, int npr
   if (!prm || !traj_in || !sens_sums) return fail(CLOUDSC2_EINVAL, "NULL argument block");
   int rc = check_parcolsum(prm, nproma, nlev, ngptot, wtable);
   if (rc) return rc;
-  const int np = (prm->levapls2 || prm->ldrain1d) ? (int)PAR_COUNT : (int)PAR_COUNT - 1;
+  const int np = par_directions(prm);
   ParColsumArgs args;
   memset(&args, 0, sizeof(args));
   unsigned mask = 0u;
@@ -1655,7 +1664,6 @@ static int parnormal_colsum_impl(const cloudsc2_params* prm, double ptsphy, int 
   if (!prm || !traj_in || !resid || !work || !normal) return fail(CLOUDSC2_EINVAL, "NULL argument block, workspace or result");
   int rc = check_parcolsum(prm, nproma, nlev, ngptot, wtable);
   if (rc) return rc;
-  const bool evap = prm->levapls2 || prm->ldrain1d;
   const cloudsc2_outputs none = {};
   const cloudsc2_outputs& wt = weight ? *weight : none;
   const cloudsc2_field *rf = fields_of(*resid), *wf = fields_of(wt);
@@ -1675,18 +1683,7 @@ static int parnormal_colsum_impl(const cloudsc2_params* prm, double ptsphy, int 
   memset(&args.cs.y, 0, sizeof(args.cs.y));
   args.work = work;
   if ((rc = parcolsum_impl(prm, ptsphy, nproma, nlev, ngptot, traj_in, wtable, args, C2F_NORMAL, stream))) return rc;
-  const hipStream_t st = (hipStream_t)stream;
-  const long long n = args.g.ncols_pad;
-  if (evap) {
-    hipLaunchKernelGGL(par_fold_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)args.g.ngptot, normal);
-  } else {  // the rows with rpecons were not written: not read, stored as zeros
-    unsigned unwritten = 1u << normal_row_g(PAR_RPECONS);
-    for (int a = 0; a < PAR_COUNT; ++a) unwritten |= 1u << normal_row_h(a, PAR_RPECONS);
-    hipLaunchKernelGGL(par_fold_rows_kernel, dim3(CLOUDSC2_NNORMAL), dim3(kParFoldBlock), 0, st, (const double*)work, n, (long long)args.g.ngptot,
-                       unwritten, normal);
-  }
-  HIP_TRY(hipGetLastError());
-  return 0;
+  return fold_normal(args.g, args.c.evap, work, normal, (hipStream_t)stream);
 }
 
 int cloudsc2_parjac_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* traj_in,

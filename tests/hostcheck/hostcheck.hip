@@ -1,6 +1,8 @@
 // TEST-ONLY: compiles the per-column device functions of csrc/cloudsc2_column.hpp for the HOST (hipcc
 // --cuda-host-only) so that their logic can be unit-tested against the oracle in a container without a GPU.
 // This library is never loaded by the package, the bench or the C ABI; the product has no CPU path.
+#ifndef CLOUDSC2_HOSTCHECK_HIP
+#define CLOUDSC2_HOSTCHECK_HIP
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -11,6 +13,7 @@
 using namespace cloudsc2;
 
 static Consts hc_consts(const cloudsc2_params& p, double ptsphy) { return make_consts(p, ptsphy); }
+static int hc_par_directions(const Consts& c) { return c.evap ? PAR_COUNT : PAR_COUNT - 1; }  // (parjac_directions of the flag word)
 
 // run-time flag word -> compile-time variant
 template <template <unsigned> class Fn, unsigned N, unsigned F = 0, class A>
@@ -92,6 +95,27 @@ static int g_hc_assign = 0;
 static double* g_hc_yy = nullptr;      // TL self-increment form: receives <y,y> per column
 static double* g_hc_ad_norms = nullptr;  // AD: (3, ncols_pad), row 0 = norm1; reverse sweep alone in the assign form with the norms formed in it
 static double g_hc_supsat_inc = -1.0;  // >= 0: hostcheck_tl runs the self-increment form with this PSUPSAT factor
+
+// The head the host builds of the three parameter sweeps share (hostcheck_parjac.hip, hostcheck_parnormal.hip, hostcheck_parcolsum.hip:
+// argument blocks with c g s in par tab): the block cleared, geometry, constants, tables (`tab` lives in the caller), the trajectory's
+// inputs and the unit ParLin of every run direction.  Returns the sweep's flag word: QSAT when in->qsat is given, PRECISE, EVAP.
+template <class Args>
+static unsigned hc_par_head(Args& a, LevelTab& tab, const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
+                            const cloudsc2_inputs* in) {
+  memset(&a, 0, sizeof(a));
+  a.g = hc_geom(nproma, nlev, ngptot);
+  a.c = hc_consts(*prm, ptsphy);
+  hc_tables(*prm, tab, a.g);
+  a.tab = &tab;
+  a.s = Strides{0, 0, 0, 0, 0};
+  hc_in(*in, a.s, a.in);
+  for (int b = 0; b < hc_par_directions(a.c); ++b) {
+    double e[PAR_COUNT] = {};
+    e[b] = 1.0;
+    a.par[b] = make_parlin(a.c, e);
+  }
+  return (in->qsat.ptr ? C2F_QSAT : 0u) | (g_hc_precise ? C2F_PRECISE : 0u) | (a.c.evap ? C2F_EVAP : 0u);
+}
 
 extern "C" {
 
@@ -204,3 +228,5 @@ int hostcheck_taylor_sweep(const cloudsc2_params* prm, double ptsphy, int nproma
 }
 
 }  // extern "C"
+
+#endif  // CLOUDSC2_HOSTCHECK_HIP

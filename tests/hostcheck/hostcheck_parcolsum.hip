@@ -23,26 +23,7 @@ static unsigned hc_parcolsum_block(const cloudsc2_outputs& blk, OutPtrs& y, long
   return mask;
 }
 
-static void hc_parcolsum_head(ParColsumArgs& a, LevelTab& tab, const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot,
-                              const cloudsc2_inputs* in, const cloudsc2_real* wtable) {
-  memset(&a, 0, sizeof(a));
-  a.g = hc_geom(nproma, nlev, ngptot);
-  a.c = hc_consts(*prm, ptsphy);
-  hc_tables(*prm, tab, a.g);
-  a.tab = &tab;
-  a.s = Strides{0, 0, 0, 0, 0};
-  hc_in(*in, a.s, a.in);
-  a.cs.w = wtable;
-  const int np = a.c.evap ? PAR_COUNT : PAR_COUNT - 1;
-  for (int b = 0; b < np; ++b) {
-    double e[PAR_COUNT] = {};
-    e[b] = 1.0;
-    a.par[b] = make_parlin(a.c, e);
-  }
-}
-
-static void hc_parcolsum_run(const ParColsumArgs& a, const cloudsc2_inputs* in, unsigned form) {
-  const unsigned f = (in->qsat.ptr ? C2F_QSAT : 0u) | (g_hc_precise ? C2F_PRECISE : 0u) | (a.c.evap ? C2F_EVAP : 0u) | form;
+static void hc_parcolsum_run(const ParColsumArgs& a, unsigned f) {
   for (long long gc = 0; gc < a.g.ncols_pad; ++gc) hc_dispatch<HcParColsum, 16>(f, gc, &a);
 }
 
@@ -55,15 +36,15 @@ int hostcheck_parjac_colsum(const cloudsc2_params* prm, double ptsphy, int nprom
                             const cloudsc2_real* wtable, const cloudsc2_outputs* sums) {
   ParColsumArgs a;
   LevelTab tab;
-  hc_parcolsum_head(a, tab, prm, ptsphy, nproma, nlev, ngptot, in, wtable);
-  const int np = a.c.evap ? PAR_COUNT : PAR_COUNT - 1;
-  for (int b = 0; b < np; ++b) {
+  const unsigned f = hc_par_head(a, tab, prm, ptsphy, nproma, nlev, ngptot, in);
+  a.cs.w = wtable;
+  for (int b = 0; b < hc_par_directions(a.c); ++b) {
     const unsigned m = hc_parcolsum_block(sums[b], a.y[b], a.cs.stride);
     if (b == 0) a.cs.mask = m;
     else if (m != a.cs.mask) return -1;
   }
   if (!a.cs.mask) return -1;
-  hc_parcolsum_run(a, in, 0u);
+  hc_parcolsum_run(a, f);
   return 0;
 }
 
@@ -73,12 +54,13 @@ int hostcheck_parnormal_colsum(const cloudsc2_params* prm, double ptsphy, int np
                                const cloudsc2_real* wtable, const cloudsc2_outputs* resid, const cloudsc2_outputs* weight, double* work) {
   ParColsumArgs a;
   LevelTab tab;
-  hc_parcolsum_head(a, tab, prm, ptsphy, nproma, nlev, ngptot, in, wtable);
+  const unsigned f = hc_par_head(a, tab, prm, ptsphy, nproma, nlev, ngptot, in);
+  a.cs.w = wtable;
   if (!(a.cs.mask = hc_parcolsum_block(*resid, a.y[0], a.cs.stride))) return -1;
   long long unused = 0;
   if (weight) hc_parcolsum_block(*weight, a.y[1], unused);
   a.work = work;
-  hc_parcolsum_run(a, in, C2F_NORMAL);
+  hc_parcolsum_run(a, f | C2F_NORMAL);
   return 0;
 }
 

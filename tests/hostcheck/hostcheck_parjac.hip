@@ -16,22 +16,12 @@ extern "C" {
 int hostcheck_tl_parjac(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* in,
                         const cloudsc2_outputs* dout) {
   TlParJacArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g = hc_geom(nproma, nlev, ngptot);
-  a.c = hc_consts(*prm, ptsphy);
-  LevelTab tab; hc_tables(*prm, tab, a.g);
-  a.tab = &tab;
-  a.s = Strides{0, 0, 0, 0, 0}; a.sp = Strides{0, 0, 0, 0, 0};
-  hc_in(*in, a.s, a.in);
-  const int np = a.c.evap ? PAR_COUNT : PAR_COUNT - 1;
-  for (int b = 0; b < np; ++b) {
-    double e[PAR_COUNT] = {};
-    e[b] = 1.0;
-    a.par[b] = make_parlin(a.c, e);
+  LevelTab tab;
+  const unsigned f = hc_par_head(a, tab, prm, ptsphy, nproma, nlev, ngptot, in);
+  for (int b = 0; b < hc_par_directions(a.c); ++b) {
     hc_out(dout[b], a.sp, a.dout[b]);
     a.sp.full = dout[b].clc.block_stride; a.sp.half = dout[b].fplsl.block_stride;
   }
-  const unsigned f = (in->qsat.ptr ? C2F_QSAT : 0u) | (g_hc_precise ? C2F_PRECISE : 0u) | (a.c.evap ? C2F_EVAP : 0u);
   for (long long gc = 0; gc < a.g.ncols_pad; ++gc) hc_dispatch<HcTlParJac, 8>(f, gc, &a);
   return 0;
 }

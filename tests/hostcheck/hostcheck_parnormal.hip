@@ -17,13 +17,8 @@ extern "C" {
 int hostcheck_parnormal(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* in,
                         const cloudsc2_outputs* resid, const cloudsc2_outputs* weight, double* work) {
   ParNormalArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g = hc_geom(nproma, nlev, ngptot);
-  a.c = hc_consts(*prm, ptsphy);
-  LevelTab tab; hc_tables(*prm, tab, a.g);
-  a.tab = &tab;
-  a.s = Strides{0, 0, 0, 0, 0}; a.sr = Strides{0, 0, 0, 0, 0};
-  hc_in(*in, a.s, a.in);
+  LevelTab tab;
+  const unsigned f = hc_par_head(a, tab, prm, ptsphy, nproma, nlev, ngptot, in);
   hc_out(*resid, a.sr, a.resid);
   // (one block stride per layout group, taken from whichever member is observed)
   a.sr.loc = resid->tent.ptr ? resid->tent.block_stride : resid->tenq.ptr ? resid->tenq.block_stride
@@ -32,14 +27,7 @@ int hostcheck_parnormal(const cloudsc2_params* prm, double ptsphy, int nproma, i
               : resid->fhpsl.ptr ? resid->fhpsl.block_stride : resid->fhpsn.block_stride;
   a.sr.full = resid->clc.ptr ? resid->clc.block_stride : resid->covptot.block_stride;
   if (weight) { Strides unused = {0, 0, 0, 0, 0}; hc_out(*weight, unused, a.weight); }
-  const int np = a.c.evap ? PAR_COUNT : PAR_COUNT - 1;
-  for (int b = 0; b < np; ++b) {
-    double e[PAR_COUNT] = {};
-    e[b] = 1.0;
-    a.par[b] = make_parlin(a.c, e);
-  }
   a.work = work;
-  const unsigned f = (in->qsat.ptr ? C2F_QSAT : 0u) | (g_hc_precise ? C2F_PRECISE : 0u) | (a.c.evap ? C2F_EVAP : 0u);
   for (long long gc = 0; gc < a.g.ncols_pad; ++gc) hc_dispatch<HcParNormal, 8>(f, gc, &a);
   return 0;
 }

@@ -16,12 +16,7 @@
 
 #include "hostcheck_parcolsum.hip"
 
-// hostcheck_parjac.hip's sweep (that file includes hostcheck.hip itself, which has no include guard)
-template <unsigned F> struct HcTlParJacA {
-  static void run(long long gc, const TlParJacArgs* a) {
-    if constexpr ((F & ~(C2F_QSAT | C2F_PRECISE | C2F_EVAP)) == 0) tl_parjac_column<F>(gc, a);
-  }
-};
+#include "hostcheck_parjac.hip"
 
 namespace {
 
@@ -75,25 +70,12 @@ int fail_at(const char* what, int icase, int satur, int precise, unsigned msum) 
 
 bool active(int ibl, int jl) { return (long long)ibl * g_nproma + jl < g_ngptot; }
 
-// the parent's planes: hostcheck_tl_parjac's body
+// the parent's planes: hostcheck_tl_parjac
 void parjac(const cloudsc2_params* prm, double ptsphy, const cloudsc2_inputs* in, OutArrays* dout, int np) {
-  TlParJacArgs a;
-  memset(&a, 0, sizeof(a));
-  a.g = hc_geom(g_nproma, g_nlev, g_ngptot);
-  a.c = hc_consts(*prm, ptsphy);
-  LevelTab tab; hc_tables(*prm, tab, a.g);
-  a.tab = &tab;
-  a.s = Strides{0, 0, 0, 0, 0}; a.sp = Strides{0, 0, 0, 0, 0};
-  hc_in(*in, a.s, a.in);
-  for (int b = 0; b < np; ++b) {
-    double e[PAR_COUNT] = {};
-    e[b] = 1.0;
-    a.par[b] = make_parlin(a.c, e);
-    hc_out(dout[b].blk, a.sp, a.dout[b]);
-    a.sp.full = dout[b].blk.clc.block_stride; a.sp.half = dout[b].blk.fplsl.block_stride;
-  }
-  const unsigned f = (in->qsat.ptr ? C2F_QSAT : 0u) | (g_hc_precise ? C2F_PRECISE : 0u) | (a.c.evap ? C2F_EVAP : 0u);
-  for (long long gc = 0; gc < a.g.ncols_pad; ++gc) hc_dispatch<HcTlParJacA, 8>(f, gc, &a);
+  cloudsc2_outputs blocks[4];
+  memset(blocks, 0, sizeof(blocks));
+  for (int b = 0; b < np; ++b) blocks[b] = dout[b].blk;
+  hostcheck_tl_parjac(prm, ptsphy, g_nproma, g_nlev, g_ngptot, in, blocks);
 }
 
 // the contract: acc = +0; acc = fl(acc + fl(w[k] * plane[k]))

@@ -23,7 +23,7 @@ FLAGSETS = (dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(
 
 def build() -> str:
     src = os.path.join(HOSTCHECK_DIR, "parcolsum_asan_main.cpp")
-    deps = [src] + [os.path.join(HOSTCHECK_DIR, f) for f in ("hostcheck_parcolsum.hip", "hostcheck.hip")] + [
+    deps = [src] + [os.path.join(HOSTCHECK_DIR, f) for f in ("hostcheck_parcolsum.hip", "hostcheck_parjac.hip", "hostcheck.hip")] + [
         os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
     if (not os.path.exists(EXE)) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
         # host code only; -O0: the instrumented sweeps take minutes to optimise and a second to run as they are
