@@ -281,6 +281,11 @@ C2_HD void make_level_in(const RawLevel& cur, real_t paph_k, real_t paph_surf, L
   x.paph_surf = paph_surf;
 }
 
+// The carries above the model top (cloudsc2.F90:305-312), the carried tangents there and the carried adjoints below the surface.  (A
+// macro: as a function, returning by value or filling a reference, it changed the instruction order of the batched and the parameter
+// sweeps, whose per-direction carries are arrays -- profiles/EXPERIMENTS.md, "Reverse sweeps: a level's loads and adjoint stores once".)
+#define C2_ZERO_CARRY(cy) ((cy).rfl = RC(0.0), (cy).sfl = RC(0.0), (cy).covptot = RC(0.0))
+
 // Tropopause pre-scan (cloudsc2.F90:315-326): the last band level whose first-guess T exceeds the one below.
 // The band is ~40 levels; its 2 x 40 loads are requested in batches of kTropBatch levels -- one HBM latency per
 // batch instead of one per level at the start of every wave.
@@ -883,7 +888,7 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
     store_top(out, o, c);
   }
 
-  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
+  Carry cy; C2_ZERO_CARRY(cy);
   real_t paph_k = in->paph[o.half];
   if (PERT) paph_k = pert(paph_k, lam);
   // offsets used inside the level loop, in the variant's offset type
@@ -1024,7 +1029,7 @@ C2_HD void taylor_column(long long gthread, TaylorArgsP ta) {
   rhcrit_setup(ztrpaus, rh);
   real_t paph_surf = RC(0.0);
   if (EVAP) paph_surf = pert(in->paph[o.half + (long long)nlev * nproma], lam);
-  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
+  Carry cy; C2_ZERO_CARRY(cy);
   real_t paph_k = pert(in->paph[o.half], lam);
   const LaneOffT<OT> ol = lane_off_as<OT>(o);
 
@@ -1134,8 +1139,8 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   else if constexpr (SPARSE) store_top_sparse(dout, ((TlSparseArgsP)a)->m.wr, op, c);  // (a is the head of a TlSparseArgs)
   else store_top(dout, op, c);
 
-  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
-  Carry dcy; dcy.rfl = RC(0.0); dcy.sfl = RC(0.0); dcy.covptot = RC(0.0);
+  Carry cy; C2_ZERO_CARRY(cy);
+  Carry dcy; C2_ZERO_CARRY(dcy);
   RawLevel cur, nxt, dcur, dnxt;
   double yy = 0.0;  // SELFINC: <y,y> of the column (cloudsc_driver_ad_mod.F90:184-195; the fluxes' top values are zero)
   real_t paph_k = in->paph[o.half], dpaph_k;
@@ -1220,94 +1225,109 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
 // transposed level.  It needs nothing from the trajectory pass but PFPLSL5/PFPLSN5 (and the cover plane with EVAP), so a
 // caller that already has them -- any earlier NL or TL sweep over the same state -- can run it alone
 // (cloudsc2_ad_launch_reverse).
+//
+// What both reverse sweeps read of a level is written once, below -- for ad_reverse_column (every reverse kernel but one) and for
+// vjp_batch_column further down (NB cotangents over one trajectory, each the bits of ad_reverse_column<F | ASSIGN | VJP>):
+//   load_reverse_traj    the trajectory side of a level: 16 inputs, PAPHP1(JK), the three checkpointed carries
+//   C2_OUT_ADJOINTS      the list of a level's ten output adjoints as they are READ, in request order; its three sources:
+//                        load_out_adjoint (planes), load_out_adjoint_sparse (planes under a mask), colsum_out_adjoint (column sums)
+// A new carried value or trajectory plane is added there, once.  The prologue, the enthalpy fold, the dense list of input-adjoint stores
+// and the assign form's stores after the loop are NOT shared: each column has its own text, as has the sparse form for its stores (it
+// says why).  As functions they cost no arithmetic, but the fp64 dense sweep with the evaporation branch ran 0.6 % slower, and only
+// with them written out are the kernels of both columns the earlier ones instruction for instruction (profiles/EXPERIMENTS.md,
+// "Reverse sweeps: a level's loads and adjoint stores once").
 // ---------------------------------------------------------------------------------------------------------
+C2_HD double adjoint_norm3(double n1, double n2);  // (defined with the adjoint test's other norms at the end of this file)
+
+// The trajectory side of a level.  cur.paph_k1 is NOT loaded: it is the paph_k of the level below, already in a register.  d, d1, last:
+// the level's offset, that of the row below it and whether it is the bottom level, as the column has them (formed here once more from
+// jk, the fp64 build spills one more SGPR in ten kernels: EXPERIMENTS.md, same section)
+template <bool HAS_QSAT, bool EVAP, class OT>
+C2_HD void load_reverse_traj(NlArgsP nl, const LaneOffT<OT>& o, OT osc, OT d, OT d1, bool last, RawLevel& cur, real_t& paph_k, Carry& cy) {
+  const InPtrs p = nl->in;
+  paph_k = ldg(p.paph, o.half + d);
+  cur.lu_k1 = last ? RC(0.0) : ldg(p.lu, o.full + d1);
+  cur.pap = ldg(p.pap, o.full + d);
+  cur.q = ldg(p.q, o.full + d);
+  cur.t = ldg(p.t, o.full + d);
+  cur.l = ldg(p.l, o.clv + d);
+  cur.i = ldg(p.i, o.clv + d);
+  cur.lude = ldg(p.lude, o.full + d);
+  cur.mfu = ldg(p.mfu, o.full + d);
+  cur.mfd = ldg(p.mfd, o.full + d);
+  cur.gt = ldg(p.gt, o.cml + d);
+  cur.gq = ldg(p.gq, o.cml + d);
+  cur.gl = ldg(p.gl, o.cml + d);
+  cur.gi = ldg(p.gi, o.cml + d);
+  cur.supsat = ldg(p.supsat, o.full + d);
+  if (HAS_QSAT) cur.qsat = ldg(p.qsat, o.full + d);
+  const OutPtrs po = nl->out;
+  cy.rfl = ldg(po.fplsl, o.half + d);  // ZRFL5(JK) = PFPLSL5(JK)
+  cy.sfl = ldg(po.fplsn, o.half + d);
+  // the carried cover matters to the evaporation branch alone; without it any value gives the same results (0 here)
+  cy.covptot = EVAP ? ldg(nl->ckpt, osc + d) : RC(0.0);
+}
+
+// The list of a level's output adjoints as the reverse sweeps read them, in request order (the non-VJP forms zero the planes after the
+// level in the order of OutPtrs, written out in ad_reverse_column): X(C2O_* bit, OutPtrs member, its layout group,
+// 1 on half levels (the level's flux is the one at jk + 1) / 0 on full levels, row of the column-sum table)
+#define C2_OUT_ADJOINTS(X)                                                                                                  \
+  X(C2O_TENT, tent, loc, 0, 0) X(C2O_TENQ, tenq, loc, 0, 1) X(C2O_TENL, tenl, loc, 0, 2) X(C2O_TENI, teni, loc, 0, 3)      \
+  X(C2O_CLC, clc, full, 0, 4) X(C2O_COVPTOT, covptot, full, 0, 9) X(C2O_FPLSN, fplsn, half, 1, 6) X(C2O_FPLSL, fplsl, half, 1, 5) \
+  X(C2O_FHPSN, fhpsn, half, 1, 8) X(C2O_FHPSL, fhpsl, half, 1, 7)
+
+// d, d1: the offsets of level jk and of the row below it
+template <class OT>
+C2_HD void load_out_adjoint(OutPtrsP pp, const LaneOffT<OT>& oa, OT d, OT d1, LevelOut& ya) {
+  const OutPtrs pa = *pp;
+#define C2_X(bit, field, group, half_level, row) ya.field = ldg(pa.field, oa.group + (half_level ? d1 : d));
+  C2_OUT_ADJOINTS(C2_X)
+#undef C2_X
+}
+// SPARSE: an output adjoint is read under its bit of `rd`, else it is an opaque zero
+template <class OT>
+C2_HD void load_out_adjoint_sparse(OutPtrsP pp, unsigned rd, const LaneOffT<OT>& oa, OT d, OT d1, LevelOut& ya) {
+  const OutPtrs pa = *pp;
+#define C2_X(bit, field, group, half_level, row) ya.field = (rd & bit) ? ldg(pa.field, oa.group + (half_level ? d1 : d)) : opaque_zero();
+  C2_OUT_ADJOINTS(C2_X)
+#undef C2_X
+}
+// COLSUM (with SPARSE): the adjoint of output n is not a plane but weight x the column's sum cotangent (colsum_cot), under the same bit;
+// the sum cotangents are re-read every level from their (nblocks, nproma) rows, which stay in cache
+C2_HD void colsum_out_adjoint(ColsumTabP cs, unsigned rd, int nlev, int jk, long long ocs, LevelOut& ya) {
+  const ColsumRowP w = (ColsumRowP)cs->w + jk;
+  const int r = nlev + 1;
+  const OutPtrs y = cs->y;
+#define C2_X(bit, field, group, half_level, row) ya.field = (rd & bit) ? colsum_cot(w[row * r + half_level], y.field[ocs]) : opaque_zero();
+  C2_OUT_ADJOINTS(C2_X)
+#undef C2_X
+}
 
 // Everything the reverse pass reads for level jk: trajectory inputs, the three checkpointed carries, the output
 // adjoints, and the OLD values of the input adjoints that are accumulated into.  (Written as `a[i] += x` after the
 // compute, each read-modify-write would wait for its own HBM round trip: the compiler cannot move a load above a
 // store that might alias.)
 struct AdLevelLoads {
-  RawLevel cur;   // trajectory inputs; paph_k1 is NOT loaded (it is the paph_k of the level below, already in a register)
+  RawLevel cur;   // trajectory inputs (load_reverse_traj)
   real_t paph_k;
   Carry cy;
   LevelOut ya;
   RawLevel xo;    // old input adjoints (PSUPSAT is assigned, not accumulated: not read)
 };
 
-// SPARSE: an output adjoint is read under its bit of `rd`, else it is an opaque zero (assign form: no old input adjoints)
-// COLSUM (with SPARSE): the adjoint of output n is not a plane but weight x the column's sum cotangent (colsum_cot), under the same bit;
-// the sum cotangents are re-read every level from their (nblocks, nproma) rows, which stay in cache (ap is the head of an AdColsumArgs)
+// ap: the level's laundered argument block (COLSUM: the head of an AdColsumArgs); SPARSE and COLSUM assign: no old input adjoints
 template <bool HAS_QSAT, bool ASSIGN, bool EVAP, class OT, bool SPARSE = false, bool COLSUM = false>
 C2_HD void ad_load_level(AdArgsP ap, const LaneOffT<OT>& o, const LaneOffT<OT>& oa, OT osc, int nproma, int nlev, int jk,
                          AdLevelLoads& L, unsigned rd = 0u, [[maybe_unused]] long long ocs = 0) {
+  static_assert(ASSIGN || !SPARSE, "the sparse reverse sweep assigns its input adjoints");
+  static_assert(SPARSE || !COLSUM, "the column-sum reverse sweep is a sparse one");
   const bool last = (jk == nlev - 1);
   const OT d = level_off(OT(), jk, nproma);
   const OT d1 = d + row_off(OT(), nproma);
-  {
-    const InPtrs p = ap->nl.in;
-    L.paph_k = ldg(p.paph, o.half + d);
-    L.cur.lu_k1 = last ? RC(0.0) : ldg(p.lu, o.full + d1);
-    L.cur.pap = ldg(p.pap, o.full + d);
-    L.cur.q = ldg(p.q, o.full + d);
-    L.cur.t = ldg(p.t, o.full + d);
-    L.cur.l = ldg(p.l, o.clv + d);
-    L.cur.i = ldg(p.i, o.clv + d);
-    L.cur.lude = ldg(p.lude, o.full + d);
-    L.cur.mfu = ldg(p.mfu, o.full + d);
-    L.cur.mfd = ldg(p.mfd, o.full + d);
-    L.cur.gt = ldg(p.gt, o.cml + d);
-    L.cur.gq = ldg(p.gq, o.cml + d);
-    L.cur.gl = ldg(p.gl, o.cml + d);
-    L.cur.gi = ldg(p.gi, o.cml + d);
-    L.cur.supsat = ldg(p.supsat, o.full + d);
-    if (HAS_QSAT) L.cur.qsat = ldg(p.qsat, o.full + d);
-    const OutPtrs po = ap->nl.out;
-    L.cy.rfl = ldg(po.fplsl, o.half + d);  // ZRFL5(JK) = PFPLSL5(JK)
-    L.cy.sfl = ldg(po.fplsn, o.half + d);
-    // the carried cover matters to the evaporation branch alone; without it any value gives the same results (0 here)
-    L.cy.covptot = EVAP ? ldg(ap->nl.ckpt, osc + d) : RC(0.0);
-  }
-  const OutPtrs pa = ap->aout;
-  if constexpr (COLSUM) {
-    static_assert(SPARSE && ASSIGN, "the column-sum reverse sweep is a sparse one");
-    const ColsumTabP cs = &((const C2_CONST_AS AdColsumArgs*)ap)->cs;
-    const ColsumRowP w = (ColsumRowP)cs->w + jk;
-    const int r = nlev + 1;
-    const OutPtrs y = cs->y;
-    L.ya.tent = (rd & C2O_TENT) ? colsum_cot(w[0 * r], y.tent[ocs]) : opaque_zero();
-    L.ya.tenq = (rd & C2O_TENQ) ? colsum_cot(w[1 * r], y.tenq[ocs]) : opaque_zero();
-    L.ya.tenl = (rd & C2O_TENL) ? colsum_cot(w[2 * r], y.tenl[ocs]) : opaque_zero();
-    L.ya.teni = (rd & C2O_TENI) ? colsum_cot(w[3 * r], y.teni[ocs]) : opaque_zero();
-    L.ya.clc = (rd & C2O_CLC) ? colsum_cot(w[4 * r], y.clc[ocs]) : opaque_zero();
-    L.ya.covptot = (rd & C2O_COVPTOT) ? colsum_cot(w[9 * r], y.covptot[ocs]) : opaque_zero();
-    L.ya.fplsn = (rd & C2O_FPLSN) ? colsum_cot(w[6 * r + 1], y.fplsn[ocs]) : opaque_zero();
-    L.ya.fplsl = (rd & C2O_FPLSL) ? colsum_cot(w[5 * r + 1], y.fplsl[ocs]) : opaque_zero();
-    L.ya.fhpsn = (rd & C2O_FHPSN) ? colsum_cot(w[8 * r + 1], y.fhpsn[ocs]) : opaque_zero();
-    L.ya.fhpsl = (rd & C2O_FHPSL) ? colsum_cot(w[7 * r + 1], y.fhpsl[ocs]) : opaque_zero();
-  } else if constexpr (SPARSE) {
-    static_assert(ASSIGN, "the sparse reverse sweep assigns its input adjoints");
-    L.ya.tent = (rd & C2O_TENT) ? ldg(pa.tent, oa.loc + d) : opaque_zero();
-    L.ya.tenq = (rd & C2O_TENQ) ? ldg(pa.tenq, oa.loc + d) : opaque_zero();
-    L.ya.tenl = (rd & C2O_TENL) ? ldg(pa.tenl, oa.loc + d) : opaque_zero();
-    L.ya.teni = (rd & C2O_TENI) ? ldg(pa.teni, oa.loc + d) : opaque_zero();
-    L.ya.clc = (rd & C2O_CLC) ? ldg(pa.clc, oa.full + d) : opaque_zero();
-    L.ya.covptot = (rd & C2O_COVPTOT) ? ldg(pa.covptot, oa.full + d) : opaque_zero();
-    L.ya.fplsn = (rd & C2O_FPLSN) ? ldg(pa.fplsn, oa.half + d1) : opaque_zero();
-    L.ya.fplsl = (rd & C2O_FPLSL) ? ldg(pa.fplsl, oa.half + d1) : opaque_zero();
-    L.ya.fhpsn = (rd & C2O_FHPSN) ? ldg(pa.fhpsn, oa.half + d1) : opaque_zero();
-    L.ya.fhpsl = (rd & C2O_FHPSL) ? ldg(pa.fhpsl, oa.half + d1) : opaque_zero();
-  } else {
-    L.ya.tent = ldg(pa.tent, oa.loc + d);
-    L.ya.tenq = ldg(pa.tenq, oa.loc + d);
-    L.ya.tenl = ldg(pa.tenl, oa.loc + d);
-    L.ya.teni = ldg(pa.teni, oa.loc + d);
-    L.ya.clc = ldg(pa.clc, oa.full + d);
-    L.ya.covptot = ldg(pa.covptot, oa.full + d);
-    L.ya.fplsn = ldg(pa.fplsn, oa.half + d1);
-    L.ya.fplsl = ldg(pa.fplsl, oa.half + d1);
-    L.ya.fhpsn = ldg(pa.fhpsn, oa.half + d1);
-    L.ya.fhpsl = ldg(pa.fhpsl, oa.half + d1);
-  }
+  load_reverse_traj<HAS_QSAT, EVAP>(&ap->nl, o, osc, d, d1, last, L.cur, L.paph_k, L.cy);
+  if constexpr (COLSUM) colsum_out_adjoint(&((const C2_CONST_AS AdColsumArgs*)ap)->cs, rd, nlev, jk, ocs, L.ya);
+  else if constexpr (SPARSE) load_out_adjoint_sparse(&ap->aout, rd, oa, d, d1, L.ya);
+  else load_out_adjoint(&ap->aout, oa, d, d1, L.ya);
   if (ASSIGN) {
     // assign form: the old input adjoints are not read (16 planes of traffic less per level)
     L.xo.pap = L.xo.q = L.xo.qsat = L.xo.t = L.xo.l = L.xo.i = L.xo.lude = L.xo.mfu = L.xo.mfd = RC(0.0);
@@ -1333,8 +1353,6 @@ C2_HD void ad_load_level(AdArgsP ap, const LaneOffT<OT>& o, const LaneOffT<OT>& 
 }
 
 // reverse sweep (cloudsc2ad.F90:877-1740); the trajectory pass has run before
-C2_HD double adjoint_norm3(double n1, double n2);
-
 template <unsigned F>
 C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| of the column with C2F_ADNORM (+inf for NaN), else 0
   constexpr bool HAS_QSAT = (F & C2F_QSAT) != 0, P = (F & C2F_PRECISE) != 0, EVAP = (F & C2F_EVAP) != 0;
@@ -1372,7 +1390,7 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   const real_t paph_bottom = in->paph[o.half + (long long)nlev * nproma];
   const real_t paph_surf = EVAP ? paph_bottom : RC(0.0);
 
-  Carry acy; acy.rfl = RC(0.0); acy.sfl = RC(0.0); acy.covptot = RC(0.0);
+  Carry acy; C2_ZERO_CARRY(acy);
   real_t paph_pending = RC(0.0);  // contribution of level jk+1 to the PAPHP1 adjoint at half level jk+1
   real_t surf_acc = RC(0.0);      // PAPHP1(KLEV+1) adjoint, written once at the end
   real_t paph_k1 = paph_bottom;
@@ -1539,7 +1557,7 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   } else if (ASSIGN) {
     ain->paph[oa64.half] = paph_pending;
     ain->paph[oa64.half + (long long)nlev * nproma] = surf_acc;
-    ain->lu[oa64.full] = RC(0.0);  // PLU(1) has no adjoint contribution (only PLU(JK+1) is read, cloudsc2.F90:435)
+    ain->lu[oa64.full] = RC(0.0);
   } else {
     ain->paph[oa64.half] += paph_pending;
     ain->paph[oa64.half + (long long)nlev * nproma] += surf_acc;
@@ -1643,12 +1661,12 @@ C2_HD void tl_batch_column(long long gcol, TlBatchArgsP a) {
   real_t paph_surf = RC(0.0);
   if (EVAP) paph_surf = in->paph[o.half + (long long)nlev * nproma];
 
-  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
+  Carry cy; C2_ZERO_CARRY(cy);
   Carry dcy[NB];
   real_t dpaph_k[NB], dpaph_surf[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0);
+    C2_ZERO_CARRY(dcy[b]);
     dpaph_surf[b] = RC(0.0);
     store_top(&a->dout[b], op, c);
     const real_t* dpaph = a->din[b].paph;
@@ -1785,10 +1803,10 @@ C2_HD void par_sweep(long long gcol, ArgsP a, End& e) {
   real_t paph_surf = RC(0.0);
   if (EVAP) paph_surf = in->paph[o.half + (long long)nlev * nproma];
 
-  Carry cy; cy.rfl = RC(0.0); cy.sfl = RC(0.0); cy.covptot = RC(0.0);
+  Carry cy; C2_ZERO_CARRY(cy);
   Carry dcy[NP];
 #pragma unroll
-  for (int b = 0; b < NP; ++b) { dcy[b].rfl = RC(0.0); dcy[b].sfl = RC(0.0); dcy[b].covptot = RC(0.0); }
+  for (int b = 0; b < NP; ++b) C2_ZERO_CARRY(dcy[b]);
   e.begin(a, c);
   RawLevel cur, nxt;
   real_t paph_k = in->paph[o.half];
@@ -2140,21 +2158,6 @@ C2_HD void parcolsum_column(long long gcol, ParColsumArgsP a) {
   par_sweep<F>(gcol, a, e);
 }
 
-template <class OT>
-C2_HD void load_out_adjoint(OutPtrsP pp, const LaneOffT<OT>& oa, OT d, OT d1, LevelOut& ya) {
-  const OutPtrs pa = *pp;
-  ya.tent = ldg(pa.tent, oa.loc + d);
-  ya.tenq = ldg(pa.tenq, oa.loc + d);
-  ya.tenl = ldg(pa.tenl, oa.loc + d);
-  ya.teni = ldg(pa.teni, oa.loc + d);
-  ya.clc = ldg(pa.clc, oa.full + d);
-  ya.covptot = ldg(pa.covptot, oa.full + d);
-  ya.fplsn = ldg(pa.fplsn, oa.half + d1);
-  ya.fplsl = ldg(pa.fplsl, oa.half + d1);
-  ya.fhpsn = ldg(pa.fhpsn, oa.half + d1);
-  ya.fhpsl = ldg(pa.fhpsl, oa.half + d1);
-}
-
 // F: C2F_QSAT (always) | C2F_PRECISE | C2F_EVAP | C2F_OFF32; the form is ad_reverse_column's C2F_ASSIGN | C2F_VJP: input adjoints
 // assigned, output adjoints read only, the PSUPSAT adjoint ax.q, the PLU(1) adjoint zero, the padded tail untouched
 template <unsigned F, int NB>
@@ -2190,7 +2193,7 @@ C2_HD void vjp_batch_column(long long gcol, VjpBatchArgsP a) {
   real_t paph_surf_b[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    acy[b].rfl = RC(0.0); acy[b].sfl = RC(0.0); acy[b].covptot = RC(0.0);
+    C2_ZERO_CARRY(acy[b]);
     paph_pending[b] = RC(0.0); surf_acc[b] = RC(0.0);
     rh_b[b] = rh; paph_surf_b[b] = paph_surf;
     C2_LAUNDER_V(rh_b[b].zeta3); C2_LAUNDER_V(rh_b[b].zrh2); C2_LAUNDER_V(rh_b[b].zdeta1); C2_LAUNDER_V(paph_surf_b[b]);
@@ -2213,29 +2216,7 @@ C2_HD void vjp_batch_column(long long gcol, VjpBatchArgsP a) {
     RawLevel cur;
     real_t paph_k;
     Carry cy;
-    {
-      const InPtrs p = ap->nl.in;
-      paph_k = ldg(p.paph, ol.half + d);
-      cur.lu_k1 = last ? RC(0.0) : ldg(p.lu, ol.full + d1);
-      cur.pap = ldg(p.pap, ol.full + d);
-      cur.q = ldg(p.q, ol.full + d);
-      cur.t = ldg(p.t, ol.full + d);
-      cur.l = ldg(p.l, ol.clv + d);
-      cur.i = ldg(p.i, ol.clv + d);
-      cur.lude = ldg(p.lude, ol.full + d);
-      cur.mfu = ldg(p.mfu, ol.full + d);
-      cur.mfd = ldg(p.mfd, ol.full + d);
-      cur.gt = ldg(p.gt, ol.cml + d);
-      cur.gq = ldg(p.gq, ol.cml + d);
-      cur.gl = ldg(p.gl, ol.cml + d);
-      cur.gi = ldg(p.gi, ol.cml + d);
-      cur.supsat = ldg(p.supsat, ol.full + d);
-      cur.qsat = ldg(p.qsat, ol.full + d);
-      const OutPtrs po = ap->nl.out;
-      cy.rfl = ldg(po.fplsl, ol.half + d);  // ZRFL5(JK) = PFPLSL5(JK)
-      cy.sfl = ldg(po.fplsn, ol.half + d);
-      cy.covptot = EVAP ? ldg(ap->nl.ckpt, osc + d) : RC(0.0);
-    }
+    load_reverse_traj<true, EVAP>(&ap->nl, ol, osc, d, d1, last, cur, paph_k, cy);
     LevelOut ycur;
     load_out_adjoint(&ap->aout[0], oa, d, d1, ycur);
     cur.paph_k1 = paph_k1;
