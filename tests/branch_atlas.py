@@ -18,21 +18,17 @@ import copy
 import ctypes as C
 import dataclasses
 import functools
-import os
-import subprocess
 
 import numpy as np
 
-from tests.util import B, HOSTCHECK_DIR, ROOT, c2, hfld, host_traj_blocks, hostcheck, increments_of, make_params, refcall, set_lib_params
+from tests.hostbuild import host_lib
+from tests.util import B, c2, hfld, host_traj_blocks, hostcheck, increments_of, make_params, refcall, set_lib_params
 
 NL_TOL = 1e-12    # the whole-field bounds the project accepts (tests/test_gpu_parity.py)
 TLAD_TOL = 1e-11
 MIN_CELLS = 32    # every class, before and after the exclusion of threshold cells
 MAX_EXCLUDED = 0.05
 
-# the census in both precisions, side by side: an fp32 process also asks the fp64 build about the same (fp32-rounded) inputs
-CENSUS_LIBS = {False: os.path.join(HOSTCHECK_DIR, "libhostcheck_census.so"), True: os.path.join(HOSTCHECK_DIR, "libhostcheck_census_sp.so")}
-CENSUS_LIB = CENSUS_LIBS[B.SINGLE]
 if B.SINGLE:
     from tests.single_checks import ERR_FACTOR  # the project's "as accurate as the reference's -DSINGLE" factor (4)
 
@@ -51,38 +47,11 @@ EVAP_ONLY = ("llo2", "dpr_clip", "llo2&dpr_clip")
 ONE_LEVEL = ("last=1",)
 
 
-def build_census(single: bool = B.SINGLE) -> str:
-    lib = CENSUS_LIBS[single]
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_census.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(lib)) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if single else []) + ["-o", lib, src])
-    return lib
-
-
-_libs = {}
-
-
-def census_lib(single: bool = B.SINGLE):
-    """The census of the process's own precision; `single` given: of that precision (its field blocks then hold elements of that
-    size, see `census`)."""
-    if single not in _libs:
-        lib = C.CDLL(build_census(single))
-        lib.hostcheck_census.argtypes = [C.POINTER(B.Params), C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs),
-                                         C.POINTER(B.Outputs), C.c_void_p]
-        lib.hostcheck_census.restype = C.c_longlong
-        lib.hostcheck_satur.argtypes = [C.POINTER(B.Params), C.c_int, C.c_int, C.c_int, B.Field, B.Field, B.Field]
-        _libs[single] = lib
-    return _libs[single]
-
-
 def census(prm, st, qsat: np.ndarray | None = None, precise: int = 0, single: bool = B.SINGLE):
     """Signature words (NBLOCKS, NLEV, NPROMA) of a state (0 in the padded tail), the state the walk left (its outputs are the
     walk's LevelOut) and the number of cells where dpr_clip and reset differ.  `single`: the precision of the census build; the
     state and qsat hold elements of that precision."""
-    lib = census_lib(single)
+    lib = host_lib("census", single)  # (its field blocks then hold elements of that precision)
     got = st.copy()
     i, o = host_traj_blocks(got, qsat, real=np.float32 if single else np.float64)
     sig = np.zeros((st.nblocks, st.nlev, st.nproma), dtype=np.uint32)
@@ -166,15 +135,13 @@ def _host_qsat(tab: dict) -> np.ndarray:
     qsat = np.zeros_like(pap)
     prm = c2.default_params(np.full(nlev, 0.5))
     f = lambda a: B.Field(a.ctypes.data, a.size)  # noqa: E731
-    hc = census_lib()  # (its own copy of hostcheck.hip: the arithmetic mode set here is not the one the tests set on hostcheck())
+    hc = host_lib("census")  # (precise for the length of this call, whatever mode the tests have set: an input recipe has one arithmetic)
     hc.hostcheck_set_precise(1)
     try:
         assert hc.hostcheck_satur(C.byref(prm), ncol, nlev, ncol, f(pap), f(t), f(qsat)) == 0
     finally:
         hc.hostcheck_set_precise(0)
     return qsat.astype(np.float64)
-
-
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ def cases(seed: int, n: int) -> list[dict]:
 def run_case(case: dict, nl_tol_fast: float, nl_tol_precise: float, tlad_tol: float) -> dict:
     """NL through the driver-level C ABI in both arithmetic modes, TL / AD at kernel level, against the CPU checker (the reference
     Fortran when oracle/_ref travelled).  Returns the worst relative errors; raises on a tolerance."""
-    from tests.test_gpu_parity import _device_tl_ad, assert_outputs_close, checker, ref_nl_state
+    from tests.gpu_util import _device_tl_ad, assert_outputs_close, checker, ref_nl_state
     from tests.util import c2, relerr, set_lib_params
 
     nproma, ngptot, flags = case["nproma"], case["ngptot"], case["flags"]

@@ -120,6 +120,7 @@ static unsigned hc_par_head(Args& a, LevelTab& tab, const cloudsc2_params* prm, 
 extern "C" {
 
 void hostcheck_set_precise(int p) { g_hc_precise = p; }
+int hostcheck_get_precise(void) { return g_hc_precise; }
 void hostcheck_set_assign(int v) { g_hc_assign = v; }  // AD: assign the input adjoints instead of accumulating (C2F_ASSIGN)
 void hostcheck_set_ad_sweep(int v) { g_hc_ad_sweep = v; }  // what cloudsc2_ad_launch_forward / _reverse run
 void hostcheck_set_self_increment(double v) { g_hc_supsat_inc = v; }  // TL: cloudsc2_tl_launch_self (negative: increments from din)

@@ -19,6 +19,7 @@ import numpy as np
 os.environ["CLOUDSC2_PRECISION"] = "single"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from tests.hostbuild import set_precise  # noqa: E402
 from tests.util import (B, c2, flat_block, flat_fields, host_traj_blocks, hostcheck, increments_of, make_params,  # noqa: E402
                         refcall, relerr, set_lib_params)
 
@@ -117,7 +118,7 @@ def host_checks():
         qsat = qsat_blocks(r32, st)
         inc = increments_of(st, qsat)
         hc = hostcheck()
-        hc.hostcheck_set_precise(precise)
+        set_precise(precise)
         print(f"host fp32: flags={flags} precise={precise}")
         got = st.copy()
         i, o = host_traj_blocks(got, qsat)
@@ -189,7 +190,7 @@ def host_checks():
                 assert np.array_equal(x2[n], x3[n]), ("off32 AD", n)
         finally:
             hc.hostcheck_set_off32(0)
-        hc.hostcheck_set_precise(0)
+        set_precise(0)
     return ok
 
 

@@ -2,7 +2,7 @@
 ``[CLOUDSC2_OFF32=0|1] [CLOUDSC2_PRECISION=single] python tests/sparse_variant_checks.py OUT.npz [small]``.
 
 The launchers choose the addressing form of the kernels once per process (CLOUDSC2_OFF32), hence one child per form.  For the four
-flag sets of tests/test_hostcheck_vjp.py x math_mode 1 / 2 x qsat given / satur, at NPROMA 32 x 100 columns (four blocks, a padded
+FLAG_SETS of tests/util.py (those of tests/test_hostcheck_vjp.py) x math_mode 1 / 2 x qsat given / satur, at NPROMA 32 x 100 columns (four blocks, a padded
 tail of 28), and for one case at NPROMA 128 x 128 columns (no tail; not with ``small``), every mask pattern of tests/sparse_patterns.py
 is launched through cloudsc2_tl_launch_sparse and cloudsc2_vjp_launch_sparse next to the dense twin on zero planes:
 

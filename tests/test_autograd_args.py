@@ -2,23 +2,13 @@
 launch: its shape / stride / dtype checks are device-free (CPU and meta tensors), the device check is a step of its own."""
 from __future__ import annotations
 
-import numpy as np
 import pytest
 import torch
 
-from tests.util import B, c2
+from tests.gpu_util import ARG_NB as NB, ARG_NLEV as NLEV, ARG_NPROMA as NPROMA, arg_inputs as inputs, arg_params as params, bad_cases
+from tests.util import B
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
-NB, NLEV, NPROMA = 3, 137, 32
-
-
-def inputs(device="cpu", nb=NB, nlev=NLEV, nproma=NPROMA, dtype=None):
-    dtype = dtype or B.torch_real()
-    return {n: torch.ones((nb, nlev + (1 if n == "paph" else 0), nproma), dtype=dtype, device=device) for n in B.IN_NAMES}
-
-
-def params(nlev=NLEV, **kw):
-    return c2.default_params(np.linspace(0.01, 1.0, nlev), **kw)
 
 
 @pytest.mark.parametrize("device", ["cpu", "meta"])
@@ -33,31 +23,6 @@ def test_a_valid_call_passes_the_layout_checks(device):
     for k, n in enumerate(("gtent", "gtenq", "gtenl", "gteni")):
         x[n] = buf[:, k]
     ag.check_layout(x, params())
-
-
-def bad_cases():
-    x = inputs(); x["t"] = x["t"].to(torch.float32 if not B.SINGLE else torch.float64)
-    yield "dtype", x, params(), "dtype"
-    x = inputs(); x["q"] = torch.ones((NB, NLEV - 1, NPROMA), dtype=B.torch_real())
-    yield "nlev mismatch", x, params(), "shape"
-    yield "prm.nlev mismatch", inputs(), params(NLEV - 1), "prm.nlev"
-    x = inputs(); x["mfu"] = torch.ones((NB, NPROMA, NLEV), dtype=B.torch_real()).transpose(1, 2)
-    yield "column stride", x, params(), "column stride"
-    x = inputs(); x["lude"] = torch.ones((NB, NLEV, 2 * NPROMA), dtype=B.torch_real())[:, :, ::2]
-    yield "column stride 2", x, params(), "column stride"
-    x = inputs(); x["l"] = torch.ones(NB * NLEV * NPROMA, dtype=B.torch_real()).as_strided((NB, NLEV, NPROMA), (7, NPROMA, 1))
-    yield "overlapping blocks", x, params(), "overlap"
-    yield "nlev > 200", inputs(nlev=B.CLOUDSC2_MAX_NLEV + 1), params(), "nlev"
-    yield "lphylin = 0", inputs(), _no_lphylin(), "lphylin"
-    x = inputs(); del x["supsat"]
-    yield "missing name", x, params(), "names"
-    yield "ngptot", inputs(), params(), "ngptot"
-
-
-def _no_lphylin():
-    p = params()
-    p.lphylin = 0
-    return p
 
 
 @pytest.mark.parametrize("case", [c[0] for c in bad_cases()])

@@ -9,16 +9,13 @@ import pytest
 import torch
 
 import dwarf_p_cloudsc2_tl_ad_amd as c2
-from tests.test_autograd_args import NB, NLEV, NPROMA, bad_cases, inputs, params
+from tests.gpu_util import (ARG_NB as NB, ARG_NLEV as NLEV, ARG_NPROMA as NPROMA, arg_inputs as inputs, arg_params as params, bad_cases,
+                            bad_weights, weights)
 from tests.util import B
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
 REAL = B.torch_real()
 OTHER = torch.float32 if not B.SINGLE else torch.float64
-
-
-def weights(device="cpu", names=("fplsl", "tent")):
-    return {n: torch.ones(NLEV + (1 if n in ag.HALF_OUT else 0), dtype=REAL, device=device) for n in names}
 
 
 def inputs15(device="cpu"):
@@ -36,30 +33,6 @@ def test_a_valid_call_passes(device):
     w = weights(device, ("fplsn",))
     w["fplsn"] = torch.ones(2 * (NLEV + 1), dtype=REAL, device=device)[::2]  # any stride
     assert ag.check_column_sums(inputs(device), params(), None, False, w)[1] == ("fplsn",)
-
-
-def bad_weights(device):
-    """(id, weights, what the message must contain)"""
-    yield "not a mapping", [torch.ones(NLEV, dtype=REAL, device=device)], "weights must map"
-    yield "none", None, "weights must map"
-    yield "empty", {}, "weights is empty"
-    w = weights(device); w["rain"] = w["tent"]
-    yield "unknown name", w, "'rain'"
-    w = weights(device); w["tent"] = [1.0] * NLEV
-    yield "not a tensor", w, "weights['tent'] is not a tensor"
-    w = weights(device); w["tent"] = torch.ones((1, NLEV), dtype=REAL, device=device)
-    yield "not 1-D", w, "weights['tent'] must be 1-D"
-    w = weights(device); w["tent"] = torch.ones(NLEV + 1, dtype=REAL, device=device)
-    yield "full-level length", w, f"weights['tent'] has length {NLEV + 1}, expected {NLEV}"
-    w = weights(device); w["fplsl"] = torch.ones(NLEV, dtype=REAL, device=device)
-    yield "half-level length", w, f"weights['fplsl'] has length {NLEV}, expected {NLEV + 1}"
-    w = weights(device); w["fplsl"] = w["fplsl"].to(OTHER)
-    yield "dtype", w, "weights['fplsl'] has dtype"
-    if device == "cpu":
-        w = weights(device); w["tent"] = w["tent"].clone().requires_grad_(True)
-        yield "requires grad", w, "weights['tent'] requires grad"
-        w = weights(device); w["tent"] = torch.ones(NLEV, dtype=REAL, device="meta")
-        yield "other device", w, "weights['tent'] is on meta"
 
 
 @pytest.mark.parametrize("device", ["cpu", "meta"])

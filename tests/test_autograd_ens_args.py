@@ -8,19 +8,11 @@ import ctypes as C
 import pytest
 import torch
 
-from tests.test_autograd_args import NB, NLEV, NPROMA, inputs, params
+from tests.gpu_util import (ARG_NB as NB, ARG_NLEV as NLEV, ARG_NPROMA as NPROMA, K, arg_inputs as inputs, arg_params as params, bad_params,
+                            four_d, pk)
 from tests.util import B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
-K = 3
-
-
-def pk(k=K, dtype=torch.float64, **kw):
-    return torch.linspace(1.0, 2.0, k, dtype=torch.float64).to(dtype).requires_grad_(kw.get("requires_grad", False))
-
-
-def four_d(t, k=K):
-    return t.unsqueeze(0).repeat(k, 1, 1, 1)
 
 
 def test_the_entry_points_are_exported():
@@ -40,21 +32,6 @@ def test_a_valid_call_passes_and_reports_layout_members_and_names():
     assert ag.check_ensemble(x, prm, None, False, {"rclcrit": pk()})[0].ngptot == NB * NPROMA
     del x["qsat"]
     assert ag.check_ensemble(x, prm, None, True, {"rclcrit": pk()})[1] == K
-
-
-def bad_params():
-    yield {}, "empty"
-    yield {"rlmin": pk()}, "unknown name"
-    yield {"rkconv": pk(), "ptsphy": pk()}, "unknown name"
-    yield {"rkconv": torch.tensor(1.0, dtype=torch.float64)}, "1-d"
-    yield {"rkconv": torch.ones(K, 2, dtype=torch.float64)}, "1-d"
-    yield {"rkconv": torch.ones(0, dtype=torch.float64)}, "1-d"
-    yield {"rkconv": pk(dtype=torch.float32)}, "dtype"
-    yield {"rkconv": torch.ones(K, dtype=torch.int64)}, "dtype"
-    yield {"rkconv": pk(), "rlptrc": pk(K + 1)}, "common length"
-    yield {"rlptrc": [250.0] * K}, "not a tensor"
-    yield [("rkconv", pk())], "must map"
-    yield None, "must map"
 
 
 @pytest.mark.parametrize("bad, match", list(bad_params()))

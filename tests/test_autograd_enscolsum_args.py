@@ -13,11 +13,9 @@ import pytest
 import torch
 
 import dwarf_p_cloudsc2_tl_ad_amd as c2
-from tests.test_autograd_args import NB, NLEV, NPROMA, inputs, params
-from tests.test_autograd_colsum_args import bad_weights, weights
-from tests.test_autograd_ens_args import K, bad_params, four_d, pk
-from tests.test_colsum_refusals import SumWorld
-from tests.test_launcher_refusals import NGPTOT as G_NGPTOT, NLEV as G_NLEV, NPROMA as G_NPROMA, params as abi_params
+from tests.gpu_util import (ARG_NB as NB, ARG_NLEV as NLEV, ARG_NPROMA as NPROMA, K, R_NGPTOT as G_NGPTOT, R_NLEV as G_NLEV,
+                            R_NPROMA as G_NPROMA, SumWorld, arg_inputs as inputs, arg_params as params, bad_params, bad_weights, four_d, pk,
+                            refusal_params as abi_params, weights)
 from tests.util import ROOT, B
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 

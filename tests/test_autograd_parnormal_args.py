@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_autograd_args import NB, NLEV, NPROMA, inputs, params
+from tests.gpu_util import ARG_NB as NB, ARG_NLEV as NLEV, ARG_NPROMA as NPROMA, arg_inputs as inputs, arg_params as params
 from tests.util import B, c2, flat_block, flat_fields, hfld
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 

@@ -8,7 +8,7 @@ import inspect
 import pytest
 import torch
 
-from tests.test_autograd_args import NB, NLEV, NPROMA, bad_cases, inputs, params
+from tests.gpu_util import ARG_NB as NB, ARG_NLEV as NLEV, ARG_NPROMA as NPROMA, arg_inputs as inputs, arg_params as params, bad_cases
 from tests.util import B
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from tests import branch_atlas as A
-from tests.test_hostcheck_vjp import vjp_lib
+from tests.hostbuild import host_lib, precise  # noqa: F401
 from tests.util import B, c2, host_traj_blocks, hostcheck, make_params, relerr
 
 BITS_VIEW = np.int32 if B.SINGLE else np.int64  # the integer of an element's size: bits are compared through it
@@ -31,16 +31,6 @@ BITS_VIEW = np.int32 if B.SINGLE else np.int64  # the integer of an element's si
 UNREACHED: dict = {}
 
 SHAPES = [(137, 96), (60, 96)]
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    for lib in (hostcheck(), vjp_lib()):
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in (hostcheck(), vjp_lib()):
-        lib.hostcheck_set_precise(0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -223,7 +213,7 @@ def _class_metric_single(nlev):
 # ---------------------------------------------------------------------------------------------------------------------
 def host_vjp(c, satur: bool) -> dict:
     """cloudsc2_vjp_launch's sweep on the host: the trajectory pass, then the reverse sweep in the vector-Jacobian form."""
-    hv = vjp_lib()
+    hv = host_lib("vjp")
     got = c.st.copy()
     i, o = host_traj_blocks(got, None if satur else c.qsat)
     scratch = np.zeros((c.st.nblocks, c.nlev, A.NPROMA), dtype=B.REAL)

@@ -1,5 +1,6 @@
 """What cloudsc2_nl_launch_colsum, cloudsc2_tl_launch_colsum and cloudsc2_vjp_launch_colsum refuse: the return code and the text of
-``cloudsc2_last_error()`` of every refusal, with the geometry and the pointers of test_launcher_refusals.py (NPROMA 8, NLEV 4, NGPTOT 12;
+``cloudsc2_last_error()`` of every refusal, with the geometry and the pointers of test_launcher_refusals.py (World in
+tests/gpu_util.py: NPROMA 8, NLEV 4, NGPTOT 12;
 dummies without a device).  All of them are checked before the device is looked for, so every case is CLOUDSC2_EINVAL on the CPU too;
 the message names the launcher, and after every refusal the calling thread's launch log is empty.  A well-formed call answers
 CLOUDSC2_ENODEVICE where there is no device."""
@@ -9,8 +10,7 @@ import ctypes as C
 
 import pytest
 
-from tests.test_launcher_refusals import NGPTOT, NLEV, NPROMA, S, SH, params
-from tests.test_sparse_refusals import DistinctWorld
+from tests.gpu_util import R_NGPTOT as NGPTOT, R_NLEV as NLEV, R_NPROMA as NPROMA, S, SH, SumWorld, refusal_params as params
 from tests.util import B
 
 EINVAL = B.CLOUDSC2_EINVAL
@@ -27,18 +27,6 @@ TRAJ = "a required input field has a NULL pointer"
 KEEP_BOTH = "keep needs both planes, fplsl and fplsn"
 KEEP_SCRATCH = "keep with LEVAPLS2/LDRAIN1D: the cover-checkpoint plane `scratch` is required"
 KEEP_STRIDE = "the kept flux planes must have the block stride of in->paph"
-
-
-class SumWorld(DistinctWorld):
-    def sums(self, tag, only=("fplsl", "fplsn"), **edit) -> B.Outputs:
-        """a block of (nblocks, nproma) sums: block stride NPROMA unless edited"""
-        blk = B.Outputs()
-        for n in only:
-            f = B.Field()
-            f.ptr = self.mem((tag, n), 4 * 2 * SH)
-            f.block_stride = edit.get(n, NPROMA)
-            setattr(blk, n, f)
-        return blk
 
 
 def cases(W: SumWorld):

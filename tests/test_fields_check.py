@@ -9,9 +9,8 @@ import subprocess
 
 import pytest
 
-from tests.util import HOSTCHECK_DIR
+from tests.util import HIPCC, HOSTCHECK_DIR
 
-HIPCC = "/opt/rocm/bin/hipcc"
 SRC = os.path.join(HOSTCHECK_DIR, "fields_check.cpp")
 
 

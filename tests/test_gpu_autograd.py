@@ -5,85 +5,15 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import DEV, ad_assign_launch, make_inputs, new, nl_launch, params, same_bits, seeded, stream, tail_zero, tl_launch
 from tests.util import B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
-
-
-def make_inputs(tab, nproma, ngptot, prm):
-    st = c2.state_from_table(tab, nproma, ngptot)
-    src = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "t": st.PT, "l": st.PCLV[:, 0], "i": st.PCLV[:, 1], "lude": st.PLUDE,
-           "lu": st.PLU, "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, 0], "gtenq": st.B_CML[:, 2], "gtenl": st.B_CML[:, 3],
-           "gteni": st.B_CML[:, 4], "supsat": st.PSUPSAT}
-    x = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in src.items()}
-    x["qsat"] = ag.satur(x["pap"], x["t"], prm, ngptot)
-    return {n: x[n] for n in B.IN_NAMES}, float(st.ptsphy), ag.Layout(st.nblocks, st.nlev, nproma, ngptot)
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
-
-
-def new(names, lay, fill=0.0):
-    return {n: torch.full(lay.shape(n), fill, dtype=B.torch_real(), device=DEV) for n in names}
-
-
-def nl_launch(x, prm, ptsphy, lay):
-    out = new(B.OUT_NAMES, lay)
-    B.check(B.lib.cloudsc2_nl_launch(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
-                                     C.byref(ag._block("out", out, lay)), B.Field(), 0.0, stream()))
-    return out
-
-
-def ad_assign_launch(x, u, prm, ptsphy, lay):
-    traj, xa = new(B.OUT_NAMES, lay), new(B.IN_NAMES, lay)
-    y = {n: u[n].clone() for n in B.OUT_NAMES}
-    scratch = torch.zeros((lay.nblocks, lay.nlev, lay.nproma), dtype=B.torch_real(), device=DEV)
-    B.check(B.lib.cloudsc2_ad_launch_assign(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
-                                            C.byref(ag._block("out", traj, lay)), C.byref(ag._block("in", xa, lay)),
-                                            C.byref(ag._block("out", y, lay)), C.c_void_p(scratch.data_ptr()), stream()))
-    return xa
-
-
-def tl_launch(x, dx, prm, ptsphy, lay):
-    dy = new(B.OUT_NAMES, lay)
-    B.check(B.lib.cloudsc2_tl_launch(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
-                                     C.byref(B.Outputs()), C.byref(ag._block("in", dx, lay)), C.byref(ag._block("out", dy, lay)),
-                                     stream()))
-    return dy
-
-
-def seeded(names, lay, seed, scale=1.0):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    out = {}
-    for n in names:
-        t = torch.randn(lay.shape(n), generator=g, dtype=B.torch_real(), device=DEV) * scale
-        if lay.tail < lay.nproma:
-            t[-1, :, lay.tail:] = 0
-        out[n] = t
-    return out
-
-
-def same_bits(a, b):
-    return torch.equal(a.view(torch.int64 if a.dtype == torch.float64 else torch.int32),
-                       b.view(torch.int64 if b.dtype == torch.float64 else torch.int32))
-
-
-def tail_zero(t, lay):
-    return lay.tail == lay.nproma or bool(torch.all(t[-1, :, lay.tail:] == 0))
-
-
-def params(tab, math_mode=0, **flags):
-    prm = c2.default_params(c2.ceta_from_table(tab), **flags)
-    prm.math_mode = math_mode
-    return prm
 
 
 @pytest.mark.parametrize("nproma,ngptot", [(32, 100), (128, 16384), (4096, 4096)])

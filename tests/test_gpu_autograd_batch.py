@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_autograd import DEV, make_inputs, new, params, same_bits, seeded, stream, tail_zero, tl_launch
+from tests.gpu_util import DEV, make_inputs, new, params, same_bits, seeded, stream, tail_zero, tl_launch
 from tests.util import B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_autograd import DEV, make_inputs, params, same_bits
+from tests.gpu_util import DEV, make_inputs, params, same_bits
 from tests.util import ROOT, B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 

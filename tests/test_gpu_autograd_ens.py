@@ -15,10 +15,8 @@ import ctypes as C
 import pytest
 import torch
 
-from tests.test_gpu_autograd import DEV, make_inputs, params, same_bits, tail_zero
-from tests.test_gpu_autograd_par import fp64_only, names_of
-from tests.test_gpu_autograd_parnormal import hip_runtime
-from tests.util import B, c2
+from tests.gpu_util import DEV, hip_runtime, make_inputs, names_of, params, same_bits, tail_zero
+from tests.util import B, c2, fp64_only
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
 pytestmark = [pytest.mark.gpu, fp64_only]

@@ -22,9 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_autograd import DEV, make_inputs, params, same_bits
-from tests.test_gpu_autograd import tail_zero as plane_tail_zero
-from tests.test_gpu_autograd_par import names_of
+from tests.gpu_util import DEV, make_inputs, names_of, params, same_bits, tail_zero as plane_tail_zero
 from tests.util import ROOT, B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 

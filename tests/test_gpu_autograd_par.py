@@ -16,26 +16,16 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_autograd import DEV, make_inputs, new, params, same_bits, seeded, stream, tail_zero
-from tests.test_gpu_autograd_satur import KEYS as KEYS15
-from tests.util import B, c2, refcall
+from tests.gpu_util import DEV, names_of, new, params, same_bits, seeded, state, stream, tail_zero
+from tests.host_sweeps import check_against_reference_differences, run_vjp_par
+from tests.hostbuild import set_precise
+from tests.util import B, FLAGS, c2, fp64_only, make_params, refcall, set_lib_params, the_tables
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
 pytestmark = pytest.mark.gpu
 
 P = c2.PARAM_NAMES
-FLAGS = [dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(lregcl=True)]
-fp64_only = pytest.mark.skipif(B.SINGLE, reason="the bounds are fp64 statements")
 GUARD = 64  # doubles after the workspace that must stay as they were
-
-
-def names_of(satur):
-    return KEYS15 if satur else list(B.IN_NAMES)
-
-
-def state(tab, nproma, ngptot, prm, satur):
-    x, ptsphy, lay = make_inputs(tab, nproma, ngptot, prm)
-    return {n: x[n] for n in names_of(satur)}, ptsphy, lay
 
 
 def forward_launch(x, prm, ptsphy, lay):
@@ -147,8 +137,6 @@ def test_forward_with_params_is_the_forward_with_the_values_in_prm(where, satur)
 @pytest.mark.parametrize("flags", [dict(), dict(levapls2=True, lregcl=True)])
 def test_par_adj_against_the_host_build(flags, satur):
     """Measured on the MI355X: see the printed figures (bound 1e-11 relative)."""
-    from tests.test_hostcheck_par import par_lib, run_vjp_par
-
     tab = c2.random_table(137, 100, seed=5)
     prm = params(tab, 1, **flags)
     nproma, ngptot = 32, 100
@@ -163,7 +151,7 @@ def test_par_adj_against_the_host_build(flags, satur):
     fwd.PFPLSL[...] = traj["fplsl"].cpu().numpy()
     fwd.PFPLSN[...] = traj["fplsn"].cpu().numpy()
     qsat = None if satur else np.ascontiguousarray(x["qsat"].cpu().numpy())
-    par_lib().hostcheck_set_precise(0)
+    set_precise(0)
     _, _, want, _ = run_vjp_par(prm, st, fwd, np.ascontiguousarray(scratch.cpu().numpy()), {n: t.cpu().numpy() for n, t in u.items()}, qsat)
     got = par_adj.cpu().numpy()
     for k, n in enumerate(P):
@@ -181,10 +169,6 @@ def test_par_adj_against_the_host_build(flags, satur):
 @pytest.mark.parametrize("flags", [dict(), dict(levapls2=True)])
 @pytest.mark.parametrize("which", [0, 1])
 def test_parameter_tangent_on_the_device_against_the_reference_differences(which, flags):
-    from tests.test_hostcheck_par import check_against_reference_differences
-    from tests.test_hostcheck_satur_lin import the_tables
-    from tests.util import make_params, set_lib_params
-
     if not refcall.have_ref():
         pytest.fail("the reference build (oracle/_ref) is missing: build() makes it")
     ref = refcall.RefLib()

@@ -14,7 +14,6 @@ memory rises by 1.85 MB (normal equations) and 1.06 MB (two sums) where a full-l
 from __future__ import annotations
 
 import copy
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -23,99 +22,20 @@ import numpy as np
 import pytest
 import torch
 
-from tests.parcolsum_yardstick import BOUND, PAR_SUMS, RPECONS_ROWS, contract_sums, row_g, row_h
-from tests.test_gpu_autograd import DEV, new, params, same_bits, stream
-from tests.test_gpu_autograd_par import fp64_only, state
-from tests.util import B, ROOT, c2
-from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
+from tests.gpu_util import DEV, params, same_bits, state
+from tests.parcolsum_variant_checks import (NPAR, act, check_sums, folded, launch_normal, launch_sums, level_weights, observations,
+                                             parjac_planes)
+from tests.parcolsum_yardstick import BOUND, RPECONS_ROWS, contract_sums, row_g, row_h
+from tests.util import B, ROOT, c2, fp64_only
 
 pytestmark = pytest.mark.gpu
 
 P = c2.PARAM_NAMES
-NPAR = len(P)
 NAN = float("nan")
-GUARD = 64  # doubles after the workspace that must stay as they were
 # test_gpu_autograd_parnormal.py's: lanes and a ragged tail, fold threads with nothing to add | a tail, fold threads that add one or two
 # columns | full blocks, sixteen columns per fold thread
 SHAPES = [(32, 100, 1), (32, 100, 2), (128, 1300, 0), (128, 16384, 0)]
 FLAGS = [dict(), dict(levapls2=True)]
-NLEV = 137
-
-
-def level_weights() -> list:
-    """(name, {sum: (nlevx,) weights}): the surface fluxes, all ten names (seeded: negative entries, exact zeros), one full-level sum"""
-    rng = np.random.default_rng(20261020)
-    every = {}
-    for n in B.OUT_NAMES:
-        nlevx = NLEV + (1 if n in ag.HALF_OUT else 0)
-        w = rng.uniform(-1.0, 1.0, nlevx)
-        w[rng.random(nlevx) < 0.2] = 0.0
-        w[0], w[-1] = -0.75, 0.625
-        every[n] = torch.from_numpy(w.astype(B.REAL)).to(DEV)
-    surface = torch.zeros(NLEV + 1, dtype=B.torch_real(), device=DEV)
-    surface[-1] = 1.0
-    return [("surface", {"fplsl": surface, "fplsn": surface.clone()}), ("all ten", every), ("tenq", {"tenq": every["tenq"]})]
-
-
-def table_of(weights: dict) -> torch.Tensor:
-    t = torch.full((len(B.OUT_NAMES), NLEV + 1), NAN, dtype=B.torch_real(), device=DEV)  # (rows and entries that must not be read: NaN)
-    for n, w in weights.items():
-        t[B.OUT_NAMES.index(n), :len(w)] = w
-    return t
-
-
-def fold(w: torch.Tensor, plane: torch.Tensor) -> torch.Tensor:
-    """the contract: acc = +0; acc = fl(acc + fl(w[k] * plane[:, k, :])), separate mul and add"""
-    acc = torch.zeros((plane.shape[0], plane.shape[2]), dtype=plane.dtype, device=plane.device)
-    for k in range(plane.shape[1]):
-        acc = torch.add(acc, torch.mul(plane[:, k, :], w[k]))
-    return acc
-
-
-def parjac_planes(x, prm, ptsphy, lay):
-    """cloudsc2_tl_launch_parjac, the parent: four blocks of ten planes (the rpecons block stays zero without the evaporation branch)"""
-    sens = [new(B.OUT_NAMES, lay) for _ in P]
-    blocks = (B.Outputs * NPAR)(*(ag._block("out", s, lay) for s in sens))
-    B.check(B.lib.cloudsc2_tl_launch_parjac(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)), blocks, stream()))
-    return sens
-
-
-def folded(sens, np_dirs, weights):
-    return [{n: fold(w, sens[k][n]) for n, w in weights.items()} for k in range(np_dirs)]
-
-
-def launch_sums(x, prm, ptsphy, lay, weights: dict, names=None):
-    """cloudsc2_parjac_launch_colsum into four NaN-prefilled blocks of (nblocks, nproma) sums"""
-    names = tuple(weights) if names is None else names
-    sums = [{n: torch.full((lay.nblocks, lay.nproma), NAN, dtype=B.torch_real(), device=DEV) for n in names} for _ in P]
-    blocks = (B.Outputs * NPAR)(*(ag._sums_block(s, lay) for s in sums))
-    B.check(B.lib.cloudsc2_parjac_launch_colsum(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
-                                                C.c_void_p(table_of(weights).data_ptr()), blocks, stream()))
-    return sums
-
-
-def act(t, lay):
-    """the active columns of a (nblocks, nproma) array in grid order"""
-    return t.reshape(-1)[:lay.ngptot]
-
-
-def check_sums(got, want, np_dirs, lay, label) -> int:
-    """bits on the active columns, NaN prefill in the tail, the rpecons block untouched when it is not run -> the number of elements that
-    differ (asserted zero by the caller, which prints it first)"""
-    differ = 0
-    for k, pname in enumerate(P):
-        for n, g in got[k].items():
-            if k >= np_dirs:
-                assert bool(torch.all(torch.isnan(g))), (label, pname, n, "the rpecons block was written without the evaporation branch")
-                continue
-            a, w = act(g, lay), act(want[k][n], lay)
-            assert bool(torch.all(torch.isfinite(a))), (label, pname, n, "an active sum was not written")
-            assert bool(torch.all(torch.isnan(g.reshape(-1)[lay.ngptot:]))), (label, pname, n, "the padded tail was touched")
-            bits = torch.int64 if a.dtype == torch.float64 else torch.int32
-            differ += int((a.contiguous().view(bits) != w.contiguous().view(bits)).sum())
-            if n not in PAR_SUMS:
-                assert bool(torch.all(a == 0.0)), (label, pname, n, "must be exactly zero")
-    return differ
 
 
 @pytest.mark.parametrize("flags", FLAGS)
@@ -192,32 +112,6 @@ def test_param_jacobian_column_sums_is_the_launcher(flags, satur):
 
 
 # ---- the normal form ----------------------------------------------------------------------------------------------------------------------
-
-def observations(lay, names, seed):
-    """seeded residuals and positive weights per column, (nblocks, nproma), NaN in the padded tail"""
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    r, w = {}, {}
-    for n in names:
-        r[n] = torch.randn((lay.nblocks, lay.nproma), generator=g, dtype=B.torch_real(), device=DEV)
-        w[n] = torch.rand((lay.nblocks, lay.nproma), generator=g, dtype=B.torch_real(), device=DEV) * 1.5 + 0.5
-        for t in (r[n], w[n]):
-            t.view(-1)[lay.ngptot:] = NAN
-    return r, w
-
-
-def launch_normal(x, prm, ptsphy, lay, weights, r, w, work=None, normal=None):
-    """cloudsc2_parnormal_launch_colsum -> (normal, work): 14 device doubles, and the NaN-prefilled workspace with its guard words.
-    w None: the weight block itself is NULL; x without qsat: SATUR in the sweep"""
-    n = C.c_longlong()
-    B.check(B.lib.cloudsc2_parnormal_work_doubles(lay.nproma, lay.ngptot, C.byref(n)))
-    work = work if work is not None else torch.full((n.value + GUARD,), NAN, dtype=torch.float64, device=DEV)
-    normal = normal if normal is not None else torch.full((B.NNORMAL,), NAN, dtype=torch.float64, device=DEV)
-    B.check(B.lib.cloudsc2_parnormal_launch_colsum(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
-                                                   C.c_void_p(table_of(weights).data_ptr()), C.byref(ag._sums_block(r, lay)),
-                                                   C.byref(ag._sums_block(w, lay)) if w is not None else None, C.c_void_p(work.data_ptr()),
-                                                   C.c_void_p(normal.data_ptr()), stream()))
-    return normal, work
-
 
 def yardstick(want_sums, np_dirs, r, w, lay):
     """{row: (want, S)} as Python floats: the folded sums of the parent's planes contracted in float64 over the active columns"""

@@ -15,9 +15,9 @@ import numpy as np
 import pytest
 import torch
 
-from tests.test_gpu_autograd import DEV, new, params, same_bits, stream, tail_zero
-from tests.test_gpu_autograd_par import FLAGS, fp64_only, state
-from tests.util import B, c2, refcall
+from tests.gpu_util import DEV, active, new, params, parjac, same_bits, single, state, tail_zero
+from tests.host_sweeps import check_against_reference_differences
+from tests.util import B, FLAGS, c2, fp64_only, make_params, refcall, set_lib_params
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
 pytestmark = pytest.mark.gpu
@@ -29,31 +29,6 @@ SHAPES = [(32, 100, 1), (32, 100, 2), (128, 16384, 0)]  # lanes, tails and full 
 
 def evap_of(prm) -> bool:
     return bool(prm.levapls2 or prm.ldrain1d)
-
-
-def parjac(x, prm, ptsphy, lay, sens=None, null_last=False):
-    """cloudsc2_tl_launch_parjac into four NaN-prefilled blocks (``null_last``: the rpecons block all NULL); x without qsat: SATUR in the sweep"""
-    sens = sens if sens is not None else [new(B.OUT_NAMES, lay, fill=NAN) for _ in P]
-    blocks = (B.Outputs * len(P))(*(ag._block("out", s, lay) for s in (sens[:-1] if null_last else sens)))
-    B.check(B.lib.cloudsc2_tl_launch_parjac(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, C.byref(ag._block("in", x, lay)),
-                                            blocks, stream()))
-    return sens
-
-
-def single(x, zero, k, prm, ptsphy, lay):
-    """cloudsc2_tl_launch_par (satur = 0) on zero-filled tangent planes with dpar = e_k, into NaN-prefilled outputs"""
-    dy = new(B.OUT_NAMES, lay, fill=NAN)
-    e = [0.0] * len(P)
-    e[k] = 1.0
-    B.check(B.lib.cloudsc2_tl_launch_par(C.byref(prm), ptsphy, lay.nproma, lay.nlev, lay.ngptot, 0, C.byref(ag._block("in", x, lay)),
-                                         C.byref(ag._block("in", zero, lay)), (C.c_double * len(P))(*e), C.byref(ag._block("out", dy, lay)),
-                                         stream()))
-    return dy
-
-
-def active(t, lay):
-    """the active columns of every block as one (nlevx, ngptot) view-free tensor"""
-    return t.transpose(0, 1).reshape(t.shape[1], -1)[:, :lay.ngptot]
 
 
 @pytest.mark.parametrize("flags", FLAGS)
@@ -175,9 +150,6 @@ def test_batched_operands_are_refused_and_the_op_refuses_vmap_over_params_as_bef
 @fp64_only
 def test_on_the_device_against_the_reference_differences():
     """seed5, levapls2 (all four directions run), NPROMA 32 x 100 columns."""
-    from tests.test_hostcheck_par import check_against_reference_differences
-    from tests.util import make_params, set_lib_params
-
     if not refcall.have_ref():
         pytest.fail("the reference build (oracle/_ref) is missing: build() makes it")
     ref = refcall.RefLib()

@@ -16,11 +16,9 @@ import ctypes as C
 import pytest
 import torch
 
+from tests.gpu_util import DEV, active, hip_runtime, new, params, parjac, same_bits, state, stream
 from tests.parnormal_yardstick import BOUND, NPAR, RPECONS_ROWS, contract, row_g, row_h
-from tests.test_gpu_autograd import DEV, new, params, same_bits, stream
-from tests.test_gpu_autograd_par import fp64_only, state
-from tests.test_gpu_autograd_parjac import active, parjac
-from tests.util import B, c2, refcall
+from tests.util import B, c2, fp64_only, refcall
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
 pytestmark = pytest.mark.gpu
@@ -216,18 +214,6 @@ def test_batched_operands_and_a_zero_rpecons_are_refused():
     evap = params(tab, levapls2=True)
     with pytest.raises(ValueError, match="rpecons"):
         c2.param_normal_equations(x, evap, ptsphy, lay.ngptot, residual=r, params={"rpecons": torch.tensor(0.0, dtype=torch.float64)})
-
-
-def hip_runtime():
-    """the HIP runtime this process already uses (the file torch mapped), for the graph queries torch does not wrap"""
-    with open("/proc/self/maps") as maps:
-        paths = sorted({line.split()[-1] for line in maps if "libamdhip64" in line})
-    assert len(paths) == 1, paths
-    hip = C.CDLL(paths[0])
-    hip.hipGraphGetNodes.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    hip.hipGraphNodeGetType.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-    hip.hipGraphGetEdges.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
-    return hip
 
 
 def test_a_captured_launch_is_a_chain_of_two_kernels_and_replays_the_eager_bits():

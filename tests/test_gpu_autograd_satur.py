@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import DEV, make_inputs, new, nl_launch, params, rel_err, same_bits, seeded, stream, tail_zero
 from tests.satur_lin_ref import satur_partials_numpy
-from tests.test_gpu_autograd import DEV, make_inputs, new, nl_launch, params, same_bits, seeded, stream, tail_zero
 from tests.util import B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
@@ -41,12 +41,6 @@ def unfused(prm, ptsphy, lay):
         x["qsat"] = ag.satur(x["pap"], x["t"], prm, lay.ngptot, differentiable=True)
         return tuple(ag.cloudsc2(x, prm, ptsphy, lay.ngptot))
     return f
-
-
-def rel_err(got: torch.Tensor, want: torch.Tensor) -> float:
-    d = float(torch.max(torch.abs(got - want)))
-    m = float(torch.max(torch.abs(want)))
-    return 0.0 if d == 0.0 else d / m if m > 0.0 else float("inf")
 
 
 @pytest.mark.parametrize("nproma,ngptot", [(32, 100), (128, 16384), (4096, 4096)])

@@ -29,9 +29,7 @@ import torch
 
 from tests import branch_atlas as A
 from tests import offset_variant_checks as ov
-from tests.test_gpu_autograd import same_bits
-from tests.test_gpu_autograd_parjac import parjac as parjac_launch, single as parjac_single
-from tests.test_gpu_autograd_satur import rel_err
+from tests.gpu_util import parjac as parjac_launch, rel_err, same_bits, single as parjac_single
 from tests.util import B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 

@@ -227,7 +227,7 @@ def test_fortran_main_loads_validates_and_writes_reference(tmp_path):
 
     import torch
 
-    from tests.test_gpu_parity import _run_fortran
+    from tests.gpu_util import _run_fortran
 
     tab = c2.synthetic_table()
     prm = c2.default_params(c2.ceta_from_table(tab))

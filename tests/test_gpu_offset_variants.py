@@ -30,8 +30,7 @@ import pytest
 import torch
 
 from tests import offset_variant_checks as ov
-from tests.test_variant_census import ASSIGN, OFF32, SATLIN, VJP
-from tests.util import ROOT, B, c2
+from tests.util import ASSIGN, B, OFF32, ROOT, SATLIN, VJP, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
 pytestmark = pytest.mark.gpu

@@ -15,49 +15,13 @@ import os
 import numpy as np
 import pytest
 
-from tests.util import B, c2, flat_fields, refcall, relerr, set_lib_params
+from tests.gpu_util import _device_tl_ad, _run_fortran, assert_outputs_close, checker, ref_nl_state, ref_qsat
+from tests.util import B, c2, refcall, relerr, set_lib_params
 
 pytestmark = pytest.mark.gpu
 
 NL_TOL = 1e-12
 TLAD_TOL = 1e-11
-
-
-def checker():
-    if refcall.have_ref():
-        return refcall.RefLib()
-    return refcall.OracleLib()
-
-
-def ref_qsat(chk, st):
-    qsat = np.zeros_like(st.PAP)
-    for ibl in range(st.nblocks):
-        icend = min(st.nproma, st.ngptot - ibl * st.nproma)
-        qsat[ibl] = chk.satur(np.ascontiguousarray(st.PAP[ibl]), np.ascontiguousarray(st.PT[ibl]), kfdia=icend)
-        qsat[ibl][:, icend:] = 0.0
-    return qsat
-
-
-def ref_nl_state(chk, st, prm, qsat=None):
-    """Reference outputs for a whole state: per-block SATUR + CLOUDSC2 exactly like cloudsc_driver_mod.F90:82-111."""
-    out = st.copy()
-    out.PCOVPTOT[...] = 0.0
-    out.B_LOC[:, 7] = 0.0
-    for ibl in range(st.nblocks):
-        icend = min(st.nproma, st.ngptot - ibl * st.nproma)
-        qs = qsat[ibl] if qsat is not None else chk.satur(np.ascontiguousarray(st.PAP[ibl]), np.ascontiguousarray(st.PT[ibl]), kfdia=icend)
-        o = chk.cloudsc2(st.ptsphy, refcall.block_inputs(st, ibl, qs), kfdia=icend, ldrain1d=bool(prm.ldrain1d))
-        for n, a in refcall.state_outputs_block(out, ibl).items():
-            a[:, :icend] = o[n][:, :icend]
-    return out
-
-
-def assert_outputs_close(ref_st, got_st, tol):
-    for n, r in ref_st.outputs().items():
-        g = got_st.outputs()[n]
-        assert np.all(np.isfinite(g)), n
-        assert relerr(r, g) <= tol, (n, relerr(r, g))
-        assert c2.validate_l1(r, g) <= tol, (n, c2.validate_l1(r, g))
 
 
 @pytest.mark.parametrize("nproma,ngptot", [(32, 100), (64, 100), (100, 100), (128, 300), (1, 7), (256, 1000), (1000, 2500),
@@ -109,76 +73,6 @@ def test_nl_random_atmospheres(seed):
     got = st.copy()
     c2.run_state(prm, got, "nl")
     assert_outputs_close(want, got, NL_TOL)
-
-
-def _device_tl_ad(tab, nproma, ngptot, flags):
-    """Run TL then AD on the GPU at kernel level (device pointers) and with the checker; returns both result sets."""
-    import torch
-
-    prm = c2.default_params(c2.ceta_from_table(tab), **flags)
-    st = c2.state_from_table(tab, nproma, ngptot)
-    nb, nlev = st.nblocks, st.nlev
-    chk = checker()
-    set_lib_params(chk, prm)
-    qsat = ref_qsat(chk, st)
-
-    ds = c2.DeviceState(st, "cuda:0")
-    ds.satur(prm)
-    torch.cuda.synchronize()
-    q_dev = ds.QSAT.cpu().numpy()
-    for ibl in range(nb):
-        icend = min(nproma, ngptot - ibl * nproma)
-        assert relerr(qsat[ibl][:, :icend], q_dev[ibl][:, :icend]) < 1e-14
-    inc = ds.increments()
-    tl_out = c2.FlatFields("out", nb, nlev, nproma, ds.device)
-    ds.tl(prm, inc, tl_out)
-    torch.cuda.synchronize()
-    tl_dev = {n: t.cpu().numpy() for n, t in tl_out.t.items()}
-    traj_dev = ds.download(st.copy())
-
-    # checker TL
-    inc_h = {n: t.cpu().numpy() for n, t in inc.t.items()}
-    tl_ref = flat_fields("out", nb, nlev, nproma)
-    traj_ref = st.copy()
-    for ibl in range(nb):
-        icend = min(nproma, ngptot - ibl * nproma)
-        dinp = {n: np.ascontiguousarray(inc_h[n][ibl]) for n in inc_h}
-        inp = refcall.block_inputs(st, ibl, qsat[ibl])
-        for d in (inp, dinp):  # keep the checker away from the uninitialised tail
-            for a in d.values():
-                a[:, icend:] = 1.0
-        o5, do = chk.cloudsc2tl(st.ptsphy, inp, dinp, kfdia=icend, ldrain1d=bool(prm.ldrain1d))
-        for n in do:
-            tl_ref[n][ibl][:, :icend] = do[n][:, :icend]
-        for n, a in refcall.state_outputs_block(traj_ref, ibl).items():
-            a[:, :icend] = o5[n][:, :icend]
-
-    # AD with y = TL output (the adjoint test's choice, cloudsc_driver_ad_mod.F90:216-237), x pre-filled with a
-    # non-zero background to check accumulation
-    rng = np.random.default_rng(5)
-    x0 = {n: rng.standard_normal(a.shape) * (np.abs(a).max() + 1e-30) for n, a in inc_h.items()}
-    adj_in = c2.FlatFields("in", nb, nlev, nproma, ds.device)
-    for n in x0:
-        adj_in.t[n].copy_(torch.from_numpy(x0[n]))
-    scratch = ds.new_scratch()
-    ds.ad(prm, adj_in, tl_out, scratch)
-    torch.cuda.synchronize()
-    x_dev = {n: t.cpu().numpy() for n, t in adj_in.t.items()}
-    y_after = {n: t.cpu().numpy() for n, t in tl_out.t.items()}
-
-    x_ref = {n: a.copy() for n, a in x0.items()}
-    for ibl in range(nb):
-        icend = min(nproma, ngptot - ibl * nproma)
-        inp = refcall.block_inputs(st, ibl, qsat[ibl])
-        for a in inp.values():
-            a[:, icend:] = 1.0
-        ain = {n: x_ref[n][ibl].copy() for n in x_ref}
-        aout = {n: tl_ref[n][ibl].copy() for n in tl_ref}  # consumed (zeroed) by the AD
-        chk.cloudsc2ad(st.ptsphy, inp, ain, aout, kfdia=icend, ldrain1d=bool(prm.ldrain1d))
-        for n in ain:
-            x_ref[n][ibl][:, :icend] = ain[n][:, :icend]
-    return dict(st=st, tl_dev=tl_dev, tl_ref=tl_ref, traj_dev=traj_dev, traj_ref=traj_ref, x_dev=x_dev, x_ref=x_ref,
-                x0=x0, y_after=y_after, inc=inc_h)
 
 
 @pytest.mark.parametrize("flags", [dict(), dict(lregcl=True), dict(levapls2=True), dict(levapls2=True, lregcl=True)])
@@ -815,21 +709,6 @@ def test_nl_without_lphylin(mode):
     lin = st.copy()
     c2.run_state(prm, lin, "nl")
     assert not np.array_equal(lin.B_LOC, got.B_LOC)  # the switch is read
-
-
-def _run_fortran(exe, *args, cwd=None, env=None):
-    import os
-    import subprocess
-
-    from tests.util import ROOT
-
-    path = os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "fortran", "build", exe)
-    if not os.path.exists(path):
-        pytest.fail(f"{path} missing: run __graft_entry__.build()")
-    full = None if env is None else {k: v for k, v in {**os.environ, **env}.items() if v != ""}  # (a variable set to "" is removed)
-    r = subprocess.run([path, *map(str, args)], capture_output=True, text=True, timeout=300, cwd=cwd, env=full)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout, r.stderr
 
 
 def test_fortran_drivers_through_iso_c_binding():

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.hostbuild import set_precise
 from tests.util import (B, c2, flat_block, flat_fields, host_traj_blocks, hostcheck, increments_of, make_params, refcall,
                         relerr, set_lib_params)
 
@@ -25,9 +26,9 @@ def oracle():
 def math_mode(request):
     """Both arithmetic variants of the kernels: shared-reciprocal fast math (default) and the reference's own
     operation order with IEEE division / libm exp (what the Taylor-test driver uses)."""
-    hostcheck().hostcheck_set_precise(int(request.param == "precise"))
+    set_precise(int(request.param == "precise"))
     yield request.param
-    hostcheck().hostcheck_set_precise(0)
+    set_precise(0)
 
 
 def oracle_qsat(oracle, st):
@@ -296,7 +297,7 @@ def test_lambda_sweep_of_the_taylor_test(oracle, nproma, ngptot, precise, off32,
     prm = make_params(tab, levapls2=levapls2)
     set_lib_params(oracle, prm)
     hc = hostcheck()
-    hc.hostcheck_set_precise(precise)
+    set_precise(precise)
     hc.hostcheck_set_off32(off32)
     try:
         st = c2.state_from_table(tab, nproma, ngptot)
@@ -352,7 +353,7 @@ def test_lambda_sweep_of_the_taylor_test(oracle, nproma, ngptot, precise, off32,
                 scale = np.abs(b[n]).max() * st.nlev
                 assert np.all(np.abs(got - acc[act]) <= 4 * np.finfo(B.REAL).eps * scale), (k, n, np.abs(got - acc[act]).max(), scale)
     finally:
-        hc.hostcheck_set_precise(0)
+        set_precise(0)
         hc.hostcheck_set_off32(0)
 
 

@@ -5,81 +5,17 @@ written."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests.test_hostcheck_vjp import host_qsat, vjp_lib
-from tests.util import (B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, host_traj_blocks, hostcheck, increments_of,
-                        make_params)
-
-BATCH_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_batch_sp.so" if B.SINGLE else "libhostcheck_batch.so")
-INT = np.int32 if B.SINGLE else np.int64
-FLAGS = [dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(lregcl=True)]  # those of test_hostcheck_vjp.py
-
-
-def build_hostcheck_batch() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_batch.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(BATCH_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(BATCH_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", BATCH_LIB, src])
-    return BATCH_LIB
-
-
-_lib = None
-
-
-def batch_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_batch())
-        pp = C.POINTER(B.Params)
-        lib.hostcheck_batch_max.restype = C.c_int
-        lib.hostcheck_tl_batch.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs), C.c_int,
-                                           C.POINTER(B.Inputs), C.POINTER(B.Outputs)]
-        lib.hostcheck_tl_batch.restype = C.c_int
-        lib.hostcheck_vjp_batch.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs), C.POINTER(B.Outputs),
-                                            C.c_int, C.POINTER(B.Inputs), C.POINTER(B.Outputs), C.c_void_p]
-        lib.hostcheck_vjp_batch.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    libs = (hostcheck(), vjp_lib(), batch_lib())
-    for lib in libs:
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in libs:
-        lib.hostcheck_set_precise(0)
-
-
-def same_bits(a: np.ndarray, b: np.ndarray) -> bool:
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(INT), np.ascontiguousarray(b).view(INT))
-
-
-def tail_checks(arrays: dict, nproma: int, ngptot: int, what: str) -> None:
-    """arrays were NaN-filled before the sweep: every active element written, the padded tail still NaN"""
-    for n, a in arrays.items():
-        for ibl in range(a.shape[0]):
-            icend = min(nproma, ngptot - ibl * nproma)
-            assert not np.any(np.isnan(a[ibl][:, :icend])), (what, "active element not written", n, ibl)
-            assert np.all(np.isnan(a[ibl][:, icend:])), (what, "padded tail touched", n, ibl)
-
-
-def block_array(kind: str, per_direction: list):
-    typ = B.Inputs if kind == "in" else B.Outputs
-    return (typ * len(per_direction))(*[flat_block(kind, d) for d in per_direction])
+from tests.hostbuild import host_lib, precise  # noqa: F401
+from tests.util import (FLAGS, B, block_array, c2, flat_block, flat_fields, host_qsat, host_traj_blocks, hostcheck, increments_of,
+                        make_params, same_bits, tail_checks)
 
 
 def test_batch_max_of_the_host_build_is_the_librarys():
-    assert batch_lib().hostcheck_batch_max() == B.lib.cloudsc2_batch_max()
+    assert host_lib("batch").hostcheck_batch_max() == B.lib.cloudsc2_batch_max()
 
 
 @pytest.mark.parametrize("flags", FLAGS)
@@ -91,7 +27,7 @@ def test_batched_columns_equal_single_direction_columns(precise, flags):
     nb = st.nblocks
     qsat = host_qsat(st)
     inc = increments_of(st, qsat)
-    hc, hv, hb = hostcheck(), vjp_lib(), batch_lib()
+    hc, hv, hb = hostcheck(), host_lib("vjp"), host_lib("batch")
     kmax = hb.hostcheck_batch_max()
     assert 2 <= kmax <= 8
 

@@ -7,99 +7,14 @@ the CPU."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_sweeps import HALF, fold, table_of, weight_patterns
+from tests.hostbuild import host_lib, precise  # noqa: F401
 from tests.sparse_patterns import NARROW, in_names
-from tests.test_hostcheck_vjp import host_qsat
-from tests.util import B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, hfld, host_traj_blocks, increments_of, make_params
-
-COLSUM_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_colsum_sp.so" if B.SINGLE else "libhostcheck_colsum.so")
-BITS = np.int32 if B.SINGLE else np.int64
-HALF = ("fplsl", "fplsn", "fhpsl", "fhpsn")
-
-
-def build_hostcheck_colsum() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_colsum.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck_sparse.hip"), os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp", "cloudsc2_fields.hpp")]
-    if (not os.path.exists(COLSUM_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(COLSUM_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", COLSUM_LIB, src])
-    return COLSUM_LIB
-
-
-_lib = None
-
-
-def colsum_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_colsum())
-        pp, pi, po = C.POINTER(B.Params), C.POINTER(B.Inputs), C.POINTER(B.Outputs)
-        geom = [pp, C.c_double, C.c_int, C.c_int, C.c_int]
-        lib.hostcheck_sparse_forward.argtypes = geom + [pi, po, C.c_void_p]
-        lib.hostcheck_nl.argtypes = geom + [pi, po, B.Field, C.c_double]
-        lib.hostcheck_sparse_tl.argtypes = geom + [C.c_int, C.c_int, pi, pi, po]
-        lib.hostcheck_sparse_vjp.argtypes = geom + [C.c_int, C.c_int, pi, po, pi, po, C.c_void_p]
-        lib.hostcheck_colsum_nl.argtypes = geom + [pi, C.c_void_p, po, po, C.c_void_p]
-        lib.hostcheck_colsum_tl.argtypes = geom + [C.c_int, pi, pi, C.c_void_p, po]
-        lib.hostcheck_colsum_vjp.argtypes = geom + [C.c_int, pi, po, pi, C.c_void_p, po, C.c_void_p]
-        for f in (lib.hostcheck_sparse_forward, lib.hostcheck_nl, lib.hostcheck_sparse_tl, lib.hostcheck_sparse_vjp, lib.hostcheck_colsum_nl,
-                  lib.hostcheck_colsum_tl, lib.hostcheck_colsum_vjp):
-            f.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    colsum_lib().hostcheck_set_precise(p)
-    yield p
-    colsum_lib().hostcheck_set_precise(0)
-
-
-def same_bits(a: np.ndarray, b: np.ndarray) -> bool:
-    return np.array_equal(np.ascontiguousarray(a).view(BITS), np.ascontiguousarray(b).view(BITS))
-
-
-def weight_patterns(nlev: int) -> list:
-    """(name, {output: weights of length nlevx}); (a) has negative entries, exact zeros and non-zero entries at both ends"""
-    rng = np.random.default_rng(20261020)
-    nlevx = lambda n: nlev + (1 if n in HALF else 0)  # noqa: E731
-    a = {}
-    for n in B.OUT_NAMES:
-        w = rng.uniform(-1.0, 1.0, nlevx(n))
-        w[rng.random(nlevx(n)) < 0.2] = 0.0
-        w[0], w[-1] = -0.75, 0.625
-        a[n] = w.astype(B.REAL)
-    assert all((w < 0).any() and (w == 0).any() for w in a.values())
-    surface = np.zeros(nlev + 1, dtype=B.REAL)
-    surface[-1] = 1.0
-    pick = lambda *names: {n: a[n] for n in names}  # noqa: E731
-    return [("all", a), ("surface", {"fplsl": surface, "fplsn": surface.copy()}), ("tent,tenq", pick("tent", "tenq")), ("covptot", pick("covptot"))]
-
-
-def table_of(weights: dict, nlev: int) -> np.ndarray:
-    """the launchers' table: ten rows of nlev + 1, NaN where a row is not given or an entry is unused"""
-    t = np.full((len(B.OUT_NAMES), nlev + 1), np.nan, dtype=B.REAL)
-    for n, w in weights.items():
-        t[B.OUT_NAMES.index(n), :len(w)] = w
-    return t
-
-
-def fold(w: np.ndarray, plane: np.ndarray) -> np.ndarray:
-    """the contract: acc = +0; acc = fl(acc + fl(w[k] * plane[:, k, :])) in the library's real type"""
-    assert w.dtype == B.REAL and plane.dtype == B.REAL and len(w) == plane.shape[1]
-    acc = np.zeros((plane.shape[0], plane.shape[2]), dtype=B.REAL)
-    for k in range(len(w)):
-        p = w[k] * plane[:, k, :]
-        acc = acc + p
-    return acc
+from tests.util import B, c2, flat_block, flat_fields, host_qsat, host_traj_blocks, increments_of, make_params, same_bits
 
 
 def sums_block(names, nb: int, nproma: int, fill=np.nan):
@@ -134,7 +49,7 @@ def test_column_sums_are_the_fold_over_the_planes(precise, flags, satur):
     nb = st.nblocks
     qsat = None if satur else host_qsat(st)
     ins = in_names(satur)
-    lib = colsum_lib()
+    lib = host_lib("colsum")
     geom = (C.byref(prm), st.ptsphy, nproma, nlev, ngptot)
     active = (np.arange(nb * nproma) < ngptot).reshape(nb, nproma)
 

@@ -7,52 +7,24 @@ No tolerance anywhere: bytes and counts."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests.util import HOSTCHECK_DIR, ROOT, B, c2, make_params
+from tests.hostbuild import host_lib
+from tests.util import PARAM_NAMES, c2, make_params
 
-PARAM_NAMES = ("rkconv", "rclcrit", "rlptrc", "rpecons")  # the order of CLOUDSC2_NPAR
 KBLOCK = 128  # kBlock of cloudsc2_sweep_kernels.hpp
 # the shapes of the GPU test: (a) 72 padded columns, less than one workgroup; (b) 256, two workgroups per member
 SHAPES = {"a": (24, 70), "b": (64, 200)}
 
 
-def build_hostcheck_ens(single: bool) -> str:
-    lib = os.path.join(HOSTCHECK_DIR, "libhostcheck_ens_sp.so" if single else "libhostcheck_ens.so")
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_ens.hip")
-    deps = [src] + [os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(lib)) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if single else []) + ["-o", lib, src])
-    return lib
-
-
-_libs: dict = {}
-
-
-def ens_lib(single: bool):
-    if single not in _libs:
-        lib = C.CDLL(build_hostcheck_ens(single))
-        pp, pd = C.POINTER(B.Params), C.POINTER(C.c_double)
-        lib.hostcheck_ens_real_bytes.restype = C.c_int
-        lib.hostcheck_ens_consts.argtypes = [pp, C.c_double, pd, pd]
-        lib.hostcheck_ens_consts.restype = C.c_int
-        lib.hostcheck_ens_member_args.argtypes = [pp, C.c_double, pd, pd, C.c_int, C.c_int]
-        lib.hostcheck_ens_member_args.restype = C.c_int
-        lib.hostcheck_ens_locate.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
-        lib.hostcheck_ens_locate.restype = None
-        assert lib.hostcheck_ens_real_bytes() == (4 if single else 8)
-        _libs[single] = lib
-    return _libs[single]
-
-
 @pytest.fixture(params=["fp64", "fp32"])
 def lib(request):
-    return ens_lib(request.param == "fp32")
+    single = request.param == "fp32"
+    lib = host_lib("ens", single)
+    assert lib.hostcheck_ens_real_bytes() == (4 if single else 8)
+    return lib
 
 
 def dvec(values):

@@ -15,69 +15,20 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_sweeps import HALF, fold, table_of, weight_patterns
+from tests.hostbuild import host_lib, precise  # noqa: F401
 from tests.sparse_patterns import in_names, patterns
-from tests.test_hostcheck_colsum import HALF, fold, same_bits, table_of, weight_patterns
-from tests.test_hostcheck_par import par_lib
-from tests.test_hostcheck_vjp import host_qsat
-from tests.util import B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, hfld, make_params
+from tests.util import FLAGS, B, c2, flat_block, flat_fields, hfld, host_qsat, make_params, same_bits
 
-LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_enscolsum_sp.so" if B.SINGLE else "libhostcheck_enscolsum.so")
 PAR = ("rkconv", "rclcrit", "rlptrc", "rpecons")
 # factors / offsets on prm's values (rlptrc: an offset in K): row 0 is prm's own
 ROWS = [dict(rkconv=1.0, rclcrit=1.0, rlptrc=0.0, rpecons=1.0), dict(rkconv=1.3, rclcrit=0.8, rlptrc=-2.0, rpecons=1.1),
         dict(rkconv=0.7, rclcrit=1.25, rlptrc=1.5, rpecons=0.9)]
 K = len(ROWS)
-
-
-def build() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_enscolsum.hip")
-    deps = [src] + [os.path.join(HOSTCHECK_DIR, f) for f in ("hostcheck_colsum.hip", "hostcheck_sparse.hip", "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp", "cloudsc2_fields.hpp")]
-    if (not os.path.exists(LIB)) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", LIB, src])
-    return LIB
-
-
-_lib = None
-
-
-def the_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build())
-        pp, pi, po, ms, pd = C.POINTER(B.Params), C.POINTER(B.Inputs), C.POINTER(B.Outputs), C.POINTER(C.c_longlong), C.c_void_p
-        geom = [pp, C.c_double, C.c_int, C.c_int, C.c_int]
-        lib.hostcheck_sparse_forward.argtypes = geom + [pi, po, C.c_void_p]
-        lib.hostcheck_colsum_vjp.argtypes = geom + [C.c_int, pi, po, pi, C.c_void_p, po, C.c_void_p]
-        lib.hostcheck_enscolsum_nl.argtypes = geom + [C.c_int, pd, pi, ms, C.c_void_p, po, ms, po, ms, C.c_void_p, C.c_longlong]
-        lib.hostcheck_enscolsum_tl.argtypes = geom + [C.c_int, C.c_int, pd, pd, pi, ms, pi, ms, C.c_void_p, po, ms]
-        lib.hostcheck_enscolsum_vjp.argtypes = geom + [C.c_int, C.c_int, pd, pi, ms, po, ms, pi, ms, C.c_void_p, po, ms, C.c_void_p,
-                                                       C.c_longlong, pd, pd]
-        lib.hostcheck_enscolsum_locate.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
-        lib.hostcheck_enscolsum_locate.restype = None
-        for f in (lib.hostcheck_sparse_forward, lib.hostcheck_colsum_vjp, lib.hostcheck_enscolsum_nl, lib.hostcheck_enscolsum_tl,
-                  lib.hostcheck_enscolsum_vjp):
-            f.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    libs = (the_lib(), par_lib())
-    for lib in libs:
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in libs:
-        lib.hostcheck_set_precise(0)
 
 
 def flat_inputs(st, qsat) -> dict:
@@ -126,9 +77,6 @@ def active_mask(nb, nproma, ngptot, nlevx=None):
     return a if nlevx is None else a[:, None, :].repeat(nlevx, 1)
 
 
-FLAGS = [dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(lregcl=True)]
-
-
 @pytest.mark.parametrize("satur", [False, True], ids=["qsat", "satur"])
 @pytest.mark.parametrize("flags", FLAGS, ids=["plain", "levapls2+lregcl", "ldrain1d", "lregcl"])
 def test_members_are_the_bits_of_their_twins(precise, flags, satur):
@@ -139,7 +87,7 @@ def test_members_are_the_bits_of_their_twins(precise, flags, satur):
     st = c2.state_from_table(tab, nproma, ngptot)
     nb = st.nblocks
     np_pad = nb * nproma
-    lib, plib = the_lib(), par_lib()
+    lib, plib = host_lib("enscolsum"), host_lib("par")
     geom = lambda p: (C.byref(p), st.ptsphy, nproma, nlev, ngptot)  # noqa: E731
     ins = in_names(satur)
     x = flat_inputs(st, None if satur else host_qsat(st))
@@ -303,7 +251,7 @@ def test_the_new_locate_function_is_a_bijection_onto_members_and_columns():
     members, wgs, block = 5, 3, 128
     m = np.empty(members * wgs * block, dtype=np.uint32)
     c = np.empty(members * wgs * block, dtype=np.int64)
-    the_lib().hostcheck_enscolsum_locate(members, wgs, block, m.ctypes.data, c.ctypes.data)
+    host_lib("enscolsum").hostcheck_enscolsum_locate(members, wgs, block, m.ctypes.data, c.ctypes.data)
     pairs = set(zip(m.tolist(), c.tolist()))
     assert pairs == {(k, j) for k in range(members) for j in range(wgs * block)}
     m = m.reshape(members * wgs, block)

@@ -13,158 +13,22 @@ satur = 1 form against the satur = 0 form: the project's own numbers.  Measured:
 the parameter term), linearity 1.4e-14, dpar = 0 against the existing TL 0.0, satur = 1 against satur = 0 fed SATUR's qsat 0.0."""
 from __future__ import annotations
 
-import copy
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests.test_hostcheck_satur_lin import (FLAG_SETS, bits, blocks_of, field_err, increments15, run_tl_satur, run_vjp_satur,
-                                            satlin_lib, the_tables, trajectory_for_reverse)
-from tests.test_hostcheck_vjp import host_qsat, vjp_lib
-from tests.util import (B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, host_traj_blocks, hostcheck, increments_of,
-                        make_params, refcall, set_lib_params)
-
-PAR_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_par_sp.so" if B.SINGLE else "libhostcheck_par.so")
-PARAM_NAMES = ("rkconv", "rclcrit", "rlptrc", "rpecons")  # the order of CLOUDSC2_NPAR
-fp64_only = pytest.mark.skipif(B.SINGLE, reason="the bounds are fp64 statements")
-
-
-def build_hostcheck_par() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_par.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(PAR_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(PAR_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", PAR_LIB, src])
-    return PAR_LIB
-
-
-_lib = None
-
-
-def par_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_par())
-        pp, pi, po, pd = C.POINTER(B.Params), C.POINTER(B.Inputs), C.POINTER(B.Outputs), C.POINTER(C.c_double)
-        lib.hostcheck_tl_par.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, pi, pi, pd, po]
-        lib.hostcheck_vjp_par.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, pi, po, pi, po, C.c_void_p, C.c_void_p, pd]
-        lib.hostcheck_tl_par.restype = lib.hostcheck_vjp_par.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    libs = (hostcheck(), vjp_lib(), satlin_lib(), par_lib())
-    for lib in libs:
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in libs:
-        lib.hostcheck_set_precise(0)
+from tests.host_sweeps import (check_against_reference_differences, field_err, increments15, run_tl_par, run_tl_satur, run_vjp_par,
+                               run_vjp_satur, trajectory_for_reverse)
+from tests.hostbuild import host_lib, precise  # noqa: F401
+from tests.util import (FLAG_SETS, PARAM_NAMES, B, bits, blocks_of, c2, flat_block, flat_fields, fp64_only, host_qsat,
+                        host_traj_blocks, hostcheck, increments_of, make_params, refcall, set_lib_params, the_tables)
 
 
 @pytest.fixture(scope="module")
 def ref():
     """the reference itself where it is built, else its C restatement"""
     return refcall.RefLib() if refcall.have_ref() else refcall.OracleLib()
-
-
-def dvec(values) -> C.Array:
-    return (C.c_double * 4)(*[float(v) for v in values])
-
-
-def run_tl_par(prm, st, inc: dict, dpar, qsat=None) -> dict:
-    """TL(dx, dp) of the host build; qsat given: the satur = 0 form (inc holds 16 fields), None: satur = 1 (15 fields)"""
-    nb, nlev, nproma = st.nblocks, st.nlev, st.nproma
-    i, _ = host_traj_blocks(st, qsat)
-    tl = flat_fields("out", nb, nlev, nproma, fill=np.nan)
-    assert par_lib().hostcheck_tl_par(C.byref(prm), st.ptsphy, nproma, nlev, st.ngptot, int(qsat is None), C.byref(i),
-                                      C.byref(flat_block("in", inc)), dvec(dpar), C.byref(flat_block("out", tl))) == 0
-    return tl
-
-
-def run_vjp_par(prm, st, fwd, scratch, u: dict, qsat=None):
-    """the input adjoints, the (read-only) output adjoints, par_adj[4] and the workspace of the host build's parameter VJP"""
-    nb, nlev, nproma = st.nblocks, st.nlev, st.nproma
-    i, _ = host_traj_blocks(st, qsat)
-    _, o = host_traj_blocks(fwd, qsat)
-    xa = flat_fields("in", nb, nlev, nproma, fill=np.nan)
-    if qsat is None:
-        del xa["qsat"]
-    y = {n: a.copy() for n, a in u.items()}
-    work = np.full((4, nb * nproma), np.nan)
-    par_adj = dvec([np.nan] * 4)
-    assert par_lib().hostcheck_vjp_par(C.byref(prm), st.ptsphy, nproma, nlev, st.ngptot, int(qsat is None), C.byref(i), C.byref(o),
-                                       C.byref(flat_block("in", xa)), C.byref(flat_block("out", y)), scratch.ctypes.data,
-                                       work.ctypes.data, par_adj) == 0
-    return xa, y, np.array(par_adj[:]), work
-
-
-def with_param(prm, name: str, value: float):
-    p = copy.copy(prm)
-    setattr(p, name, value)
-    return p
-
-
-def reference_difference(ref, prm, st, qs, name: str, h: float) -> dict:
-    """(F(p (1 + h)) - F(p (1 - h))) / (2 h p) of the reference's NL kernel, one block"""
-    p0 = getattr(prm, name)
-    outs = []
-    for s in (+1.0, -1.0):
-        set_lib_params(ref, with_param(prm, name, p0 * (1.0 + s * h)))
-        outs.append(ref.cloudsc2(st.ptsphy, refcall.block_inputs(st, 0, qs), ldrain1d=bool(prm.ldrain1d)))
-    set_lib_params(ref, prm)
-    return {n: (outs[0][n] - outs[1][n]) / (2.0 * h * p0) for n in B.OUT_NAMES}
-
-
-def exact_zero_fields(name: str, evap: bool) -> tuple:
-    if name == "rpecons" and not evap:
-        return tuple(B.OUT_NAMES)
-    z = ["clc", "covptot"]
-    if name == "rclcrit" and evap:
-        z.append("teni")
-    return tuple(z)
-
-
-def check_against_reference_differences(ref, prm, st, qs, tl_of, label: str) -> float:
-    """tl_of(k) -> the parameter tangent for dpar = e_k as {field: (nlev[+1], 100)}; returns the worst error of the case"""
-    evap = bool(prm.levapls2 or prm.ldrain1d)
-    worst = 0.0
-    for k, name in enumerate(PARAM_NAMES):
-        fd5 = reference_difference(ref, prm, st, qs, name, 1e-5)
-        fd6 = reference_difference(ref, prm, st, qs, name, 1e-6)
-        tl = tl_of(k)
-        out = np.zeros(st.ngptot, dtype=bool)
-        for n in B.OUT_NAMES:
-            m = float(np.max(np.abs(fd6[n])))
-            if m > 0.0:
-                out |= np.max(np.abs(fd5[n] - fd6[n]), axis=0) > 1e-5 * m
-        assert out.sum() <= 2, (label, name, "columns left out", int(out.sum()))
-        keep = ~out
-        zeros = exact_zero_fields(name, evap)
-        errs = {}
-        for n in B.OUT_NAMES:
-            got, want = tl[n][:, keep], fd6[n][:, keep]
-            assert not np.any(np.isnan(got)), (label, name, n)
-            if n in zeros:
-                assert np.all(got == 0.0) and np.all(want == 0.0), (label, name, n, "must be exactly zero")
-                continue
-            m = float(np.max(np.abs(want)))
-            if m == 0.0:  # a field the reference does not move at all (tenl under rpecons): nor may the tangent
-                assert np.all(got == 0.0), (label, name, n, "the reference's difference vanishes, the tangent does not")
-                continue
-            errs[n] = float(np.max(np.abs(got - want))) / m
-        e = max(errs.values()) if errs else 0.0
-        print(f"{label} {name}: left out {int(out.sum())}, worst {e:.3e} " + " ".join(f"{n} {v:.1e}" for n, v in errs.items()))
-        for n, v in errs.items():
-            assert v <= 1e-5, (label, name, n, v)
-        worst = max(worst, e)
-    return worst
 
 
 @fp64_only
@@ -292,8 +156,8 @@ def test_superset_of_the_existing_sweeps_and_linearity(precise, flags, satur):
         _, o = host_traj_blocks(fwd, hq)
         xo = flat_fields("in", nb, nlev, nproma, fill=np.nan)
         y = {n: a.copy() for n, a in u.items()}
-        assert vjp_lib().hostcheck_vjp_sweep(C.byref(prm), st.ptsphy, nproma, nlev, ngptot, C.byref(i), C.byref(o),
-                                             C.byref(flat_block("in", xo)), C.byref(flat_block("out", y)), scratch.ctypes.data, 2, 1) == 0
+        assert host_lib("vjp").hostcheck_vjp_sweep(C.byref(prm), st.ptsphy, nproma, nlev, ngptot, C.byref(i), C.byref(o),
+                                                   C.byref(flat_block("in", xo)), C.byref(flat_block("out", y)), scratch.ctypes.data, 2, 1) == 0
     assert set(xp) == set(xo)
     for n in xp:
         assert np.array_equal(bits(xp[n]), bits(xo[n])), ("not the bits of the existing VJP", n)

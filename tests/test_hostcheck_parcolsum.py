@@ -11,58 +11,17 @@ order; the test prints every case."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_sweeps import NGPTOT, NPROMA, fold, run_parjac, table_of, weight_patterns
+from tests.hostbuild import host_lib, precise  # noqa: F401
 from tests.parcolsum_yardstick import BOUND, PAR_SUMS, RPECONS_ROWS, contract_sums
-from tests.test_hostcheck_colsum import fold, same_bits, table_of, weight_patterns
-from tests.test_hostcheck_par import PARAM_NAMES, par_lib
-from tests.test_hostcheck_parjac import NGPTOT, NPROMA, parjac_lib, run_parjac
-from tests.test_hostcheck_satur_lin import FLAG_SETS, blocks_of, satlin_lib, the_tables
-from tests.test_hostcheck_vjp import host_qsat, vjp_lib
-from tests.util import B, HOSTCHECK_DIR, ROOT, c2, flat_block, host_traj_blocks, hostcheck, make_params
+from tests.util import (FLAG_SETS, PARAM_NAMES, B, blocks_of, c2, flat_block, host_qsat, host_traj_blocks, make_params, same_bits,
+                        the_tables)
 
-PARCOLSUM_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_parcolsum_sp.so" if B.SINGLE else "libhostcheck_parcolsum.so")
 NLEV = 137
-
-
-def build_hostcheck_parcolsum() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_parcolsum.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(PARCOLSUM_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(PARCOLSUM_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", PARCOLSUM_LIB, src])
-    return PARCOLSUM_LIB
-
-
-_lib = None
-
-
-def parcolsum_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_parcolsum())
-        head = [C.POINTER(B.Params), C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs), C.c_void_p]
-        lib.hostcheck_parjac_colsum.argtypes = head + [C.POINTER(B.Outputs)]
-        lib.hostcheck_parnormal_colsum.argtypes = head + [C.POINTER(B.Outputs), C.POINTER(B.Outputs), C.c_void_p]
-        lib.hostcheck_parjac_colsum.restype = lib.hostcheck_parnormal_colsum.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    libs = (hostcheck(), vjp_lib(), satlin_lib(), par_lib(), parjac_lib(), parcolsum_lib())
-    for lib in libs:
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in libs:
-        lib.hostcheck_set_precise(0)
 
 
 def patterns() -> list:
@@ -84,8 +43,8 @@ def run_sums(prm, st, qsat, weights: dict) -> list:
     table = table_of(weights, st.nlev)
     sums = [{n: np.full((st.nblocks, st.nproma), np.nan, dtype=B.REAL) for n in weights} for _ in PARAM_NAMES]
     blocks = (B.Outputs * len(PARAM_NAMES))(*(flat_block("out", s) for s in sums))
-    assert parcolsum_lib().hostcheck_parjac_colsum(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(i), table.ctypes.data,
-                                                   blocks) == 0
+    assert host_lib("parcolsum").hostcheck_parjac_colsum(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(i), table.ctypes.data,
+                                                         blocks) == 0
     return sums
 
 
@@ -122,9 +81,9 @@ def run_normal(prm, st, qsat, weights: dict, r: dict, w) -> np.ndarray:
     table = table_of(weights, st.nlev)
     work = np.full((B.NNORMAL, st.nblocks * st.nproma), np.nan)
     before = {id(a): a.copy() for a in list(r.values()) + list((w or {}).values())}
-    assert parcolsum_lib().hostcheck_parnormal_colsum(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(i), table.ctypes.data,
-                                                      C.byref(flat_block("out", r)),
-                                                      C.byref(flat_block("out", w)) if w is not None else None, work.ctypes.data) == 0
+    assert host_lib("parcolsum").hostcheck_parnormal_colsum(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(i), table.ctypes.data,
+                                                            C.byref(flat_block("out", r)),
+                                                            C.byref(flat_block("out", w)) if w is not None else None, work.ctypes.data) == 0
     for a in list(r.values()) + list((w or {}).values()):
         assert same_bits(a, before[id(a)]), "the sweep changed a residual or a weight"
     return work

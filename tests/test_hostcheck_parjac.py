@@ -4,63 +4,19 @@
 Every direction must be the bits of the single-direction parameter TL (hostcheck_tl_par, satur = 0) run on all-zero increments with
 dpar = e_k: the host builds are compiled without contraction, so this holds exactly or the sweep is not the same arithmetic.  The form
 with SATUR evaluated in the sweep (qsat NULL) must be the bits of the form fed the host SATUR's plane.  Against the reference: central
-differences of its NL kernel, through check_against_reference_differences of tests/test_hostcheck_par.py -- bound 1e-5 of a field's
+differences of its NL kernel, through check_against_reference_differences of tests/host_sweeps.py -- tests/test_hostcheck_par.py's bound 1e-5 of a field's
 maximum at relative step 1e-6, a column left out when the steps 1e-5 and 1e-6 disagree by more than that, at most 2 of 100 columns;
 numbers established there from the reference alone.  Measured here, worst over the 8 cases: 1.658e-06 (synthetic, no evaporation,
 rkconv), no column left out but one (seed5, levapls2, rpecons) -- the figures of the single-direction sweep, whose bits these are."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from tests.test_hostcheck_par import (PARAM_NAMES, check_against_reference_differences, exact_zero_fields, fp64_only, par_lib,
-                                      run_tl_par)
-from tests.test_hostcheck_satur_lin import FLAG_SETS, bits, blocks_of, satlin_lib, the_tables
-from tests.test_hostcheck_vjp import host_qsat, vjp_lib
-from tests.util import (B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, host_traj_blocks, hostcheck, increments_of, make_params,
-                        refcall, set_lib_params)
-
-PARJAC_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_parjac_sp.so" if B.SINGLE else "libhostcheck_parjac.so")
-NPROMA, NGPTOT = 32, 100
-
-
-def build_hostcheck_parjac() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_parjac.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(PARJAC_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(PARJAC_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", PARJAC_LIB, src])
-    return PARJAC_LIB
-
-
-_lib = None
-
-
-def parjac_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_parjac())
-        lib.hostcheck_tl_parjac.argtypes = [C.POINTER(B.Params), C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs),
-                                            C.POINTER(B.Outputs)]
-        lib.hostcheck_tl_parjac.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    libs = (hostcheck(), vjp_lib(), satlin_lib(), par_lib(), parjac_lib())
-    for lib in libs:
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in libs:
-        lib.hostcheck_set_precise(0)
+from tests.host_sweeps import NGPTOT, NPROMA, check_against_reference_differences, exact_zero_fields, run_parjac, run_tl_par
+from tests.hostbuild import precise  # noqa: F401
+from tests.util import (FLAG_SETS, PARAM_NAMES, B, bits, blocks_of, c2, columns, fp64_only, host_qsat, increments_of, make_params,
+                        refcall, set_lib_params, the_tables)
 
 
 @pytest.fixture(scope="module")
@@ -69,24 +25,10 @@ def ref():
     return refcall.RefLib() if refcall.have_ref() else refcall.OracleLib()
 
 
-def run_parjac(prm, st, qsat=None) -> list:
-    """the four blocks of the host build's sweep, NaN-prefilled; qsat None: SATUR evaluated in the sweep"""
-    i, _ = host_traj_blocks(st, qsat)
-    sens = [flat_fields("out", st.nblocks, st.nlev, st.nproma, fill=np.nan) for _ in PARAM_NAMES]
-    blocks = (B.Outputs * len(PARAM_NAMES))(*(flat_block("out", s) for s in sens))
-    assert parjac_lib().hostcheck_tl_parjac(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(i), blocks) == 0
-    return sens
-
-
 def unit(k: int) -> list:
     e = [0.0] * len(PARAM_NAMES)
     e[k] = 1.0
     return e
-
-
-def columns(a: np.ndarray, ngptot: int) -> np.ndarray:
-    """(nblocks, nlevx, nproma) -> (nlevx, ngptot): the active columns in grid order"""
-    return a.transpose(1, 0, 2).reshape(a.shape[1], -1)[:, :ngptot]
 
 
 @pytest.mark.parametrize("flags", FLAG_SETS)

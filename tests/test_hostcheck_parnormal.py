@@ -10,55 +10,14 @@ evaporation branch, the subset), 2.4e-15 in fp32; the test prints every case."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_sweeps import NGPTOT, NPROMA, run_parjac
+from tests.hostbuild import host_lib, precise  # noqa: F401
 from tests.parnormal_yardstick import BOUND, RPECONS_ROWS, contract
-from tests.test_hostcheck_par import par_lib
-from tests.test_hostcheck_parjac import NGPTOT, NPROMA, columns, parjac_lib, run_parjac
-from tests.test_hostcheck_satur_lin import FLAG_SETS, blocks_of, satlin_lib, the_tables
-from tests.test_hostcheck_vjp import host_qsat, vjp_lib
-from tests.util import B, HOSTCHECK_DIR, ROOT, c2, flat_block, host_traj_blocks, hostcheck, make_params, refcall
-
-PARNORMAL_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_parnormal_sp.so" if B.SINGLE else "libhostcheck_parnormal.so")
-
-
-def build_hostcheck_parnormal() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_parnormal.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(PARNORMAL_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(PARNORMAL_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", PARNORMAL_LIB, src])
-    return PARNORMAL_LIB
-
-
-_lib = None
-
-
-def parnormal_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_parnormal())
-        lib.hostcheck_parnormal.argtypes = [C.POINTER(B.Params), C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs),
-                                            C.POINTER(B.Outputs), C.POINTER(B.Outputs), C.c_void_p]
-        lib.hostcheck_parnormal.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    libs = (hostcheck(), vjp_lib(), satlin_lib(), par_lib(), parjac_lib(), parnormal_lib())
-    for lib in libs:
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in libs:
-        lib.hostcheck_set_precise(0)
+from tests.util import FLAG_SETS, B, blocks_of, c2, columns, flat_block, host_qsat, host_traj_blocks, make_params, refcall, the_tables
 
 
 def observations(st, seed: int):
@@ -82,9 +41,9 @@ def run_parnormal(prm, st, qsat, r: dict, w) -> np.ndarray:
     """the host sweep's workspace (CLOUDSC2_NNORMAL, padded columns), NaN-prefilled; w None: the weight block itself is NULL"""
     i, _ = host_traj_blocks(st, qsat)
     work = np.full((B.NNORMAL, st.nblocks * st.nproma), np.nan)
-    assert parnormal_lib().hostcheck_parnormal(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(i),
-                                               C.byref(flat_block("out", r)), C.byref(flat_block("out", w)) if w is not None else None,
-                                               work.ctypes.data) == 0
+    assert host_lib("parnormal").hostcheck_parnormal(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(i),
+                                                     C.byref(flat_block("out", r)), C.byref(flat_block("out", w)) if w is not None else None,
+                                                     work.ctypes.data) == 0
     return work
 
 

@@ -10,70 +10,24 @@ a 1e-3 relative error in dqs/dt gives 1.2e-4)."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.host_sweeps import field_err, increments15, run_tl_satur, run_vjp_satur, trajectory_for_reverse
+from tests.hostbuild import host_lib, precise  # noqa: F401
 from tests.satur_lin_ref import satur_numpy, satur_partials_numpy
-from tests.test_hostcheck_vjp import host_qsat, vjp_lib
-from tests.util import (B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, hfld, host_traj_blocks, hostcheck, increments_of,
-                        make_params, refcall, set_lib_params)
+from tests.util import (FLAG_SETS, B, bits, blocks_of, c2, flat_block, flat_fields, fp64_only, hfld, host_qsat, host_traj_blocks,
+                        hostcheck, increments_of, make_params, refcall, set_lib_params, the_tables)
 
-SATLIN_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_satur_lin_sp.so" if B.SINGLE else "libhostcheck_satur_lin.so")
 SAT_NAMES = tuple(n for n in B.IN_NAMES if n != "qsat")
-FLAG_SETS = [dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(lregcl=True)]
 TLAD_TOL = 1e-11
-fp64_only = pytest.mark.skipif(B.SINGLE, reason="the bounds are fp64 statements")
-
-
-def build_hostcheck_satur_lin() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_satur_lin.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(SATLIN_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(SATLIN_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", SATLIN_LIB, src])
-    return SATLIN_LIB
-
-
-_lib = None
-
-
-def satlin_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_satur_lin())
-        pp, pi, po = C.POINTER(B.Params), C.POINTER(B.Inputs), C.POINTER(B.Outputs)
-        lib.hostcheck_satur_lin.argtypes = [pp, C.c_int, C.c_int, C.c_int] + [B.Field] * 5
-        lib.hostcheck_tl_satur.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, pi, pi, po]
-        lib.hostcheck_vjp_satur.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, pi, po, pi, po, C.c_void_p]
-        for f in (lib.hostcheck_satur_lin, lib.hostcheck_tl_satur, lib.hostcheck_vjp_satur):
-            f.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    libs = (hostcheck(), vjp_lib(), satlin_lib())
-    for lib in libs:
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in libs:
-        lib.hostcheck_set_precise(0)
 
 
 @pytest.fixture(scope="module")
 def ref():
     """the reference itself where it is built, else its C restatement"""
     return refcall.RefLib() if refcall.have_ref() else refcall.OracleLib()
-
-
-def the_tables():
-    return [("synthetic", c2.synthetic_table()), ("seed5", c2.random_table(137, 100, seed=5))]
 
 
 def one_block(a2d: np.ndarray) -> np.ndarray:
@@ -84,8 +38,8 @@ def one_block(a2d: np.ndarray) -> np.ndarray:
 def hc_satur_lin(prm, pap: np.ndarray, t: np.ndarray, want_qsat: bool = True):
     nb, nlev, nproma = pap.shape
     q, dp, dt = (np.full_like(pap, np.nan) for _ in range(3))
-    assert satlin_lib().hostcheck_satur_lin(C.byref(prm), nproma, nlev, nb * nproma, hfld(pap), hfld(t),
-                                            hfld(q) if want_qsat else B.Field(), hfld(dp), hfld(dt)) == 0
+    assert host_lib("satur_lin").hostcheck_satur_lin(C.byref(prm), nproma, nlev, nb * nproma, hfld(pap), hfld(t),
+                                                     hfld(q) if want_qsat else B.Field(), hfld(dp), hfld(dt)) == 0
     return q, dp, dt
 
 
@@ -94,10 +48,6 @@ def hc_satur(prm, pap: np.ndarray, t: np.ndarray) -> np.ndarray:
     q = np.full_like(pap, np.nan)
     assert hostcheck().hostcheck_satur(C.byref(prm), nproma, nlev, nb * nproma, hfld(pap), hfld(t), hfld(q)) == 0
     return q
-
-
-def bits(a: np.ndarray) -> np.ndarray:
-    return a.view(np.int32 if B.SINGLE else np.int64)
 
 
 @pytest.mark.parametrize("which", [0, 1])
@@ -168,33 +118,6 @@ def test_the_clamp_on_purpose(precise, ref, which):
     n = int(clamped[:5].sum())
     assert 450 <= n < 500, (name, "clamped of the 500 points of the top five levels", n)
     assert clamped[:3].sum() >= 299
-
-
-def blocks_of(st):
-    for ibl in range(st.nblocks):
-        yield ibl, min(st.nproma, st.ngptot - ibl * st.nproma)
-
-
-def increments15(st) -> dict:
-    inc = increments_of(st, np.zeros_like(st.PAP))
-    del inc["qsat"]
-    return inc
-
-
-def run_tl_satur(prm, st, inc15) -> dict:
-    nb, nlev, nproma = st.nblocks, st.nlev, st.nproma
-    i, _ = host_traj_blocks(st, None)
-    tl = flat_fields("out", nb, nlev, nproma, fill=np.nan)
-    assert satlin_lib().hostcheck_tl_satur(C.byref(prm), st.ptsphy, nproma, nlev, st.ngptot, C.byref(i), C.byref(flat_block("in", inc15)),
-                                           C.byref(flat_block("out", tl))) == 0
-    return tl
-
-
-def field_err(ref_blocks: list, got_blocks: list) -> float:
-    """max |got - ref| over the active columns relative to the field's maximum there"""
-    d = max(float(np.max(np.abs(g - r))) for r, g in zip(ref_blocks, got_blocks))
-    m = max(float(np.max(np.abs(r))) for r in ref_blocks)
-    return 0.0 if d == 0.0 else d / m
 
 
 @fp64_only
@@ -289,28 +212,6 @@ def test_composite_taylor_test_by_the_reference(precise, ref, case):
     assert min(abs(1.0 - r) for r in r0) > 1.0, (case, r0)
 
 
-def trajectory_for_reverse(prm, st, qsat):
-    """PFPLSL5 / PFPLSN5 and the cover checkpoints, as cloudsc2_ad_launch_forward leaves them"""
-    scratch = np.zeros((st.nblocks, st.nlev, st.nproma), dtype=B.REAL)
-    fwd = st.copy()
-    fi, fo = host_traj_blocks(fwd, qsat)
-    assert vjp_lib().hostcheck_vjp_sweep(C.byref(prm), st.ptsphy, st.nproma, st.nlev, st.ngptot, C.byref(fi), C.byref(fo), None, None,
-                                         scratch.ctypes.data, 1, 0) == 0
-    return fwd, scratch
-
-
-def run_vjp_satur(prm, st, fwd, scratch, u: dict):
-    nb, nlev, nproma = st.nblocks, st.nlev, st.nproma
-    i, _ = host_traj_blocks(st, None)
-    _, o = host_traj_blocks(fwd, None)
-    xa = flat_fields("in", nb, nlev, nproma, fill=np.nan)
-    del xa["qsat"]  # no plane for it: a write through its (NULL) pointer would fault
-    y = {n: a.copy() for n, a in u.items()}
-    assert satlin_lib().hostcheck_vjp_satur(C.byref(prm), st.ptsphy, nproma, nlev, st.ngptot, C.byref(i), C.byref(o),
-                                            C.byref(flat_block("in", xa)), C.byref(flat_block("out", y)), scratch.ctypes.data) == 0
-    return xa, y
-
-
 @fp64_only
 @pytest.mark.parametrize("flags", FLAG_SETS)
 def test_dot_product_identity_of_the_fused_sweeps(precise, flags):
@@ -357,8 +258,8 @@ def test_fused_vjp_against_the_existing_vjp_composed_with_the_partials(precise, 
     _, o = host_traj_blocks(fwd, qsat)
     xv = flat_fields("in", nb, nlev, nproma, fill=np.nan)
     y = {n: a.copy() for n, a in u.items()}
-    assert vjp_lib().hostcheck_vjp_sweep(C.byref(prm), st.ptsphy, nproma, nlev, ngptot, C.byref(i), C.byref(o), C.byref(flat_block("in", xv)),
-                                         C.byref(flat_block("out", y)), scratch.ctypes.data, 2, 1) == 0
+    assert host_lib("vjp").hostcheck_vjp_sweep(C.byref(prm), st.ptsphy, nproma, nlev, ngptot, C.byref(i), C.byref(o), C.byref(flat_block("in", xv)),
+                                               C.byref(flat_block("out", y)), scratch.ctypes.data, 2, 1) == 0
     _, dp, dt = hc_satur_lin(prm, np.ascontiguousarray(st.PAP), np.ascontiguousarray(st.PT))
     want = {"pap": xv["pap"] + dp * xv["qsat"], "t": xv["t"] + dt * xv["qsat"]}
     for n in SAT_NAMES:

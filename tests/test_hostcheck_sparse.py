@@ -5,60 +5,13 @@ Absent planes are NULL pointers: a missing guard in the column functions is a se
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.hostbuild import host_lib, precise  # noqa: F401
 from tests.sparse_patterns import in_names, patterns
-from tests.test_hostcheck_vjp import host_qsat
-from tests.util import (B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, host_traj_blocks, hostcheck, increments_of,
-                        make_params)
-
-SPARSE_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_sparse_sp.so" if B.SINGLE else "libhostcheck_sparse.so")
-BITS = np.int32 if B.SINGLE else np.int64
-
-
-def build_hostcheck_sparse() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_sparse.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp", "cloudsc2_fields.hpp")]
-    if (not os.path.exists(SPARSE_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(SPARSE_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", SPARSE_LIB, src])
-    return SPARSE_LIB
-
-
-_lib = None
-
-
-def sparse_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_sparse())
-        pp, pi, po = C.POINTER(B.Params), C.POINTER(B.Inputs), C.POINTER(B.Outputs)
-        lib.hostcheck_sparse_forward.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, pi, po, C.c_void_p]
-        lib.hostcheck_sparse_tl.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pi, pi, po]
-        lib.hostcheck_sparse_vjp.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, pi, po, pi, po, C.c_void_p]
-        for f in (lib.hostcheck_sparse_forward, lib.hostcheck_sparse_tl, lib.hostcheck_sparse_vjp):
-            f.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    for lib in (hostcheck(), sparse_lib()):
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in (hostcheck(), sparse_lib()):
-        lib.hostcheck_set_precise(0)
-
-
-def same_bits(a: np.ndarray, b: np.ndarray) -> bool:
-    return np.array_equal(np.ascontiguousarray(a).view(BITS), np.ascontiguousarray(b).view(BITS))
+from tests.util import B, c2, flat_block, flat_fields, host_qsat, host_traj_blocks, increments_of, make_params, same_bits
 
 
 def check_written(got: dict, want: dict, nb: int, nproma: int, ngptot: int, what) -> None:
@@ -82,7 +35,7 @@ def test_sparse_sweeps_have_the_dense_bits(precise, flags, satur):
     nb = st.nblocks
     qsat = None if satur else host_qsat(st)
     ins = in_names(satur)
-    lib = sparse_lib()
+    lib = host_lib("sparse")
     geom = (C.byref(prm), st.ptsphy, nproma, nlev, ngptot)
 
     # the trajectory: complete in every launch (PFPLSL5 / PFPLSN5 and the cover checkpoints from the trajectory pass)

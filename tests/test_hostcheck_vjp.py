@@ -5,60 +5,12 @@ adjoints except PSUPSAT, which is the true derivative, the output adjoints left 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests.util import (B, HOSTCHECK_DIR, ROOT, c2, flat_block, flat_fields, host_traj_blocks, hostcheck, increments_of,
-                        make_params)
-
-VJP_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_vjp_sp.so" if B.SINGLE else "libhostcheck_vjp.so")
-
-
-def build_hostcheck_vjp() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck_vjp.hip")
-    deps = [src, os.path.join(HOSTCHECK_DIR, "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(VJP_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(VJP_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", VJP_LIB, src])
-    return VJP_LIB
-
-
-_lib = None
-
-
-def vjp_lib():
-    global _lib
-    if _lib is None:
-        lib = C.CDLL(build_hostcheck_vjp())
-        lib.hostcheck_vjp_sweep.argtypes = [C.POINTER(B.Params), C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs),
-                                            C.POINTER(B.Outputs), C.POINTER(B.Inputs), C.POINTER(B.Outputs), C.c_void_p, C.c_int,
-                                            C.c_int]
-        lib.hostcheck_vjp_sweep.restype = C.c_int
-        _lib = lib
-    return _lib
-
-
-def host_qsat(st) -> np.ndarray:
-    qsat = np.zeros_like(st.PAP)
-    pap, t = np.ascontiguousarray(st.PAP), np.ascontiguousarray(st.PT)
-    f = lambda a: B.Field(a.ctypes.data, int(np.prod(a.shape[1:])))  # noqa: E731
-    prm = c2.default_params(np.full(st.nlev, 0.5))
-    assert hostcheck().hostcheck_satur(C.byref(prm), st.nproma, st.nlev, st.ngptot, f(pap), f(t), f(qsat)) == 0
-    return qsat
-
-
-@pytest.fixture(params=["fast", "precise"])
-def precise(request):
-    p = int(request.param == "precise")
-    for lib in (hostcheck(), vjp_lib()):
-        lib.hostcheck_set_precise(p)
-    yield p
-    for lib in (hostcheck(), vjp_lib()):
-        lib.hostcheck_set_precise(0)
+from tests.hostbuild import host_lib, precise  # noqa: F401
+from tests.util import B, c2, flat_block, flat_fields, host_qsat, host_traj_blocks, hostcheck, increments_of, make_params
 
 
 @pytest.mark.skipif(B.SINGLE, reason="the 1e-12 identity is an fp64 statement")
@@ -72,7 +24,7 @@ def test_vjp_sweep_against_assign_form(precise, flags):
     qsat = host_qsat(st)
     inc = increments_of(st, qsat)  # v = 0.01 x, PSUPSAT's included (nonzero)
     assert np.any(inc["supsat"] != 0.0)
-    hc, hv = hostcheck(), vjp_lib()
+    hc, hv = hostcheck(), host_lib("vjp")
 
     # u = TL v (and the trajectory outputs, PFPLSL5 / PFPLSN5 among them, written by the same sweep)
     got = st.copy()

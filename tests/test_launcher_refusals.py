@@ -19,70 +19,15 @@ import json
 import os
 import sys
 
-import numpy as np
 import pytest
 
-from tests.util import B, c2
+from tests.gpu_util import R_NB as NB, R_NGPTOT as NGPTOT, R_NLEV as NLEV, R_NPROMA as NPROMA, S, SH, World, refusal_params as params
+from tests.util import B
 
 JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "launcher_refusals.json")
-NPROMA, NLEV, NGPTOT, NB = 8, 4, 12, 2
-S, SH = NPROMA * NLEV, NPROMA * (NLEV + 1)  # block strides of the full-level and the half-level fields
 NCOLS = NB * NPROMA
 K = 2  # members of the ensemble cases
-HALF = ("paph", "fplsl", "fplsn", "fhpsl", "fhpsn")
 RP, DP = C.POINTER(B.c_real), C.POINTER(C.c_double)
-
-
-def params(**kw) -> B.Params:
-    p = c2.default_params(np.linspace(0.01, 1.0, NLEV))
-    for n, v in kw.items():
-        setattr(p, n, v)
-    return p
-
-
-class World:
-    """The pointers of the calls: dummies without a device, else device memory allocated once and kept (4 x the extent of a field
-    per field, so that a stride of a mismatch case stays inside too)."""
-
-    def __init__(self, device: bool):
-        self.device = device
-        self.kept = {}
-
-    def mem(self, key, n: int, real: bool = True) -> int:
-        if not self.device:
-            return 256
-        if key not in self.kept:
-            import torch
-
-            self.kept[key] = torch.zeros(n, dtype=B.torch_real() if real else torch.float64, device="cuda:0")
-        return self.kept[key].data_ptr()
-
-    def field(self, key, half: bool = False, stride: int | None = None) -> B.Field:
-        f = B.Field()
-        f.ptr = self.mem(key, 4 * NB * SH)
-        f.block_stride = stride if stride is not None else (SH if half else S)
-        return f
-
-    def block(self, cls, names, tag, only=None, **edit):
-        """edit[name] = None: a NULL field; an integer: that block stride.  only: the other fields are NULL."""
-        blk = cls()
-        for n in names:
-            if (only is not None and n not in only) or (n in edit and edit[n] is None):
-                continue
-            setattr(blk, n, self.field((tag, n), n in HALF, edit.get(n)))
-        return blk
-
-    def ins(self, tag="traj", **edit) -> B.Inputs:
-        return self.block(B.Inputs, B.IN_NAMES, tag, **edit)
-
-    def outs(self, tag="traj", **edit) -> B.Outputs:
-        return self.block(B.Outputs, B.OUT_NAMES, tag, **edit)
-
-    def dbl(self, key, n: int = 128 * NCOLS) -> C.c_void_p:
-        return C.c_void_p(self.mem(key, n, real=False))
-
-    def real(self, key, n: int = 4 * NB * SH) -> C.c_void_p:
-        return C.c_void_p(self.mem(key, n))
 
 
 def cases(W: World):

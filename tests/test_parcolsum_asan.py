@@ -12,31 +12,17 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.test_hostcheck_vjp import host_qsat
-from tests.test_sparse_asan import sanitizer_runtimes
-from tests.util import B, HOSTCHECK_DIR, ROOT, c2, increments_of, make_params
+from tests.hostbuild import SANITIZED_EXE_FLAGS, build
+from tests.util import B, HOSTCHECK_DIR, c2, host_qsat, increments_of, make_params, sanitizer_runtimes
 
-HIPCC = "/opt/rocm/bin/hipcc"
-EXE = os.path.join(HOSTCHECK_DIR, "parcolsum_asan_main_sp" if B.SINGLE else "parcolsum_asan_main")
 FLAGSETS = (dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(lregcl=True))
-
-
-def build() -> str:
-    src = os.path.join(HOSTCHECK_DIR, "parcolsum_asan_main.cpp")
-    deps = [src] + [os.path.join(HOSTCHECK_DIR, f) for f in ("hostcheck_parcolsum.hip", "hostcheck_parjac.hip", "hostcheck.hip")] + [
-        os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(EXE)) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
-        # host code only; -O0: the instrumented sweeps take minutes to optimise and a second to run as they are
-        subprocess.check_call([HIPCC, "--cuda-host-only", "-x", "hip", "-O0", "-g", "-fno-omit-frame-pointer", "-Xarch_host",
-                               "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", EXE, src])
-    return EXE
 
 
 def test_parameter_column_sums_under_the_host_sanitizers(tmp_path):
     if not sanitizer_runtimes():
         pytest.skip("no AddressSanitizer / UndefinedBehaviorSanitizer runtime in this toolchain")
-    exe = build()
+    exe = build(os.path.join(HOSTCHECK_DIR, "parcolsum_asan_main.cpp"), os.path.join(HOSTCHECK_DIR, "parcolsum_asan_main" + ("_sp" if B.SINGLE else "")),
+                flags=SANITIZED_EXE_FLAGS)
     nproma, nlev, ngptot = 8, 137, 12
     tab = c2.random_table(nlev, 30, seed=11)
     st = c2.state_from_table(tab, nproma, ngptot)

@@ -1,5 +1,6 @@
 """What cloudsc2_parjac_launch_colsum and cloudsc2_parnormal_launch_colsum refuse: the return code and the text of
-``cloudsc2_last_error()`` of every refusal, with the geometry and the pointers of test_launcher_refusals.py (NPROMA 8, NLEV 4, NGPTOT 12;
+``cloudsc2_last_error()`` of every refusal, with the geometry and the pointers of test_launcher_refusals.py (World in
+tests/gpu_util.py: NPROMA 8, NLEV 4, NGPTOT 12;
 dummies without a device, device memory of more than the implied extent with one).  All of them are checked before the device is looked
 for, so every case is CLOUDSC2_EINVAL on the CPU too; the message names the launcher; the cases whose loss would still be a valid small
 launch run again under ``-m gpu``.  After every refusal the calling thread's launch log is empty.  A well-formed call answers
@@ -12,8 +13,7 @@ import os
 
 import pytest
 
-from tests.test_colsum_refusals import SumWorld
-from tests.test_launcher_refusals import NGPTOT, NLEV, NPROMA, S, params
+from tests.gpu_util import R_NGPTOT as NGPTOT, R_NLEV as NLEV, R_NPROMA as NPROMA, S, SumWorld, refusal_params as params
 from tests.util import B, ROOT
 
 EINVAL = B.CLOUDSC2_EINVAL

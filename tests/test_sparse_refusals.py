@@ -1,5 +1,6 @@
 """What cloudsc2_tl_launch_sparse and cloudsc2_vjp_launch_sparse refuse: the return code and the text of ``cloudsc2_last_error()`` of
-every refusal, with the geometry and the pointers of test_launcher_refusals.py (NPROMA 8, NLEV 4, NGPTOT 12; dummies without a device,
+every refusal, with the geometry and the pointers of test_launcher_refusals.py (World in
+tests/gpu_util.py: NPROMA 8, NLEV 4, NGPTOT 12; dummies without a device,
 device memory of more than the implied extent with one).  All of them are checked before the device is looked for, so every case is
 CLOUDSC2_EINVAL on the CPU too; the cases whose loss would still be a valid small launch run again under ``-m gpu``.  After every
 refusal the calling thread's launch log is empty."""
@@ -9,7 +10,7 @@ import ctypes as C
 
 import pytest
 
-from tests.test_launcher_refusals import NGPTOT, NLEV, NPROMA, S, SH, World, params
+from tests.gpu_util import DistinctWorld, R_NGPTOT as NGPTOT, R_NLEV as NLEV, R_NPROMA as NPROMA, S, SH, World, refusal_params as params
 from tests.util import B
 
 EINVAL = B.CLOUDSC2_EINVAL
@@ -26,15 +27,6 @@ NO_COT = "sparse reverse sweep: no cotangent is given (every adj_out field is NU
 NO_GRAD = "sparse reverse sweep: no gradient is wanted (every adj_in field is NULL)"
 STRIDE = "sparse sweep: the present fields of one layout group must share one block stride"
 TWICE = "sparse sweep: a written plane is given twice"
-
-
-class DistinctWorld(World):
-    """World whose dummies differ from field to field: the sparse launchers refuse a written plane that is given twice"""
-
-    def mem(self, key, n: int, real: bool = True) -> int:
-        if self.device:
-            return super().mem(key, n, real)
-        return 4096 * (1 + self.kept.setdefault(key, len(self.kept)))
 
 
 def cases(W: World):

@@ -12,14 +12,9 @@ import threading
 
 import pytest
 
-from tests.util import B, c2
+from tests.util import (ADNORM, ASSIGN, CKPT, EVAP, NOLIN, OFF32, PARLIN, PERT, PRECISE, QSAT, SATLIN, SELFINC, TRAJ, VJP,  # noqa: F401
+                        B, c2)
 
-# C2F_* of csrc/cloudsc2_column.hpp (several bits mean different things to different families)
-QSAT, PRECISE, EVAP, OFF32 = 1, 2, 4, 32
-PERT = TRAJ = ASSIGN = 8
-CKPT = SELFINC = ADNORM = 16
-NOLIN = VJP = 64
-SATLIN, PARLIN = 128, 256
 PEO = PRECISE | EVAP | OFF32
 KMAX = B.lib.cloudsc2_batch_max()
 WORDS = range(1024)

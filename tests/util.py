@@ -4,57 +4,19 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
+import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from tests.hostbuild import HIPCC, HOSTCHECK_DIR, ROOT, B, host_lib  # noqa: F401  (ROOT is on sys.path from here on)
 
 import dwarf_p_cloudsc2_tl_ad_amd as c2  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import binding as B  # noqa: E402
 from oracle import refcall  # noqa: E402
-
-HOSTCHECK_DIR = os.path.join(ROOT, "tests", "hostcheck")
-HOSTCHECK_LIB = os.path.join(HOSTCHECK_DIR, "libhostcheck_sp.so" if B.SINGLE else "libhostcheck.so")
-
-
-def build_hostcheck() -> str:
-    if os.environ.get("CLOUDSC2_HOSTCHECK_LIB"):  # a differently built copy, e.g. the AddressSanitizer build of test_sanitize.py
-        return os.environ["CLOUDSC2_HOSTCHECK_LIB"]
-    src = os.path.join(HOSTCHECK_DIR, "hostcheck.hip")
-    deps = [src] + [os.path.join(ROOT, "dwarf_p_cloudsc2_tl_ad_amd", "csrc", f) for f in ("cloudsc2_level.hpp", "cloudsc2_column.hpp")]
-    if (not os.path.exists(HOSTCHECK_LIB)) or any(os.path.getmtime(d) > os.path.getmtime(HOSTCHECK_LIB) for d in deps):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-std=c++17"] + (["-DCLOUDSC2_SINGLE"] if B.SINGLE else []) + ["-o", HOSTCHECK_LIB, src])
-    return HOSTCHECK_LIB
-
-
-_hc = None
 
 
 def hostcheck():
     """The per-column device functions compiled for the host (tests/hostcheck) -- a unit-test vehicle, not a product path."""
-    global _hc
-    if _hc is None:
-        lib = C.CDLL(build_hostcheck())
-        pp = C.POINTER(B.Params)
-        lib.hostcheck_satur.argtypes = [pp, C.c_int, C.c_int, C.c_int, B.Field, B.Field, B.Field]
-        lib.hostcheck_nl.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs), C.POINTER(B.Outputs),
-                                     B.Field, C.c_double]
-        lib.hostcheck_tl.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs), C.POINTER(B.Outputs),
-                                     C.POINTER(B.Inputs), C.POINTER(B.Outputs)]
-        lib.hostcheck_ad.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs), C.POINTER(B.Outputs),
-                                     C.POINTER(B.Inputs), C.POINTER(B.Outputs), C.c_void_p]
-        lib.hostcheck_set_self_increment.argtypes = [C.c_double]
-        lib.hostcheck_set_yy.argtypes = [C.c_void_p]
-        lib.hostcheck_set_ad_norms.argtypes = [C.c_void_p]
-        lib.hostcheck_get_norm3_max.restype = C.c_double
-        lib.hostcheck_taylor_sweep.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(B.Inputs), C.POINTER(B.Outputs),
-                                               C.POINTER(B.Outputs), C.c_void_p]
-        _hc = lib
-    return _hc
+    return host_lib("")
 
 
 def hfld(a: np.ndarray, offset: int = 0, stride: int | None = None, real=None) -> B.Field:
@@ -127,3 +89,77 @@ def relerr(ref: np.ndarray, got: np.ndarray) -> float:
     if m == 0.0:
         return 0.0 if d == 0.0 else np.inf
     return d / m
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# what the host-build tests share
+# ---------------------------------------------------------------------------------------------------------------------
+BITS = np.int32 if B.SINGLE else np.int64  # the integer of an element's size: bits are compared through it
+PARAM_NAMES = c2.PARAM_NAMES  # rkconv, rclcrit, rlptrc, rpecons: the order of CLOUDSC2_NPAR
+FLAG_SETS = FLAGS = [dict(), dict(levapls2=True, lregcl=True), dict(ldrain1d=True), dict(lregcl=True)]
+fp64_only = pytest.mark.skipif(B.SINGLE, reason="the bounds are fp64 statements")
+
+
+# C2F_* of csrc/cloudsc2_column.hpp (several bits mean different things to different families)
+QSAT, PRECISE, EVAP, OFF32 = 1, 2, 4, 32
+PERT = TRAJ = ASSIGN = 8
+CKPT = SELFINC = ADNORM = 16
+NOLIN = VJP = 64
+SATLIN, PARLIN = 128, 256
+
+
+def the_tables():
+    return [("synthetic", c2.synthetic_table()), ("seed5", c2.random_table(137, 100, seed=5))]
+
+
+def host_qsat(st) -> np.ndarray:
+    qsat = np.zeros_like(st.PAP)
+    pap, t = np.ascontiguousarray(st.PAP), np.ascontiguousarray(st.PT)
+    f = lambda a: B.Field(a.ctypes.data, int(np.prod(a.shape[1:])))  # noqa: E731
+    prm = c2.default_params(np.full(st.nlev, 0.5))
+    assert hostcheck().hostcheck_satur(C.byref(prm), st.nproma, st.nlev, st.ngptot, f(pap), f(t), f(qsat)) == 0
+    return qsat
+
+
+def bits(a: np.ndarray) -> np.ndarray:
+    return a.view(BITS)
+
+
+def same_bits(a: np.ndarray, b: np.ndarray) -> bool:
+    return np.array_equal(np.ascontiguousarray(a).view(BITS), np.ascontiguousarray(b).view(BITS))
+
+
+def blocks_of(st):
+    for ibl in range(st.nblocks):
+        yield ibl, min(st.nproma, st.ngptot - ibl * st.nproma)
+
+
+def columns(a: np.ndarray, ngptot: int) -> np.ndarray:
+    """(nblocks, nlevx, nproma) -> (nlevx, ngptot): the active columns in grid order"""
+    return a.transpose(1, 0, 2).reshape(a.shape[1], -1)[:, :ngptot]
+
+
+def tail_checks(arrays: dict, nproma: int, ngptot: int, what: str) -> None:
+    """arrays were NaN-filled before the sweep: every active element written, the padded tail still NaN"""
+    for n, a in arrays.items():
+        for ibl in range(a.shape[0]):
+            icend = min(nproma, ngptot - ibl * nproma)
+            assert not np.any(np.isnan(a[ibl][:, :icend])), (what, "active element not written", n, ibl)
+            assert np.all(np.isnan(a[ibl][:, icend:])), (what, "padded tail touched", n, ibl)
+
+
+def block_array(kind: str, per_direction: list):
+    typ = B.Inputs if kind == "in" else B.Outputs
+    return (typ * len(per_direction))(*[flat_block(kind, d) for d in per_direction])
+
+
+def sanitizer_runtimes() -> bool:
+    """the static AddressSanitizer and UndefinedBehaviorSanitizer runtimes an executable links"""
+    for lib in ("libclang_rt.asan-x86_64.a", "libclang_rt.ubsan_standalone-x86_64.a"):
+        try:
+            p = subprocess.run(["/opt/rocm/lib/llvm/bin/clang", f"-print-file-name={lib}"], capture_output=True, text=True, timeout=60).stdout.strip()
+        except (OSError, subprocess.SubprocessError):
+            return False
+        if not (os.path.isabs(p) and os.path.exists(p)):
+            return False
+    return True

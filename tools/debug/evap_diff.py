@@ -5,7 +5,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np  # noqa: E402
 
-from tests.test_gpu_parity import checker, ref_nl_state  # noqa: E402
+from tests.gpu_util import checker, ref_nl_state  # noqa: E402
 from tests.util import c2, set_lib_params  # noqa: E402
 
 tab = c2.random_table(137, 64, seed=11)

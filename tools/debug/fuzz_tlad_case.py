@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np  # noqa: E402
 
 from tests.fuzz_cases import cases  # noqa: E402
-from tests.test_gpu_parity import _device_tl_ad  # noqa: E402
+from tests.gpu_util import _device_tl_ad  # noqa: E402
 from tests.util import c2  # noqa: E402
 
 case, seed = int(sys.argv[1]), int(sys.argv[2])

@@ -7,7 +7,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from tests.test_gpu_parity import checker, ref_nl_state  # noqa: E402
+from tests.gpu_util import checker, ref_nl_state  # noqa: E402
 from tests.util import c2, set_lib_params  # noqa: E402
 
 from tests.fuzz_cases import cases  # noqa: E402
