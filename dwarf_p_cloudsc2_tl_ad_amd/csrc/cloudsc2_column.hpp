@@ -460,24 +460,31 @@ enum : unsigned {
                      // with respect to RKCONV, RCLCRIT, RLPTRC, RPECONS (struct ParLin).  The argument block is TlParArgs / AdParArgs.
                      // TL: four parameter tangents add their source terms.  Reverse sweep: the lane sums its column's contributions
                      // in four doubles and stores them to the launch's workspace, which a second kernel folds in a fixed order
-                     // (cloudsc2_tl_launch_par, cloudsc2_vjp_launch_par; kernels: cloudsc2_kern_{tl,vjp}_par.hip)
+                     // (cloudsc2_tl_launch_par, cloudsc2_vjp_launch_par; kernels: the units tl_par, vjp_par)
   C2F_SPARSE = 512u, // TL (without TRAJ / SELFINC; with PARLIN only as C2F_MEMBER says) and the VJP form of the reverse sweep, each with QSAT or with
                      // SATLIN: only the planes of the launch's two bit masks are moved (struct SparseMasks below).  The argument block is
                      // TlSparseArgs / AdSparseArgs (cloudsc2_tl_launch_sparse, cloudsc2_vjp_launch_sparse; kernels:
-                     // cloudsc2_kern_{tl,vjp}_sparse.hip).  Off in every other instantiation.
+                     // the units tl_sparse, vjp_sparse).  Off in every other instantiation.
   C2F_COLSUM = 1024u, // NL (LPHYLIN form, never with PERT; with CKPT: the two flux planes and the cover checkpoint are kept), TL and the
                      // reverse sweep (both with SPARSE): an output is not a plane but its per-column weighted level sum (struct ColsumTab
                      // below).  NL / TL fold the level's outputs into accumulators and store one row per sum after the last level; the
                      // reverse sweep forms the cotangent of a level as weight x the column's sum cotangent.  The argument block is
                      // NlColsumArgs / TlColsumArgs / AdColsumArgs (cloudsc2_{nl,tl,vjp}_launch_colsum; kernels:
-                     // cloudsc2_kern_{nl,tl,vjp}_colsum.hip).  Off in every other instantiation.
+                     // the units {nl,tl,vjp}_colsum).  Off in every other instantiation.
   C2F_MEMBER = 2048u, // NL and TL with COLSUM: the column belongs to a member of an ensemble, so it is not the grid's global column; the lane
                      // keeps it in an LDS slot for the store of the sums after the level loop (ColsumAcc).  The TL and the reverse sweep of
                      // an ensemble's column sums are SPARSE | COLSUM | PARLIN: the parameter tangents add their source terms while absent
                      // field tangents are opaque zeros; the parameter adjoints are summed while the gradient planes are stored under the
                      // write mask, which may be empty.  The argument block is NlColsumArgs / TlEnsColsumArgs / AdEnsColsumArgs
-                     // (cloudsc2_{nl,tl,vjp}_launch_ens_colsum; kernels: cloudsc2_kern_{nl,tl,vjp}_ens_colsum.hip).
+                     // (cloudsc2_{nl,tl,vjp}_launch_ens_colsum; kernels: the units {nl,tl,vjp}_ens_colsum).
 };
+
+// Waves per SIMD a sweep is built for, from its flag word: the kernels' launch bounds, the priority code of tl_column and the launchers'
+// choice between keeping a launch's waves abreast and pacing it all read it here (cloudsc2_sweep_kernels.hpp says what was measured).
+// NL (every kernel over nl_column alone): three without the evaporation branch, which fit 168 VGPRs; the others take what they need.
+constexpr int nl_waves_per_simd(unsigned f) { return (f & C2F_EVAP) ? 1 : 3; }
+// TL (every kernel over tl_column): three in fp32 with 32-bit offsets and without the evaporation branch, one otherwise -- all of fp64.
+constexpr int tl_waves_per_simd(unsigned f) { return (sizeof(real_t) == 4 && (f & C2F_OFF32) && !(f & C2F_EVAP)) ? 3 : 1; }
 
 // ---------------------------------------------------------------------------------------------------------
 // Sparse sweeps (C2F_SPARSE): presence of a plane is a property of the LAUNCH
@@ -1114,7 +1121,7 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   const int nlev = a->g.nlev, nproma = a->g.nproma;
   // only the fp32 variants that run three waves per SIMD (tl_kernel's launch bounds) share their SIMDs; the others -- all fp64
   // ones -- are compiled without the priority code (one more live SGPR costs the register-tight fp64 kernel 4 %)
-  constexpr bool FAIRV = sizeof(real_t) == 4 && (F & C2F_OFF32) != 0 && !EVAP;
+  constexpr bool FAIRV = tl_waves_per_simd(F) == 3;
   const int fair = FAIRV ? a->g.fair : 0;
   LevelTabP tab = (LevelTabP)a->tab;
   ConstsP c = C2_CONSTS(a);

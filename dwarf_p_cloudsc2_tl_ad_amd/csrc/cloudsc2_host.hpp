@@ -8,8 +8,9 @@
 //   cloudsc2_driver.hip   the host-array drivers and the resident state
 //   cloudsc2_helpers.hip  host-only helpers of the C ABI (default parameters, offsets, validation text, the synthetic table, verdicts)
 //
-// The sweeps' kernels are in the family units cloudsc2_kern_<family>.hip, one per name of the Makefile's FAMILIES (cloudsc2_sweep_kernels.hpp).  A __global__ kernel stays in the unit
-// that launches it: without relocatable device code a kernel cannot be launched by name from another unit's code object.  Everything
+// The sweeps' kernels are in the family units, cloudsc2_kern.hip compiled once per name of the Makefile's FAMILIES; the table of
+// cloudsc2_sweep_kernels.hpp (C2_ROWS_<unit>) says which variant tables each holds and how the host numbers them.  Any other __global__
+// kernel stays in the unit that launches it: without relocatable device code a kernel cannot be launched by name from another unit's code object.  Everything
 // here has external linkage inside namespace cloudsc2; the link's version script (cloudsc2_hip.map) keeps it out of the dynamic symbol
 // table, where only the C ABI appears.
 #pragma once
@@ -60,23 +61,34 @@ int validate_launch_impl(const cloudsc2_real* table, int klon, int period, long 
 
 inline unsigned grid_for(long long ncols, int block) { return (unsigned)((ncols + block - 1) / block); }
 
-// The kernel families of the sweeps, as cloudsc2_kernel_occupancy, cloudsc2_variant_built and the launch log number them
+// The ten numbered kernel families of the sweeps, as cloudsc2_variant_built and the launch log number them; cloudsc2_kernel_occupancy
+// knows the first seven under the same numbers and five unnumbered tables as CLOUDSC2_KERNEL_* (10..14).  The rows of the table in
+// cloudsc2_sweep_kernels.hpp name these in their `family` and `kernel` columns (kNone: no number); the registry of cloudsc2_policy.hip
+// asserts that the rows' family numbers are exactly 0 .. kFamCount-1.
 enum SweepFamily {
   kFamNl = 0, kFamTl = 1, kFamAd = 2, kFamAdReverse = 3, kFamTlBatch = 4, kFamVjpBatch = 5, kFamTlParjac = 6, kFamTlPar = 7,
   kFamVjpPar = 8, kFamTaylor = 9, kFamCount = 10
 };
-// the variant's entry point (nullptr: not built); the batched families' word is flags + 64 x directions (cloudsc2_policy.hip)
+constexpr int kNone = -1;
+// the variant's entry point (nullptr: not built, or no such family); a walk of the registry (cloudsc2_policy.hip)
 const void* variant_entry(int family, unsigned word);
 // The calling thread's launch log (cloudsc2_debug_launch_log): a thread-local array of plain integers, no device call -- harmless
-// during stream capture.  Every sweep launch passes launch_variant, which records the kernel it has enqueued.
+// during stream capture.  Every launch of a numbered family passes launch_variant, which records the kernel it has enqueued.
 void log_launch(int family, unsigned word);
 
+// THE launch of a sweep kernel: `workgroups` of kBlock threads over the one by-value argument block.  The unnumbered tables' launchers
+// call it directly (nothing is logged for them), the numbered families' through launch_variant.
 template <class Args>
-int launch_variant(SweepFamily family, unsigned word, KernelFn<Args> fn, const Args& args, long long ncols, hipStream_t st) {
+int launch_kernel(KernelFn<Args> fn, const Args& args, unsigned workgroups, hipStream_t st) {
   if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   Args a = args;
   void* argv[] = {&a};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(ncols, kBlock)), dim3(kBlock), argv, 0, st));
+  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(workgroups), dim3(kBlock), argv, 0, st));
+  return 0;
+}
+template <class Args>
+int launch_variant(SweepFamily family, unsigned word, KernelFn<Args> fn, const Args& args, long long ncols, hipStream_t st) {
+  if (int rc = launch_kernel(fn, args, grid_for(ncols, kBlock), st)) return rc;
   log_launch(family, word);
   return 0;
 }
@@ -88,6 +100,13 @@ int launch_variant(SweepFamily family, unsigned word, KernelFn<Args> fn, const A
 //   nap   the lighter SIMDs of the fullest CUs may nap on top of that (the NL sweep's own launches),
 //   pace  the kernel whose launch of a few partial rounds of workgroups is paced (nullptr: not paced).
 void schedule(Geom& g, const void* fair, bool nap, const void* pace);
+// A launch over tl_column with flag word f: the fp32 variants that run three waves per SIMD (tl_waves_per_simd) share their SIMDs like
+// the NL kernel does: -3.7 % at 160 000 columns with the waves kept abreast; the fp64 TL and both adjoints run one wave per SIMD and
+// lose 1-5 % (profiles/r03_wave_times.txt); they are paced instead.
+inline void schedule_tl(Geom& g, unsigned f, const void* fn) {
+  const bool abreast = tl_waves_per_simd(f) == 3;
+  schedule(g, abreast ? fn : nullptr, false, abreast ? nullptr : fn);
+}
 int device_prepare();  // the synchronous moment: probes the current device once per process, caches the verdicts
 
 // ---- placement allocator (cloudsc2_alloc.hip) ---------------------------------------------------------------------------------------

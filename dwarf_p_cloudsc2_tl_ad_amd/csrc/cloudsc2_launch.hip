@@ -10,29 +10,10 @@
 // appear only in the two test-norm kernels.
 
 #include "cloudsc2_host.hpp"
-#ifdef C2_SINGLE_TU  // one translation unit (experiment / diagnostic builds): the family units are part of this one
-#include "cloudsc2_kern_nl.hip"
-#include "cloudsc2_kern_tl.hip"
-#include "cloudsc2_kern_ad.hip"
-#include "cloudsc2_kern_taylor.hip"
-#include "cloudsc2_kern_tl_batch.hip"
-#include "cloudsc2_kern_vjp_batch.hip"
-#include "cloudsc2_kern_tl_par.hip"
-#include "cloudsc2_kern_vjp_par.hip"
-#include "cloudsc2_kern_tl_parjac.hip"
-#include "cloudsc2_kern_parnormal.hip"
-#include "cloudsc2_kern_parcolsum.hip"
-#include "cloudsc2_kern_nl_ens.hip"
-#include "cloudsc2_kern_tl_ens.hip"
-#include "cloudsc2_kern_vjp_ens.hip"
-#include "cloudsc2_kern_tl_sparse.hip"
-#include "cloudsc2_kern_vjp_sparse.hip"
-#include "cloudsc2_kern_nl_colsum.hip"
-#include "cloudsc2_kern_tl_colsum.hip"
-#include "cloudsc2_kern_vjp_colsum.hip"
-#include "cloudsc2_kern_nl_ens_colsum.hip"
-#include "cloudsc2_kern_tl_ens_colsum.hip"
-#include "cloudsc2_kern_vjp_ens_colsum.hip"
+#ifdef C2_SINGLE_TU  // one translation unit (experiment / diagnostic builds): every row's table here, in place of the family units
+namespace cloudsc2 {
+C2_KERNEL_TABLES(C2_DEFINE_VARIANT)
+}  // namespace cloudsc2
 #endif
 
 using namespace cloudsc2;
@@ -40,8 +21,8 @@ using namespace cloudsc2;
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------
-// kernels: the sweeps' __global__ wrappers and their variant tables are cloudsc2_sweep_kernels.hpp + the family units
-// cloudsc2_kern_<family>.hip (the Makefile's FAMILIES); here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
+// kernels: the sweeps' __global__ wrappers and the table of their variant tables are cloudsc2_sweep_kernels.hpp, the tables themselves
+// the family units (cloudsc2_kern.hip per name of the Makefile's FAMILIES); here: SATUR as a kernel of its own, the data-format kernels and the test-norm kernels
 // ---------------------------------------------------------------------------------------------------------
 template <bool P>
 __global__ void __launch_bounds__(kBlock) satur_kernel(SaturArgs args) {
@@ -550,19 +531,14 @@ size_t ens_blocks_bytes(int members) { return ((size_t)members * kEnsBlockBytes 
 // Two launches, neither paced nor logged: the members' argument blocks, then the sweep over members x ceil(ncols_pad / kBlock) workgroups.
 template <class Args>
 int ens_launch(KernelFn<EnsArgs<Args>> fn, const Args& tmpl, double ptsphy, const EnsSpec& e, hipStream_t st) {
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
-  const Geom& g = geom_of(tmpl);
-  const unsigned wgs = grid_for(g.ncols_pad, kBlock);
-  if ((long long)wgs * e.members > 0x7fffffffLL) return fail(CLOUDSC2_EINVAL, "ensemble: members x workgroups per member exceeds the grid limit");
-  Args* blocks = (Args*)e.workspace;
-  hipLaunchKernelGGL(ens_args_kernel<Args>, dim3(grid_for(e.members, kEnsArgsBlock)), dim3(kEnsArgsBlock), 0, st, tmpl, e.ms, ptsphy, e.members,
-                     e.params, e.dparams, blocks);
-  HIP_TRY(hipGetLastError());
   EnsArgs<Args> a;
-  a.blocks = blocks; a.wgs_per_member = wgs;
-  void* argv[] = {&a};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(wgs * (unsigned)e.members), dim3(kBlock), argv, 0, st));
-  return 0;
+  a.blocks = (Args*)e.workspace; a.wgs_per_member = grid_for(geom_of(tmpl).ncols_pad, kBlock);
+  if (!fn) return launch_kernel(fn, a, 0, st);  // (its refusal comes first, and before the members' blocks are written)
+  if ((long long)a.wgs_per_member * e.members > 0x7fffffffLL) return fail(CLOUDSC2_EINVAL, "ensemble: members x workgroups per member exceeds the grid limit");
+  hipLaunchKernelGGL(ens_args_kernel<Args>, dim3(grid_for(e.members, kEnsArgsBlock)), dim3(kEnsArgsBlock), 0, st, tmpl, e.ms, ptsphy, e.members,
+                     e.params, e.dparams, (Args*)e.workspace);
+  HIP_TRY(hipGetLastError());
+  return launch_kernel(fn, a, a.wgs_per_member * (unsigned)e.members, st);
 }
 
 // What a TL launch runs.  pert_in NULL: the increments are 0.01*x of the trajectory inputs (C2F_SELFINC), supsat_inc * PSUPSAT for PSUPSAT,
@@ -604,14 +580,9 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   args.supsat_inc = (real_t)m.supsat_inc;
   args.yy = m.yy;
   const hipStream_t st = (hipStream_t)stream;
-  // the fp32 TL variants that run three waves per SIMD (tl_kernel's launch bounds) share their SIMDs like the NL kernel does:
-  // -3.7 % at 160 000 columns with the waves kept abreast; the fp64 TL and both adjoints run one wave per SIMD and lose 1-5 %
-  // (profiles/r03_wave_times.txt); they are paced instead
-  const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);
   if (!m.dpar) {
     if (m.ens) return fail(CLOUDSC2_EINVAL, "ensemble: the parameter form of the TL sweep (dpar) is required");
-    const void* tl = (const void*)tl_variant(w.f);
-    schedule(args.g, abreast ? tl : nullptr, false, abreast ? nullptr : tl);
+    schedule_tl(args.g, w.f, (const void*)tl_variant(w.f));
     return launch_variant(kFamTl, w.f, tl_variant(w.f), args, w.g.ncols_pad, st);
   }
   w.f |= C2F_PARLIN;
@@ -619,8 +590,7 @@ int tl_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   pargs.a = args;
   pargs.par = make_parlin(w.c, m.dpar);  // (an ensemble's template: overwritten whole by every member's row)
   if (m.ens) return ens_launch(tl_ens_variant(w.f), pargs, ptsphy, *m.ens, st);
-  const void* tl = (const void*)tl_par_variant(w.f);
-  schedule(pargs.a.g, abreast ? tl : nullptr, false, abreast ? nullptr : tl);
+  schedule_tl(pargs.a.g, w.f, (const void*)tl_par_variant(w.f));
   return launch_variant(kFamTlPar, w.f, tl_par_variant(w.f), pargs, w.g.ncols_pad, st);
 }
 
@@ -1077,12 +1047,8 @@ int cloudsc2_tl_launch_sparse(const cloudsc2_params* prm, double ptsphy, int npr
   args.c = w.c; args.g = w.g; args.s = w.s; args.in = w.in; args.out = w.out; args.tab = w.tab;
   args.supsat_inc = 0; args.yy = nullptr;
   const KernelFn<TlSparseArgs> fn = tl_sparse_variant(w.f);
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
-  const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);  // (tl_launch_impl says why)
-  schedule(args.g, abreast ? (const void*)fn : nullptr, false, abreast ? nullptr : (const void*)fn);
-  void* argv[] = {&sargs};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
-  return 0;
+  schedule_tl(args.g, w.f, (const void*)fn);
+  return launch_kernel(fn, sargs, grid_for(w.g.ncols_pad, kBlock), (hipStream_t)stream);
 }
 
 int cloudsc2_vjp_launch_sparse(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
@@ -1110,11 +1076,8 @@ int cloudsc2_vjp_launch_sparse(const cloudsc2_params* prm, double ptsphy, int np
   args.nl = w.nl();
   args.nl.ckpt = const_cast<cloudsc2_real*>(scratch);
   const KernelFn<AdSparseArgs> fn = vjp_sparse_variant(w.f);
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(args.nl.g, nullptr, false, (const void*)fn);
-  void* argv[] = {&sargs};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
-  return 0;
+  return launch_kernel(fn, sargs, grid_for(w.g.ncols_pad, kBlock), (hipStream_t)stream);
 }
 
 // ---- column sums formed in the sweeps (C2F_COLSUM) -------------------------------------------------------------------------------------
@@ -1184,11 +1147,8 @@ static int nl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
   cargs.a.ckpt = (keep && w.c.evap) ? scratch : nullptr;
   if (ens) return ens_launch(nl_ens_colsum_variant(w.f), cargs, ptsphy, *ens, (hipStream_t)stream);  // (neither paced nor kept abreast)
   const KernelFn<NlColsumArgs> fn = nl_colsum_variant(w.f);
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(cargs.a.g, (const void*)fn, !keep, nullptr);
-  void* argv[] = {&cargs};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
-  return 0;
+  return launch_kernel(fn, cargs, grid_for(w.g.ncols_pad, kBlock), (hipStream_t)stream);
 }
 
 static int tl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
@@ -1222,12 +1182,8 @@ static int tl_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
     return ens_launch(tl_ens_colsum_variant(w.f), eargs, ptsphy, *ens, (hipStream_t)stream);
   }
   const KernelFn<TlColsumArgs> fn = tl_colsum_variant(w.f);
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
-  const bool abreast = sizeof(real_t) == 4 && (w.f & C2F_OFF32) && !(w.f & C2F_EVAP);  // (tl_launch_impl says why)
-  schedule(args.g, abreast ? (const void*)fn : nullptr, false, abreast ? nullptr : (const void*)fn);
-  void* argv[] = {&cargs};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
-  return 0;
+  schedule_tl(args.g, w.f, (const void*)fn);
+  return launch_kernel(fn, cargs, grid_for(w.g.ncols_pad, kBlock), (hipStream_t)stream);
 }
 
 static int vjp_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
@@ -1270,12 +1226,9 @@ static int vjp_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma
     eargs.work = (double*)((char*)ens->workspace + ens_blocks_bytes(ens->members));
     if ((rc = ens_launch(vjp_ens_colsum_variant(w.f), eargs, ptsphy, *ens, (hipStream_t)stream))) return rc;
     if (kEnsColsumFieldsPass && sargs.m.wr) {  // fp32: the field gradients once more, in the column-sum twin's bits, over the same blocks
-      const KernelFn<VjpEnsColsumKArgs> fields = vjp_ens_colsum_fields_variant(w.f);
-      if (!fields) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
       VjpEnsColsumKArgs ka;
       ka.blocks = (const AdEnsColsumArgs*)ens->workspace; ka.wgs_per_member = grid_for(w.g.ncols_pad, kBlock);
-      void* argv[] = {&ka};
-      HIP_TRY(hipLaunchKernel((const void*)fields, dim3(ka.wgs_per_member * (unsigned)ens->members), dim3(kBlock), argv, 0, (hipStream_t)stream));
+      if ((rc = launch_kernel(vjp_ens_colsum_fields_variant(w.f), ka, ka.wgs_per_member * (unsigned)ens->members, (hipStream_t)stream))) return rc;
     }
     hipLaunchKernelGGL(par_fold_ens_kernel, dim3(PAR_COUNT, (unsigned)ens->members), dim3(kParFoldBlock), 0, (hipStream_t)stream,
                        (const double*)eargs.work, w.g.ncols_pad, (long long)w.g.ngptot, ens->par_adj);
@@ -1283,11 +1236,8 @@ static int vjp_colsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma
     return 0;
   }
   const KernelFn<AdColsumArgs> fn = vjp_colsum_variant(w.f);
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(args.nl.g, nullptr, false, (const void*)fn);
-  void* argv[] = {&cargs};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
-  return 0;
+  return launch_kernel(fn, cargs, grid_for(w.g.ncols_pad, kBlock), (hipStream_t)stream);
 }
 
 int cloudsc2_nl_launch_colsum(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const cloudsc2_inputs* in,
@@ -1467,13 +1417,14 @@ int cloudsc2_tl_launch_batch(const cloudsc2_params* prm, double ptsphy, int npro
   TlBatchArgs args;
   args.c = w.c; args.g = w.g; args.s = w.s; args.sp = sp; args.in = w.in; args.tab = w.tab;
   return for_each_chunk(nbatch, [&](int first, int count) {
-    const KernelFn<TlBatchArgs> fn = tl_batch_variant(w.f, count);  // (the direction count is the kernel's compile-time one)
+    const unsigned word = w.f + 64u * (unsigned)count;  // (the direction count is the kernel's compile-time one)
+    const KernelFn<TlBatchArgs> fn = tl_batch_variant(word);
     for (int b = 0; b < kBatchMax; ++b) {  // (the sets from `count` on are not read: valid pointers all the same)
       args.din[b] = din[first + (b < count ? b : 0)];
       args.dout[b] = dout[first + (b < count ? b : 0)];
     }
     schedule(args.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
-    return launch_variant(kFamTlBatch, w.f + 64u * (unsigned)count, fn, args, w.g.ncols_pad, (hipStream_t)stream);
+    return launch_variant(kFamTlBatch, word, fn, args, w.g.ncols_pad, (hipStream_t)stream);
   });
 }
 
@@ -1508,13 +1459,14 @@ int cloudsc2_vjp_launch_batch(const cloudsc2_params* prm, double ptsphy, int npr
   args.nl.ckpt = const_cast<cloudsc2_real*>(scratch);
   args.sa = sa;
   return for_each_chunk(nbatch, [&](int first, int count) {
-    const KernelFn<VjpBatchArgs> fn = vjp_batch_variant(w.f, count);
+    const unsigned word = w.f + 64u * (unsigned)count;
+    const KernelFn<VjpBatchArgs> fn = vjp_batch_variant(word);
     for (int b = 0; b < kBatchMax; ++b) {
       args.ain[b] = ain[first + (b < count ? b : 0)];
       args.aout[b] = aout[first + (b < count ? b : 0)];
     }
     schedule(args.nl.g, nullptr, false, kPaceBatch ? (const void*)fn : nullptr);
-    return launch_variant(kFamVjpBatch, w.f + 64u * (unsigned)count, fn, args, w.g.ncols_pad, (hipStream_t)stream);
+    return launch_variant(kFamVjpBatch, word, fn, args, w.g.ncols_pad, (hipStream_t)stream);
   });
 }
 
@@ -1594,11 +1546,8 @@ int cloudsc2_parnormal_launch(const cloudsc2_params* prm, double ptsphy, int npr
   if ((rc = par_sweep_args(w, prm, ptsphy, nproma, nlev, ngptot, traj_in, {sr.full, sr.half, sr.loc}, args))) return rc;
   const unsigned f = w.f & ~C2F_OFF32;  // (64-bit offsets always: a 32-bit form is not built)
   args.sr = sr; args.work = work;
-  const KernelFn<ParNormalArgs> fn = parnormal_variant(f);
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(args.g, nullptr, false, nullptr);
-  void* argv[] = {&args};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
+  if ((rc = launch_kernel(parnormal_variant(f), args, grid_for(w.g.ncols_pad, kBlock), (hipStream_t)stream))) return rc;
   return fold_normal(w.g, w.c.evap, work, normal, (hipStream_t)stream);
 }
 
@@ -1616,12 +1565,8 @@ static int parcolsum_impl(const cloudsc2_params* prm, double ptsphy, int nproma,
   memset(&w.out, 0, sizeof(w.out));
   if ((rc = par_sweep_args(w, prm, ptsphy, nproma, nlev, ngptot, traj_in, {args.cs.stride}, args))) return rc;
   args.cs.w = wtable;
-  const KernelFn<ParColsumArgs> fn = parcolsum_variant(w.f | form);
-  if (!fn) return fail(CLOUDSC2_EINVAL, "kernel variant not built");
   schedule(args.g, nullptr, false, nullptr);
-  void* argv[] = {&args};
-  HIP_TRY(hipLaunchKernel((const void*)fn, dim3(grid_for(w.g.ncols_pad, kBlock)), dim3(kBlock), argv, 0, (hipStream_t)stream));
-  return 0;
+  return launch_kernel(parcolsum_variant(w.f | form), args, grid_for(w.g.ncols_pad, kBlock), (hipStream_t)stream);
 }
 // what both launchers refuse first
 static int check_parcolsum(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, const cloudsc2_real* wtable) {

@@ -236,35 +236,48 @@ std::pair<int, int> cached_rules(int device, int per_cu) {
   return {-1, -1};
 }
 
-// workgroups per CU of every TL / AD variant that a launch may pace (their occupancy, asked of the runtime), distinct
+// The registry: the host's columns of the table in cloudsc2_sweep_kernels.hpp, one entry per variant table (pure host: the tables
+// themselves are the family units')
+struct KernelTable {
+  int family;      // cloudsc2_variant_built's and the launch log's number, or kNone
+  int kernel;      // cloudsc2_kernel_occupancy's number, or kNone
+  bool paced;      // device_prepare probes the pacing rule at its kernels' occupancies
+  unsigned slots;  // words 0 .. slots-1
+  const void* (*entry)(unsigned word);
+};
+#define C2_REGISTER(name, Args, slots, valid, family, kernel, paced) \
+  {family, kernel, paced, slots, [](unsigned word) { return (const void*)name##_variant(word); }},
+constexpr KernelTable kTables[] = {C2_KERNEL_TABLES(C2_REGISTER)};
+#undef C2_REGISTER
+constexpr bool families_numbered() {  // every number 0 .. kFamCount-1 names exactly one table
+  for (int family = 0; family < kFamCount; ++family) {
+    int n = 0;
+    for (const KernelTable& t : kTables) n += t.family == family;
+    if (n != 1) return false;
+  }
+  for (const KernelTable& t : kTables)
+    if (t.family != kNone && (t.family < 0 || t.family >= kFamCount)) return false;
+  return true;
+}
+static_assert(families_numbered(), "the rows' family numbers are enum SweepFamily's: 0 .. kFamCount-1, each once");
+// the entry of the one table whose column `number` (&KernelTable::family or ::kernel) holds `id`; nullptr: no such table, word not built
+const void* table_entry(int KernelTable::*number, int id, unsigned word) {
+  if (id != kNone)
+    for (const KernelTable& t : kTables)
+      if (t.*number == id) return t.entry(word);
+  return nullptr;
+}
+
+// workgroups per CU of every TL / AD variant that a launch may pace (their occupancy, asked of the runtime), distinct: every slot of
+// the paced tables (occupancy_known skips one that is not built)
 std::vector<int> paced_kernel_occupancies() {
   std::vector<int> out;
-  auto add = [&](const void* fn) {
-    Occupancy o;
-    if (occupancy_known(fn, &o) && std::find(out.begin(), out.end(), o.per_cu) == out.end()) out.push_back(o.per_cu);
-  };
-  for (unsigned f = 0; f < 64; ++f) {
-    add((const void*)tl_variant(f));
-    add((const void*)ad_variant(f));
-    add((const void*)ad_reverse_variant(f));
-  }
-  for (unsigned f = 64; f < 128; ++f) add((const void*)ad_reverse_variant(f));  // the vector-Jacobian forms (C2F_VJP)
-  for (unsigned f = C2F_SATLIN; f < 2u * C2F_SATLIN; ++f) {  // SATUR differentiated in the sweep (C2F_SATLIN)
-    add((const void*)tl_variant(f));
-    add((const void*)ad_reverse_variant(f));
-  }
-  for (unsigned f = 0; f < 64; ++f) {  // the batched sweeps
-    for (int nb = 2; nb <= kBatchMax; ++nb) {
-      add((const void*)tl_batch_variant(f, nb));
-      add((const void*)vjp_batch_variant(f, nb));
+  for (const KernelTable& t : kTables) {
+    if (!t.paced) continue;
+    for (unsigned word = 0; word < t.slots; ++word) {
+      Occupancy o;
+      if (occupancy_known(t.entry(word), &o) && std::find(out.begin(), out.end(), o.per_cu) == out.end()) out.push_back(o.per_cu);
     }
-    add((const void*)tl_parjac_variant(f));  // the parameter Jacobian's sweep
-  }
-  for (unsigned f = 0; f < 2u * C2F_SATLIN; ++f) {  // the sparse sweeps (C2F_SPARSE), with QSAT or with SATLIN
-    add((const void*)tl_sparse_variant(f));
-    add((const void*)vjp_sparse_variant(f));
-    add((const void*)tl_colsum_variant(f));  // the column-sum sweeps (C2F_COLSUM), scheduled like the sparse ones
-    add((const void*)vjp_colsum_variant(f));
   }
   return out;
 }
@@ -397,22 +410,7 @@ int device_prepare() {
   return 0;
 }
 
-// one lookup for cloudsc2_kernel_occupancy and cloudsc2_variant_built (pure host: the tables of the family units)
-const void* variant_entry(int family, unsigned word) {
-  switch (family) {
-    case kFamNl: return (const void*)nl_variant(word);
-    case kFamTl: return (const void*)tl_variant(word);
-    case kFamAd: return (const void*)ad_variant(word);
-    case kFamAdReverse: return (const void*)ad_reverse_variant(word);
-    case kFamTlBatch: return (const void*)tl_batch_variant(word % 64u, (int)(word / 64u));  // flags + 64 x directions
-    case kFamVjpBatch: return (const void*)vjp_batch_variant(word % 64u, (int)(word / 64u));
-    case kFamTlParjac: return (const void*)tl_parjac_variant(word);
-    case kFamTlPar: return (const void*)tl_par_variant(word);
-    case kFamVjpPar: return (const void*)vjp_par_variant(word);
-    case kFamTaylor: return (const void*)taylor_variant(word);
-    default: return nullptr;
-  }
-}
+const void* variant_entry(int family, unsigned word) { return table_entry(&KernelTable::family, family, word); }
 
 }  // namespace cloudsc2
 
@@ -461,14 +459,8 @@ int cloudsc2_device_rules(int workgroups_per_cu, int* nl_nap, int* pacing) {
 int cloudsc2_kernel_occupancy(int kernel, int flags, int* workgroups_per_cu) {
   if (!workgroups_per_cu) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: NULL argument");
   if (int rc = require_device()) return rc;
-  // (the sparse TL and reverse sweeps have no family number: the header's kernel numbers of their own)
-  const void* fn = kernel >= kFamNl && kernel <= kFamTlParjac  ? variant_entry(kernel, (unsigned)flags)
-                   : kernel == CLOUDSC2_KERNEL_TL_SPARSE        ? (const void*)tl_sparse_variant((unsigned)flags)
-                   : kernel == CLOUDSC2_KERNEL_VJP_SPARSE       ? (const void*)vjp_sparse_variant((unsigned)flags)
-                   : kernel == CLOUDSC2_KERNEL_NL_COLSUM        ? (const void*)nl_colsum_variant((unsigned)flags)
-                   : kernel == CLOUDSC2_KERNEL_TL_COLSUM        ? (const void*)tl_colsum_variant((unsigned)flags)
-                   : kernel == CLOUDSC2_KERNEL_VJP_COLSUM       ? (const void*)vjp_colsum_variant((unsigned)flags)
-                                                                : nullptr;
+  // (the registry's `kernel` column: families 0..6 under their own numbers, the sparse and column-sum tables under the header's)
+  const void* fn = table_entry(&KernelTable::kernel, kernel, (unsigned)flags);
   if (!fn) return fail(CLOUDSC2_EINVAL, "cloudsc2_kernel_occupancy: no such kernel variant in this build");
   Occupancy o;
   HIP_TRY(occupancy(fn, &o));

@@ -225,6 +225,8 @@ int cloudsc2_simd_population(long long workgroups, int cus, long long block, int
  * 4 batched TL, 5 batched reverse sweep, 6 the parameter Jacobian's sweep; flags = its C2F_* variant bits, cloudsc2_column.hpp; for the batched sweeps, whose kernels
  * are built per direction count, plus 64 x the directions of the launch, 2..cloudsc2_batch_max()) as the runtime reports them
  * (the sweeps of cloudsc2_tl_launch_satur / cloudsc2_vjp_launch_satur: kernel 1 / 3 with C2F_SATLIN = 128 among the flags).
+ * Kernels 10..14 are the CLOUDSC2_KERNEL_* numbers below (sparse and column-sum sweeps); 7, 8, 9 and anything else are refused.
+ * The numbering is one column of the table of variant tables in csrc/cloudsc2_sweep_kernels.hpp.
  *
  * What a caller with its own hipMalloc should expect.  The same kernel on the same data runs 0.78 or 0.92 ms (NL, 160 000 columns:
  * 0.73 vs 0.63 of the HBM peak) depending on WHERE in the HBM the state lies (profiles/r02_hbm_placement.md); cloudsc2_device_malloc*
@@ -803,6 +805,7 @@ int cloudsc2_validate_header(char* buf, int buflen);
  *   needed.  family 0..6 as cloudsc2_kernel_occupancy's `kernel` (0 NL, 1 TL, 2 AD both sweeps, 3 AD reverse sweep, 4 batched TL,
  *   5 batched reverse sweep, 6 the parameter Jacobian's sweep), 7 TL with the parameter tangents, 8 reverse sweep with the parameter
  *   adjoints, 9 the Taylor sweep; flags = the variant's C2F_* word (cloudsc2_column.hpp), for families 4 and 5 plus 64 x directions.
+ *   (The `family` column of the table of variant tables in csrc/cloudsc2_sweep_kernels.hpp; the other tables have no number.)
  * cloudsc2_debug_launch_log  the sweep kernels the CALLING THREAD's launcher calls have enqueued since its last
  *   cloudsc2_debug_launch_log_reset, in order: returns their number and writes the (family, word) pairs of the first min(max, 64) of
  *   them.  The log keeps 64 entries; further launches are counted but not recorded, so a return value above 64 says that the record

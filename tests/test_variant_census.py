@@ -1,8 +1,8 @@
 """The census of kernel variants this build ships (cloudsc2_variant_built) and the semantics of the calling thread's launch log
 (cloudsc2_debug_launch_log), as far as they show without a device.
 
-The expected sets are restated here from the validity expressions of the variant tables (csrc/cloudsc2_kern_*.hip,
-par_variant_valid / batch_kernel_valid / parjac_variant_valid in csrc/cloudsc2_sweep_kernels.hpp), not taken from the function under
+The expected sets are restated here from the validity predicates of the variant tables (the `valid` column of the table in
+csrc/cloudsc2_sweep_kernels.hpp: nl_variant_valid ... taylor_variant_valid, each next to its kernel there), not taken from the function under
 test: a table that grows or loses a variant fails here until the census -- and tests/test_gpu_offset_variants.py, which must then
 launch it -- is brought up to date."""
 from __future__ import annotations
@@ -20,19 +20,19 @@ KMAX = B.lib.cloudsc2_batch_max()
 WORDS = range(1024)
 
 
-def _nl(f):  # cloudsc2_kern_nl.hip, table of 128
+def _nl(f):  # nl_variant_valid, table of 128
     return f < 128 and (bool(f & EVAP) and not f & (PERT | NOLIN) if f & CKPT else not (f & NOLIN and f & PERT))
 
 
-def _tl(f):  # cloudsc2_kern_tl.hip, table of 256
+def _tl(f):  # tl_variant_valid, table of 256
     return f < 64 or (f < 256 and (f & ~PEO) == SATLIN)
 
 
-def _ad(f):  # cloudsc2_kern_ad.hip, table of 64
+def _ad(f):  # ad_variant_valid, table of 64
     return f < 64 and not f & ADNORM
 
 
-def _ad_reverse(f):  # cloudsc2_kern_ad.hip, table of 256
+def _ad_reverse(f):  # ad_reverse_variant_valid, table of 256
     if f >= 256:
         return False
     if f & SATLIN:
@@ -49,11 +49,11 @@ def _parjac(f):  # parjac_variant_valid, table of 64
     return not f & ~(QSAT | PEO)
 
 
-def _par(form):  # par_variant_valid, tables of 512
+def _par(form):  # tl_par_variant_valid / vjp_par_variant_valid (par_variant_valid), tables of 512
     return lambda f: f < 512 and (f & ~PEO) in (PARLIN | form | QSAT, PARLIN | form | SATLIN)
 
 
-def _taylor(f):  # cloudsc2_kern_taylor.hip, table of 64
+def _taylor(f):  # taylor_variant_valid, table of 64
     return f < 64 and not f & (PERT | CKPT)
 
 
