@@ -8,8 +8,8 @@ library and raises if it has not been built -- there is no CPU fallback.
 from . import binding  # noqa: F401  (raises ImportError when libcloudsc2_hip.so is missing)
 from .binding import (Cloudsc2Error, Params, adjoint_verdict, default_params, device_available, get_math_mode,  # noqa: F401
                       set_math_mode, taylor_verdict)
-from .state import (Cloudsc2State, bytes_per_column, ceta_from_table, column_range, nblocks_of, random_table,  # noqa: F401
-                    state_from_table, synthetic_table, validate_l1)
+from .state import (Cloudsc2State, bytes_per_column, ceta_from_table, column_range, nblocks_of, op_inputs, op_outputs,  # noqa: F401
+                    random_table, state_from_table, synthetic_table, validate_l1)
 from .driver import (DeviceState, FlatFields, ResidentState, cloudsc_driver, cloudsc_driver_ad, cloudsc_driver_tl,  # noqa: F401
                      run_state)
 from .autograd import (PARAM_NAMES, Cloudsc2Outputs, NormalEquations, check_column_sums, check_ensemble, check_ensemble_column_sums,  # noqa: F401,E402

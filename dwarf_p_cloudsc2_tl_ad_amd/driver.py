@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding as B
-from .state import PLANE_A, PLANE_Q, PLANE_QI, PLANE_QL, PLANE_QV, PLANE_T, Cloudsc2State, nblocks_of
+from .state import PLANE_A, PLANE_Q, PLANE_QI, PLANE_QL, PLANE_QV, PLANE_T, Cloudsc2State, nblocks_of, op_inputs, op_outputs
 
 _dp = C.POINTER(C.c_double)
 _rp = C.POINTER(B.c_real)
@@ -293,6 +293,13 @@ class DeviceState:
         o.fhpsl = _fld(self.PFHPSL, 0, H); o.fhpsn = _fld(self.PFHPSN, 0, H)
         return o
 
+    def op_inputs(self, qsat: bool = True) -> dict:
+        """the differentiable op's inputs as views of this state (state.op_inputs); qsat=False: the 15 names of autograd.SAT_NAMES"""
+        return {n: t for n, t in op_inputs(self).items() if qsat or n != "qsat"}
+
+    def op_outputs(self) -> dict:
+        return op_outputs(self)
+
     def zero_plane(self) -> B.Field:
         # TENDENCY_LOC(IBL)%cld(:,:,NCLV)=0 (cloudsc_driver_mod.F90:88): plane QV of B_LOC
         S = self.nproma * self.nlev
@@ -408,11 +415,7 @@ class DeviceState:
         """dx = 0.01 * x for the 16 inputs (cloudsc_driver_tl_mod.F90:156-171); ZSUPSAT = 0 in the adjoint test
         (cloudsc_driver_ad_mod.F90:139).  `into`: an existing input set (e.g. one half of FlatFields.pair) to fill."""
         ff = into if into is not None else FlatFields("in", self.nb, self.nlev, self.nproma, self.device, zero=False)
-        src = {"paph": self.PAPH, "pap": self.PAP, "q": self.PQ, "qsat": self.QSAT, "t": self.PT,
-               "l": self.PCLV[:, 0], "i": self.PCLV[:, 1], "lude": self.PLUDE, "lu": self.PLU, "mfu": self.PMFU,
-               "mfd": self.PMFD, "gtent": self.B_CML[:, PLANE_T], "gtenq": self.B_CML[:, PLANE_Q],
-               "gtenl": self.B_CML[:, PLANE_QL], "gteni": self.B_CML[:, PLANE_QI], "supsat": self.PSUPSAT}
-        for n, s in src.items():
+        for n, s in op_inputs(self).items():
             if n == "supsat" and zero_supsat:
                 ff.t[n].zero_()
             else:

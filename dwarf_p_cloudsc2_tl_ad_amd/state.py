@@ -162,6 +162,26 @@ class Cloudsc2State:
         }
 
 
+def op_inputs(st, qsat=None) -> dict:
+    """The differentiable op's named inputs (binding.IN_NAMES, in that order) as views of the arrays of ``st`` (a Cloudsc2State, a
+    DeviceState, anything with their attribute names): the mapping of cloudsc_driver_mod.F90:94-107, written here once.  ``qsat``: the
+    argument if given, else ``st.QSAT`` if the state has one, else the key is absent (the 15 names of autograd.SAT_NAMES)."""
+    if qsat is None:
+        qsat = getattr(st, "QSAT", None)
+    x = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "qsat": qsat, "t": st.PT, "l": st.PCLV[:, NCLDQL], "i": st.PCLV[:, NCLDQI],
+         "lude": st.PLUDE, "lu": st.PLU, "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, PLANE_T], "gtenq": st.B_CML[:, PLANE_Q],
+         "gtenl": st.B_CML[:, PLANE_QL], "gteni": st.B_CML[:, PLANE_QI], "supsat": st.PSUPSAT}
+    if qsat is None:
+        del x["qsat"]
+    return x
+
+
+def op_outputs(st) -> dict:
+    """The op's named outputs (binding.OUT_NAMES, in that order) as views of a state's arrays (cloudsc_driver_mod.F90:94-107)."""
+    return {"tent": st.B_LOC[:, PLANE_T], "tenq": st.B_LOC[:, PLANE_Q], "tenl": st.B_LOC[:, PLANE_QL], "teni": st.B_LOC[:, PLANE_QI],
+            "clc": st.PA, "fplsl": st.PFPLSL, "fplsn": st.PFPLSN, "fhpsl": st.PFHPSL, "fhpsn": st.PFHPSN, "covptot": st.PCOVPTOT}
+
+
 def state_from_table(tab: dict, nproma: int, ngptot: int, col0: int = 0, poison_outputs: float | None = None,
                      real=None) -> Cloudsc2State:
     """LOAD of cloudsc2_array_state_mod.F90:153-203 with the table standing in for input.h5: tile the inputs

@@ -263,17 +263,14 @@ def have_oracle() -> bool:
 # ---------------------------------------------------------------------------------------------------------------------
 def block_inputs(st, ibl: int, qsat: np.ndarray | None = None) -> dict:
     """The 16 kernel inputs of block ibl as contiguous (KLEV[+1], KLON) arrays (cloudsc_driver_mod.F90:94-107)."""
-    c = np.ascontiguousarray
-    return {
-        "paph": c(st.PAPH[ibl]), "pap": c(st.PAP[ibl]), "q": c(st.PQ[ibl]),
-        "qsat": c(qsat) if qsat is not None else np.zeros_like(st.PAP[ibl]), "t": c(st.PT[ibl]),
-        "l": c(st.PCLV[ibl, 0]), "i": c(st.PCLV[ibl, 1]), "lude": c(st.PLUDE[ibl]), "lu": c(st.PLU[ibl]),
-        "mfu": c(st.PMFU[ibl]), "mfd": c(st.PMFD[ibl]), "gtent": c(st.B_CML[ibl, 0]), "gtenq": c(st.B_CML[ibl, 2]),
-        "gtenl": c(st.B_CML[ibl, 3]), "gteni": c(st.B_CML[ibl, 4]), "supsat": c(st.PSUPSAT[ibl]),
-    }
+    from dwarf_p_cloudsc2_tl_ad_amd.state import op_inputs
+
+    x = {n: np.ascontiguousarray(a[ibl]) for n, a in op_inputs(st).items()}
+    x["qsat"] = np.ascontiguousarray(qsat) if qsat is not None else np.zeros_like(st.PAP[ibl])  # (a block's own, not the state's)
+    return {n: x[n] for n in IN16}
 
 
 def state_outputs_block(st, ibl: int) -> dict:
-    return {"tent": st.B_LOC[ibl, 0], "tenq": st.B_LOC[ibl, 2], "tenl": st.B_LOC[ibl, 3], "teni": st.B_LOC[ibl, 4],
-            "clc": st.PA[ibl], "fplsl": st.PFPLSL[ibl], "fplsn": st.PFPLSN[ibl], "fhpsl": st.PFHPSL[ibl],
-            "fhpsn": st.PFHPSN[ibl], "covptot": st.PCOVPTOT[ibl]}
+    from dwarf_p_cloudsc2_tl_ad_amd.state import op_outputs
+
+    return {n: a[ibl] for n, a in op_outputs(st).items()}

@@ -551,9 +551,7 @@ def class_err(ref: np.ndarray, got: np.ndarray, mask: np.ndarray) -> float:
 # the host build of the sweeps on a case (tests/hostcheck): results as (NLEVx, NGPTOT) matrices, like the reference's
 # ---------------------------------------------------------------------------------------------------------------------
 def state_outputs(st) -> dict:
-    out = {"tent": st.B_LOC[:, 0], "tenq": st.B_LOC[:, 2], "tenl": st.B_LOC[:, 3], "teni": st.B_LOC[:, 4], "clc": st.PA,
-           "fplsl": st.PFPLSL, "fplsn": st.PFPLSN, "fhpsl": st.PFHPSL, "fhpsn": st.PFHPSN, "covptot": st.PCOVPTOT}
-    return {n: active_cols(np.ascontiguousarray(a), st.ngptot) for n, a in out.items()}
+    return {n: active_cols(np.ascontiguousarray(a), st.ngptot) for n, a in c2.op_outputs(st).items()}
 
 
 def blocks_of(d: dict, fill: float = 0.0) -> dict:

@@ -93,10 +93,7 @@ def run_case(chk: Checks, tag, tab, nproma, ngptot, flags, mode, satur):
     nlev = lay.nlev
     ptsphy = float(st.ptsphy)
     G = ov.geom(prm, ptsphy, lay)
-    src = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "t": st.PT, "l": st.PCLV[:, 0], "i": st.PCLV[:, 1], "lude": st.PLUDE, "lu": st.PLU,
-           "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, 0], "gtenq": st.B_CML[:, 2], "gtenl": st.B_CML[:, 3], "gteni": st.B_CML[:, 4],
-           "supsat": st.PSUPSAT}
-    flat = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in src.items()}
+    flat = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in c2.op_inputs(st).items()}
     flat["qsat"] = ag.satur(flat["pap"], flat["t"], prm, ngptot)
     ins = in_names(satur)
     x = ov.packed("in", ins, lay, values=flat)

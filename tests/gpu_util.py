@@ -23,10 +23,7 @@ KEYS15 = list(ag.SAT_NAMES)  # the inputs without qsat: SATUR in the sweep
 # ---- the differentiable op on the device (tests/test_gpu_autograd*.py) ----
 def make_inputs(tab, nproma, ngptot, prm):
     st = c2.state_from_table(tab, nproma, ngptot)
-    src = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "t": st.PT, "l": st.PCLV[:, 0], "i": st.PCLV[:, 1], "lude": st.PLUDE,
-           "lu": st.PLU, "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, 0], "gtenq": st.B_CML[:, 2], "gtenl": st.B_CML[:, 3],
-           "gteni": st.B_CML[:, 4], "supsat": st.PSUPSAT}
-    x = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in src.items()}
+    x = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in c2.op_inputs(st).items()}
     x["qsat"] = ag.satur(x["pap"], x["t"], prm, ngptot)
     return {n: x[n] for n in B.IN_NAMES}, float(st.ptsphy), ag.Layout(st.nblocks, st.nlev, nproma, ngptot)
 

@@ -251,10 +251,7 @@ def run_case(rec: Record, tag: str, tab, nproma, ngptot, flags, mode, nl_only):
     st = c2.state_from_table(tab, nproma, ngptot)
     lay = ag.Layout(st.nblocks, st.nlev, nproma, ngptot)
     ptsphy = float(st.ptsphy)
-    src = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "t": st.PT, "l": st.PCLV[:, 0], "i": st.PCLV[:, 1], "lude": st.PLUDE, "lu": st.PLU,
-           "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, 0], "gtenq": st.B_CML[:, 2], "gtenl": st.B_CML[:, 3], "gteni": st.B_CML[:, 4],
-           "supsat": st.PSUPSAT}
-    flat = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in src.items()}
+    flat = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in c2.op_inputs(st).items()}
     flat["qsat"] = ag.satur(flat["pap"], flat["t"], prm, ngptot)  # (cloudsc2_satur_launch: not a sweep, not logged)
     x = packed("in", B.IN_NAMES, lay, values=flat)
     x15 = {n: x[n] for n in IN15}

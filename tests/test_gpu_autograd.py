@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests.gpu_util import DEV, ad_assign_launch, make_inputs, new, nl_launch, params, same_bits, seeded, stream, tail_zero, tl_launch
+from tests.test_op_inputs import inputs_by_hand
 from tests.util import B, c2
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
 
@@ -28,6 +29,23 @@ def test_forward_is_the_nl_sweep(nproma, ngptot):
     for n in B.OUT_NAMES:
         assert same_bits(getattr(out, n), want[n]), n
         assert tail_zero(getattr(out, n), lay), n
+
+
+def test_a_device_states_op_inputs_are_views_the_op_takes_as_they_are():
+    tab = c2.synthetic_table()
+    prm = params(tab)
+    ds = c2.DeviceState.from_table(tab, 32, 100)  # 4 blocks, the last with 4 active columns
+    x = ds.op_inputs()
+    want = dict(inputs_by_hand(ds), qsat=ds.QSAT)
+    assert list(x) == list(B.IN_NAMES)
+    for n in B.IN_NAMES:
+        assert x[n].data_ptr() == want[n].data_ptr() and x[n].stride() == want[n].stride() and x[n].shape == want[n].shape, n
+    lay = ag.check_layout(x, prm, 100)
+    taken = ag.normalize(x, lay, ag.IN_GROUPS)
+    assert all(taken[n].data_ptr() == x[n].data_ptr() for n in B.IN_NAMES), "inputs would be copied"
+    x15 = ds.op_inputs(qsat=False)
+    assert list(x15) == list(ag.SAT_NAMES) and all(x15[n].data_ptr() == x[n].data_ptr() for n in x15)
+    assert ds.op_outputs()["tenq"].data_ptr() == ds.B_LOC[:, 2].data_ptr()
 
 
 @pytest.mark.parametrize("math_mode", [1, 2])

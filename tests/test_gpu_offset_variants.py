@@ -217,10 +217,7 @@ def small():
     prm.math_mode = 1  # (the word below: no PRECISE whatever the process default)
     st = c2.state_from_table(tab, 32, 100)
     lay = ag.Layout(st.nblocks, st.nlev, 32, 100)
-    x = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-         for n, a in (("paph", st.PAPH), ("pap", st.PAP), ("q", st.PQ), ("t", st.PT), ("l", st.PCLV[:, 0]), ("i", st.PCLV[:, 1]), ("lude", st.PLUDE),
-                      ("lu", st.PLU), ("mfu", st.PMFU), ("mfd", st.PMFD), ("gtent", st.B_CML[:, 0]), ("gtenq", st.B_CML[:, 2]),
-                      ("gtenl", st.B_CML[:, 3]), ("gteni", st.B_CML[:, 4]), ("supsat", st.PSUPSAT))}
+    x = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in c2.op_inputs(st).items()}
     return x, prm, float(st.ptsphy), lay
 
 
@@ -310,10 +307,7 @@ def setup(levapls2: bool):
         st = c2.state_from_table(tab, NPROMA, NGPTOT)
         lay = ag.Layout(st.nblocks, st.nlev, NPROMA, NGPTOT)
         ptsphy = float(st.ptsphy)
-        src = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "t": st.PT, "l": st.PCLV[:, 0], "i": st.PCLV[:, 1], "lude": st.PLUDE, "lu": st.PLU,
-               "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, 0], "gtenq": st.B_CML[:, 2], "gtenl": st.B_CML[:, 3],
-               "gteni": st.B_CML[:, 4], "supsat": st.PSUPSAT}
-        x = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in src.items()}
+        x = {n: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for n, a in c2.op_inputs(st).items()}
         x["qsat"] = ag.satur(x["pap"], x["t"], prm, NGPTOT)
         x = {n: x[n] for n in B.IN_NAMES}
         x15 = {n: x[n] for n in ov.IN15}

@@ -326,11 +326,7 @@ def test_lambda_sweep_of_the_taylor_test(oracle, nproma, ngptot, precise, off32,
                 out[n] = np.ascontiguousarray(a.transpose(1, 0, 2)).reshape(st.nlev, ncols_pad)
             return out
 
-        def out_arrays(s):
-            return {"tent": s.B_LOC[:, 0], "tenq": s.B_LOC[:, 2], "tenl": s.B_LOC[:, 3], "teni": s.B_LOC[:, 4], "clc": s.PA,
-                    "covptot": s.PCOVPTOT, "fplsl": s.PFPLSL, "fplsn": s.PFPLSN, "fhpsl": s.PFHPSL, "fhpsn": s.PFHPSN}
-
-        b = columns(out_arrays(base))
+        b = columns(c2.op_outputs(base))
         act = np.arange(ncols_pad) < ngptot  # (blocks are contiguous: global column = ibl*nproma + jl)
         assert np.all(np.isnan(colsum[:, ~act])) and np.all(np.isfinite(colsum[:, act]))
         tlc = columns(tl)
@@ -344,7 +340,7 @@ def test_lambda_sweep_of_the_taylor_test(oracle, nproma, ngptot, precise, off32,
             pert = st.copy()
             ip, op = host_traj_blocks(pert, qsat)
             hc.hostcheck_nl(C.byref(prm), st.ptsphy, nproma, st.nlev, ngptot, C.byref(ip), C.byref(op), B.Field(), lam)
-            pc = columns(out_arrays(pert))
+            pc = columns(c2.op_outputs(pert))
             for f, n in enumerate(names):
                 acc = np.zeros(ncols_pad)
                 for jk in range(st.nlev):

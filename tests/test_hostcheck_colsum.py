@@ -59,9 +59,7 @@ def test_column_sums_are_the_fold_over_the_planes(precise, flags, satur):
     scratch = np.zeros((nb, nlev, nproma), dtype=B.REAL)
     assert lib.hostcheck_sparse_forward(*geom, C.byref(i), C.byref(o), scratch.ctypes.data) == 0
     S = nproma * nlev
-    planes = {"tent": traj.B_LOC[:, 0], "tenq": traj.B_LOC[:, 2], "tenl": traj.B_LOC[:, 3], "teni": traj.B_LOC[:, 4], "clc": traj.PA,
-              "covptot": traj.PCOVPTOT, "fplsl": traj.PFPLSL, "fplsn": traj.PFPLSN, "fhpsl": traj.PFHPSL, "fhpsn": traj.PFHPSN}
-    planes = {n: np.ascontiguousarray(a, dtype=B.REAL) for n, a in planes.items()}
+    planes = {n: np.ascontiguousarray(a, dtype=B.REAL) for n, a in c2.op_outputs(traj).items()}
     assert planes["tent"].shape == (nb, nlev, nproma) and planes["fplsl"].shape == (nb, nlev + 1, nproma) and S
 
     inc = increments_of(st, host_qsat(st))  # v = 0.01 x

@@ -32,10 +32,7 @@ K = len(ROWS)
 
 
 def flat_inputs(st, qsat) -> dict:
-    src = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "qsat": qsat, "t": st.PT, "l": st.PCLV[:, 0], "i": st.PCLV[:, 1], "lude": st.PLUDE,
-           "lu": st.PLU, "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, 0], "gtenq": st.B_CML[:, 2], "gtenl": st.B_CML[:, 3],
-           "gteni": st.B_CML[:, 4], "supsat": st.PSUPSAT}
-    return {n: np.ascontiguousarray(a, dtype=B.REAL) for n, a in src.items() if a is not None}
+    return {n: np.ascontiguousarray(a, dtype=B.REAL) for n, a in c2.op_inputs(st, qsat).items()}
 
 
 def with_row(prm, row):

@@ -64,10 +64,7 @@ def flat_block(kind: str, arrays: dict):
 
 def increments_of(st: c2.Cloudsc2State, qsat: np.ndarray, zero_supsat: bool = False) -> dict:
     """dx = 0.01*x for the 16 inputs, flat (NBLOCKS, NLEVx, NPROMA) (cloudsc_driver_tl_mod.F90:156-171)."""
-    src = {"paph": st.PAPH, "pap": st.PAP, "q": st.PQ, "qsat": qsat, "t": st.PT, "l": st.PCLV[:, 0], "i": st.PCLV[:, 1],
-           "lude": st.PLUDE, "lu": st.PLU, "mfu": st.PMFU, "mfd": st.PMFD, "gtent": st.B_CML[:, 0], "gtenq": st.B_CML[:, 2],
-           "gtenl": st.B_CML[:, 3], "gteni": st.B_CML[:, 4], "supsat": st.PSUPSAT}
-    out = {n: np.ascontiguousarray(a * B.REAL(0.01)) for n, a in src.items()}
+    out = {n: np.ascontiguousarray(a * B.REAL(0.01)) for n, a in c2.op_inputs(st, qsat).items()}
     if zero_supsat:
         out["supsat"][...] = 0.0
     return out

@@ -16,7 +16,7 @@ import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing_harness as th
 
 NLEV = 137
 R, H = NLEV, NLEV + 1
@@ -41,25 +41,16 @@ def byte_ratio(sweep, k, kmax):
 def run(first, ngptot, reps):
     import torch
 
-    import dwarf_p_cloudsc2_tl_ad_amd as c2
     from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
     from dwarf_p_cloudsc2_tl_ad_amd import binding as B
-    from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T
 
-    assert not B.SINGLE, "fp64 measurement"
     nproma, nlev = 128, NLEV
     kmax = B.lib.cloudsc2_batch_max()
-    tab = c2.synthetic_table(nlev)
-    prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True)
-    ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-    ds.satur(prm)
-    x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-         "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-         "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-    lay = ag.check_layout(x, prm, ngptot)
-    ptsphy, dev = float(ds.ptsphy), ds.device
-    st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-    new = lambda names: {n: torch.empty(lay.shape(n), dtype=torch.float64, device=dev) for n in names}  # noqa: E731
+    case = th.setup(ngptot, nproma, nlev, prepare=False)
+    prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
+    st = lambda: th.stream(dev)  # noqa: E731
+    new = lambda names: th.new(names, lay, dev)  # noqa: E731
+    timed = lambda step: th.median_ms(step, reps)  # noqa: E731
     gen = torch.Generator(device=dev).manual_seed(0)
     K2 = 2 * kmax
     vs = [{n: t * (0.01 * (j + 1)) for n, t in x.items()} for j in range(K2)]
@@ -74,20 +65,6 @@ def run(first, ngptot, reps):
     dyb, xab = [ag._block("out", d, lay) for d in dys], [ag._block("in", a, lay) for a in xas]
     none = B.Outputs()
     head = (C.byref(prm), ptsphy, nproma, nlev, ngptot, C.byref(xb))
-
-    def timed(step):
-        for _ in range(5):
-            step()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            step()
-            b.record()
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        return statistics.median(ms)
 
     def legs(k):
         vin, dout = (B.Inputs * k)(*vb[:k]), (B.Outputs * k)(*dyb[:k])
@@ -138,10 +115,10 @@ def summarise(files):
         for name in runs[0][group]:
             rows = [r[group][name] for r in runs]
             loops = [r["loop_ms"] for r in rows]
-            spread = (max(loops) - min(loops)) / statistics.median(loops)
+            spread = th.spread(rows, ("loop_ms",))
             ratios = [r["ratio"] for r in rows]
             e = {"loop_ms": loops, "batch_ms": [r["batch_ms"] for r in rows], "first": [r["first"] for r in runs], "ratio": ratios,
-                 "ratio_median": round(statistics.median(ratios), 4), "yardstick_spread": round(spread, 4),
+                 "ratio_median": round(statistics.median(ratios), 4), "yardstick_spread": spread,
                  "beats_the_yardstick_by_more_than_its_spread_in_every_pair": all(1.0 - q > spread for q in ratios)}
             if group == "kernels":
                 sweep, k = name.split("_K")

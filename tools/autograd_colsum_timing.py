@@ -16,28 +16,20 @@ NPROMA 128, fp64: medians of REPS event-timed calls after warm-up, and peak memo
 import ctypes as C
 import json
 import os
-import statistics
-import subprocess
 import sys
 
+import timing_harness as th
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 
 def alternate(tree, rest):
-    me, yard = [sys.executable, os.path.abspath(__file__), "run", *rest], [sys.executable, os.path.join(tree, "tools", "autograd_timing.py"), *rest[:2]]
-    runs = []
-    for order in ((yard, me), (me, yard)):
-        for _ in range(3):
-            for cmd in order:
-                r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=tree if cmd is yard else ROOT)
-                if r.returncode != 0:
-                    print(r.stdout[-2000:], r.stderr[-2000:])
-                    return r.returncode  # (nothing more is started after a process that did not end well)
-                runs.append({"which": "yardstick" if cmd is yard else "colsum", "result": json.loads(r.stdout.strip().splitlines()[-1])})
+    runs = th.children({"yardstick": ([sys.executable, os.path.join(tree, "tools", "autograd_timing.py"), *rest[:2]], tree),
+                        "colsum": ([sys.executable, os.path.abspath(__file__), "run", *rest], ROOT)})
+    if isinstance(runs, int):
+        return runs
     y = [r["result"] for r in runs if r["which"] == "yardstick"]
-    spread = {k: round((max(p[k]["ms"] for p in y) - min(p[k]["ms"] for p in y)) / statistics.median(p[k]["ms"] for p in y), 4)
-              for k in ("forward", "backward", "vjp_kernel", "tl_kernel_no_traj")}
+    spread = {k: th.spread(y, (k, "ms")) for k in ("forward", "backward", "vjp_kernel", "tl_kernel_no_traj")}
     print("yardstick spread over its processes:", json.dumps(spread))
     with open(os.path.join(ROOT, "profiles", "autograd_colsum_timing.json"), "w") as f:
         json.dump({"yardstick_spread": spread, "processes": runs}, f)
@@ -47,49 +39,24 @@ def alternate(tree, rest):
 def run(rest):
     import torch
 
-    import dwarf_p_cloudsc2_tl_ad_amd as c2
     from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
     from dwarf_p_cloudsc2_tl_ad_amd import binding as B
-    from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T
 
     ngptot = int(rest[0]) if len(rest) > 0 else 160000
     reps = int(rest[1]) if len(rest) > 1 else 30
     evap = len(rest) > 2 and rest[2] == "evap"
     nproma, nlev = 128, 137
-    assert not B.SINGLE, "fp64 measurement"
-    tab = c2.synthetic_table(nlev)
-    prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True, levapls2=evap)
-    ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-    ds.satur(prm)
-    dev = ds.device
-    ptsphy = float(ds.ptsphy)
-    st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-    x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-         "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-         "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-    lay = ag.check_layout(x, prm, ngptot)
-    ag._prepare(dev)
+    case = th.setup(ngptot, nproma, nlev, levapls2=evap)
+    prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
+    st = lambda: th.stream(dev)  # noqa: E731
     HALF = ("paph", "fplsl", "fplsn", "fhpsl", "fhpsn")
     R, H = 8 * nlev, 8 * (nlev + 1)
     plane_bytes = lambda names: sum(H if n in HALF else R for n in names)  # noqa: E731
     traj_b = plane_bytes(B.IN_NAMES)
     kept_b = 2 * R + (R if evap else 0)  # what the keep form stores and the reverse sweep re-reads (the fluxes' top level apart)
 
-    def timed(step):
-        for _ in range(5):
-            step()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            step()
-            b.record()
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        return round(statistics.median(ms), 4)
-
-    new = lambda names: {n: torch.empty(lay.shape(n), dtype=torch.float64, device=dev) for n in names}  # noqa: E731
+    timed = lambda step: th.median_ms(step, reps, ndigits=4)  # noqa: E731
+    new = lambda names: th.new(names, lay, dev)  # noqa: E731
     sums = lambda names: {n: torch.zeros((lay.nblocks, nproma), dtype=torch.float64, device=dev) for n in names}  # noqa: E731
     g = torch.Generator(device=dev).manual_seed(0)
     w = {n: 2 * torch.rand(lay.nlevx(n), generator=g, dtype=torch.float64, device=dev) - 1 for n in B.OUT_NAMES}

@@ -8,19 +8,14 @@ its cost, so the times are wall clock between two device synchronisations.
     python tools/autograd_ens_timing.py run [NGPTOT [K [REPS [evap]]]]     ONE JSON object with the median times
 It writes nothing but that line."""
 import json
-import os
 import statistics
 import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing_harness as th
+import torch
 
-import torch  # noqa: E402
-
-import dwarf_p_cloudsc2_tl_ad_amd as c2  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import binding as B  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T  # noqa: E402
+import dwarf_p_cloudsc2_tl_ad_amd as c2
+from dwarf_p_cloudsc2_tl_ad_amd import binding as B
 
 args = sys.argv[2:] if len(sys.argv) > 1 and sys.argv[1] == "run" else sys.argv[1:]
 ngptot = int(args[0]) if len(args) > 0 else 160000
@@ -30,16 +25,8 @@ evap = len(args) > 3 and args[3] == "evap"
 nproma, nlev = 128, 137
 LOSS = ("tent", "fplsl", "covptot")
 
-tab = c2.synthetic_table(nlev)
-prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True, levapls2=evap)
-ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-ds.satur(prm)
-x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-     "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-     "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-lay = ag.check_layout(x, prm, ngptot)
-ptsphy = float(ds.ptsphy)
-dev = ds.device
+case = th.setup(ngptot, nproma, nlev, prepare=False, fp64=False, levapls2=evap)
+prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
 dtype = B.torch_real()
 
 factors = torch.linspace(0.8, 1.2, K, dtype=torch.float64, device=dev)
@@ -85,22 +72,7 @@ torch.cuda.synchronize()
 same = all(bool(ge[i][k] == gl[k][i]) for k in range(K) for i in range(len(c2.PARAM_NAMES)))
 del ge, gl
 
-
-def timed(step):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = step()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    del r
-    return (t1 - t0) * 1e3
-
-
-ms = {k: [] for k in forms}
-names = list(forms)
-for r in range(reps):
-    for k in names[r % 4:] + names[:r % 4]:
-        ms[k].append(timed(forms[k]))
+ms = th.rotated(forms, reps, th.wall_ms, 4)
 
 res = {"ngptot": ngptot, "members": K, "nproma": nproma, "nlev": nlev, "precision": "fp32" if B.SINGLE else "fp64", "reps": reps,
        "evap": evap, "device": torch.cuda.get_device_name(dev), "clock": "wall, between device synchronisations",

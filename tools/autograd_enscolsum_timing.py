@@ -18,32 +18,21 @@ import os
 import statistics
 import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import timing_harness as th
+
 STEPS = ("forward", "forward_backward_params", "forward_backward_t_q_params")
 
 
 def run(route, ngptot, K, reps, evap):
-    sys.path.insert(0, ROOT)
     import torch
 
     import dwarf_p_cloudsc2_tl_ad_amd as c2
-    from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
     from dwarf_p_cloudsc2_tl_ad_amd import binding as B
-    from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T
 
     nproma, nlev = 128, 137
-    tab = c2.synthetic_table(nlev)
-    prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True, levapls2=evap)
-    ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-    ds.satur(prm)
-    x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-         "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-         "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-    lay = ag.check_layout(x, prm, ngptot)
-    ptsphy = float(ds.ptsphy)
-    dev = ds.device
+    case = th.setup(ngptot, nproma, nlev, prepare=False, fp64=False, levapls2=evap)
+    prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
     dtype = B.torch_real()
     plane = lay.nblocks * lay.nlev * lay.nproma * torch.empty((), dtype=dtype).element_size()
 
@@ -82,15 +71,6 @@ def run(route, ngptot, K, reps, evap):
             step()
     torch.cuda.synchronize()
 
-    def timed(step):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        r = step()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        del r
-        return (t1 - t0) * 1e3
-
     def peak(step):
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats(dev)
@@ -101,11 +81,7 @@ def run(route, ngptot, K, reps, evap):
         del r
         return rise / plane
 
-    ms = {k: [] for k in forms}
-    names = list(forms)
-    for r in range(reps):
-        for k in names[r % 3:] + names[:r % 3]:
-            ms[k].append(timed(forms[k]))
+    ms = th.rotated(forms, reps, th.wall_ms, 3)
     y = forward()
     gp = backward_params()
     torch.cuda.synchronize()

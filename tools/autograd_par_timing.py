@@ -13,14 +13,12 @@ import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing_harness as th
+import torch
 
-import torch  # noqa: E402
-
-import dwarf_p_cloudsc2_tl_ad_amd as c2  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import binding as B  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T  # noqa: E402
+import dwarf_p_cloudsc2_tl_ad_amd as c2
+from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
+from dwarf_p_cloudsc2_tl_ad_amd import binding as B
 
 args = sys.argv[2:] if len(sys.argv) > 1 and sys.argv[1] == "run" else sys.argv[1:]
 parent = C.CDLL(os.path.abspath(args[0]))
@@ -32,22 +30,14 @@ for name in ("cloudsc2_vjp_launch", "cloudsc2_tl_launch"):
     getattr(parent, name).argtypes = getattr(B.lib, name).argtypes
     getattr(parent, name).restype = C.c_int
 
-tab = c2.synthetic_table(nlev)
-prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True, levapls2=evap)
-ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-ds.satur(prm)
-x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-     "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-     "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-lay = ag.check_layout(x, prm, ngptot)
-ptsphy = float(ds.ptsphy)
-dev = ds.device
+case = th.setup(ngptot, nproma, nlev, prepare=False, fp64=False, levapls2=evap)
+prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
 dtype = B.torch_real()
 g = torch.Generator(device=dev).manual_seed(0)
 u = {n: torch.randn(lay.shape(n), generator=g, dtype=dtype, device=dev) for n in B.OUT_NAMES}
 v = {n: 0.01 * t for n, t in x.items()}
-st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-new = lambda names: {n: torch.empty(lay.shape(n), dtype=dtype, device=dev) for n in names}  # noqa: E731
+st = lambda: th.stream(dev)  # noqa: E731
+new = lambda names: th.new(names, lay, dev)  # noqa: E731
 
 traj, xa, dy = new(B.OUT_NAMES), new(B.IN_NAMES), new(B.OUT_NAMES)
 scratch = torch.zeros((lay.nblocks, nlev, nproma), dtype=dtype, device=dev)
@@ -78,15 +68,7 @@ for _ in range(5):
     for step in steps.values():
         step()
 torch.cuda.synchronize()
-ms = {k: [] for k in steps}
-for _ in range(reps):
-    for k, step in steps.items():
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step()
-        b.record()
-        b.synchronize()
-        ms[k].append(a.elapsed_time(b))
+ms = th.rotated(steps, reps, th.event_ms, 1)  # (the same order in every repetition)
 
 res = {"ngptot": ngptot, "nproma": nproma, "nlev": nlev, "precision": "fp32" if B.SINGLE else "fp64", "reps": reps, "evap": evap,
        "device": torch.cuda.get_device_name(dev), "par_adj": par_adj.cpu().tolist()}

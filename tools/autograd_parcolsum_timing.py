@@ -17,27 +17,20 @@ import ctypes as C
 import json
 import os
 import statistics
-import subprocess
 import sys
 
+import timing_harness as th
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 
 def alternate(rest):
-    cmd = lambda which: [sys.executable, os.path.abspath(__file__), "run", which, *rest]  # noqa: E731
-    runs = []
-    for order in (("route", "new"), ("new", "route")):
-        for _ in range(3):
-            for which in order:
-                r = subprocess.run(cmd(which), capture_output=True, text=True, timeout=600, cwd=ROOT)
-                if r.returncode != 0:
-                    print(r.stdout[-2000:], r.stderr[-2000:])
-                    return r.returncode  # (nothing more is started after a process that did not end well)
-                runs.append({"which": which, "result": json.loads(r.stdout.strip().splitlines()[-1])})
+    runs = th.children({which: ([sys.executable, os.path.abspath(__file__), "run", which, *rest], ROOT) for which in ("route", "new")})
+    if isinstance(runs, int):
+        return runs
     med = lambda which, k: statistics.median(p["result"]["rows"][k]["ms"] for p in runs if p["which"] == which)  # noqa: E731
     y = [p["result"]["rows"] for p in runs if p["which"] == "route"]
-    spread = {k: round((max(p[k]["ms"] for p in y) - min(p[k]["ms"] for p in y)) / statistics.median(p[k]["ms"] for p in y), 4) for k in y[0]}
+    spread = {k: th.spread(y, (k, "ms")) for k in y[0]}
     print("route spread over its processes:", json.dumps(spread))
     summary = {"route_normal_equations_ms": med("route", "normal_equations_route"), "route_sums_ms": med("route", "sums_route"),
                "route_parjac_kernel_ms": med("route", "parjac_kernel"), "new_normal_equations_ms": med("new", "normal_equations"),
@@ -55,38 +48,14 @@ def run(which, rest):
     import dwarf_p_cloudsc2_tl_ad_amd as c2
     from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
     from dwarf_p_cloudsc2_tl_ad_amd import binding as B
-    from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T
 
     ngptot = int(rest[0]) if len(rest) > 0 else 160000
     reps = int(rest[1]) if len(rest) > 1 else 30
     nproma, nlev = 128, 137
-    assert not B.SINGLE, "fp64 measurement"
-    tab = c2.synthetic_table(nlev)
-    prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True, levapls2=True)
-    ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-    ds.satur(prm)
-    dev = ds.device
-    ptsphy = float(ds.ptsphy)
-    st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-    x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-         "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-         "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-    lay = ag.check_layout(x, prm, ngptot)
-    ag._prepare(dev)
-
-    def timed(step):
-        for _ in range(5):
-            step()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            step()
-            b.record()
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        return round(statistics.median(ms), 4)
+    case = th.setup(ngptot, nproma, nlev, levapls2=True)
+    prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
+    st = lambda: th.stream(dev)  # noqa: E731
+    timed = lambda step: th.median_ms(step, reps, ndigits=4)  # noqa: E731
 
     surface = torch.zeros(nlev + 1, dtype=torch.float64, device=dev)
     surface[-1] = 1

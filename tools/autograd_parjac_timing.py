@@ -8,18 +8,15 @@ Bytes per column (NLEV 137, fp64): 17 544 + NP x 10 992 against NP x 46 080, i.e
 fresh processes and take the median of the medians (profiles/autograd_parjac_timing.json)."""
 import ctypes as C
 import json
-import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing_harness as th
+import torch
 
-import torch  # noqa: E402
-
-import dwarf_p_cloudsc2_tl_ad_amd as c2  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import binding as B  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T  # noqa: E402
+import dwarf_p_cloudsc2_tl_ad_amd as c2
+from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
+from dwarf_p_cloudsc2_tl_ad_amd import binding as B
 
 args = sys.argv[2:] if len(sys.argv) > 1 and sys.argv[1] == "run" else sys.argv[1:]
 ngptot = int(args[0]) if len(args) > 0 else 160000
@@ -29,19 +26,11 @@ nproma, nlev = 128, 137
 NPAR = len(c2.PARAM_NAMES)
 np_run = NPAR if evap else NPAR - 1
 
-tab = c2.synthetic_table(nlev)
-prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True, levapls2=evap)
-ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-ds.satur(prm)
-x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-     "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-     "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-lay = ag.check_layout(x, prm, ngptot)
-ptsphy = float(ds.ptsphy)
-dev = ds.device
+case = th.setup(ngptot, nproma, nlev, prepare=False, fp64=False, levapls2=evap)
+prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
 dtype = B.torch_real()
-st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-new = lambda names: {n: torch.empty(lay.shape(n), dtype=dtype, device=dev) for n in names}  # noqa: E731
+st = lambda: th.stream(dev)  # noqa: E731
+new = lambda names: th.new(names, lay, dev)  # noqa: E731
 
 # one zero plane per tangent field, as a caller without the new launcher has them (the single launcher reads all 16)
 zero = {n: torch.zeros(lay.shape(n), dtype=dtype, device=dev) for n in B.IN_NAMES}
@@ -85,22 +74,12 @@ torch.cuda.synchronize()
 same = all(torch.equal(sens[k][n].view(torch.int64), loop_out[k][n].view(torch.int64)) for k in range(np_run) for n in B.OUT_NAMES) \
     if not B.SINGLE else None
 
-
-def timed(step):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    step()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
 ms = {f"{k}_{form}": [] for k in pairs for form in ("loop", "parjac")}
 for r in range(reps):
     for k, (loop, fused) in pairs.items():
         order = (("loop", loop), ("parjac", fused)) if r % 2 == 0 else (("parjac", fused), ("loop", loop))
         for form, step in order:
-            ms[f"{k}_{form}"].append(timed(step))
+            ms[f"{k}_{form}"].append(th.event_ms(step))
 
 res = {"ngptot": ngptot, "nproma": nproma, "nlev": nlev, "precision": "fp32" if B.SINGLE else "fp64", "reps": reps, "evap": evap,
        "directions": np_run, "device": torch.cuda.get_device_name(dev), "same_bits_as_the_loop": same,

@@ -9,18 +9,15 @@ Bytes per column (NLEV 137, fp64): 17 544 + 2 x 10 992 + 14 x 8 = 39 640 against
 alone, and at least 127 464 with a contraction that read every plane exactly once.  It writes nothing but that line."""
 import ctypes as C
 import json
-import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing_harness as th
+import torch
 
-import torch  # noqa: E402
-
-import dwarf_p_cloudsc2_tl_ad_amd as c2  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import binding as B  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T  # noqa: E402
+import dwarf_p_cloudsc2_tl_ad_amd as c2
+from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
+from dwarf_p_cloudsc2_tl_ad_amd import binding as B
 
 args = sys.argv[2:] if len(sys.argv) > 1 and sys.argv[1] == "run" else sys.argv[1:]
 ngptot = int(args[0]) if len(args) > 0 else 160000
@@ -30,19 +27,11 @@ nproma, nlev = 128, 137
 NPAR = len(c2.PARAM_NAMES)
 np_run = NPAR if evap else NPAR - 1
 
-tab = c2.synthetic_table(nlev)
-prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True, levapls2=evap)
-ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-ds.satur(prm)
-x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-     "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-     "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-lay = ag.check_layout(x, prm, ngptot)
-ptsphy = float(ds.ptsphy)
-dev = ds.device
+case = th.setup(ngptot, nproma, nlev, prepare=False, fp64=False, levapls2=evap)
+prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
 dtype = B.torch_real()
-st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-new = lambda names: {n: torch.empty(lay.shape(n), dtype=dtype, device=dev) for n in names}  # noqa: E731
+st = lambda: th.stream(dev)  # noqa: E731
+new = lambda names: th.new(names, lay, dev)  # noqa: E731
 
 gen = torch.Generator(device=dev).manual_seed(1)
 resid = {n: torch.randn(lay.shape(n), generator=gen, dtype=dtype, device=dev) for n in B.OUT_NAMES}
@@ -88,21 +77,7 @@ jtj, jtr = torch_contraction()
 got = normal.cpu().tolist()
 agree = max(abs(got[B.NNORMAL - NPAR + a] - float(jtr[a])) / max(abs(float(jtr[a])), 1e-300) for a in range(np_run))
 
-
-def timed(step):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    step()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b)
-
-
-ms = {k: [] for k in forms}
-names = list(forms)
-for r in range(reps):
-    for k in names[r % 3:] + names[:r % 3]:
-        ms[k].append(timed(forms[k]))
+ms = th.rotated(forms, reps, th.event_ms, 3)
 
 res = {"ngptot": ngptot, "nproma": nproma, "nlev": nlev, "precision": "fp32" if B.SINGLE else "fp64", "reps": reps, "evap": evap,
        "directions": np_run, "device": torch.cuda.get_device_name(dev), "jtr_relative_difference_from_torch": agree}

@@ -10,23 +10,22 @@ the fused op through torch next to the unfused route (satur(differentiable=True)
         alternation; writes the medians, the spreads and the ratios"""
 import ctypes as C
 import json
-import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import timing_harness as th
 
 
 def summarise(out_path, parent_path, new_path):
     parent = [json.loads(line) for line in open(parent_path) if line.startswith("{")]
     new = [json.loads(line) for line in open(new_path) if line.startswith("{")]
     med = lambda rows, k: statistics.median(r[k]["ms"] for r in rows)  # noqa: E731
-    spread = lambda rows, k: (max(r[k]["ms"] for r in rows) - min(r[k]["ms"] for r in rows)) / med(rows, k)  # noqa: E731
+    spread = lambda rows, k: th.spread(rows, (k, "ms"))  # noqa: E731
     res = {"pairs": min(len(parent), len(new)), "ngptot": new[0]["ngptot"], "nproma": new[0]["nproma"], "precision": new[0]["precision"],
            "device": new[0]["device"], "runs_parent": parent, "runs_new": new}
     for name, pk, nk in (("tl", "tl_kernel_no_traj", "tl_kernel_satur"), ("vjp", "vjp_kernel", "vjp_kernel_satur")):
-        res[name] = {"parent_ms": round(med(parent, pk), 4), "parent_spread": round(spread(parent, pk), 4),
-                     "fused_ms": round(med(new, nk), 4), "fused_spread": round(spread(new, nk), 4),
+        res[name] = {"parent_ms": round(med(parent, pk), 4), "parent_spread": spread(parent, pk),
+                     "fused_ms": round(med(new, nk), 4), "fused_spread": spread(new, nk),
                      "ratio": round(med(new, nk) / med(parent, pk), 4),
                      "byte_ratio": round(new[0][nk]["bytes_per_column"] / parent[0][pk]["bytes_per_column"], 4),
                      "same_commit_unfused_ms": round(med(new, pk), 4)}
@@ -44,54 +43,27 @@ if len(sys.argv) > 1 and sys.argv[1] == "summarise":
 
 import torch  # noqa: E402
 
-import dwarf_p_cloudsc2_tl_ad_amd as c2  # noqa: E402
 from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag  # noqa: E402
 from dwarf_p_cloudsc2_tl_ad_amd import binding as B  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T  # noqa: E402
 
-PEAK = 8e12  # B/s, HBM3E of one MI355X
 args = sys.argv[2:] if len(sys.argv) > 1 and sys.argv[1] == "run" else sys.argv[1:]
 ngptot = int(args[0]) if len(args) > 0 else 160000
 reps = int(args[1]) if len(args) > 1 else 30
 nproma, nlev = 128, 137
 RB = B.REAL_BYTES
 
-tab = c2.synthetic_table(nlev)
-prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True)
-ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-ds.satur(prm)
-x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-     "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-     "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
+case = th.setup(ngptot, nproma, nlev, prepare=False, fp64=False)
+prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
 x15 = {n: x[n] for n in ag.SAT_NAMES}
-lay = ag.check_layout(x15, prm, ngptot, satur=True)
-ptsphy = float(ds.ptsphy)
-dev = ds.device
 dtype = B.torch_real()
 assert all(t.data_ptr() == ag.normalize(x15, lay, ag.SAT_GROUPS)[n].data_ptr() for n, t in x15.items()), "inputs would be copied"
 g = torch.Generator(device=dev).manual_seed(0)
 u = {n: torch.randn(lay.shape(n), generator=g, dtype=dtype, device=dev) for n in B.OUT_NAMES}
 v = {n: 0.01 * t for n, t in x.items()}
 v15 = {n: v[n] for n in ag.SAT_NAMES}
-st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-new = lambda names: {n: torch.empty(lay.shape(n), dtype=dtype, device=dev) for n in names}  # noqa: E731
-
-
-def timed(step):
-    """median ms of `step` between two events"""
-    for _ in range(5):
-        step()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
-
+st = lambda: th.stream(dev)  # noqa: E731
+new = lambda names: th.new(names, lay, dev)  # noqa: E731
+timed = lambda step: th.median_ms(step, reps)  # noqa: E731
 
 # the kernels alone, on preallocated buffers
 traj = new(B.OUT_NAMES)
@@ -154,10 +126,7 @@ tl_s_b = tl_b - RB * 2 * R        # no qsat trajectory plane, no qsat tangent pl
 vjp_s_b = vjp_b - RB * 2 * R      # no qsat trajectory plane, no qsat adjoint plane
 sat_b, sat_lin_b = RB * 3 * R, RB * 5 * R
 
-
-def row(ms, b):
-    return {"ms": round(ms, 4), "bytes_per_column": b, "frac_of_8TBps": round(b * ngptot / (ms * 1e-3) / PEAK, 3)}
-
+row = lambda ms, b: th.row(ms, b, ngptot)  # noqa: E731
 
 print(json.dumps({
     "ngptot": ngptot, "nproma": nproma, "nlev": nlev, "precision": "fp32" if B.SINGLE else "fp64", "reps": reps,

@@ -9,49 +9,30 @@ backward and jvp through torch, dense op against sparse op.  Prints ONE JSON obj
     python tools/autograd_sparse_timing.py [NGPTOT [REPS]]"""
 import ctypes as C
 import json
-import os
-import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import timing_harness as th
+import torch
 
-import dwarf_p_cloudsc2_tl_ad_amd as c2  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import binding as B  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T  # noqa: E402
+import dwarf_p_cloudsc2_tl_ad_amd as c2
+from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
+from dwarf_p_cloudsc2_tl_ad_amd import binding as B
 
 ngptot = int(sys.argv[1]) if len(sys.argv) > 1 else 160000
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 nproma, nlev = 128, 137
-assert not B.SINGLE, "fp64 measurement"
 
-tab = c2.synthetic_table(nlev)
-ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-dev = ds.device
-ptsphy = float(ds.ptsphy)
-st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
+case = th.setup(ngptot, nproma, nlev)  # (one state under both parameter sets: QSAT is filled again per set below)
+tab, ds, x, lay, ptsphy, dev = case.tab, case.ds, case.x, case.lay, case.ptsphy, case.dev
+st = lambda: th.stream(dev)  # noqa: E731
+new = lambda names: th.new(names, lay, dev)  # noqa: E731
+timed = lambda step: th.median_ms(step, reps, ndigits=4)  # noqa: E731
 HALF = ("paph", "fplsl", "fplsn", "fhpsl", "fhpsn")
 R, H = 8 * nlev, 8 * (nlev + 1)  # bytes per column of a full-level plane and of a half-level plane written whole
 
 
 def plane_bytes(names):
     return sum(H if n in HALF else R for n in names)
-
-
-def timed(step):
-    for _ in range(5):
-        step()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return round(statistics.median(ms), 4)
 
 
 CASES = {  # name: (input side, output side) of the derivative blocks
@@ -65,12 +46,6 @@ result = {"ngptot": ngptot, "nproma": nproma, "nlev": nlev, "precision": "fp64",
 for evap in (False, True):
     prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True, levapls2=evap)
     ds.satur(prm)
-    x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-         "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-         "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-    lay = ag.check_layout(x, prm, ngptot)
-    ag._prepare(dev)
-    new = lambda names: {n: torch.empty(lay.shape(n), dtype=torch.float64, device=dev) for n in names}  # noqa: E731
     g = torch.Generator(device=dev).manual_seed(0)
     u = {n: torch.randn(lay.shape(n), generator=g, dtype=torch.float64, device=dev) for n in B.OUT_NAMES}
     v = {n: 0.01 * t for n, t in x.items()}

@@ -7,62 +7,28 @@ the fraction of 8 TB/s that is.
     python tools/autograd_timing.py [NGPTOT [REPS]]"""
 import ctypes as C
 import json
-import os
-import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import timing_harness as th
+import torch
 
-import dwarf_p_cloudsc2_tl_ad_amd as c2  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd import binding as B  # noqa: E402
-from dwarf_p_cloudsc2_tl_ad_amd.state import PLANE_Q, PLANE_QI, PLANE_QL, PLANE_T  # noqa: E402
+from dwarf_p_cloudsc2_tl_ad_amd import autograd as ag
+from dwarf_p_cloudsc2_tl_ad_amd import binding as B
 
-PEAK = 8e12  # B/s, HBM3E of one MI355X
 ngptot = int(sys.argv[1]) if len(sys.argv) > 1 else 160000
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 nproma, nlev = 128, 137
-assert not B.SINGLE, "fp64 measurement"
 
-tab = c2.synthetic_table(nlev)
-prm = c2.default_params(c2.ceta_from_table(tab), lregcl=True)
-ds = c2.DeviceState.from_table(tab, nproma, ngptot)
-ds.satur(prm)
-x = {"paph": ds.PAPH, "pap": ds.PAP, "q": ds.PQ, "qsat": ds.QSAT, "t": ds.PT, "l": ds.PCLV[:, 0], "i": ds.PCLV[:, 1],
-     "lude": ds.PLUDE, "lu": ds.PLU, "mfu": ds.PMFU, "mfd": ds.PMFD, "gtent": ds.B_CML[:, PLANE_T], "gtenq": ds.B_CML[:, PLANE_Q],
-     "gtenl": ds.B_CML[:, PLANE_QL], "gteni": ds.B_CML[:, PLANE_QI], "supsat": ds.PSUPSAT}
-lay = ag.check_layout(x, prm, ngptot)
-ptsphy = float(ds.ptsphy)
-dev = ds.device
+case = th.setup(ngptot, nproma, nlev, prepare=False)
+prm, x, lay, ptsphy, dev = case.prm, case.x, case.lay, case.ptsphy, case.dev
 xs = {n: t.detach().requires_grad_() for n, t in x.items()}  # views of the state's arena: no copies in the op
 assert all(t.data_ptr() == ag.normalize(x, lay, ag.IN_GROUPS)[n].data_ptr() for n, t in x.items()), "inputs would be copied"
 g = torch.Generator(device=dev).manual_seed(0)
 u = {n: torch.randn(lay.shape(n), generator=g, dtype=torch.float64, device=dev) for n in B.OUT_NAMES}
 v = {n: 0.01 * t for n, t in x.items()}
-st = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)  # noqa: E731
-new = lambda names: {n: torch.empty(lay.shape(n), dtype=torch.float64, device=dev) for n in names}  # noqa: E731
-
-
-def timed(step, pre=None):
-    """median ms of `step` between two events; `pre` (untimed) runs before each"""
-    for _ in range(5):
-        if pre:
-            pre()
-        step()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        if pre:
-            pre()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        step()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
-
+st = lambda: th.stream(dev)  # noqa: E731
+new = lambda names: th.new(names, lay, dev)  # noqa: E731
+timed = lambda step, pre=None: th.median_ms(step, reps, pre=pre)  # noqa: E731
 
 # forward / backward / jvp through torch
 fwd_ms = timed(lambda: ag.cloudsc2(xs, prm, ptsphy, ngptot))
@@ -114,10 +80,7 @@ clone_b = 8 * 2 * outs10 + rev_b
 tl_b = 8 * (2 * traj_in + outs10)
 jvp_b = fwd_b + tl_b
 
-
-def row(ms, b):
-    return {"ms": round(ms, 4), "bytes_per_column": b, "frac_of_8TBps": round(b * ngptot / (ms * 1e-3) / PEAK, 3)}
-
+row = lambda ms, b: th.row(ms, b, ngptot)  # noqa: E731
 
 print(json.dumps({
     "ngptot": ngptot, "nproma": nproma, "nlev": nlev, "precision": "fp64", "reps": reps, "device": torch.cuda.get_device_name(dev),
