@@ -13,5 +13,6 @@ from .state import (Cloudsc2State, bytes_per_column, ceta_from_table, column_ran
 from .driver import (DeviceState, FlatFields, ResidentState, cloudsc_driver, cloudsc_driver_ad, cloudsc_driver_tl,  # noqa: F401
                      run_state)
 from .autograd import (PARAM_NAMES, Cloudsc2Outputs, NormalEquations, check_column_sums, check_ensemble, check_ensemble_column_sums,  # noqa: F401,E402
-                       check_sum_residual, cloudsc2, cloudsc2_column_sums, cloudsc2_ensemble, cloudsc2_ensemble_column_sums,
+                       check_param_maps, check_sum_residual, cloudsc2, cloudsc2_column_sums, cloudsc2_ensemble,
+                       cloudsc2_ensemble_column_sums, cloudsc2_param_maps,
                        param_jacobian, param_jacobian_column_sums, param_normal_equations, param_normal_equations_column_sums, satur)

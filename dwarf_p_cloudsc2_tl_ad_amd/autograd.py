@@ -34,6 +34,13 @@ member is the bits of the 0-d ``params`` call with its row.  The 0-d ``params`` 
 the one launch whose constants sit in the kernel-argument segment, its bits, launch log and refusals are what callers and tests rely
 on, and a single parameter set has no table to derive on the device.
 
+Parameter maps.  ``cloudsc2_param_maps(inputs, prm, ptsphy, ngptot, satur, params={name: (nblocks, nproma) device tensor})`` is the
+spatial counterpart of the ensemble: the four constants are FIELDS, a value per column.  Before the level loop a lane loads its four
+doubles from a ``(4, nblocks, nproma)`` table and derives its constants with the host's expressions in their order
+(``cloudsc2_nl_launch_parmap`` / ``cloudsc2_tl_launch_parmap`` / ``cloudsc2_vjp_launch_parmap``); the gradient of a map is the lane's
+four parameter adjoints, stored per column with no fold.  Nothing is read on the host, so it captures in a graph like the ensemble;
+column c of every output and field gradient is the bits of the 0-d ``params`` call with column c's values.
+
 Sparse losses.  A loss usually touches a few outputs (surface precipitation, the ``t`` / ``q`` tendencies) and wants a few gradients
 (``t``, ``q``), yet the dense backward reads ten cotangent planes -- zeros allocated for the outputs that took no part -- and writes
 all 16 gradients before ``needs_input_grad`` throws most away.  ``cloudsc2(..., sparse=True)`` is the same forward with gradients
@@ -1403,6 +1410,186 @@ def _ens_table(inputs, names, prm: B.Params, params, pnames, K: int, dev: torch.
     given = dict(zip(pnames, ps))
     return torch.stack([given[n] if n in given else torch.full((K,), float(getattr(prm, n)), dtype=torch.float64, device=dev)
                         for n in PARAM_NAMES], dim=1)
+
+
+# ---- cloudsc2_param_maps: the four parameters as (nblocks, nproma) fields, read on the device ---------------------------------------------
+
+_NO_VMAP_PARMAP = ("cloudsc2_param_maps: torch.func.vmap, jacfwd, jacrev and is_grads_batched=True are not supported (batched "
+                   "directions of the parameter-map sweeps are not built); use .backward() / torch.autograd.grad / torch.func.grad / "
+                   "torch.func.vjp, or torch.autograd.forward_ad / torch.func.jvp, one direction at a time")
+
+_NO_SECOND_PARMAP = ("cloudsc2_param_maps: double backward (and forward-over-reverse, reverse-over-forward) is not supported: the sweeps "
+                     "are first-order derivatives of CLOUDSC2")
+
+
+def check_param_maps(inputs, prm: B.Params, ngptot: int | None = None, satur: bool = False, params=None) -> tuple:
+    """Every check of :func:`cloudsc2_param_maps` that needs no device; returns ``(layout, the given names in PARAM_NAMES order)``.
+    Runs on CPU tensors; raises ``ValueError``."""
+    if not hasattr(params, "keys"):
+        raise ValueError(f"params must map names of {PARAM_NAMES} to (nblocks, nproma) float64 tensors; got {type(params)}")
+    if len(params.keys()) == 0:
+        raise ValueError(f"params is empty: a parameter map gives at least one of {PARAM_NAMES}")
+    unknown = sorted(set(params.keys()) - set(PARAM_NAMES), key=str)
+    if unknown:
+        raise ValueError(f"params: unknown name(s) {unknown}; the differentiable parameters are {PARAM_NAMES}")
+    pnames = tuple(n for n in PARAM_NAMES if n in params.keys())
+    for n in pnames:
+        p = params[n]
+        if not isinstance(p, torch.Tensor):
+            raise ValueError(f"params[{n!r}] is not a tensor")
+        if p.dim() < 2:
+            raise ValueError(f"params[{n!r}] has shape {tuple(p.shape)}: a parameter map is a 2-d (nblocks, nproma) tensor with one value per "
+                             "column; one value for all columns is cloudsc2(..., params={name: 0-d tensor}), one value per member "
+                             "cloudsc2_ensemble(..., params={name: (K,) tensor})")
+        if p.dtype != torch.float64:
+            raise ValueError(f"params[{n!r}] has dtype {p.dtype}; parameters are float64 in both builds (the constants of cloudsc2_params are C doubles)")
+    lay = check_layout(inputs, prm, ngptot, satur=satur)
+    for n in pnames:
+        if tuple(params[n].shape) != (lay.nblocks, lay.nproma):
+            raise ValueError(f"params[{n!r}] has shape {tuple(params[n].shape)}, expected (nblocks, nproma) = {(lay.nblocks, lay.nproma)}")
+    return lay, pnames
+
+
+def _map_table(t: torch.Tensor) -> torch.Tensor:
+    """a (4, nblocks, nproma) table as the launchers read it -- (CLOUDSC2_NPAR, ncols_pad) doubles by padded column: plain, contiguous"""
+    return _raw(t).detach().contiguous()
+
+
+@_no_vmap(_NO_VMAP_PARMAP)
+@_inner(raises=_NO_SECOND_PARMAP)
+class _Cloudsc2ParmapTl(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, (4, nblocks, nproma) values, (4, nblocks, nproma) tangents, *n trajectory inputs, *n tangents)
+    -> 10 output tangents: ``cloudsc2_tl_launch_parmap``.  Differentiating it again raises ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, ptab, dptab, *ts):
+        names, groups = _names(satur)
+        n = len(names)
+        x = dict(zip(names, ts[:n]))
+        like = x["pap"]
+        dev = like.device
+        dx = normalize(dict(zip(names, ts[n:])), lay, groups)
+        dy = _new(B.OUT_NAMES, lay, like)
+        ptab, dptab = _map_table(ptab), _map_table(dptab)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_tl_launch_parmap(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur), _ptr(ptab),
+                                                    _ptr(dptab), C.byref(_block("in", x, lay)), C.byref(_block("in", dx, lay)),
+                                                    C.byref(_block("out", dy, lay)), _stream(dev)))
+        return tuple(dy[k] for k in B.OUT_NAMES)
+
+
+@_no_vmap(_NO_VMAP_PARMAP)
+@_inner(raises=_NO_SECOND_PARMAP)
+class _Cloudsc2ParmapVjp(torch.autograd.Function):
+    """forward(prm, ptsphy, layout, satur, (4, nblocks, nproma) values, *n trajectory inputs, PFPLSL5, PFPLSN5, cover scratch, *10 output
+    adjoints) -> n input adjoints and the ``(4, nblocks, nproma)`` parameter adjoints, padded tail zero: ``cloudsc2_vjp_launch_parmap``.
+    Differentiating it again (double backward) raises ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, ptab, *ts):
+        names, _ = _names(satur)
+        x, fplsl, fplsn, scratch, ys = _split(names, ts)
+        like = x["pap"]
+        dev = like.device
+        y = normalize(dict(zip(B.OUT_NAMES, ys)), lay, OUT_GROUPS)
+        xa = _new(names, lay, like)
+        ptab = _map_table(ptab)
+        par_adj = torch.empty((len(PARAM_NAMES), lay.nblocks, lay.nproma), dtype=torch.float64, device=dev)
+        if lay.tail < lay.nproma:
+            par_adj[:, -1, lay.tail:] = 0  # (the sweep assigns the active columns)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_vjp_launch_parmap(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, int(satur), _ptr(ptab),
+                                                     C.byref(_block("in", x, lay)), C.byref(_traj_out(fplsl, fplsn, lay)),
+                                                     C.byref(_block("in", xa, lay)), C.byref(_block("out", y, lay)), _scratch_ptr(scratch),
+                                                     _ptr(par_adj), _stream(dev)))
+        return tuple(xa[k] for k in names) + (par_adj,)
+
+
+@_no_vmap(_NO_VMAP_PARMAP)
+class _Cloudsc2Parmap(torch.autograd.Function):
+    # forward(prm, ptsphy, layout, satur, the (4, nblocks, nproma) value table, *n inputs) -> 10 outputs + the cover-checkpoint scratch:
+    # cloudsc2_nl_launch_parmap.  The table is a device tensor nobody reads on the host.  backward: one cloudsc2_vjp_launch_parmap; jvp:
+    # one cloudsc2_tl_launch_parmap.
+
+    @staticmethod
+    def forward(prm, ptsphy, lay, satur, ptab, *xs):
+        names, _ = _names(satur)
+        x = dict(zip(names, xs))
+        like = x["pap"]
+        dev = like.device
+        out = _new(B.OUT_NAMES, lay, like)
+        scratch = torch.empty((lay.nblocks, lay.nlev, lay.nproma) if _evap(prm) else (0,), dtype=like.dtype, device=dev)
+        ptab = _map_table(ptab)
+        with torch.cuda.device(dev):
+            B.check(B.lib.cloudsc2_nl_launch_parmap(C.byref(prm), float(ptsphy), lay.nproma, lay.nlev, lay.ngptot, _ptr(ptab),
+                                                    C.byref(_block("in", x, lay)), C.byref(_block("out", out, lay)), _scratch_ptr(scratch),
+                                                    _stream(dev)))
+        return tuple(out[n] for n in B.OUT_NAMES) + (scratch,)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        prm, ptsphy, lay, satur, ptab, *xs = inputs
+        _save_trajectory(ctx, xs, output[FPLSL], output[FPLSN], output[-1], table=ptab, prm=prm, ptsphy=ptsphy, lay=lay, satur=satur)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        _refuse_batched(grads, _NO_VMAP_PARMAP)
+        ptab, *saved = ctx.saved_tensors
+        lay, like = ctx.lay, saved[0]
+        need_p, need_x = ctx.needs_input_grad[4], ctx.needs_input_grad[5:]
+        if not need_p and not any(need_x):
+            return (None,) * (5 + len(need_x))
+        y = _zero_filled(B.OUT_NAMES, grads[:10], lay, like)  # (an output that took no part: one shared zero plane)
+        *xa, par_adj = _Cloudsc2ParmapVjp.apply(ctx.prm, ctx.ptsphy, lay, ctx.satur, ptab, *saved, *(y[n] for n in B.OUT_NAMES))
+        return (None,) * 4 + (par_adj if need_p else None,) + tuple(a if nd else None for a, nd in zip(xa, need_x))
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        _refuse_batched(tangents, _NO_VMAP_PARMAP)
+        names, _ = _names(ctx.satur)
+        ptab, *xs = ctx.saved_tensors
+        dptab = tangents[4] if tangents[4] is not None else torch.zeros_like(ptab)
+        dx = _zero_filled(names, tangents[5:], ctx.lay, xs[0])  # (no tangent: one shared zero plane)
+        dy = _Cloudsc2ParmapTl.apply(ctx.prm, ctx.ptsphy, ctx.lay, ctx.satur, ptab, dptab, *xs, *(dx[n] for n in names))
+        return tuple(dy) + (None,)
+
+
+def cloudsc2_param_maps(inputs, prm: B.Params, ptsphy: float, ngptot: int | None = None, satur: bool = False, params=None) -> Cloudsc2Outputs:
+    """CLOUDSC2 with ``rkconv``, ``rclcrit``, ``rlptrc``, ``rpecons`` as FIELDS: a value per column, read on the device.
+
+    ``params`` maps a non-empty subset of ``PARAM_NAMES`` to ``(nblocks, nproma)`` ``float64`` tensors ON THE INPUTS' DEVICE (float64 in
+    both builds); a name that is not given keeps ``prm``'s value in every column.  Nothing is read on the host: the
+    ``(4, nblocks, nproma)`` table is assembled with torch ops and every lane derives its constants from its column of it, so the call
+    does not synchronise, and after one eager call with the same CETA the forward and ``torch.autograd.grad`` of it can be captured in
+    ``torch.cuda.graph`` -- a replay after ``params[name].copy_(new)`` computes with the new values.  The values in the padded tail of a
+    map are not read.
+
+    ``inputs`` and ``satur`` are those of :func:`cloudsc2`.  Returns a :class:`Cloudsc2Outputs`.  ``.backward()``,
+    ``torch.autograd.grad``, ``torch.func.grad`` / ``vjp``, ``forward_ad`` and ``torch.func.jvp`` (with tangent maps) differentiate with
+    respect to the maps -- the gradient of a map is ``(nblocks, nproma)`` float64 on the device, column c holding d loss / d p[c], the
+    padded tail zero -- and the fields; ``torch.func.vmap`` / ``jacfwd`` / ``jacrev`` and ``is_grads_batched`` raise
+    ``NotImplementedError``, and so does double backward.  ``prm.lphylin = 0`` is refused.  It is not combined with ``sparse``, the
+    column-sum ops or the ensemble ops.  With the evaporation branch (``levapls2`` / ``ldrain1d``) every column's ``rpecons`` must be
+    non-zero: a map lives on the device and is NOT checked (a zero gives non-finite ``rpecons`` derivatives); ``prm``'s own value is
+    checked when it is used.
+
+    Promise: column c of every output, output tangent and field gradient is bit for bit what
+    ``cloudsc2(inputs, prm, ptsphy, ngptot, satur=..., params={the four 0-d values of column c})`` gives at that column; columns are
+    independent.  The gradient of a map is, per active column, that column's contribution to the 0-d parameter gradient of that call
+    (the row of ``cloudsc2_vjp_launch_par``'s workspace) before its fold."""
+    names, groups, (lay, pnames), dev = _enter(inputs, prm, ngptot, satur, check_param_maps, params)
+    ps = tuple(params[n] for n in pnames)
+    _refuse_batched(ps + tuple(inputs[n] for n in names), _NO_VMAP_PARMAP)
+    for n, p in zip(pnames, ps):
+        if p.device != dev:
+            raise ValueError(f"params[{n!r}] is on {p.device}: parameter maps live on the inputs' device {dev} (they are read there)")
+    if _evap(prm) and "rpecons" not in pnames and prm.rpecons == 0.0:
+        raise ValueError("cloudsc2_param_maps with the evaporation branch (levapls2 / ldrain1d): rpecons must not be 0")
+    _prepare(dev)
+    given = dict(zip(pnames, ps))
+    ptab = torch.stack([given[n] if n in given else torch.full((lay.nblocks, lay.nproma), float(getattr(prm, n)), dtype=torch.float64, device=dev)
+                        for n in PARAM_NAMES], dim=0)
+    return Cloudsc2Outputs(*_apply(_Cloudsc2Parmap, (prm, float(ptsphy), lay, bool(satur), ptab), inputs, names, groups, lay)[:10])
 
 
 # ---- cloudsc2_column_sums: per-column weighted level sums of the outputs, formed in the sweeps ------------------------------------------

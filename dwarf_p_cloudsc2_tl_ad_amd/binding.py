@@ -210,6 +210,16 @@ def _load() -> C.CDLL:
                                                    C.POINTER(Outputs), ms, C.POINTER(Inputs), ms, C.c_void_p, C.POINTER(Outputs), ms,
                                                    C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cloudsc2_vjp_launch_ens_colsum.restype = C.c_int
+    # per-column parameter maps: the values, their tangents and adjoints are device tables (CLOUDSC2_NPAR, ncols_pad) by padded column
+    lib.cloudsc2_nl_launch_parmap.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Inputs), C.POINTER(Outputs),
+                                              C.c_void_p, C.c_void_p]
+    lib.cloudsc2_nl_launch_parmap.restype = C.c_int
+    lib.cloudsc2_tl_launch_parmap.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Inputs),
+                                              C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p]
+    lib.cloudsc2_tl_launch_parmap.restype = C.c_int
+    lib.cloudsc2_vjp_launch_parmap.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(Inputs),
+                                               C.POINTER(Outputs), C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cloudsc2_vjp_launch_parmap.restype = C.c_int
     # the sensitivities of the outputs to all parameters in one sweep: (Outputs * CLOUDSC2_NPAR)(...), no tangent planes
     lib.cloudsc2_tl_launch_parjac.argtypes = [pp, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(Inputs), C.POINTER(Outputs), C.c_void_p]
     lib.cloudsc2_tl_launch_parjac.restype = C.c_int
@@ -328,7 +338,7 @@ lib = _load()
 # every symbol include/cloudsc2_hip.h declares
 EXPORTED = ("cloudsc2_params_default", "cloudsc2_last_error", "cloudsc2_device_available", "cloudsc2_current_device", "cloudsc2_set_math_mode",
             "cloudsc2_get_math_mode", "cloudsc2_real_bytes", "cloudsc2_nl_launch",
-            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_tl_launch_sparse", "cloudsc2_vjp_launch_sparse", "cloudsc2_nl_launch_colsum", "cloudsc2_tl_launch_colsum", "cloudsc2_vjp_launch_colsum", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch_parjac", "cloudsc2_ens_workspace_bytes", "cloudsc2_nl_launch_ens", "cloudsc2_tl_launch_ens", "cloudsc2_vjp_launch_ens", "cloudsc2_nl_launch_ens_colsum", "cloudsc2_tl_launch_ens_colsum", "cloudsc2_vjp_launch_ens_colsum", "cloudsc2_parnormal_work_doubles", "cloudsc2_parnormal_launch", "cloudsc2_parjac_launch_colsum", "cloudsc2_parnormal_launch_colsum", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
+            "cloudsc2_satur_launch", "cloudsc2_satur_lin_launch", "cloudsc2_tl_launch_satur", "cloudsc2_vjp_launch_satur", "cloudsc2_tl_launch_sparse", "cloudsc2_vjp_launch_sparse", "cloudsc2_nl_launch_colsum", "cloudsc2_tl_launch_colsum", "cloudsc2_vjp_launch_colsum", "cloudsc2_par_work_doubles", "cloudsc2_tl_launch_par", "cloudsc2_vjp_launch_par", "cloudsc2_tl_launch_parjac", "cloudsc2_ens_workspace_bytes", "cloudsc2_nl_launch_ens", "cloudsc2_tl_launch_ens", "cloudsc2_vjp_launch_ens", "cloudsc2_nl_launch_ens_colsum", "cloudsc2_tl_launch_ens_colsum", "cloudsc2_vjp_launch_ens_colsum", "cloudsc2_nl_launch_parmap", "cloudsc2_tl_launch_parmap", "cloudsc2_vjp_launch_parmap", "cloudsc2_parnormal_work_doubles", "cloudsc2_parnormal_launch", "cloudsc2_parjac_launch_colsum", "cloudsc2_parnormal_launch_colsum", "cloudsc2_tl_launch", "cloudsc2_tl_launch_self", "cloudsc2_ad_launch", "cloudsc2_ad_launch_assign",
             "cloudsc2_ad_launch_forward", "cloudsc2_ad_launch_reverse", "cloudsc2_vjp_launch", "cloudsc2_batch_max", "cloudsc2_tl_launch_batch", "cloudsc2_vjp_launch_batch", "cloudsc2_ad_launch_reverse_norms", "cloudsc2_taylor_sums_launch",
             "cloudsc2_taylor_sweep_work_doubles", "cloudsc2_taylor_sweep_launch", "cloudsc2_adjoint_norms_launch", "cloudsc2_nl_run", "cloudsc2_tl_taylor_run", "cloudsc2_ad_symmetry_run",
             "cloudsc2_release_workspace", "cloudsc2_taylor_verdict", "cloudsc2_adjoint_verdict",

@@ -477,7 +477,38 @@ enum : unsigned {
                      // field tangents are opaque zeros; the parameter adjoints are summed while the gradient planes are stored under the
                      // write mask, which may be empty.  The argument block is NlColsumArgs / TlEnsColsumArgs / AdEnsColsumArgs
                      // (cloudsc2_{nl,tl,vjp}_launch_ens_colsum; kernels: the units {nl,tl,vjp}_ens_colsum).
+  C2F_PARMAP = 4096u, // NL (LPHYLIN form, never with PERT or COLSUM), TL and the reverse sweep (both with PARLIN, never with SPARSE): RKCONV,
+                     // RCLCRIT, RLPTRC, RPECONS are not constants of the launch but (nblocks, nproma) maps.  Before the level loop the lane
+                     // loads its four doubles (and, TL, its four tangents) from a (PAR_COUNT, ncols_pad) table and derives its constants
+                     // (lane_consts); the level functions take them in place of the launch's (LanePar).  The reverse sweep stores the
+                     // lane's four adjoints to a table of that layout, which is the result: there is no fold.  The argument block is
+                     // NlParmapArgs / TlParmapArgs / AdParmapArgs (cloudsc2_{nl,tl,vjp}_launch_parmap; kernels: cloudsc2_parmap.hip).
 };
+
+// C2F_PARMAP: the sweep's own block first, then the tables -- (PAR_COUNT, ncols_pad) doubles indexed by padded column -- and the
+// time step as make_consts was given it (Consts::ptsphy is its real_t rounding)
+struct NlParmapArgs {
+  NlArgs a; const double* par; double ptsphy;
+};
+struct TlParmapArgs {
+  TlArgs a; const double* par; const double* dpar; double ptsphy;
+};
+struct AdParmapArgs {
+  AdArgs a; const double* par; double* apar; double ptsphy;  // apar: assigned in every active column
+};
+typedef const C2_CONST_AS NlParmapArgs* NlParmapArgsP;
+typedef const C2_CONST_AS TlParmapArgs* TlParmapArgsP;
+typedef const C2_CONST_AS AdParmapArgs* AdParmapArgsP;
+// the lane's constants from its column of the table(s); dpar may be NULL
+C2_HD void lane_load(LanePar& lp, ConstsP c, double ptsphy, const double* par, const double* dpar, long long np, long long gcol) {
+  double v[PAR_COUNT], dv[PAR_COUNT];
+#pragma unroll
+  for (int i = 0; i < PAR_COUNT; ++i) {
+    v[i] = par[i * np + gcol];
+    dv[i] = dpar ? dpar[i * np + gcol] : 0.0;
+  }
+  lane_consts(lp, c->evap, c->lregcl, ptsphy, v, dpar ? dv : nullptr);
+}
 
 // Waves per SIMD a sweep is built for, from its flag word: the kernels' launch bounds, the priority code of tl_column and the launchers'
 // choice between keeping a launch's waves abreast and pacing it all read it here (cloudsc2_sweep_kernels.hpp says what was measured).
@@ -840,6 +871,9 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
   constexpr bool MEMBER = (F & C2F_MEMBER) != 0;  // (gcol is the column of an ensemble's member)
   static_assert(!MEMBER || COLSUM, "C2F_MEMBER: the column sums of an ensemble's member");
   constexpr bool ONEWAVE = CKPT && (!COLSUM || EVAP);
+  constexpr bool PARMAP = (F & C2F_PARMAP) != 0;  // (a is the head of an NlParmapArgs)
+  static_assert(!PARMAP || (LIN && !PERT && !COLSUM), "C2F_PARMAP: the LPHYLIN form, never perturbed, output planes");
+  typedef typename std::conditional<PARMAP, LanePar, NoLane>::type LP;
   LaneOff o; bool active;
   if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
   const int nlev = a->g.nlev, nproma = a->g.nproma;
@@ -876,6 +910,8 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
   real_t ztrpaus = tropopause<PERT>(c, tab, in, o, &a->g, lam);
   RhCrit rh;
   rhcrit_setup(ztrpaus, rh);
+  [[maybe_unused]] LP lp;
+  if constexpr (PARMAP) lane_load(lp, c, ((NlParmapArgsP)a)->ptsphy, ((NlParmapArgsP)a)->par, nullptr, a->g.ncols_pad, gcol);
 
   real_t paph_surf = RC(0.0);
   if (EVAP) {
@@ -926,7 +962,8 @@ C2_HD void nl_column(long long gcol, NlArgsP a) {
     if (CKPT && EVAP) stg(ckpt, oscl + level_off(OT(), jk, nproma), cy.covptot);  // ZCOVPTOT5(JK-1)
     LevelTraj tr;
     LevelOut lo;
-    level_forward<P, EVAP, LIN>(c, k, rh, x, cy, tr, lo);
+    if constexpr (PARMAP) level_forward<P, EVAP, LIN, LP>(c, k, rh, x, cy, tr, lo, lp);
+    else level_forward<P, EVAP, LIN>(c, k, rh, x, cy, tr, lo);
     C2_LAUNDER(ap);
     if constexpr (COLSUM) {
       const ColsumTabP cs = &((const C2_CONST_AS NlColsumArgs*)ap)->cs;
@@ -1113,6 +1150,9 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   static_assert(!SATLIN || (!HAS_QSAT && !STORE_TRAJ && !SELFINC), "C2F_SATLIN: SATUR fused, no trajectory stores, increments given");
   static_assert(!SPARSE || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC), "C2F_SPARSE: QSAT or SATLIN, no trajectory stores, increments given");
   static_assert(!PARLIN || ((HAS_QSAT != SATLIN) && !STORE_TRAJ && !SELFINC), "C2F_PARLIN: QSAT or SATLIN, no trajectory stores, increments given");
+  constexpr bool PARMAP = (F & C2F_PARMAP) != 0;  // (a is the head of a TlParmapArgs)
+  static_assert(!PARMAP || (PARLIN && !SPARSE), "C2F_PARMAP: the dense parameter form");
+  typedef typename std::conditional<PARMAP, LanePar, NoLane>::type LP;
   typedef typename std::conditional<(F & C2F_OFF32) != 0, unsigned, long long>::type OT;
   LaneOff o, op; bool active;
   if (!lane_setup(&a->g, &a->s, gcol, o, active)) return;
@@ -1131,6 +1171,9 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
   real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->g, RC(0.0));
   RhCrit rh;
   rhcrit_setup(ztrpaus, rh);
+  [[maybe_unused]] LP lp;
+  if constexpr (PARMAP)
+    lane_load(lp, c, ((TlParmapArgsP)a)->ptsphy, ((TlParmapArgsP)a)->par, ((TlParmapArgsP)a)->dpar, a->g.ncols_pad, gcol);
 
   real_t paph_surf = RC(0.0), dpaph_surf = RC(0.0);
   if (EVAP) {
@@ -1195,8 +1238,10 @@ C2_HD void tl_column(long long gcol, TlArgsP a) {
     make_level_in(dcur, dpaph_k, dpaph_surf, dx);
     LevelTraj tr;
     LevelOut lo, dlo;
-    level_forward<P, EVAP>(c, k, rh, x, cy, tr, lo);
-    if constexpr (MEMBER) level_tl<true>(c, k, x, tr, dx, dcy, dlo, &((TlEnsColsumArgsP)ap)->par);
+    if constexpr (PARMAP) level_forward<P, EVAP, true, LP>(c, k, rh, x, cy, tr, lo, lp);
+    else level_forward<P, EVAP>(c, k, rh, x, cy, tr, lo);
+    if constexpr (PARMAP) level_tl<true, LP>(c, k, x, tr, dx, dcy, dlo, nullptr, lp);
+    else if constexpr (MEMBER) level_tl<true>(c, k, x, tr, dx, dcy, dlo, &((TlEnsColsumArgsP)ap)->par);
     else if constexpr (PARLIN) level_tl<true>(c, k, x, tr, dx, dcy, dlo, &((TlParArgsP)ap)->par);  // (a is the head of a TlParArgs)
     else level_tl(c, k, x, tr, dx, dcy, dlo);
     C2_LAUNDER(ap);
@@ -1375,6 +1420,9 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   // PARLIN with SPARSE: the column sums of an ensemble's member (a is the head of an AdEnsColsumArgs); the write mask may be empty
   constexpr bool MEMBER = SPARSE && PARLIN;
   static_assert(!MEMBER || COLSUM, "parameter adjoints of a sparse reverse sweep: the column-sum form of an ensemble");
+  constexpr bool PARMAP = (F & C2F_PARMAP) != 0;  // (a is the head of an AdParmapArgs)
+  static_assert(!PARMAP || (PARLIN && !SPARSE), "C2F_PARMAP: the dense parameter form");
+  typedef typename std::conditional<PARMAP, LanePar, NoLane>::type LP;
   typedef typename std::conditional<OFF32, unsigned, long long>::type OT;
   LaneOff o, oa64; bool active;
   if (!lane_setup(&a->nl.g, &a->nl.s, gcol, o, active)) return 0.0;
@@ -1394,6 +1442,8 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   real_t ztrpaus = tropopause<false>(c, tab, in, o, &a->nl.g, RC(0.0));
   RhCrit rh;
   rhcrit_setup(ztrpaus, rh);
+  [[maybe_unused]] LP lp;
+  if constexpr (PARMAP) lane_load(lp, c, ((AdParmapArgsP)a)->ptsphy, ((AdParmapArgsP)a)->par, nullptr, a->nl.g.ncols_pad, gcol);
   const real_t paph_bottom = in->paph[o.half + (long long)nlev * nproma];
   const real_t paph_surf = EVAP ? paph_bottom : RC(0.0);
 
@@ -1440,12 +1490,14 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
     make_level_in(cur, L.paph_k, paph_surf, x);
     LevelTraj tr;
     LevelOut lo;
-    level_forward<P, EVAP>(c, k, rh, x, L.cy, tr, lo);
+    if constexpr (PARMAP) level_forward<P, EVAP, true, LP>(c, k, rh, x, L.cy, tr, lo, lp);
+    else level_forward<P, EVAP>(c, k, rh, x, L.cy, tr, lo);
 
     ya.fplsn = ya.fplsn - ya.fhpsn * c->rlstt;
     ya.fplsl = ya.fplsl - ya.fhpsl * c->rlvtt;
     LevelIn ax;
-    if constexpr (MEMBER) level_ad<true>(c, k, x, tr, ya, acy, ax, &((AdEnsColsumArgsP)ap)->par, &pacc);
+    if constexpr (PARMAP) level_ad<true, LP>(c, k, x, tr, ya, acy, ax, nullptr, &pacc, lp);
+    else if constexpr (MEMBER) level_ad<true>(c, k, x, tr, ya, acy, ax, &((AdEnsColsumArgsP)ap)->par, &pacc);
     else if constexpr (PARLIN) level_ad<true>(c, k, x, tr, ya, acy, ax, &((AdParArgsP)ap)->par, &pacc);  // (a is the head of an AdParArgs)
     else level_ad(c, k, x, tr, ya, acy, ax);
     if constexpr (SATLIN) {  // the adjoint of qsat goes to pap and t through SATUR's transpose; it has no plane of its own
@@ -1571,7 +1623,8 @@ C2_HD double ad_reverse_column(long long gcol, AdArgsP a) {  // returns |norm3| 
   }
   if constexpr (PARLIN) {  // the lane's four sums: consecutive lanes, consecutive doubles of each row (gcol < ncols_pad: lane_setup)
     double* work;
-    if constexpr (MEMBER) work = ((AdEnsColsumArgsP)a)->work;
+    if constexpr (PARMAP) work = ((AdParmapArgsP)a)->apar;  // (the result itself)
+    else if constexpr (MEMBER) work = ((AdEnsColsumArgsP)a)->work;
     else work = ((AdParArgsP)a)->work;
     const long long np = a->nl.g.ncols_pad;
 #pragma unroll

@@ -7,6 +7,7 @@
 //   cloudsc2_alloc.hip    the placement allocator behind cloudsc2_device_malloc*
 //   cloudsc2_driver.hip   the host-array drivers and the resident state
 //   cloudsc2_helpers.hip  host-only helpers of the C ABI (default parameters, offsets, validation text, the synthetic table, verdicts)
+//   cloudsc2_parmap.hip   per-column parameter maps: cloudsc2_{nl,tl,vjp}_launch_parmap and their kernels (no family: see below)
 //
 // The sweeps' kernels are in the family units, cloudsc2_kern.hip compiled once per name of the Makefile's FAMILIES; the table of
 // cloudsc2_sweep_kernels.hpp (C2_ROWS_<unit>) says which variant tables each holds and how the host numbers them.  Any other __global__
@@ -59,7 +60,57 @@ int get_tables(const cloudsc2_params& p, const LevelTab** dev, int* kb0, int* kb
 int validate_launch_impl(const cloudsc2_real* table, int klon, int period, long long start, int nlevx, int ndim, int nproma,
                          long long ngptot, cloudsc2_field field, double* workspace, double* stats, void* stream, long long ncols_minmax);
 
+// the part of check_geom that needs no device (a launcher that refuses its whole call before it looks for one)
+int check_geom_args(const cloudsc2_params* prm, int nproma, int nlev, int ngptot);
+void fill_geom(Geom& g, int nproma, int nlev, int ngptot);  // what check_geom leaves in g (fair = 0, no pacing)
+// refusals several launchers share (each entry point keeps its own order of them)
+int check_satur(int satur);
+int require_qsat(int satur, const cloudsc2_inputs* traj_in);
+
 inline unsigned grid_for(long long ncols, int block) { return (unsigned)((ncols + block - 1) / block); }
+
+// The start every sweep launcher shares: check (the geometry; `missing`: the message for a NULL argument block) -> resolve (the
+// trajectory's inputs and outputs; a launcher resolves its own further blocks after these) -> tables -> constants -> common flags.
+struct Sweep {
+  Geom g;
+  Strides s = {0, 0, 0, 0, 0};
+  InPtrs in;
+  OutPtrs out;
+  const LevelTab* tab = nullptr;
+  Consts c;
+  unsigned f = 0;
+
+  int begin(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, const char* missing) {
+    const int rc = check_geom(prm, nproma, nlev, ngptot, g);
+    return rc ? rc : missing ? fail(CLOUDSC2_EINVAL, missing) : 0;
+  }
+  int trajectory(const cloudsc2_inputs& ti, const cloudsc2_outputs& to, bool out_required) {
+    const int rc = resolve_in(ti, false, s, in);
+    return rc ? rc : resolve_out(to, out_required, s, out);
+  }
+  // C2F_QSAT, C2F_PRECISE, C2F_EVAP, and C2F_OFF32 (32-bit byte offsets) when every buffer the sweep touches -- the trajectory's and
+  // those of the `more` strides -- is smaller than 4 GiB
+  int finish(const cloudsc2_params& prm, double ptsphy, bool qsat, std::initializer_list<long long> more) {
+    if (int rc = get_tables(prm, &tab, &g.kb0, &g.kb1)) return rc;
+    c = make_consts(prm, ptsphy);
+    if (qsat) f |= C2F_QSAT;
+    if (precise_of(&prm)) f |= C2F_PRECISE;
+    if (c.evap) f |= C2F_EVAP;
+    static const bool allow32 = !(getenv("CLOUDSC2_OFF32") && atoi(getenv("CLOUDSC2_OFF32")) == 0);  // 0: measurements only
+    long long stride = std::max({s.full, s.half, s.cml, s.clv, s.loc});
+    for (long long x : more) stride = std::max(stride, x);
+    const long long span = stride * (g.ncols_pad / g.nproma) + (long long)g.nproma * (g.nlev + 2);
+    if (allow32 && span * (long long)sizeof(real_t) < (1LL << 32)) f |= C2F_OFF32;
+    return 0;
+  }
+  // the NL sweep's argument block (no zero plane, no perturbation, no checkpoint)
+  NlArgs nl() const {
+    NlArgs a;
+    a.c = c; a.g = g; a.s = s; a.in = in; a.out = out; a.tab = tab;
+    a.zero_plane = nullptr; a.zero_stride = 0; a.lam = 0.0; a.ckpt = nullptr;
+    return a;
+  }
+};
 
 // The ten numbered kernel families of the sweeps, as cloudsc2_variant_built and the launch log number them; cloudsc2_kernel_occupancy
 // knows the first seven under the same numbers and five unnumbered tables as CLOUDSC2_KERNEL_* (10..14).  The rows of the table in

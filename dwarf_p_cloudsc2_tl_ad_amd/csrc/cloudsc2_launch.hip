@@ -452,61 +452,25 @@ int get_tables(const cloudsc2_params& p, const LevelTab** dev, int* kb0, int* kb
   *dev = e.dev; *kb0 = e.kb0; *kb1 = e.kb1;
   return 0;
 }
-int check_geom(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, Geom& g) {
+int check_geom_args(const cloudsc2_params* prm, int nproma, int nlev, int ngptot) {
   if (!prm) return fail(CLOUDSC2_EINVAL, "params is NULL");
   if (nproma < 1 || nlev < 2 || ngptot < 1) return fail(CLOUDSC2_EINVAL, "nproma >= 1, nlev >= 2, ngptot >= 1 required");
   if (nlev > CLOUDSC2_MAX_NLEV) return fail(CLOUDSC2_EINVAL, "nlev exceeds CLOUDSC2_MAX_NLEV");
   if (prm->nlev != nlev) return fail(CLOUDSC2_EINVAL, "params.nlev does not match nlev");
   if (prm->math_mode < 0 || prm->math_mode > 2) return fail(CLOUDSC2_EINVAL, "params.math_mode must be 0 (default), 1 (fast) or 2 (precise)");
-  if (!device_ok()) return no_device();
+  return 0;
+}
+void fill_geom(Geom& g, int nproma, int nlev, int ngptot) {
   g.nproma = nproma; g.nlev = nlev; g.ngptot = ngptot; g.ncols_pad = ncols_pad(nproma, ngptot);
   g.kb0 = 0; g.kb1 = 0; g.fair = 0;
+}
+int check_geom(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, Geom& g) {
+  if (int rc = check_geom_args(prm, nproma, nlev, ngptot)) return rc;
+  if (!device_ok()) return no_device();
+  fill_geom(g, nproma, nlev, ngptot);
   return 0;
 }
 namespace {
-
-// The start every sweep launcher shares: check (the geometry; `missing`: the message for a NULL argument block) -> resolve (the
-// trajectory's inputs and outputs; a launcher resolves its own further blocks after these) -> tables -> constants -> common flags.
-struct Sweep {
-  Geom g;
-  Strides s = {0, 0, 0, 0, 0};
-  InPtrs in;
-  OutPtrs out;
-  const LevelTab* tab = nullptr;
-  Consts c;
-  unsigned f = 0;
-
-  int begin(const cloudsc2_params* prm, int nproma, int nlev, int ngptot, const char* missing) {
-    const int rc = check_geom(prm, nproma, nlev, ngptot, g);
-    return rc ? rc : missing ? fail(CLOUDSC2_EINVAL, missing) : 0;
-  }
-  int trajectory(const cloudsc2_inputs& ti, const cloudsc2_outputs& to, bool out_required) {
-    const int rc = resolve_in(ti, false, s, in);
-    return rc ? rc : resolve_out(to, out_required, s, out);
-  }
-  // C2F_QSAT, C2F_PRECISE, C2F_EVAP, and C2F_OFF32 (32-bit byte offsets) when every buffer the sweep touches -- the trajectory's and
-  // those of the `more` strides -- is smaller than 4 GiB
-  int finish(const cloudsc2_params& prm, double ptsphy, bool qsat, std::initializer_list<long long> more) {
-    if (int rc = get_tables(prm, &tab, &g.kb0, &g.kb1)) return rc;
-    c = make_consts(prm, ptsphy);
-    if (qsat) f |= C2F_QSAT;
-    if (precise_of(&prm)) f |= C2F_PRECISE;
-    if (c.evap) f |= C2F_EVAP;
-    static const bool allow32 = !(getenv("CLOUDSC2_OFF32") && atoi(getenv("CLOUDSC2_OFF32")) == 0);  // 0: measurements only
-    long long stride = std::max({s.full, s.half, s.cml, s.clv, s.loc});
-    for (long long x : more) stride = std::max(stride, x);
-    const long long span = stride * (g.ncols_pad / g.nproma) + (long long)g.nproma * (g.nlev + 2);
-    if (allow32 && span * (long long)sizeof(real_t) < (1LL << 32)) f |= C2F_OFF32;
-    return 0;
-  }
-  // the NL sweep's argument block (no zero plane, no perturbation, no checkpoint)
-  NlArgs nl() const {
-    NlArgs a;
-    a.c = c; a.g = g; a.s = s; a.in = in; a.out = out; a.tab = tab;
-    a.zero_plane = nullptr; a.zero_stride = 0; a.lam = 0.0; a.ckpt = nullptr;
-    return a;
-  }
-};
 
 // What an ensemble launcher hands its parent's implementation: the parent checks the call and builds the argument block exactly as for
 // its own launch (from the caller's parameter block: the template), then ens_launch runs it for `members` members instead.
@@ -695,16 +659,18 @@ int ad_launch_impl(const cloudsc2_params* prm, double ptsphy, int nproma, int nl
   return launch_variant(kFamAdReverse, f, ad_reverse_variant(f), args, n, st);
 }
 
+}  // namespace
 // refusals several launchers share (each entry point keeps its own order of them)
 int check_satur(int satur) {
   return satur == 0 || satur == 1 ? 0 : fail(CLOUDSC2_EINVAL, "satur must be 0 (qsat given) or 1 (SATUR differentiated in the sweep)");
 }
+int require_qsat(int satur, const cloudsc2_inputs* traj_in) {
+  return !satur && traj_in && !traj_in->qsat.ptr ? fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required") : 0;
+}
+namespace {
 int check_rpecons(const cloudsc2_params* prm) {  // (its partial is formed as ZBETA / RPECONS)
   return prm && (prm->levapls2 || prm->ldrain1d) && prm->rpecons == 0.0
              ? fail(CLOUDSC2_EINVAL, "parameter derivative with the evaporation branch: rpecons must not be 0") : 0;
-}
-int require_qsat(int satur, const cloudsc2_inputs* traj_in) {
-  return !satur && traj_in && !traj_in->qsat.ptr ? fail(CLOUDSC2_EINVAL, "satur = 0: traj_in->qsat is required") : 0;
 }
 // what the two parameter launchers check before their parents' checks
 int check_par(const cloudsc2_params* prm, int satur) {

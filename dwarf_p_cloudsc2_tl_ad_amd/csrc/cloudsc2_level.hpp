@@ -339,6 +339,57 @@ C2_HD void ens_consts(Consts& c, double ptsphy, const double* par, const double*
   p.spare[0] = p.spare[1] = p.spare[2] = RC(0.0);
 }
 
+// Per-column parameter maps (C2F_PARMAP in cloudsc2_column.hpp): a LANE carries its own RKCONV, RCLCRIT, RLPTRC, RPECONS, so what the
+// level functions read of them is not a wave-uniform constant but a value per lane.  LanePar holds every derived constant that
+// depends on the four -- the members of Consts that ens_consts rewrites, and ParLin -- and the level functions take it as a template
+// argument LP in place of k0[K0_RLPTRC], k3, kt1[KT1_ZLCRIT_*_R2], kt2[KT2_CK_*], Consts::rpecons and the launch's ParLin.  NoLane
+// (the default) is every other instantiation: the constants of the launch, untouched.
+struct NoLane {};
+struct LanePar {
+  // level_forward
+  real_t rlptrc, rpecons, zlcrit_l, zlcrit_l_r, zckcodtl, zlcrit_i, zlcrit_i_r, zckcodti;
+  // level_tl / level_ad
+  real_t zlcrit_l_r2, zlcrit_i_r2, ck_l, ck_i;
+  ParLin pl;
+};
+template <class LP> struct is_lane { static constexpr bool value = true; };
+template <> struct is_lane<NoLane> { static constexpr bool value = false; };
+// what PAR forms of level_tl / level_ad read their ParLin through: the launch's, or the lane's own
+template <class LP>
+C2_HD auto parlin_of(ParLinP pl, const LP& lp) {
+  if constexpr (is_lane<LP>::value) return &lp.pl;
+  else return pl;
+}
+// A lane's constants from its four doubles (PAR_* order): ens_consts' expressions in their order, roundings to real_t included, so
+// that every member has the bytes make_consts / fill_stage_blocks / make_parlin give for a parameter block holding these four values.
+// evap, lregcl: Consts::evap, Consts::lregcl; ptsphy: the double make_consts was given; dpar may be NULL (no tangents).
+C2_HD void lane_consts(LanePar& l, int evap, int lregcl, double ptsphy, const double* par, const double* dpar) {
+  const double rkconv = par[PAR_RKCONV], rclcrit = par[PAR_RCLCRIT];
+  const real_t ptsphy_r = ptsphy;
+  l.rpecons = par[PAR_RPECONS]; l.rlptrc = par[PAR_RLPTRC];
+  l.zckcodtl = RC(2.0) * rkconv * ptsphy;
+  l.zckcodti = RC(5.0) * rkconv * ptsphy;
+  const real_t zckcodtla = l.zckcodtl / RC(100.0);
+  const real_t zckcodtia = l.zckcodti / RC(100.0);
+  l.zlcrit_l = evap ? RC(1.9) * rclcrit : rclcrit * RC(2.0);
+  l.zlcrit_i = evap ? RC(1.e-04) : rclcrit * RC(2.0);
+  l.zlcrit_l_r = RC(1.0) / l.zlcrit_l;
+  l.zlcrit_i_r = RC(1.0) / l.zlcrit_i;
+  l.zlcrit_l_r2 = l.zlcrit_l_r * l.zlcrit_l_r;
+  l.zlcrit_i_r2 = l.zlcrit_i_r * l.zlcrit_i_r;
+  l.ck_l = lregcl ? zckcodtla : l.zckcodtl;
+  l.ck_i = lregcl ? zckcodtia : l.zckcodti;
+  ParLin& p = l.pl;
+  for (int i = 0; i < PAR_COUNT; ++i) p.dpar[i] = dpar ? (real_t)dpar[i] : RC(0.0);
+  p.dck_l = RC(2.0) * ptsphy_r;
+  p.dck_i = RC(5.0) * ptsphy_r;
+  const real_t dlc_l = evap ? RC(1.9) : RC(2.0), dlc_i = evap ? RC(0.0) : RC(2.0);
+  p.crc_l = -RC(2.0) * l.zckcodtl * dlc_l * (l.zlcrit_l_r * l.zlcrit_l_r * l.zlcrit_l_r);
+  p.crc_i = -RC(2.0) * l.zckcodti * dlc_i * (l.zlcrit_i_r * l.zlcrit_i_r * l.zlcrit_i_r);
+  p.rpecons_r = evap ? RC(1.0) / l.rpecons : RC(0.0);
+  p.spare[0] = p.spare[1] = p.spare[2] = RC(0.0);
+}
+
 // Raw inputs of one level (dummy arguments of CLOUDSC2 at (JL,JK); cloudsc2.F90:124-143).
 struct LevelIn {
   real_t paph_k, paph_k1;  // PAPHP1(JK), PAPHP1(JK+1)
@@ -583,9 +634,11 @@ struct LevelTraj {
 // LIN is `LPHYLIN .OR. LDRAIN1D` (cloudsc2.F90:349), true in every shipped configuration (the three mains force LPHYLIN=.true.,
 // dwarf_cloudsc.F90:107) and always for the trajectories of CLOUDSC2TL / CLOUDSC2AD, which have no other form; false selects the
 // FOEALFA / FOEEWM form of stage A (:365-369) in the NL sweep.
-template <bool P, bool EVAP, bool LIN = true>
+// LP: NoLane, or the lane's own parameter constants (LanePar) in place of the launch's.
+template <bool P, bool EVAP, bool LIN = true, class LP = NoLane>
 C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const LevelIn& x, Carry& cy,
-                         LevelTraj& t, LevelOut& o) {
+                         LevelTraj& t, LevelOut& o, [[maybe_unused]] const LP& lp = LP()) {
+  constexpr bool LANE = is_lane<LP>::value;
   const real_t zqmax = RC(0.5), zeps2 = RC(1.e-10);
   const int rvtmp2_zero = c->rvtmp2_zero;
   const bool evap = EVAP;
@@ -594,6 +647,9 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
   StageBlock k0, k1;
   c2_block2(&c->k0, &c->k1, k0, k1);
   const real_t ptsphy = k0.v[K0_PTSPHY], rtt = k0.v[K0_RTT];
+  real_t rlptrc;
+  if constexpr (LANE) rlptrc = lp.rlptrc;
+  else rlptrc = k0.v[K0_RLPTRC];
 
   // first guess (cloudsc2.F90:255-258) and thermodynamic constants (:272-276)
   t.ztp2 = x.t + ptsphy * x.gt;
@@ -641,7 +697,7 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
   } else {
     real_t z3es, z4es, r4;
     if (P) {
-      real_t u = RC(0.17) * (t.ztp2 - k0.v[K0_RLPTRC]);
+      real_t u = RC(0.17) * (t.ztp2 - rlptrc);
       real_t ch = cosh(u);  // TL/AD only
       t.zcosh2r = RC(1.0) / (ch * ch);
       real_t zoealfaw = RC(0.545) * (tanh(u) + RC(1.0));
@@ -650,7 +706,7 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
       r4 = RC(0.0);
     } else if (t.cold) {
       // tanh(u)+1 = 2 e^{2u}/(e^{2u}+1),  1/cosh^2(u) = 4 e^{2u}/(e^{2u}+1)^2,  u = 0.17 (T - RLPTRC)
-      real_t e2 = c2_exp(RC(0.34) * (t.ztp2 - k0.v[K0_RLPTRC]));
+      real_t e2 = c2_exp(RC(0.34) * (t.ztp2 - rlptrc));
       real_t re = c2_rcp(e2 + RC(1.0));
       real_t th1 = RC(2.0) * e2 * re;
       t.zcosh2r = RC(2.0) * th1 * re;
@@ -803,21 +859,29 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
     // ---- block k3 ----
     const StageBlock k3 = c2_block(&c->k3);
     rtt3 = k3.v[K3_RTT];
+    real_t zlcrit_l, zlcrit_l_r, zckcodtl, zlcrit_i, zlcrit_i_r, zckcodti;
+    if constexpr (LANE) {
+      zlcrit_l = lp.zlcrit_l; zlcrit_l_r = lp.zlcrit_l_r; zckcodtl = lp.zckcodtl;
+      zlcrit_i = lp.zlcrit_i; zlcrit_i_r = lp.zlcrit_i_r; zckcodti = lp.zckcodti;
+    } else {
+      zlcrit_l = k3.v[K3_ZLCRIT_L]; zlcrit_l_r = k3.v[K3_ZLCRIT_L_R]; zckcodtl = k3.v[K3_ZCKCODTL];
+      zlcrit_i = k3.v[K3_ZLCRIT_I]; zlcrit_i_r = k3.v[K3_ZLCRIT_I_R]; zckcodti = k3.v[K3_ZCKCODTI];
+    }
     t.rclc = recip<P>(t.clc);
     t.zcldl = quot<P>(t.zqlwc1, t.clc, t.rclc);
-    real_t ql = quot<P>(t.zcldl, k3.v[K3_ZLCRIT_L], k3.v[K3_ZLCRIT_L_R]);
+    real_t ql = quot<P>(t.zcldl, zlcrit_l, zlcrit_l_r);
     t.zexp3 = ex<P>(-(ql * ql));
-    t.zdl = k3.v[K3_ZCKCODTL] * (RC(1.0) - t.zexp3);
+    t.zdl = zckcodtl * (RC(1.0) - t.zexp3);
     t.zexpdl = ex<P>(-t.zdl);
     real_t zlnew = t.clc * t.zcldl * t.zexpdl;
     t.zprr = t.zqlwc1 - zlnew;
     t.zqlwc = t.zqlwc1 - t.zprr;
 
     t.zcldi = quot<P>(t.zqiwc1, t.clc, t.rclc);
-    real_t qi = quot<P>(t.zcldi, k3.v[K3_ZLCRIT_I], k3.v[K3_ZLCRIT_I_R]);
+    real_t qi = quot<P>(t.zcldi, zlcrit_i, zlcrit_i_r);
     t.zexp1 = ex<P>(RC(0.025) * (t.ztp1 - rtt3));
     t.zexp2 = ex<P>(-(qi * qi));
-    t.zdi = k3.v[K3_ZCKCODTI] * t.zexp1 * (RC(1.0) - t.zexp2);
+    t.zdi = zckcodti * t.zexp1 * (RC(1.0) - t.zexp2);
     t.zexpdi = ex<P>(-t.zdi);
     real_t zinew = t.clc * t.zcldi * t.zexpdi;
     t.zprs = t.zqiwc1 - zinew;
@@ -852,6 +916,9 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
   t.zpreclr = RC(0.0); t.omc = RC(1.0); t.zsqp = RC(1.0);
   if (t.llo2) {
     t.omc = RC(1.0) - t.clc;
+    real_t rpecons;
+    if constexpr (LANE) rpecons = lp.rpecons;
+    else rpecons = c->rpecons;
     if (!P) {
       // fast arithmetic (round 5): the block's seven IEEE divisions on three refined v_rcp_f64 (1/covptot1 and 1/omc^2 from one,
       // 1/covpclr, 1/prtot and 1/p_surf from one, 1/(1 + beta dt corqs) alone), the division by ZDTGDP = dt g / dp as a product
@@ -863,7 +930,7 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
       t.zpreclr1 = t.zprtot * t.covpclr * r_cov1;
       t.zqe = x.qs - (x.qs - t.zqlim) * t.covpclr * r_omc2;
       t.zsqp = sqrt(x.pap * r_psurf);
-      t.zbeta = c->rg * c->rpecons * c2_exp(RC(0.5777) * log(t.zsqp * RC(196.46365422396858) * t.zpreclr1 * r_clr));  // 1 / 5.09e-3
+      t.zbeta = c->rg * rpecons * c2_exp(RC(0.5777) * log(t.zsqp * RC(196.46365422396858) * t.zpreclr1 * r_clr));  // 1 / 5.09e-3
       t.zb = ptsphy4 * t.zbeta * (x.qs - t.zqe) * c2_rcp(RC(1.0) + t.zbeta * ptsphy4 * t.zcorqs);
       t.zdtgdp = c->zcons2_r * t.rdp;
       t.zdpr1 = t.covpclr * t.zb * zcons2dp;
@@ -885,7 +952,7 @@ C2_HD void level_forward(ConstsP c, const LevelCst& k, const RhCrit& rh, const L
       t.zpreclr1 = t.zprtot * t.covpclr / t.covptot1;
       t.zqe = x.qs - (x.qs - t.zqlim) * t.covpclr / (t.omc * t.omc);
       t.zsqp = sqrt(x.pap / x.paph_surf);
-      t.zbeta = c->rg * c->rpecons * pow(t.zsqp / RC(5.09e-3) * t.zpreclr1 / t.covpclr, RC(0.5777));
+      t.zbeta = c->rg * rpecons * pow(t.zsqp / RC(5.09e-3) * t.zpreclr1 / t.covpclr, RC(0.5777));
       t.zb = ptsphy4 * t.zbeta * (x.qs - t.zqe) / (RC(1.0) + t.zbeta * ptsphy4 * t.zcorqs);
       t.zdtgdp = ptsphy4 * c->rg / (x.paph_k1 - x.paph_k);
       t.zdpr1 = t.covpclr * t.zb / t.zdtgdp;
@@ -1014,18 +1081,24 @@ C2_HD real_t regcl_factor(real_t zqpd5, real_t zqcd5, real_t zscalm) {
 // CUADJTQSTL KCALL=0 (cuadjtqstl.F90:333-405).  dx = perturbation inputs, dcy = perturbation carries.
 // ---------------------------------------------------------------------------------------------------------
 // PAR: the four parameter tangents pl->dpar add their source terms at the parameters' use sites (struct ParLin).
-template <bool PAR = false>
+// LP: NoLane, or the lane's own parameter constants and ParLin (LanePar) in place of the launch's (pl_ is then not read).
+template <bool PAR = false, class LP = NoLane>
 C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelTraj& t, const LevelIn& dx,
-                    Carry& dcy, LevelOut& dout, [[maybe_unused]] ParLinP pl = nullptr) {
+                    Carry& dcy, LevelOut& dout, [[maybe_unused]] ParLinP pl_ = nullptr, [[maybe_unused]] const LP& lp = LP()) {
+  [[maybe_unused]] const auto pl = parlin_of(pl_, lp);
   // constants of this function from three 64-byte blocks (one scalar-cache wait)
   StageBlock kt0, kt1, kt2;
   c2_block3(&c->kt0, &c->kt1, &c->kt2, kt0, kt1, kt2);
   const real_t ptsphy = kt0.v[KT0_PTSPHY], rtt = kt0.v[KT0_RTT], r3ies = kt0.v[KT0_R3IES], r4ies = kt0.v[KT0_R4IES],
                r3les = kt0.v[KT0_R3LES], r4les = kt0.v[KT0_R4LES], r5les = kt0.v[KT0_R5LES], r5ies = kt0.v[KT0_R5IES];
   const real_t retv = kt1.v[KT1_RETV], zcons3 = kt1.v[KT1_ZCONS3], rg = kt1.v[KT1_RG], zqtmst = kt1.v[KT1_ZQTMST],
-               zcons2 = kt1.v[KT1_ZCONS2], zmeltp2 = kt1.v[KT1_ZMELTP2], zlcrit_l_r2 = kt1.v[KT1_ZLCRIT_L_R2],
-               zlcrit_i_r2 = kt1.v[KT1_ZLCRIT_I_R2];
-  const real_t ck_l = kt2.v[KT2_CK_L], ck_i = kt2.v[KT2_CK_I];
+               zcons2 = kt1.v[KT1_ZCONS2], zmeltp2 = kt1.v[KT1_ZMELTP2];
+  real_t zlcrit_l_r2, zlcrit_i_r2, ck_l, ck_i;
+  if constexpr (is_lane<LP>::value) {
+    zlcrit_l_r2 = lp.zlcrit_l_r2; zlcrit_i_r2 = lp.zlcrit_i_r2; ck_l = lp.ck_l; ck_i = lp.ck_i;
+  } else {
+    zlcrit_l_r2 = kt1.v[KT1_ZLCRIT_L_R2]; zlcrit_i_r2 = kt1.v[KT1_ZLCRIT_I_R2]; ck_l = kt2.v[KT2_CK_L]; ck_i = kt2.v[KT2_CK_I];
+  }
   const int lregcl = c->lregcl, rvtmp2_zero = c->rvtmp2_zero;
   (void)r4ies; (void)r4les; (void)zcons3; (void)zmeltp2; (void)rvtmp2_zero;
   // first guess
@@ -1292,18 +1365,24 @@ C2_HD void level_tl(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelT
 #else
 #define C2_PAR_COPY(name, x) const real_t name = (x)
 #endif
-template <bool PAR = false>
+template <bool PAR = false, class LP = NoLane>
 C2_HD void level_ad(ConstsP c, const LevelCst& k, const LevelIn& x, const LevelTraj& t, const LevelOut& ya,
-                    Carry& acy, LevelIn& ax, [[maybe_unused]] ParLinP pl = nullptr, [[maybe_unused]] ParAcc* pacc = nullptr) {
+                    Carry& acy, LevelIn& ax, [[maybe_unused]] ParLinP pl_ = nullptr, [[maybe_unused]] ParAcc* pacc = nullptr,
+                    [[maybe_unused]] const LP& lp = LP()) {
+  [[maybe_unused]] const auto pl = parlin_of(pl_, lp);
   // constants of this function from three 64-byte blocks (one scalar-cache wait)
   StageBlock kt0, kt1, kt2;
   c2_block3(&c->kt0, &c->kt1, &c->kt2, kt0, kt1, kt2);
   const real_t ptsphy = kt0.v[KT0_PTSPHY], rtt = kt0.v[KT0_RTT], r3ies = kt0.v[KT0_R3IES], r4ies = kt0.v[KT0_R4IES],
                r3les = kt0.v[KT0_R3LES], r4les = kt0.v[KT0_R4LES], r5les = kt0.v[KT0_R5LES], r5ies = kt0.v[KT0_R5IES];
   const real_t retv = kt1.v[KT1_RETV], zcons3 = kt1.v[KT1_ZCONS3], rg = kt1.v[KT1_RG], zqtmst = kt1.v[KT1_ZQTMST],
-               zcons2 = kt1.v[KT1_ZCONS2], zmeltp2 = kt1.v[KT1_ZMELTP2], zlcrit_l_r2 = kt1.v[KT1_ZLCRIT_L_R2],
-               zlcrit_i_r2 = kt1.v[KT1_ZLCRIT_I_R2];
-  const real_t ck_l = kt2.v[KT2_CK_L], ck_i = kt2.v[KT2_CK_I];
+               zcons2 = kt1.v[KT1_ZCONS2], zmeltp2 = kt1.v[KT1_ZMELTP2];
+  real_t zlcrit_l_r2, zlcrit_i_r2, ck_l, ck_i;
+  if constexpr (is_lane<LP>::value) {
+    zlcrit_l_r2 = lp.zlcrit_l_r2; zlcrit_i_r2 = lp.zlcrit_i_r2; ck_l = lp.ck_l; ck_i = lp.ck_i;
+  } else {
+    zlcrit_l_r2 = kt1.v[KT1_ZLCRIT_L_R2]; zlcrit_i_r2 = kt1.v[KT1_ZLCRIT_I_R2]; ck_l = kt2.v[KT2_CK_L]; ck_i = kt2.v[KT2_CK_I];
+  }
   const int lregcl = c->lregcl, rvtmp2_zero = c->rvtmp2_zero;
   (void)r4ies; (void)r4les; (void)zcons3; (void)zmeltp2; (void)rvtmp2_zero;
   // adjoints of level-local quantities

@@ -543,6 +543,33 @@ int cloudsc2_vjp_launch_ens(const cloudsc2_params* prm, double ptsphy, int nprom
                             const long long* adj_out_mstride, const cloudsc2_real* scratch, long long scratch_mstride, void* workspace,
                             double* par_adj, void* stream);
 
+/* Per-column parameter maps: rkconv, rclcrit, rlptrc, rpecons as (nblocks, nproma) FIELDS, read on the device.  The spatial counterpart
+ * of the ensemble launchers: there a member has its own four values, here a column has.  A lane loads its four doubles before the level
+ * loop and derives its constants with the expressions of the host's derivation in their order, so column c of everything a launcher
+ * writes is the bits its scalar parent gives for a prm holding column c's four values:
+ *   cloudsc2_nl_launch_parmap   cloudsc2_ad_launch_forward (qsat given, or NULL: SATUR evaluated in the sweep; the cover checkpoint
+ *                               `scratch` is kept exactly with LEVAPLS2 .OR. LDRAIN1D),
+ *   cloudsc2_tl_launch_parmap   cloudsc2_tl_launch_par, the parameter tangents column c of dpar_dev,
+ *   cloudsc2_vjp_launch_parmap  cloudsc2_vjp_launch_par; column c of par_adj_dev is ASSIGNED that column's row of the parent's
+ *                               workspace, in every active column.  There is no fold.
+ *   par_dev, dpar_dev, par_adj_dev   device, (CLOUDSC2_NPAR, ncols_pad) doubles, ncols_pad = nblocks x nproma: row k is parameter k in
+ *                               CLOUDSC2_NPAR order, indexed by padded column number block x nproma + lane (the layout of the parent's
+ *                               workspace).  Read / written by the kernels only, in active columns only: the padded tail is not touched.
+ *   With the evaporation branch every column's rpecons must not be 0; the values live on the device, so this is NOT checked.
+ * CLOUDSC2_EINVAL, before a device is looked for: a NULL table, satur other than 0 or 1, prm->lphylin = 0, a NULL argument block or
+ * required field, block strides that differ within a layout group, and the parents' other refusals.  No launcher allocates, copies or
+ * synchronises (apart from the CETA table of a grid's first use); each is one plain kernel node under stream capture.  Not paced, no
+ * kernel family of cloudsc2_variant_built / cloudsc2_kernel_occupancy, no launch-log entry. */
+int cloudsc2_nl_launch_parmap(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, const double* par_dev,
+                              const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out, cloudsc2_real* scratch, void* stream);
+int cloudsc2_tl_launch_parmap(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                              const double* par_dev, const double* dpar_dev, const cloudsc2_inputs* traj_in,
+                              const cloudsc2_inputs* pert_in, const cloudsc2_outputs* pert_out, void* stream);
+int cloudsc2_vjp_launch_parmap(const cloudsc2_params* prm, double ptsphy, int nproma, int nlev, int ngptot, int satur,
+                               const double* par_dev, const cloudsc2_inputs* traj_in, const cloudsc2_outputs* traj_out,
+                               const cloudsc2_inputs* adj_in, const cloudsc2_outputs* adj_out /* read only */,
+                               const cloudsc2_real* scratch, double* par_adj_dev, void* stream);
+
 /* Column sums of an ensemble's members: the column-sum launchers for `members` parameter sets in ONE call, the parameters read on the
  * device, no output, cotangent or tangent plane.  What a calibration needs of a member is K x (a few) x one value per column; the
  * dense ensemble writes ten planes per member.  Argument blocks, member strides, params_dev / dparams_dev / par_adj and the workspace
